@@ -2,7 +2,7 @@
 """Headline benchmark: Mpixels/s of the 3x3 depthwise conv2d (Gaussian 3x3, sigma 0.8, reflect border -- the
 call gaussian_blur_image makes) over 4K fp32 3-channel frames, image-sharded over N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: spawns its own N ranks (see below)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # N > 1: spawns its own N ranks (see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                     # or is launched as one rank of N
 
@@ -33,6 +33,8 @@ The JSON line also carries
   cpu_baseline (N = 1) the reference's CPU path (pad(reflect) + conv2d(groups=C) through torch CPU ops, the exact call
                sequence of gaussian_blur_image) timed on this box's host cores on a bounded sample; `legs`: the same on
                one thread, and cfg4's Conv2d+ReLU on the fastest pool size and on one thread.
+  dump_outputs (with --dump-outputs DIR) the .npy files written: a seeded sample of the output of the last timed step
+               (see dump_outputs); the inputs are seeded too, so two builds run with the same arguments compare file for file.
 """
 from __future__ import annotations
 
@@ -75,7 +77,15 @@ def parse(argv=None):
     p.add_argument("--force-dist", action="store_true",
                    help="initialise the process group even for a single rank (exercises the RCCL calls on a one-GPU box)")
     p.add_argument("--launch-timeout", type=float, default=1500.0, help="launcher: seconds before the child is killed")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write a fixed, seeded sample of what the last step computed as DIR/<name>.npy "
+                        "(float32 / float64, at most 64 MB in all): two builds run with the same arguments can be compared file for file")
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.control_plane_only:
+        p.error("--dump-outputs needs real launches: --control-plane-only computes nothing")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ launcher (no torch)
@@ -398,6 +408,40 @@ def cpu_legs(x_frame, threads: int, cfg4_in):
     return legs
 
 
+DUMP_SAMPLE = 1 << 21  # output elements sampled over a rank's whole shard (divided among the ranks of a job)
+DUMP_CORNER = 256  # side of the two full-resolution corner tiles (all channels) that hold the reflect border
+
+
+def dump_outputs(y, out_dir, rank: int, world: int, seed: int = 7000) -> dict:
+    """Untimed, after the timed region: what the last timed step left in the rank's output shard y (n, C, H, W) -> .npy files.
+    The shard is 12.7 GB by default, so this writes a sample that is fixed by the arguments alone: the elements at DUMP_SAMPLE / world
+    flat indices drawn with a seeded Philox generator (their indices alongside, as float64, exact below 2**53), plus the
+    top-left tile of the first frame and the bottom-right tile of the last one, where the border handling lives.  Rank r
+    of a multi-rank job suffixes its files with _rank<r>.  Returns {file: bytes}."""
+    import numpy as np
+    import torch
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    flat = y.view(-1)
+    rng = np.random.Generator(np.random.Philox(seed + rank))
+    idx = np.sort(rng.integers(0, flat.numel(), size=max(1, DUMP_SAMPLE // world), dtype=np.int64))
+    c = DUMP_CORNER
+    arrays = {
+        f"y_sample{sfx}": flat[torch.from_numpy(idx).to(y.device)].cpu().numpy(),
+        f"y_sample_index{sfx}": idx.astype(np.float64),
+        f"y_first_frame_top_left{sfx}": y[0, :, :c, :c].cpu().numpy(),
+        f"y_last_frame_bottom_right{sfx}": y[-1, :, -c:, -c:].cpu().numpy(),
+    }
+    written = {}
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(arr))
+        written[f"{name}.npy"] = int(arr.nbytes)
+    return written
+
+
 def kernel_source_sha() -> str:
     """SHA-256 (16 hex digits) of the sources of the headline kernel: ties profiles/traffic_latest.json to the kernel
     it was measured on even when unrelated files of the library change."""
@@ -504,6 +548,7 @@ def run_rank(a) -> int:
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = sharding.max_over_ranks(elapsed, red_dev)
+    dumped = dump_outputs(y, a.dump_outputs, rank, world) if a.dump_outputs and not dry else None
 
     # ---- untimed: per-rank launch statistics, parity against the oracle, checksum of the WHOLE output
     alg_bytes = n * C * H * W * BYTES_PER_ELEMENT
@@ -586,6 +631,9 @@ def run_rank(a) -> int:
                    "checksum_all_frames": sum(p["checksum"] for p in per_rank)},
         "per_rank": per_rank,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": str(Path(a.dump_outputs).resolve()), "files": dumped,
+                               "of": "a seeded sample of the output of the last timed step" + (" (rank 0's files)" if world > 1 else "")}
     if dry:
         out["rehearsal"] = "control-plane-only: launcher, rendezvous, barriers, reductions and gathers ran; NO kernel was launched and nothing was measured"
     traffic_file = ROOT / "profiles" / "traffic_latest.json"

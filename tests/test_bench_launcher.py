@@ -106,3 +106,36 @@ def test_rccl_calls_on_a_one_rank_group():
     d = _line(r.stdout)
     assert d["config"]["backend"].startswith("RCCL") and d["n_gpus"] == 1 and d["value"] > 0
     assert d["parity"]["gpu_vs_oracle_bit_exact"] is True and len(d["per_rank"]) == 1
+
+
+def test_dump_outputs_and_steps_arguments_are_checked():
+    r = _run([sys.executable, BENCH, "--control-plane-only", "--dump-outputs", "unused"])
+    assert r.returncode != 0 and "--dump-outputs needs real launches" in r.stderr and not r.stdout.strip()
+    r = _run([sys.executable, BENCH, "--control-plane-only", "--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_same_arguments_same_files(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same sample of the last timed step's output, float32 /
+    float64 and at most 64 MB; --steps sets the number of timed steps and the line carries ms_per_step."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        r = _run([sys.executable, BENCH, "--frames-per-gpu", "2", "--steps", "4", "--warmup", "1", "--no-configs",
+                  "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _line(r.stdout)
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["parity"]["gpu_vs_oracle_bit_exact"] is True
+        assert set(d["dump_outputs"]["files"]) == {p.name for p in (tmp_path / name).iterdir()}
+        runs.append(d)
+    files = sorted(runs[0]["dump_outputs"]["files"])
+    assert files == sorted(runs[1]["dump_outputs"]["files"]) and "y_sample.npy" in files
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    y = np.load(tmp_path / "a" / "y_sample.npy")
+    assert np.isfinite(y).all() and 0.0 <= y.min() and y.max() <= 1.0  # a blur of uniform [0, 1) frames
