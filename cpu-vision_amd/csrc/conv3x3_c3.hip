@@ -30,12 +30,8 @@ namespace mv {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef MV_C3_NT
-#define MV_C3_NT 0  // plain stores: the write-only stream of this layer runs 5-10 % faster than with non-temporal stores (profiles/r02_tune_conv_c3_plain_stores.log, tools/micro/store_pattern.hip)
-#endif
-#ifndef MV_C3_ABLATE_MFMA
-#define MV_C3_ABLATE_MFMA 0  // profiling builds only (wrong results): 1 = no MFMA, 2 = no stores
-#endif
+// Plain stores: the write-only stream of this layer runs 5-10 % faster than with non-temporal stores
+// (profiles/r02_tune_conv_c3_plain_stores.log, tools/micro/store_pattern.hip).
 
 struct C3Args {
   const float* x;
@@ -228,15 +224,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c3(const C3Args A) {
     const int cu = (i & 3) + 8 * (i >> 2);
     f32x4 v = {c3_act<RELU>(acc[0][i]), c3_act<RELU>(acc[1][i]), c3_act<RELU>(acc[2][i]), c3_act<RELU>(acc[3][i])};
     f32x4* dst = reinterpret_cast<f32x4*>(simg + (size_t)cu * plane * sizeof(float) + voff);
-    if (MV_C3_ABLATE_MFMA == 2) {
-      if (v.x == 12345.678f) *dst = v;
-    } else if ((FULL || ok) && (FULLM || 32 * m + cu + 4 * hf < cout)) {
-#if MV_C3_NT
-      __builtin_nontemporal_store(v, dst);
-#else
-      *dst = v;
-#endif
-    }
+    if ((FULL || ok) && (FULLM || 32 * m + cu + 4 * hf < cout)) *dst = v;
   };
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
@@ -267,8 +255,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c3(const C3Args A) {
         const float b0 = elem(row[c3_row(k0)], a + c3_dx(k0));                                           \
         const float b1 = (k1 < kK) ? elem(row[c3_row(k1 < kK ? k1 : 0)], a + c3_dx(k1)) : 1.0f;           \
         const float bsel = hf ? b1 : b0;                                                                 \
-        if (MV_C3_ABLATE_MFMA == 1) { if (s == 0) cur[a] = zero; cur[a][s] += afr[s] * bsel; }           \
-        else cur[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(afr[s], bsel, s == 0 ? zero : cur[a], 0, 0, 0); \
+        cur[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(afr[s], bsel, s == 0 ? zero : cur[a], 0, 0, 0);      \
         if (have_prev) {                                                                                 \
           const int slot = 4 * s + a;                                                                    \
           if (slot % 3 == 2 && slot / 3 < 16) drain(prev, slot / 3, vo_prev, ok_prev);                    \

@@ -26,23 +26,6 @@
 #include "mv_act.h"
 #include "mv_conv.h"
 
-#ifndef MV_GEN_TAPREGS
-#define MV_GEN_TAPREGS 1  // A/B builds: 0 = the B operand's address add behind the MFMA on every tile shape
-#endif
-#ifndef MV_GEN_R
-#define MV_GEN_R 3  // SPEC: register sets of the loader waves = chunks of global loads in flight (A/B builds: 4..6)
-#endif
-#ifndef MV_GEN_LEAN
-#define MV_GEN_LEAN 1  // A/B builds: 0 = the loader waves stage as the general kernel does
-#endif
-#ifndef MV_GEN_DENSE
-#define MV_GEN_DENSE 1  // lean loader with buffer loads + an LDS address set per buffer, compute loop without any VALU (A/B: 0)
-#endif
-#ifndef MV_GEN_ABLATE
-#define MV_GEN_ABLATE 0  // profiling builds only (wrong results): 1 = no global loads after chunk 1, 2 = no LDS stores after
-                         // chunk 1, 3 = neither, 4 = no MFMAs (tools/ab_conv.py)
-#endif
-
 namespace mv {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -176,9 +159,10 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
   // one per buffer, and the chunk loop unrolled by two take the add away altogether -- 75 clocks per step in the compute waves --
   // but the loader wave on the same SIMD then gets too few issue slots and the workgroup waits for IT:
   // profiles/r03_trace_conv_gen.log.)
-  constexpr bool kTapRegs = (PT == 1) && SPEC && MV_GEN_TAPREGS;  // (measured 0.5-1 % slower in the 256-thread kernels of large grids)
+  constexpr bool kTapRegs = (PT == 1) && SPEC;  // (measured 0.5-1 % slower in the 256-thread kernels of large grids)
   typedef const __attribute__((address_space(3))) float lds_cf;
-  constexpr bool kDense = FAST == 2 && SPEC && (MT * PT == 1) && MV_GEN_LEAN && MV_GEN_TAPREGS && MV_GEN_DENSE;
+  // dense: the lean loader with buffer loads + an LDS address set per buffer, a compute loop without any VALU
+  constexpr bool kDense = FAST == 2 && SPEC && (MT * PT == 1);
   int baddr[kTapRegs ? kStepsPerChunk : 1];  // LDS byte address of this lane's B operand at step s, buffer 0
   int baddr1[kDense ? kStepsPerChunk : 1];   // ... buffer 1 (kDense: no add left in the loop)
   if constexpr (kTapRegs) {
@@ -204,8 +188,9 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
   constexpr int XP = kXP;   // float4 of input per thread held in registers (maps up to ~120 wide; wider: direct staging)
   constexpr int WQ = kCK * 9 / 4;                 // float4 per channel row of a weight chunk (9)
   constexpr int WU = (kBM * WQ + 255) / 256;      // float4 of weights per thread (5 for 128 channels)
-  // R register sets: chunk c's loads land in set c % R and are consumed R chunks after they were issued (SPEC: 3)
-  constexpr int R = SPEC ? (kDense ? 4 : MV_GEN_R) : 1;
+  // R register sets: chunk c's loads land in set c % R and are consumed R chunks after they were issued (SPEC: 3 = chunks of
+  // global loads in flight; 4..6 were measured too)
+  constexpr int R = SPEC ? (kDense ? 4 : 3) : 1;
   f32x4 wreg[R][WU], xreg[R][XP];
   const int nq = A.vec_rows ? (((w + 4) >> 2) + 1) : (w + 2);  // groups of 4 tile columns 4q-3 .. 4q, up to column w + 1
   const int xitems = kCK * nrows * nq;
@@ -262,7 +247,7 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
   // the barrier (tools/trace_conv_gen.py, profiles/r03_trace_conv_gen.log).  Lean staging: the loads take a wave-uniform base
   // pointer (SALU) plus a chunk-invariant 32-bit lane offset; weight rows beyond cout are loaded as they come (their output rows are
   // never stored); input items outside the image are not written at all -- their LDS cells are zeroed once, below.
-  constexpr bool kLean = FAST && SPEC && MV_GEN_LEAN;
+  constexpr bool kLean = FAST && SPEC;
   unsigned woff[WU], xoff[XP];
 #pragma unroll
   for (int u = 0; u < WU; ++u) woff[u] = wsrc[u] >= 0 ? (unsigned)(wsrc[u] * (long long)sizeof(float)) : 0u;
@@ -438,13 +423,13 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
       // vmcnt(0) -- selected through a run-time index it waited for everything, i.e. prefetched one chunk ahead, not R.
       auto step = [&](int c, auto RC) {
         MV_GEN_STAMP();  // loader +0: past the barrier
-        if (c + 1 < nch && (!(MV_GEN_ABLATE & 2) || c < 1)) {
+        if (c + 1 < nch) {
           float* xin_n = lds + ((c + 1) & 1) * bufsz + kLead;
           float* wfr_n = xin_n + kCK * A.max_rows * pitch;
           lstore(cb0 + c + 1, xin_n, wfr_n, RC);
         }
         MV_GEN_STAMP();  // loader +1: chunk c + 1 written to LDS (issued)
-        if (!(MV_GEN_ABLATE & 1) || c < 1) gload(cb0 + min(c + 1 + R, last), RC);
+        gload(cb0 + min(c + 1 + R, last), RC);
         MV_GEN_STAMP();  // loader +2: chunk c + 1 + R requested
         __syncthreads();
       };
@@ -496,8 +481,7 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
         for (int m = 0; m < MT; ++m) {
 #pragma unroll
           for (int j = 0; j < PT; ++j) {
-            if (MV_GEN_ABLATE == 4) acc[j][m][s & 15] += av_c[m] * bv_c[j];
-            else acc[j][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av_c[m], bv_c[j], acc[j][m], 0, 0, 0);
+            acc[j][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av_c[m], bv_c[j], acc[j][m], 0, 0, 0);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -552,8 +536,7 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
         }
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          if (MV_GEN_ABLATE == 4) acc[0][m][s & 15] += avr[s & 1][m] * bvr[s & 1];
-          else acc[0][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(avr[s & 1][m], bvr[s & 1], acc[0][m], 0, 0, 0);
+          acc[0][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(avr[s & 1][m], bvr[s & 1], acc[0][m], 0, 0, 0);
         }
         if (s + 1 < kStepsPerChunk) {
           fetch_a(s + 1, avr[(s + 1) & 1]);
@@ -565,8 +548,8 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
     }
     MV_GEN_STAMP();  // compute +1: the chunk's MFMAs issued
     if (!SPEC && ch + 1 < nch) {
-      if (!(MV_GEN_ABLATE & 2) || ch < 1) lstore(cb0 + ch + 1, xin_n, wfr_n, ic0{});  // the other buffer: nobody reads it during this chunk
-      if (ch + 2 < nch && (!(MV_GEN_ABLATE & 1) || ch < 1)) gload(cb0 + ch + 2, ic0{});  // in flight during the next chunk's MFMAs
+      lstore(cb0 + ch + 1, xin_n, wfr_n, ic0{});  // the other buffer: nobody reads it during this chunk
+      if (ch + 2 < nch) gload(cb0 + ch + 2, ic0{});  // in flight during the next chunk's MFMAs
     }
     __syncthreads();
   }

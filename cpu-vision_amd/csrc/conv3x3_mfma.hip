@@ -27,15 +27,7 @@
 
 namespace mv {
 
-#ifndef MV_CONV_NT
-#define MV_CONV_NT 1
-#endif
-#ifndef MV_CONV_ABLATE_STORE
-#define MV_CONV_ABLATE_STORE 0  // profiling builds only: results are wrong
-#endif
-#ifndef MV_CONV_ABLATE_MFMA
-#define MV_CONV_ABLATE_MFMA 0
-#endif
+// Output stores are non-temporal.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -176,10 +168,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
     }
   }
   __syncthreads();
-#if defined(MV_CONV_PROLOGUE_ONLY)
-  if (xin[tid] == 12345.678f) A.y[tid] = 1.f;
-  return;
-#endif
 
   const int ntiles = th * A.ntx;
   const size_t plane = (size_t)h * w;
@@ -196,13 +184,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
         for (int i = 0; i < 16; ++i) {
           const int cu = 32 * (m0 + m) + (i & 3) + 8 * (i >> 2);  // + 4*hf (in ybase): wave-uniform part
           const float v = act<RELU>(acc[m][i]);
-#if MV_CONV_ABLATE_STORE
-          if (v == 12345.678f) yo[(size_t)cu * plane] = v;
-#elif MV_CONV_NT
           if (FULLM || cu + 4 * hf < cout) __builtin_nontemporal_store(v, yo + (size_t)cu * plane);
-#else
-          if (FULLM || cu + 4 * hf < cout) yo[(size_t)cu * plane] = v;
-#endif
         }
       }
     }
@@ -213,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
     //   v_accvgpr_read + bias + ReLU + store, 2-3 values per k-step, and fetches the B fragments of tile j+1.
     // One wave therefore keeps its SIMD's matrix pipe busy by itself; without this the waves of a CU fall into
     // lockstep (all in their MFMA chains, then all in their epilogues) and chain / epilogue / stores add up
-    // instead of overlapping (measured: 0.75 ms = 0.23 + 0.29 + store tail; tools/tune_dw3x3.py --op conv).
+    // instead of overlapping (measured: 0.75 ms = 0.23 + 0.29 + store tail; profiles/r01_tune_conv_ablation_v2.log).
     static_assert(MT == 2, "pipelined path is written for two 32-channel tiles");
     float afr[MT][KS];
     int off[KS];
@@ -237,8 +219,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
     // output address = uniform base (SGPR pair) + 32-bit per-lane byte offset -> global_store ... saddr form,
     // the per-channel stride is added on the scalar unit
     char* const simg = reinterpret_cast<char*>(A.y + (size_t)img * cout * plane);
-    float sink = 0.f;  // only used by the MV_CONV_ABLATE_STORE == 3 profiling build
-    (void)sink;
     auto tile_voff = [&](int j, bool& ok) -> unsigned {
       const int t = wave + 4 * j, ly = t / A.ntx, nx = t - ly * A.ntx;
       const int px = xb + nx * 32 + l31;
@@ -253,21 +233,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
           const int cu = 32 * m + (i & 3) + 8 * (i >> 2);
           const float r = act<RELU>(acc[m][i]);
           float* dst = reinterpret_cast<float*>(simg + (size_t)cu * plane * sizeof(float) + voff);
-#if MV_CONV_ABLATE_STORE == 3
-          // no store instructions at all: fold the value into a per-lane sink (kept alive, stored once at the end)
-          sink += r;
-          (void)dst;
-#elif MV_CONV_ABLATE_STORE == 2
-          // same instruction stream, but every store lands in one L2-resident 4 MiB window
-          dst = reinterpret_cast<float*>(reinterpret_cast<char*>(A.y) + (((size_t)cu * plane * 4 + voff) & 0x3FFFFCu));
-          *dst = r;
-#elif MV_CONV_ABLATE_STORE
-          if (r == 12345.678f) *dst = r;
-#elif MV_CONV_NT
           if ((FULLW || ok) && (FULLM || cu + 4 * hf < cout)) __builtin_nontemporal_store(r, dst);
-#else
-          if ((FULLW || ok) && (FULLM || cu + 4 * hf < cout)) *dst = r;
-#endif
         }
       }
     };
@@ -314,9 +280,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
         drain(accA, vl, okl, 0, 32);
       }
 #undef MV_STAGE
-#if MV_CONV_ABLATE_STORE == 3
-      if (sink == 12345.678f) A.y[tid] = sink;
-#endif
     }
   } else {
     for (int m0 = 0; m0 < A.mtiles; m0 += MT) {

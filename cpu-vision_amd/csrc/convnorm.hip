@@ -491,10 +491,7 @@ int launch_conv3x3_smallcin(const float* x, const float* w, float* y, int64_t n,
 //   epilogue   a LANE owns one output channel and its registers 4g..4g+3 are 4 CONSECUTIVE pixels: one set of channel
 //              terms per lane, one 16-byte store per 4 outputs.  (With channels as rows every output needed its own
 //              address, predicate and 4-byte store and the epilogue cost 2.5x the matrix work.)
-#ifndef MV_PK
-#define MV_PK 32
-#endif
-constexpr int kPK = MV_PK;  // channels per K chunk (tools/tune_convnorm.py builds -DMV_PK=64 variants)
+constexpr int kPK = 32;  // channels per K chunk
 constexpr int kWP = kPK + 1;
 
 struct PwArgs {
@@ -552,9 +549,6 @@ __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& 
               const f32x4 r = *reinterpret_cast<const f32x4*>(A.e.res + row + p);
               v[0] = r.x + v[0], v[1] = r.y + v[1], v[2] = r.z + v[2], v[3] = r.w + v[3];
             }
-#ifdef MV_ABLATE_STORE
-            if (v[0] == 12345.678f)
-#endif
             *reinterpret_cast<f32x4*>(A.y + row + p) =
                 (f32x4){epi_act<ACTK>(v[0], cl), epi_act<ACTK>(v[1], cl), epi_act<ACTK>(v[2], cl), epi_act<ACTK>(v[3], cl)};
           } else {
@@ -642,11 +636,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
       const int row = idx / (PXB / 4), q = idx % (PXB / 4);
       const int k = kc + row, p = p0 + 4 * q;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#ifdef MV_ABLATE_XLOAD
-      if (k < K && HW == 12345) {
-#else
       if (k < K) {
-#endif
         const float* src = X + (size_t)k * HW + p;
         if (A.vec_x && p + 3 < HW) {
           v = *reinterpret_cast<const f32x4*>(src);
@@ -661,7 +651,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
     }
   };
   auto lstore = [&]() {
-#ifndef MV_ABLATE_WLDS
 #pragma unroll
     for (int u = 0; u < WU; ++u) {
       const int idx = tid + 256 * u;
@@ -670,7 +659,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
 #pragma unroll
       for (int i = 0; i < 4; ++i) wl[row * kWP + 4 * q + i] = e[i];
     }
-#endif
 #pragma unroll
     for (int u = 0; u < XU; ++u) {
       const int idx = tid + 256 * u;
@@ -712,11 +700,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
-#ifdef MV_ABLATE_MFMA
-            acc[t][s & 15] += wc * xc[t];
-#else
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[t], wc, acc[t], 0, 0, 0);  // rows = pixels, columns = channels
-#endif
           }
           __builtin_amdgcn_sched_barrier(0);
           if (s + 1 < kPK / 2) {
@@ -767,10 +751,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
   float* tb = xs + wave * (32 * kTP);
   const PwTile tile = {j0 + mt * 32, pw0, ntiles, img};
   const bool res = A.e.res != nullptr;
-#ifdef MV_ABLATE_EPI
-  if (acc[0][0] == 12345.678f) A.y[tid] = acc[NT - 1][15] + acc[0][3];
-  return;
-#endif
   if (A.e.act <= 2 && A.e.affine == 2 && A.e.bias == nullptr) {
     res ? pw_store<NT, 0, true, true>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, true>(acc, tile, A, tb, lane);
   } else if (A.e.act == 3) {

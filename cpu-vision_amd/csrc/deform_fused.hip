@@ -27,23 +27,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));  // dword-aligned 16-byte access
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef MV_DF_ABLATE
-// tools/ab_deform.py builds ablation variants: 1 no gather, 2 no MFMAs, 4 no W staging, 16 no window staging,
-// 32 MFMA operands read once per chunk, 64 no corner reads
-#define MV_DF_ABLATE 0
-#endif
-#ifndef MV_DF_PRIO
-#define MV_DF_PRIO 1  // 0 none, 1 consumer waves first, 2 producer waves first (0.454 / 0.452 / 0.463 ms: profiles/r02_ab_deform_roles_final.log)
-#endif
-#ifndef MV_DF_DEPTH
-#define MV_DF_DEPTH 3
-#endif
 constexpr int kFTW = 16;                 // tile width in output pixels (a 32-pixel MFMA tile = two rows of the tile)
 constexpr int kFMargin = 6;              // |offset| served from the staged window
 constexpr int kFWinU = 12;               // window floats per producer thread and chunk (registers)
 constexpr int kFWU = 10;                 // W float4 per producer thread and chunk (registers)
 constexpr int kFKMax = 40;               // K (cb * taps) per chunk at most
-constexpr int kFDepth = MV_DF_DEPTH;     // k-steps of MFMA operands in flight in a consumer wave
+constexpr int kFDepth = 3;               // k-steps of MFMA operands in flight in a consumer wave
 constexpr int kFTP = 36;                 // transpose buffer pitch of the epilogue
 
 // tile geometry per MW = 32-channel tiles of a workgroup: pixels, (channel, pixel) tiles per consumer wave
@@ -312,13 +301,6 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
     auto tap_read = [&](const float* win, int mi, TapRead& r) {
       r.P = par[mi * PX + pt];
       const float* q = win + max(__float_as_int(r.P.w), 0) * cb;
-#if MV_DF_ABLATE & 64
-      if (CB == 4) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) r.v[0][c] = r.P.x, r.v[1][c] = r.P.y, r.v[2][c] = r.P.z, r.v[3][c] = r.P.x + c;
-        return;
-      }
-#endif
       if (CB == 4) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(q), bq = *reinterpret_cast<const f32x4*>(q + 4);
         const f32x4 c2 = *reinterpret_cast<const f32x4*>(q + wp * 4), d = *reinterpret_cast<const f32x4*>(q + wp * 4 + 4);
@@ -403,9 +385,6 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
     int cur_og = uni((g * cg) / cog), og_left = chunks_per_og - uni(((g * cg) % cog) / cb);
 
     if (KCP > KC && tid < PX) xs0[KC * XP + tid] = 0.f, xs0[xs_sz + KC * XP + tid] = 0.f;  // pad row of an odd chunk
-#if MV_DF_PRIO == 2
-    __builtin_amdgcn_s_setprio(2);
-#endif
     compute_params(cur_og);
     gload_window(0);
     gload_weights(0);
@@ -426,32 +405,22 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
       if (it + 1 < chunks) {
         if (--og_left == 0) og_left = chunks_per_og, compute_params(++cur_og);
         const int og = cur_og;
-#if !(MV_DF_ABLATE & 1)
         gather_reads(it + 1);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         MV_DF_STAMP(it, 1);
-#if !(MV_DF_ABLATE & 16)
         if (it + 2 < chunks) gload_window(it + 2);
         __builtin_amdgcn_sched_barrier(0);
-#endif
-#if !(MV_DF_ABLATE & 4)
         store_weights((it + 1) & 1);
         __builtin_amdgcn_sched_barrier(0);
         if (it + 2 < chunks) gload_weights(it + 2);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         MV_DF_STAMP(it, 2);
-#if !(MV_DF_ABLATE & 16)
         // (its buffer was last read by gather(it), before the barrier that opened this iteration; the corner reads above use the
         // other one)
         if (it + 2 < chunks) store_window(it & 1);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         MV_DF_STAMP(it, 5);
-#if !(MV_DF_ABLATE & 1)
         gather_writes(it + 1, og);
-#endif
         MV_DF_STAMP(it, 6);
       }
       __syncthreads();
@@ -474,16 +443,11 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
   __syncthreads();
   __syncthreads();
   __syncthreads();  // chunk 0 ready
-#if MV_DF_PRIO == 1
+  // consumer waves first (none / consumers / producers first: 0.454 / 0.452 / 0.463 ms, profiles/r02_ab_deform_roles_final.log)
   __builtin_amdgcn_s_setprio(2);
-#endif
   for (int it = 0; it < chunks; ++it) {
     MV_DF_STAMP(it, 0);
-#if MV_DF_ABLATE & 2
-    if (A.act == 77) {
-#else
     if (live) {
-#endif
       const float* wpnt = wl0 + (it & 1) * wl_sz + (mt0 * 32 + l31) * WP + hf;        // W[channel l31 of tile m][2s + hf]
       const float* xpnt = xs0 + (it & 1) * xs_sz + hf * XP + pg * (PT * 32) + l31;    // columns[2s + hf][pixel l31 of tile t]
       if (KCT) {
@@ -498,11 +462,6 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
 #pragma unroll
           for (int t = 0; t < PT; ++t) xq[d][t] = xpnt[2 * d * XP + t * 32];
         }
-#if MV_DF_ABLATE & 32
-#define MV_DF_OPERANDS(s) false
-#else
-#define MV_DF_OPERANDS(s) ((s) + D < KS)
-#endif
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
           float wc[MT], xc[PT];
@@ -510,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
           for (int m = 0; m < MT; ++m) wc[m] = wq[s % D][m];
 #pragma unroll
           for (int t = 0; t < PT; ++t) xc[t] = xq[s % D][t];
-          if (MV_DF_OPERANDS(s)) {
+          if (s + D < KS) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) wq[s % D][m] = wpnt[m * 32 * WP + 2 * (s + D)];
 #pragma unroll

@@ -49,30 +49,9 @@ struct Dw3x3Args {
   FramePtrs fp;  // mv_*_v: per-frame base pointers for x / y0 (n == 0: contiguous batch; never with a second output)
 };
 
-// Tuning knobs (compile-time; tools/tune_dw3x3.py builds variants with -D and A/Bs them in one process).
-#ifndef MV_DW3X3_GROUP
-#define MV_DW3X3_GROUP 4  // rows prefetched ahead of the arithmetic
-#endif
-#ifndef MV_DW3X3_NT_STORE
-#define MV_DW3X3_NT_STORE 1  // outputs are never re-read: keep them out of L2 so halo rows stay
-#endif
-#ifndef MV_DW3X3_NT_LOAD
-#define MV_DW3X3_NT_LOAD 0
-#endif
-#ifndef MV_DW3X3_XCD
-#define MV_DW3X3_XCD 1  // XCD-contiguous work map
-#endif
-// Ablation switches for profiling builds only (results are WRONG when set): tools/tune_dw3x3.py.
-#ifndef MV_ABLATE_HALO
-#define MV_ABLATE_HALO 0
-#endif
-#ifndef MV_ABLATE_SHFL
-#define MV_ABLATE_SHFL 0
-#endif
-#ifndef MV_ABLATE_MATH
-#define MV_ABLATE_MATH 0
-#endif
-constexpr int kGroup = MV_DW3X3_GROUP;
+// Output stores are non-temporal: outputs are never re-read, so keeping them out of L2 leaves it to the halo rows.
+// The work map is XCD-contiguous.
+constexpr int kGroup = 4;  // rows prefetched ahead of the arithmetic
 
 struct Row {
   float l, a, b, c, d, r;  // columns x-1, x .. x+3, x+4
@@ -100,11 +79,7 @@ __device__ inline Raw load_raw(const T* rowp, int xs, int w, int lane, int lpr =
   if (VEC) {
     if (xs < w) {
       if constexpr (sizeof(T) == 4) {
-#if MV_DW3X3_NT_LOAD
-        f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(rowp + xs));
-#else
         f4 v = *reinterpret_cast<const f4*>(rowp + xs);
-#endif
         q.a = v.x, q.b = v.y, q.c = v.z, q.d = v.w;
       } else {
         u8x4 v = *reinterpret_cast<const u8x4*>(rowp + xs);
@@ -126,9 +101,7 @@ __device__ inline Raw load_raw(const T* rowp, int xs, int w, int lane, int lpr =
   }
   int hx = (lane == 0) ? xs - 1 : xs + 4;
   bool hl = (lane == 0 && xs > 0) || (lane == lpr - 1 && xs + 4 < w);
-#if !MV_ABLATE_HALO
   if (hl) q.h = ldf(rowp + hx);
-#endif
   return q;
 }
 
@@ -137,12 +110,8 @@ template <int BORDER>
 __device__ inline Row finalize(const Raw& q, int xs, int w, int lane, int lpr = kWave) {
   Row r;
   r.a = q.a, r.b = q.b, r.c = q.c, r.d = q.d;
-#if MV_ABLATE_SHFL
-  float up = q.d, dn = q.a;
-#else
   float up = __shfl_up(q.d, 1);    // lane-1's x+3  -> my x-1
   float dn = __shfl_down(q.a, 1);  // lane+1's x    -> my x+4
-#endif
   r.l = (lane == 0) ? q.h : up;
   r.r = (lane == lpr - 1) ? q.h : dn;
   if (BORDER == MV_BORDER_REFLECT) {
@@ -174,10 +143,6 @@ __device__ inline float tap9(const float (&w)[9], float p0, float p1, float p2, 
 }
 
 __device__ inline void conv_row(const float (&w)[9], const Row& t, const Row& m, const Row& b, float (&o)[4]) {
-#if MV_ABLATE_MATH
-  o[0] = m.a + t.l + b.r, o[1] = m.b, o[2] = m.c, o[3] = m.d + w[0];
-  return;
-#endif
   o[0] = tap9(w, t.l, t.a, t.b, m.l, m.a, m.b, b.l, b.a, b.b);
   o[1] = tap9(w, t.a, t.b, t.c, m.a, m.b, m.c, b.a, b.b, b.c);
   o[2] = tap9(w, t.b, t.c, t.d, m.b, m.c, m.d, b.b, b.c, b.d);
@@ -192,11 +157,7 @@ __device__ inline void store4(T* rowp, int xs, int w, const float (&o)[4]) {
     if (xs < w) {
       if constexpr (sizeof(T) == 4) {
         f4 v = {o[0], o[1], o[2], o[3]};
-#if MV_DW3X3_NT_STORE
         __builtin_nontemporal_store(v, reinterpret_cast<f4*>(rowp + xs));
-#else
-        *reinterpret_cast<f4*>(rowp + xs) = v;
-#endif
       } else {
         u8x4 v = {(unsigned char)(int)o[0], (unsigned char)(int)o[1], (unsigned char)(int)o[2],
                   (unsigned char)(int)o[3]};
@@ -227,11 +188,7 @@ template <typename T, int BORDER, int EPI, bool VEC, bool MULTI>
 __global__ __launch_bounds__(256) void k_dw3x3(const Dw3x3Args A) {
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;
-#if MV_DW3X3_XCD
   const long long item = (long long)xcd_remap(blockIdx.x, A.nblocks) * 4 + wave;
-#else
-  const long long item = (long long)blockIdx.x * 4 + wave;
-#endif
   if (item >= A.nitems) return;  // whole wave leaves: no barriers in this kernel
   const int seg = (int)(item % A.col_segs);
   const long long t = item / A.col_segs;
@@ -337,7 +294,7 @@ static int env_int(const char* name, int dflt) {
 static void plan(Dw3x3Args& a, int64_t planes, int h, int w) {
   a.h = h, a.w = w;
   a.col_segs = (w + 255) / 256;
-  // Strip height.  Measured on MI355X (tools/tune_dw3x3.py, 64 x 4K frames, interleaved rounds): 8 rows per
+  // Strip height.  Measured on MI355X (profiles/r01_tune_dw3x3_*.log, 64 x 4K frames, interleaved rounds): 8 rows per
   // strip (two prefetch groups) is the fastest -- 6.15 TB/s vs 5.6 at 16 rows and 5.1 at 64 -- because many
   // short waves keep the concurrently running blocks on adjacent addresses (whole row bands), and the two halo
   // rows a strip shares with its neighbours are then served by L2 instead of HBM.

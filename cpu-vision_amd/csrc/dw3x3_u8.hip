@@ -42,10 +42,8 @@ struct Dw3x3U8Args {
   FramePtrs fp;      // mv_*_v: per-frame base pointers (n == 0: contiguous batch)
 };
 
-#ifndef MV_U8_GROUP
-#define MV_U8_GROUP 3  // 3 rows: 91 VGPRs = 5 waves per SIMD (4: 112 VGPRs); A/B in tools/ab_libs.py: 2-4 % faster
-#endif
-constexpr int kU8Group = MV_U8_GROUP;  // raw rows in flight per wave
+// 3 rows: 91 VGPRs = 5 waves per SIMD (4: 112 VGPRs); A/B in tools/ab_libs.py: 2-4 % faster
+constexpr int kU8Group = 3;  // raw rows in flight per wave
 
 struct RawU8 {
   u32x4 v;                // 16 pixels

@@ -33,11 +33,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32b __attribute__((aligned(1)));
-#ifdef MV_DWK_ALIGNED_TYPES  // A/B only: aligned 16-byte types (valid for W % 16 == 0)
-typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
-#else
 typedef unsigned int u32x4b __attribute__((ext_vector_type(4), aligned(1)));  // 16-byte access at any byte address
-#endif
 
 constexpr int kSepY = 9;  // where the column taps of the separable form start in DwkU8Args::w (sides up to 9)
 
@@ -56,16 +52,7 @@ struct DwkU8Args {
   float tie_thresh;
 };
 
-#ifndef MV_DWK_PF
-#define MV_DWK_PF 3
-#endif
-#ifndef MV_DWK_MINWAVES
-#define MV_DWK_MINWAVES 1
-#endif
-#ifndef MV_DWK_MINWAVES_SEP7
-#define MV_DWK_MINWAVES_SEP7 3  // 7x7 separable: 166 VGPRs instead of 178 = 3 waves per SIMD, no spills (0.424 -> 0.413 ms)
-#endif
-constexpr int kDwkPF = MV_DWK_PF;  // raw rows in flight per wave
+constexpr int kDwkPF = 3;  // raw rows in flight per wave
 
 struct RawRow {
   u32x4 v;         // 16 pixels
@@ -129,11 +116,7 @@ __device__ inline unsigned dwk_border_px(const uint8_t* rowp, int c, int w, bool
 __device__ inline RawRow dwk_load(const uint8_t* rowp, const DwkRole& L, bool zero) {
   RawRow q;
   const u32x4b t = *reinterpret_cast<const u32x4b*>(rowp + L.xs);
-#if MV_DWK_ABLATE == 3
-  const unsigned hv = 0u;
-#else
   const unsigned hv = *reinterpret_cast<const u32b*>(rowp + L.hofs);
-#endif
   q.v = zero ? (u32x4){0u, 0u, 0u, 0u} : (u32x4){t.x, t.y, t.z, t.w};
   q.halo = zero ? 0u : hv;
   return q;
@@ -171,21 +154,8 @@ __device__ inline void dwk_window(const RawRow& q, const DwkRole& L, const uint8
   }
 }
 
-#ifndef MV_DWK_NT
-#define MV_DWK_NT 1
-#endif
-#ifndef MV_DWK_TIE_ABLATE
-#define MV_DWK_TIE_ABLATE 0
-#endif
-#ifndef MV_DWK_ABLATE
-#define MV_DWK_ABLATE 0  // profiling builds only (wrong results): 1 = no stores, 2 = no arithmetic (copy with the same
-#endif                   // memory pattern), 3 = no halo load
 __device__ inline void dwk_store(u32x4b v, u32x4b* p) {
-#if MV_DWK_NT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 template <typename F, int... I>
@@ -198,9 +168,10 @@ __device__ inline void dwk_static_for(F&& f) {
 }
 
 // MULTI: several strips per wave (images up to 512 pixels wide); otherwise the strip -- and with it every row address -- is
-// wave-uniform and stays in scalar registers
+// wave-uniform and stays in scalar registers.  Waves per SIMD: 7x7 separable 3 (166 VGPRs instead of 178, no spills:
+// 0.424 -> 0.413 ms), nine column taps 2.
 template <int KY, int KX, int BORDER, bool MULTI, bool SEP, bool BYTES, bool TIES = false>
-__global__ __launch_bounds__(256, (SEP && KY == 7 && MV_DWK_MINWAVES < MV_DWK_MINWAVES_SEP7) ? MV_DWK_MINWAVES_SEP7 : ((SEP && KY == 9 && MV_DWK_MINWAVES < 2) ? 2 : MV_DWK_MINWAVES)) void k_dwk_u8(const DwkU8Args A) {
+__global__ __launch_bounds__(256, (SEP && KY == 7) ? 3 : ((SEP && KY == 9) ? 2 : 1)) void k_dwk_u8(const DwkU8Args A) {
   constexpr int RY = KY / 2, RX = KX / 2;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -251,12 +222,6 @@ __global__ __launch_bounds__(256, (SEP && KY == 7 && MV_DWK_MINWAVES < MV_DWK_MI
     // last stage first: output row t - RY receives kernel row KY-1
     unsigned out[4] = {0u, 0u, 0u, 0u};
     if constexpr (SEP) {
-#if MV_DWK_ABLATE == 2
-      out[0] = raw.v.x, out[1] = raw.v.y, out[2] = raw.v.z, out[3] = raw.v.w ^ raw.halo;
-      if (t - t_first >= KY - 1 && t <= t_last && L.valid)
-        dwk_store((u32x4b){out[0], out[1], out[2], out[3]}, reinterpret_cast<u32x4b*>(yp + (size_t)(t - RY) * w + xs));
-      return;
-#endif
       float tie_far = 0.f, tie_even = 0.f;  // TIES: the largest |blur - rint(blur)| of the lane's 16 pixels (0.5 = exactly on a tie)
 #pragma unroll
       for (int p = 0; p < 16; ++p) {
@@ -288,21 +253,13 @@ __global__ __launch_bounds__(256, (SEP && KY == 7 && MV_DWK_MINWAVES < MV_DWK_MI
           acc[0][p] = fmaf(A.w[kSepY], tmp, 0.f);
         }
       }
-#if MV_DWK_ABLATE == 1
-      if (t - t_first >= KY - 1 && t <= t_last && L.valid && out[0] == 0x12345678u && out[3] == 0x9abcdef0u)
-#else
       if (t - t_first >= KY - 1 && t <= t_last && L.valid)
-#endif
         dwk_store((u32x4b){out[0], out[1], out[2], out[3]}, reinterpret_cast<u32x4b*>(yp + (size_t)(t - RY) * w + xs));
       if constexpr (TIES) {
         // a lane-row that holds a value within the separable-vs-2-D error bound of a rounding tie: k_u8_tie_fixup recomputes its
         // 16 pixels with the reference's 2-D chain (mv_common.h: TieList).  Rows outside the strip are never flagged.
         const bool stored = t - t_first >= KY - 1 && t <= t_last && L.valid;
-#if MV_DWK_TIE_ABLATE == 1  // profiling builds only (wrong results): the flag is computed and dropped
-        if (stored && tie_far > A.tie_thresh && xs == 0x7fffffff) tie_push(tw, true, 0ull, lane);
-#else
         tie_push(tw, stored && tie_far > A.tie_thresh, ((unsigned long long)plane * h + (unsigned)(t - RY)) * w + xs, lane);
-#endif
       }
       return;
     }
@@ -454,10 +411,7 @@ int launch_sep_u8x16(const uint8_t* x, uint8_t* y, const float* k1d_x, const flo
   fill_frames(a.fp);
   for (int i = 0; i < kx; ++i) a.w[i] = k1d_x[i];
   for (int j = 0; j < ky; ++j) a.w[kSepY + j] = k1d_y[j];
-#ifndef MV_SEPU8_ROWS
-#define MV_SEPU8_ROWS 64
-#endif
-  int rows = MV_SEPU8_ROWS;
+  int rows = 64;
   if (ky >= 7 || kx >= 7) {
     // the 7-tap instantiations hold 3 waves per SIMD = 3 workgroups per CU: with so few in flight a partial last round of
     // workgroups shows (32 x 4K: 64-row strips = 4.25 rounds; 90-row strips = 3.0 rounds, 0.394 -> 0.371 ms).  Pick the strip

@@ -13,8 +13,6 @@
 //      outer product k1d_y[j]*k1d_x[i] -- bit-identical to _misc.py:97) and, for the templated
 //      sizes, are hoisted to registers.
 // The fma chain per output is the oracle's (dy outer, dx inner, from +0): bit-identical results.
-#include <cstdlib>
-
 #include "mv_common.h"
 
 namespace mv {
@@ -27,10 +25,7 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef unsigned char u8x4u __attribute__((ext_vector_type(4), aligned(1)));
 
 constexpr int kTileW = 256;
-#ifndef MV_TILE_RPT
-#define MV_TILE_RPT 4  // output rows per lane for the templated sizes (tile height = 4 * RPT)
-#endif
-constexpr int kRptSized = MV_TILE_RPT;
+constexpr int kRptSized = 4;  // output rows per lane for the templated sizes (tile height = 4 * RPT)
 
 enum { TAPS_BY_VALUE = 0, TAPS_DEVICE = 1, TAPS_OUTER = 2 };
 
@@ -347,14 +342,9 @@ static int launch_sized(const TileArgs& a, bool vec, size_t lds_bytes, hipStream
                        RPT, vec ? "vec16" : "scalar", TW);
 }
 
-// TW / RPT: 256 / (4 sized, 8 run-time sizes) for images; 128 / 4, 64 / 2, 32 / 1 (all 32 rows high) for fp32 images at most
-// that wide
-template <typename T, int TW, int RPTS, int RPTG>
-static int launch_tw(TileArgs& a, int64_t planes, bool vec, hipStream_t s) {
+// The tile grid of a TW x ((1024 / TW) * rpt) tile, and the LDS it stages
+static int tile_grid(TileArgs& a, int64_t planes, int TW, int rpt, size_t* lds_out) {
   const int ky = a.ky, kx = a.kx;
-  const bool sized = (ky == 3 && kx == 3) || (ky == 5 && kx == 5) || (ky == 7 && kx == 7) || (ky == 5 && kx == 3) ||
-                     (ky == 3 && kx == 5) || (ky == 9 && kx == 9) || (ky == 11 && kx == 11);
-  const int rpt = sized ? RPTS : RPTG;
   const int th = (1024 / TW) * rpt;
   const int L = ((kx / 2) + 3) & ~3;
   const int pitch = L + TW + L;
@@ -365,6 +355,19 @@ static int launch_tw(TileArgs& a, int64_t planes, bool vec, hipStream_t s) {
   const long long nb = (long long)planes * a.tiles_x * a.tiles_y;
   if (nb > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "dwtile: batch too large for one launch");
   a.nblocks = (unsigned)nb;
+  *lds_out = lds_bytes;
+  return MV_OK;
+}
+
+// TW / RPT: 256 / (4 sized, 8 run-time sizes) for images; 128 / 4, 64 / 2, 32 / 1 (all 32 rows high) for fp32 images at most
+// that wide
+template <typename T, int TW, int RPTS, int RPTG>
+static int launch_tw(TileArgs& a, int64_t planes, bool vec, hipStream_t s) {
+  const int ky = a.ky, kx = a.kx;
+  const bool sized = (ky == 3 && kx == 3) || (ky == 5 && kx == 5) || (ky == 7 && kx == 7) || (ky == 5 && kx == 3) ||
+                     (ky == 3 && kx == 5) || (ky == 9 && kx == 9) || (ky == 11 && kx == 11);
+  size_t lds_bytes;
+  if (const int e = tile_grid(a, planes, TW, sized ? RPTS : RPTG, &lds_bytes)) return e;
   if (ky == 3 && kx == 3) return launch_sized<T, 3, 3, RPTS, TW>(a, vec, lds_bytes, s);
   if (ky == 5 && kx == 5) return launch_sized<T, 5, 5, RPTS, TW>(a, vec, lds_bytes, s);
   if (ky == 7 && kx == 7) return launch_sized<T, 7, 7, RPTS, TW>(a, vec, lds_bytes, s);
@@ -384,16 +387,13 @@ static int launch_typed(TileArgs& a, int64_t planes, bool vec, hipStream_t s) {
     if (a.w <= 128) return launch_tw<T, 128, 4, 4>(a, planes, vec, s);
   }
   if constexpr (sizeof(T) == 4) {
-    // tuning knob (tools/perf_single_frame.py): tile height of the templated sizes, 8 / 16 (default) / 32 rows
-    if (const char* e = tune_env("MV_TILE_RPT_SIZED")) {
-      if (atoi(e) == 2) return launch_tw<T, kTileW, 2, 8>(a, planes, vec, s);
-      if (atoi(e) == 8) return launch_tw<T, kTileW, 8, 8>(a, planes, vec, s);
-      if (atoi(e) == 4) return launch_tw<T, kTileW, 4, 8>(a, planes, vec, s);
-    }
     // one or a few frames per launch: 8-row tiles double the workgroups in flight (single 720p frame 8.8 -> 7.3 us, single
     // 4K frame 42.1 -> 40.5 us, 1080p unchanged at 13.6; profiles/r01_perf_single_frame.log); batches keep 16 rows
-    if (a.ky == 3 && a.kx == 3 && planes * ((a.w + kTileW - 1) / kTileW) * ((a.h + 15) / 16) < 8192)
-      return launch_tw<T, kTileW, 2, 8>(a, planes, vec, s);
+    if (a.ky == 3 && a.kx == 3 && planes * ((a.w + kTileW - 1) / kTileW) * ((a.h + 15) / 16) < 8192) {
+      size_t lds_bytes;
+      if (const int e = tile_grid(a, planes, kTileW, 2, &lds_bytes)) return e;
+      return launch_sized<T, 3, 3, 2, kTileW>(a, vec, lds_bytes, s);
+    }
   }
   return launch_tw<T, kTileW, kRptSized, 8>(a, planes, vec, s);
 }

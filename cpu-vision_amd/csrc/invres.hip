@@ -878,11 +878,9 @@ static int pitch_b128(int v) {  // a multiple of 4 whose quarter is odd: 8 lanes
   return (v / 4) % 2 ? v : v + 4;
 }
 
-// waves per workgroup of k_invres for a block shape (tuning build: MV_IR_WAVES forces 4 or 8)
-static int ir_waves(int w, int stride, int cin, int cout) {
-  if (const char* e = tune_env("MV_IR_WAVES")) return atoi(e) == 8 ? 8 : 4;
-  (void)cin, (void)cout;
-  // tools/sweep_ir_waves.py (profiles/r03_sweep_ir_waves.log): 8 waves are 4-9 % ahead on the 28-pixel blocks and the stride-1
+// waves per workgroup of k_invres for a block shape
+static constexpr int ir_waves(int w, int stride) {
+  // 4 against 8 waves, interleaved (profiles/r03_sweep_ir_waves.log): 8 waves are 4-9 % ahead on the 28-pixel blocks and the stride-1
   // 14-pixel ones (batch 1 and 64 alike), level on 14 -> 7, 10-20 % behind on the 7 x 7 blocks (4 tiles of 98 pixels for 8 waves)
   return (w == 28 || (w == 14 && stride == 1)) ? 8 : 4;
 }
@@ -918,7 +916,7 @@ static IrGeom ir_geometry(int64_t n, int cin, int hidden, int cout, int h, int w
   const int w1p = (cin / 4) % 2 ? cin : cin + 4;
   g.hp = pitch_b128(32 * ((g.npin_max + 31) / 32));  // whole 32-pixel tiles: phase 1 stores a tile's rows without per-pixel bounds
   int off = round4(kHC * w1p);
-  const int tbuf = ir_waves(w, stride, cin, cout) * 32 * 36;  // the epilogue's per-wave transpose buffers live in the dead hidden tile
+  const int tbuf = ir_waves(w, stride) * 32 * 36;  // the epilogue's per-wave transpose buffers live in the dead hidden tile
   g.off_hid = off, off += kHC * g.hp > tbuf ? kHC * g.hp : tbuf;
   g.off_dws = off, off += 32 * g.ptout * 36;
   g.off_w2 = off, off += cout * 36;
@@ -928,25 +926,13 @@ static IrGeom ir_geometry(int64_t n, int cin, int hidden, int cout, int h, int w
   return g;
 }
 
-// wide maps (k_invres_wide): output rows per region by (map side, stride)
-// (output rows per region, waves per workgroup, waves per SIMD the registers are bounded for): the variants built per block shape;
-// index 0 is the product's choice, the others are reachable through MV_IRW_VARIANT in the tuning build (tools/perf_invres.py)
+// wide maps (k_invres_wide): (output rows per region, waves per workgroup, waves per SIMD the registers are bounded for) by
+// (map side, stride): the fastest of the variants swept in profiles/r03_sweep_irw.log
 struct IrwVariant { int orows, waves, occ; };
-static const IrwVariant kIrw112[] = {{2, 8, 2}, {1, 4, 2}, {1, 8, 2}, {2, 4, 1}, {2, 16, 4}};
-static const IrwVariant kIrw56s1[] = {{7, 8, 2}, {2, 4, 2}, {2, 8, 2}, {4, 8, 2}, {4, 4, 1}, {7, 16, 4}};
-static const IrwVariant kIrw56s2[] = {{4, 8, 2}, {2, 4, 2}, {2, 8, 2}, {2, 4, 1}, {1, 4, 2}, {7, 8, 2}, {7, 16, 4}};
-static int irw_variant_index(int count) {
-  const char* e = tune_env("MV_IRW_VARIANT");
-  const int v = (e && *e) ? atoi(e) : 0;
-  return v >= 0 && v < count ? v : 0;
+static constexpr IrwVariant irw_variant(int w, int stride) {
+  if (w == 112) return stride == 1 ? IrwVariant{4, 8, 2} : IrwVariant{2, 8, 2};
+  return stride == 1 ? IrwVariant{7, 8, 2} : IrwVariant{4, 8, 2};
 }
-static const IrwVariant kIrw112s1[] = {{4, 8, 2}, {2, 8, 2}, {4, 16, 4}, {2, 4, 2}};
-static IrwVariant irw_variant(int w, int stride) {
-  if (w == 112 && stride == 1) return kIrw112s1[irw_variant_index(4)];
-  if (w == 112) return kIrw112[irw_variant_index(5)];
-  return stride == 1 ? kIrw56s1[irw_variant_index(6)] : kIrw56s2[irw_variant_index(7)];
-}
-static int irw_orows(int w, int stride) { return irw_variant(w, stride).orows; }
 
 static bool irw_shape(int cin, int hidden, int cout, int h, int w, int stride) {
   if (h != w || hidden < 32 || hidden % 8 || cout < 1 || cout > 32) return false;
@@ -960,14 +946,14 @@ static IrGeom irw_geometry(int64_t n, int cin, int hidden, int cout, int h, int 
   IrGeom g = {};
   if (n <= 0 || (stride != 1 && stride != 2) || !irw_shape(cin, hidden, cout, h, w, stride)) return g;
   const int ow = w / stride;
-  g.imgs = 1, g.orows = irw_orows(w, stride), g.strips = ow / g.orows;
+  const IrwVariant var = irw_variant(w, stride);
+  g.imgs = 1, g.orows = var.orows, g.strips = ow / g.orows;
   g.rh_max = (g.orows - 1) * stride + 3;
   g.npin_max = g.rh_max * w;
   g.npout_max = g.orows * ow;
   g.ptout = (g.npout_max + 31) / 32;
   const int w1p = (cin / 4) % 2 ? cin : cin + 4;
   g.hp = pitch_b128(32 * ((g.npin_max + 31) / 32));  // (hidden == cin: the flat copy of the input rows needs rh_max * w <= hp, the same bound)
-  const IrwVariant var = irw_variant(w, stride);
   const int tbuf = var.waves * 32 * 36;  // the epilogue's per-wave transpose buffers live in the dead hidden tile
   int off = hidden == cin ? 0 : round4(kHC * w1p);  // no expansion: no expand weights
   g.off_hid = off, off += kHC * g.hp > tbuf ? kHC * g.hp : tbuf;
@@ -991,9 +977,11 @@ static IrGeom irw_geometry(int64_t n, int cin, int hidden, int cout, int h, int 
   return g;
 }
 
-template <int W, int STRIDE, int ORH, int CIN, int NW, int OCC, bool EXPAND = true>
+template <int W, int STRIDE, int CIN, bool EXPAND = true>
 static int irw_launch(const IrArgs& a, const IrGeom& g, unsigned regions, hipStream_t s) {
-  auto kern = k_invres_wide<W, STRIDE, ORH, CIN, NW, OCC, EXPAND>;
+  constexpr IrwVariant V = irw_variant(W, STRIDE);
+  constexpr int ORH = V.orows, NW = V.waves;
+  auto kern = k_invres_wide<W, STRIDE, ORH, CIN, NW, V.occ, EXPAND>;
   static int lds_limit = 0;  // per instantiation; raised once (a benign race: two first callers set the same value)
   if (lds_limit < (int)g.lds_bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes);
@@ -1010,8 +998,9 @@ static int irw_launch(const IrArgs& a, const IrGeom& g, unsigned regions, hipStr
   return check_launchf("k_invres_wide<%d,s%d,rows%d,cin%d,waves%d,slices%d>%s", W, STRIDE, ORH, CIN, NW, g.slices, EXPAND ? "" : " (no expansion)");
 }
 
-template <int W, int STRIDE, int PTOUT, int COT, int CINQ, int NW>
-static int ir_launch_nw(const IrArgs& a, const IrGeom& g, unsigned regions, hipStream_t s) {
+template <int W, int STRIDE, int PTOUT, int COT, int CINQ>
+static int ir_launch(const IrArgs& a, const IrGeom& g, unsigned regions, hipStream_t s) {
+  constexpr int NW = ir_waves(W, STRIDE);
   auto kern = k_invres<W, STRIDE, PTOUT, COT, CINQ, NW>;
   static int lds_limit = 0;  // per instantiation; raised once (a benign race: two first callers set the same value)
   if (lds_limit < (int)g.lds_bytes) {
@@ -1020,11 +1009,6 @@ static int ir_launch_nw(const IrArgs& a, const IrGeom& g, unsigned regions, hipS
   }
   hipLaunchKernelGGL(kern, dim3(regions, (unsigned)g.slices), dim3(64 * NW), g.lds_bytes, s, a);
   return check_launchf("k_invres<%d,s%d,cin%d,cout%d,slices%d>%s", W, STRIDE, 32 * CINQ, 32 * COT, g.slices, NW == 8 ? " (8 waves)" : "");
-}
-template <int W, int STRIDE, int PTOUT, int COT, int CINQ>
-static int ir_launch(const IrArgs& a, const IrGeom& g, unsigned regions, hipStream_t s) {
-  if (ir_waves(W, STRIDE, 32 * CINQ, 32 * COT) == 8) return ir_launch_nw<W, STRIDE, PTOUT, COT, CINQ, 8>(a, g, regions, s);
-  return ir_launch_nw<W, STRIDE, PTOUT, COT, CINQ, 4>(a, g, regions, s);
 }
 
 // the instantiations: MobileNetV2's blocks on 28 / 14 / 7-pixel maps (width multiplier 1.0, 224 x 224 input)
@@ -1091,22 +1075,10 @@ int launch_invres(const float* x, const float* w1, const float* a1, const float*
   a.hp = g.hp, a.off_hid = g.off_hid, a.off_dws = g.off_dws, a.off_w2 = g.off_w2, a.off_terms = g.off_terms;
   int rc = MV_ERR_UNSUPPORTED;
   const unsigned r = (unsigned)regions;
-  if (wide) {
-    const IrwVariant v = irw_variant(w, stride);
-#define MV_IRW_CASE(W_, S_, CIN_, R_, NW_, OCC_) \
-    if (w == W_ && stride == S_ && v.orows == R_ && v.waves == NW_ && v.occ == OCC_) rc = irw_launch<W_, S_, R_, CIN_, NW_, OCC_>(a, g, r, s)
-    MV_IRW_CASE(112, 2, 16, 2, 4, 1); MV_IRW_CASE(112, 2, 16, 1, 4, 2); MV_IRW_CASE(112, 2, 16, 1, 8, 2); MV_IRW_CASE(112, 2, 16, 2, 8, 2);
-    if (w == 112 && stride == 1) {
-      if (v.orows == 4 && v.waves == 8) rc = irw_launch<112, 1, 4, 32, 8, 2, false>(a, g, r, s);
-      else if (v.orows == 2 && v.waves == 8) rc = irw_launch<112, 1, 2, 32, 8, 2, false>(a, g, r, s);
-      else if (v.orows == 4) rc = irw_launch<112, 1, 4, 32, 16, 4, false>(a, g, r, s);
-      else rc = irw_launch<112, 1, 2, 32, 4, 2, false>(a, g, r, s);
-    }
-    MV_IRW_CASE(112, 2, 16, 2, 16, 4); MV_IRW_CASE(56, 1, 24, 7, 16, 4); MV_IRW_CASE(56, 2, 24, 7, 8, 2); MV_IRW_CASE(56, 2, 24, 7, 16, 4);
-    MV_IRW_CASE(56, 1, 24, 4, 4, 1); MV_IRW_CASE(56, 1, 24, 2, 4, 2); MV_IRW_CASE(56, 1, 24, 2, 8, 2); MV_IRW_CASE(56, 1, 24, 4, 8, 2); MV_IRW_CASE(56, 1, 24, 7, 8, 2);
-    MV_IRW_CASE(56, 2, 24, 2, 4, 1); MV_IRW_CASE(56, 2, 24, 2, 4, 2); MV_IRW_CASE(56, 2, 24, 2, 8, 2); MV_IRW_CASE(56, 2, 24, 4, 8, 2); MV_IRW_CASE(56, 2, 24, 1, 4, 2);
-#undef MV_IRW_CASE
-  }
+  if (wide && w == 112 && stride == 1) rc = irw_launch<112, 1, 32, false>(a, g, r, s);  // (irw_shape: cin == hidden == 32)
+  else if (wide && w == 112) rc = irw_launch<112, 2, 16>(a, g, r, s);
+  else if (wide && stride == 1) rc = irw_launch<56, 1, 24>(a, g, r, s);
+  else if (wide) rc = irw_launch<56, 2, 24>(a, g, r, s);
   else if (w == 28 && stride == 1) rc = ir_launch<28, 1, 7, 1, 1>(a, g, r, s);
   else if (w == 28) rc = ir_launch<28, 2, 4, 2, 1>(a, g, r, s);
   else if (w == 14 && stride == 1 && cin == 64 && cout == 64) rc = ir_launch<14, 1, 7, 2, 2>(a, g, r, s);

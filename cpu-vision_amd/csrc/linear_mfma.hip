@@ -204,7 +204,8 @@ __global__ __launch_bounds__(256, 2) void k_linear(const LinArgs A) {
 //   * W tile [feature row][k] at pitch 68 (16-byte reads of consecutive rows fall on distinct banks): one ds_read_b128 = 4 taps,
 //     x rows read as 16-byte broadcasts;
 //   * k past the slice's end is staged as zeros in BOTH operands (a +0 product at the end of the chain: an exact no-op).
-// kGK = k per stage (64: 256-byte pieces of 128 weight rows per stage; 128: 512-byte pieces, half the workgroups per CU)
+// kGK = k per stage: 256-byte pieces of 128 weight rows per stage (128, i.e. 512-byte pieces and half the workgroups per CU,
+// measured 6-15 % slower: profiles/r03_ab_gemv.log)
 template <bool RELU, bool SLICED, int kGK = 64>
 __global__ __launch_bounds__(256, 2) void k_linear_gemv(const LinArgs A) {
   constexpr int kGPitch = kGK + 4;  // W tile pitch (floats): pitch / 4 odd
@@ -392,9 +393,7 @@ int launch_linear_sliced(const float* x, const float* w, const float* b, float* 
   a.vec_y = (m % 4 == 0) && ((uintptr_t)ws % 16 == 0);
   const long long nb = (long long)a.mblocks * a.nblocks_n * slices;  // < 512 * 128 by construction
   const bool gemv = n <= 4 && linear_gemv() && a.vec_w && a.vec_x;
-  if (gemv && tune_env("MV_GEMV_K128"))
-    hipLaunchKernelGGL((k_linear_gemv<false, true, 128>), dim3((unsigned)nb), dim3(256), 0, s, a);
-  else if (gemv)
+  if (gemv)
     hipLaunchKernelGGL((k_linear_gemv<false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((k_linear<false, 1, true>), dim3((unsigned)nb), dim3(256), 0, s, a);

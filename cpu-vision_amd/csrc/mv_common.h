@@ -140,11 +140,7 @@ __device__ inline void tie_flush(TieList* T, const TieWave& W, int lane, unsigne
   if (W.n == 0) return;
   seg &= kTieSegs - 1;
   unsigned base = 0;
-#ifdef MV_TIE_ABLATE_ATOMIC  // profiling builds only (wrong results): every wave writes at the list's start
-  if (lane == 0) base = 0;
-#else
   if (lane == 0) base = atomicAdd(&T->seg_count[seg], (unsigned)W.n);
-#endif
   base = __builtin_amdgcn_readfirstlane(base);
   const unsigned cap = T->capacity;
   for (int i = lane; i < W.n; i += kWave)

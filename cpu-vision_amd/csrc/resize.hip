@@ -212,7 +212,7 @@ struct ResizeFusedArgs {
   int ntx, nty, nrmax;  // taps kept per column / row window; rows of the LDS temporary
 };
 
-// MAXT: compile-time bound of a column window's taps (8 or 16; 0 = run-time loop).  With the bound the width pass issues the
+// MAXT: compile-time bound of a column window's taps (16; 0 = run-time loop).  With the bound the width pass issues the
 // RB x MAXT loads of RB rows back to back (tap index clamped into the window, bytes kept raw) and only then runs the chains; the
 // run-time loop `for j < xsize: t = fma((float)src[j], w[j], t)` waits a memory round trip per tap (taps past xsize are skipped, so
 // the chain is the same).  Which form runs: launch_resize.
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void k_resize_fused(const ResizeFusedArgs F) {
      // loads first and running this pass from there was tried: 0.104 -> 0.121 ms on 64 photos of 375 x 500.)
     const int xmin = xmins[lane], xsize = xsizes[lane];
     if constexpr (MAXT > 0) {
-      constexpr int RB = MAXT <= 8 ? 4 : 2;  // rows in flight per wave
+      constexpr int RB = 2;  // rows in flight per wave
       float wj[MAXT];
 #pragma unroll
       for (int j = 0; j < MAXT; ++j) wj[j] = (j < xsize) ? wx[j * 64 + lane] : 0.f;
@@ -449,20 +449,17 @@ int launch_resize(const void* x, void* y, bool u8, int64_t planes, int channels,
       if (blocks == 0) return MV_OK;
       // batched loads pay from 9 taps up (24 x 1080p -> 256 / 224: 0.191 -> 0.167 ms); with 5 taps (375 x 500 photos) eight workgroups
       // per CU already hide the per-tap round trips and the batched form's address arithmetic costs more than it saves (0.107 ->
-      // 0.122 ms): the run-time loop stays there.  MV_RESIZE_TAPS (tuning build) forces 0 / 8 / 16.
-      int maxt = f.ntx <= 8 ? 0 : 16;  // f.ntx <= kFusedMaxTaps = 15
-      if (const char* e = tune_env("MV_RESIZE_TAPS")) maxt = atoi(e) >= f.ntx || atoi(e) == 0 ? atoi(e) : maxt;
+      // 0.122 ms): the run-time loop stays there.
+      const bool batched = f.ntx > 8;  // f.ntx <= kFusedMaxTaps = 15
       auto launch = [&](auto kern) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, f);
       };
       if (u8) {
-        if (maxt == 8) launch(k_resize_fused<uint8_t, 8>);
-        else if (maxt == 16) launch(k_resize_fused<uint8_t, 16>);
+        if (batched) launch(k_resize_fused<uint8_t, 16>);
         else launch(k_resize_fused<uint8_t, 0>);
       } else {
-        if (maxt == 8) launch(k_resize_fused<float, 8>);
-        else if (maxt == 16) launch(k_resize_fused<float, 16>);
+        if (batched) launch(k_resize_fused<float, 16>);
         else launch(k_resize_fused<float, 0>);
       }
       return check_launchf("k_resize_fused<%s,th%d>", u8 ? "u8" : "f32", f.th);

@@ -29,19 +29,10 @@ namespace mv {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-#ifndef MV_SEPFAST_GROUP
-#define MV_SEPFAST_GROUP 4
-#endif
-#ifndef MV_SEPFAST_ROWS_SOBEL
-#define MV_SEPFAST_ROWS_SOBEL 48  // run time flat 16..48 (profiles/r03_sweep_sepfast_order.log: 32 -> 48 within 0.3-0.7 %), 64 slower; 48 re-reads
-                                  // 6 halo rows per 48 instead of per 32 (FETCH_SIZE 1.06x -> 1.04x of the input)
-#endif
-#ifndef MV_SEPFAST_NT
-#define MV_SEPFAST_NT 1  // non-temporal stores for gx / gy (0: plain stores -- tools/ab_alloc_lottery.py --variant)
-#endif
-#ifndef MV_SEPFAST_ROWS_BLUR
-#define MV_SEPFAST_ROWS_BLUR 16   // 8/16: 6.0 TB/s, 32: 5.86, 64: 5.64: --op sep5
-#endif
+constexpr int kSepFastGroup = 4;  // raw rows loaded ahead of the arithmetic
+constexpr int kRowsSobel = 48;  // run time flat 16..48 (profiles/r03_sweep_sepfast_order.log: 32 -> 48 within 0.3-0.7 %), 64 slower; 48 re-reads
+                                // 6 halo rows per 48 instead of per 32 (FETCH_SIZE 1.06x -> 1.04x of the input)
+constexpr int kRowsBlur = 16;   // 8/16: 6.0 TB/s, 32: 5.86, 64: 5.64: --op sep5
 
 struct SepFastArgs {
   const float* x;
@@ -107,7 +98,7 @@ __global__ __launch_bounds__(256) void k_sepfast(const SepFastArgs A) {
   constexpr int E = SOBEL ? 1 : 0;   // extra blurred columns per side
   constexpr int HL = R + E;          // raw neighbours per side
   constexpr int NC = 4 + 2 * E;      // blurred columns a lane evaluates
-  constexpr int G = MV_SEPFAST_GROUP;
+  constexpr int G = kSepFastGroup;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const long long item = (long long)xcd_remap(blockIdx.x, A.nblocks) * 4 + wave;
   if (item >= A.nitems) return;
@@ -230,13 +221,8 @@ __global__ __launch_bounds__(256) void k_sepfast(const SepFastArgs A) {
           if (xs < w) {
             const size_t o = poff + (size_t)oy * w + xs;
             f4 v1 = {ogx[0], ogx[1], ogx[2], ogx[3]}, v2 = {ogy[0], ogy[1], ogy[2], ogy[3]};
-#if MV_SEPFAST_NT
-            __builtin_nontemporal_store(v1, reinterpret_cast<f4*>(A.gx + o));
+            __builtin_nontemporal_store(v1, reinterpret_cast<f4*>(A.gx + o));  // non-temporal: never re-read
             __builtin_nontemporal_store(v2, reinterpret_cast<f4*>(A.gy + o));
-#else
-            *reinterpret_cast<f4*>(A.gx + o) = v1;
-            *reinterpret_cast<f4*>(A.gy + o) = v2;
-#endif
           }
         };
         const int oy = by - 1;
@@ -283,7 +269,7 @@ int launch_sepfast(const float* x, float* y, float* gx, float* gy, bool sobel, i
   if (!sobel) fill_frames(a.fp);
   for (int i = 0; i < k; ++i) a.t.x[i] = k1d_x[i], a.t.y[i] = k1d_y[i];
   a.col_segs = (w + 255) / 256;
-  int rows = sf_env_int("MV_SEPFAST_ROWS", sobel ? MV_SEPFAST_ROWS_SOBEL : MV_SEPFAST_ROWS_BLUR);
+  int rows = sf_env_int("MV_SEPFAST_ROWS", sobel ? kRowsSobel : kRowsBlur);
   if (rows < 1) rows = 1;
   if (rows > h) rows = h;
   a.rows = rows;

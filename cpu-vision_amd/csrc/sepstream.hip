@@ -394,7 +394,7 @@ bool sepstream_supported(const void* x, const void* y, bool u8, int h, int w, in
 }
 
 template <typename T, int KB, int PX, int S>
-static int stream_launch_pf(StreamArgs& a, int64_t planes, const float* k1d_x, const float* k1d_y, hipStream_t s) {
+static int stream_launch(StreamArgs& a, int64_t planes, const float* k1d_x, const float* k1d_y, hipStream_t s) {
   constexpr int KBP = KB + 1;
   for (int i = 0; i < 128; ++i) a.taps[i] = 0.f;
   for (int i = 0; i < a.kx; ++i) a.taps[(KB - a.kx) / 2 + i] = k1d_x[i];   // centred: zero taps on both sides
@@ -412,14 +412,8 @@ static int stream_launch_pf(StreamArgs& a, int64_t planes, const float* k1d_x, c
   a.nitems = (long long)planes * a.strips * a.col_segs;
   if (a.nitems > 4LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "separable: batch too large for one launch");
   a.nblocks = (unsigned)((a.nitems + 3) / 4);
-  int pf = KB <= 23 ? 2 : 4;  // measured (profiles/r01_perf_separable.log): deeper rings cost a wave per SIMD below KB = 31
-  if (const char* e = tune_env("MV_SEPSTREAM_PF")) pf = atoi(e);
-  if (pf <= 1)
-    hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, 1>), dim3(a.nblocks), dim3(256), 0, s, a);
-  else if (pf <= 2)
-    hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, 2>), dim3(a.nblocks), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, 4>), dim3(a.nblocks), dim3(256), 0, s, a);
+  constexpr int PF = KB <= 23 ? 2 : 4;  // measured (profiles/r01_perf_separable.log): deeper rings cost a wave per SIMD below KB = 31
+  hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, PF>), dim3(a.nblocks), dim3(256), 0, s, a);
   return check_launch("k_sepstream");
 }
 
@@ -433,17 +427,17 @@ int launch_sepstream(const void* x, void* y, bool u8, int64_t planes, int h, int
   fill_frames(a.fp);
   const int kmax = kx > ky ? kx : ky;
   if (u8) {
-    if (kmax <= 15) return stream_launch_pf<uint8_t, 15, 4, 1>(a, planes, k1d_x, k1d_y, s);
-    if (kmax <= 23) return stream_launch_pf<uint8_t, 23, 4, 1>(a, planes, k1d_x, k1d_y, s);
-    if (kmax <= 31) return stream_launch_pf<uint8_t, 31, 4, 2>(a, planes, k1d_x, k1d_y, s);
-    if (kmax <= 47) return stream_launch_pf<uint8_t, 47, 2, 1>(a, planes, k1d_x, k1d_y, s);
-    return stream_launch_pf<uint8_t, 63, 2, 1>(a, planes, k1d_x, k1d_y, s);
+    if (kmax <= 15) return stream_launch<uint8_t, 15, 4, 1>(a, planes, k1d_x, k1d_y, s);
+    if (kmax <= 23) return stream_launch<uint8_t, 23, 4, 1>(a, planes, k1d_x, k1d_y, s);
+    if (kmax <= 31) return stream_launch<uint8_t, 31, 4, 2>(a, planes, k1d_x, k1d_y, s);
+    if (kmax <= 47) return stream_launch<uint8_t, 47, 2, 1>(a, planes, k1d_x, k1d_y, s);
+    return stream_launch<uint8_t, 63, 2, 1>(a, planes, k1d_x, k1d_y, s);
   }
-  if (kmax <= 15) return stream_launch_pf<float, 15, 4, 1>(a, planes, k1d_x, k1d_y, s);
-  if (kmax <= 23) return stream_launch_pf<float, 23, 4, 1>(a, planes, k1d_x, k1d_y, s);
-  if (kmax <= 31) return stream_launch_pf<float, 31, 4, 2>(a, planes, k1d_x, k1d_y, s);
-  if (kmax <= 47) return stream_launch_pf<float, 47, 2, 1>(a, planes, k1d_x, k1d_y, s);
-  return stream_launch_pf<float, 63, 2, 1>(a, planes, k1d_x, k1d_y, s);
+  if (kmax <= 15) return stream_launch<float, 15, 4, 1>(a, planes, k1d_x, k1d_y, s);
+  if (kmax <= 23) return stream_launch<float, 23, 4, 1>(a, planes, k1d_x, k1d_y, s);
+  if (kmax <= 31) return stream_launch<float, 31, 4, 2>(a, planes, k1d_x, k1d_y, s);
+  if (kmax <= 47) return stream_launch<float, 47, 2, 1>(a, planes, k1d_x, k1d_y, s);
+  return stream_launch<float, 63, 2, 1>(a, planes, k1d_x, k1d_y, s);
 }
 
 }  // namespace mv

@@ -188,8 +188,7 @@ __global__ __launch_bounds__(256, KXB <= 23 ? 4 : 2) void k_u8_tie_fixup(const T
   }
   // pass 2: the edge lane-rows (reflection inside the window, or a ragged lane-row), ONE PIXEL per thread.  Done inside pass 1 -- a
   // lane walking its NPX pixels one after the other -- every wave that held a single edge lane-row (40-50 % of them) ran 4 / 16
-  // per-pixel chains behind its fast path: 1.9 ms instead of 1.3 at 23 x 23 (-DMV_TIEFIX_ABLATE_EDGES build).
-#ifndef MV_TIEFIX_ABLATE_EDGES
+  // per-pixel chains behind its fast path: 1.9 ms instead of 1.3 at 23 x 23.
   const long long work = (long long)count * NPX;
   for (long long i = gid; i < work; i += stride) {
     const unsigned long long first = entry(i / NPX);
@@ -199,7 +198,6 @@ __global__ __launch_bounds__(256, KXB <= 23 ? 4 : 2) void k_u8_tie_fixup(const T
     if (!fast && ox < A.w)
       A.y[plane * plane_px + (long long)oy * A.w + ox] = blur2d_u8<KXB>(A.x + plane * plane_px, A.h, A.w, oy, ox, A.kx, A.ky, tx, ty);
   }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------- host side

@@ -1,13 +1,9 @@
 #!/usr/bin/env python3
-"""A/B + ablation of the general-cin 3x3 conv (csrc/conv3x3_gen.hip) over whole-library variants
-(cpu-vision_amd/lib/libmi355vision_<name>.so, built with MV_BUILD_VARIANT / MV_HIPCC_EXTRA), interleaved rounds in one process.
-
-    MV_BUILD_VARIANT=noload MV_HIPCC_EXTRA=-DMV_GEN_ABLATE=1 python -c "import __graft_entry__ as g; g.build()"
-    python tools/ab_conv.py base noload nostore neither nomfma
-A name of the form KEY=VALUE[,KEY=VALUE] is the base library with those environment knobs set around its launches
-(the launchers read MV_CONV_SHAPE / MV_CONV_SPEC / MV_CONV_COLFAST at every call):
+"""A/B of the general-cin 3x3 conv (csrc/conv3x3_gen.hip) over environment-knob variants, interleaved rounds in one process.
+`base` is the product library; a name of the form KEY=VALUE[,KEY=VALUE] is the tuning library with those environment knobs set
+around its launches (the launchers read MV_CONV_SHAPE / MV_CONV_SPEC / MV_CONV_COLFAST at every call):
     python tools/ab_conv.py base MV_CONV_COLFAST=1 MV_CONV_SHAPE=2,MV_CONV_SPEC=1
---batch=N keeps only the cases of that batch size.
+--batch=N keeps only the cases of that batch size.  Every variant must compute the same bits.
 """
 import os
 import ctypes as C
@@ -28,7 +24,7 @@ for n in names:
     if "=" in n:
         envs[n] = dict(kv.split("=", 1) for kv in n.split(","))
     # KEY=VALUE names need the -DMV_TUNING build: the product library reads no environment variable
-    p = ROOT / "cpu-vision_amd" / "lib" / ("libmi355vision.so" if n == "base" else "libmi355vision_tuning.so" if "=" in n else f"libmi355vision_{n}.so")
+    p = ROOT / "cpu-vision_amd" / "lib" / ("libmi355vision.so" if n == "base" else "libmi355vision_tuning.so")
     lib = C.CDLL(str(p))
     lib.mv_conv3x3_bias_relu_f32.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_int] * 5 + [C.c_void_p]
     libs[n] = lib
@@ -63,7 +59,7 @@ for n_img, cin, cout, hw in cases:
             t = timed(lambda: lib.mv_conv3x3_bias_relu_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), n_img, cin, hw, hw, cout, 1, s))
             for k in envs.get(n, {}):
                 os.environ.pop(k, None)
-            if r == 0 and n not in ("noload", "nostore", "neither", "neither0", "nomfma", "nomfma6"):  # every non-ablation variant computes the same bits
+            if r == 0:  # every variant computes the same bits
                 if ref is None:
                     ref = y.clone()
                 else:

@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """A/B of library variants on deform_conv2d (runs on the GPU box), interleaved rounds in one process.
 
-    MV_BUILD_VARIANT=dfnog MV_VARIANT_SOURCES=deform_fused.hip MV_HIPCC_EXTRA=-DMV_DF_ABLATE=1 python cpu-vision_amd/_build.py
-    python tools/ab_deform.py [--shape 8,256,256,64] base tuning@MV_DEFORM_UNFUSED=1 dfnog       (name[@ENV=VAL,...])
-Variants whose name starts with `df` are ablations (wrong results on purpose); every other one must equal the first bit for bit."""
+    python tools/ab_deform.py [--shape 8,256,256,64] base tuning@MV_DEFORM_UNFUSED=1       (name[@ENV=VAL,...])
+Every variant must equal the first bit for bit."""
 import argparse
 import ctypes as C
 import os
@@ -61,11 +60,10 @@ kern = {}
 for spec in a.specs:
     kern[spec] = call(spec)
     torch.cuda.synchronize()
-    if not spec.startswith("df"):
-        if first is None:
-            first = y.clone()
-        else:
-            assert torch.equal(first, y), f"{spec} differs from {a.specs[0]}"
+    if first is None:
+        first = y.clone()
+    else:
+        assert torch.equal(first, y), f"{spec} differs from {a.specs[0]}"
 times = {sp: [] for sp in a.specs}
 for r in range(a.rounds):
     for spec in a.specs:

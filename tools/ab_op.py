@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Generic A/B of library variants on one operator, interleaved rounds in one process (runs on the GPU box).
 
-    MV_BUILD_VARIANT=c3plain MV_VARIANT_SOURCES=conv3x3_c3.hip MV_HIPCC_EXTRA=-DMV_C3_NT=0 python cpu-vision_amd/_build.py
-    python tools/ab_op.py --op conv tuning c3plain tuning@MV_C3_TH=8        (name[@ENV=VAL,...]; 'base' = the product library)
+    python tools/ab_op.py --op conv base tuning@MV_C3_TH=8        (name[@ENV=VAL,...]; 'base' = the product library)
 ops: conv (cfg4), sobel5 (cfg3), sep5, blur3 (32 x 4K f32), u8blur3, u8sharp, sharp
 Every variant must produce the same bytes (checked on a strided sample)."""
 import argparse
@@ -18,7 +17,6 @@ import torch  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--op", default="conv")
 ap.add_argument("--rounds", type=int, default=14)
-ap.add_argument("--no-check", action="store_true", help="ablation builds produce wrong results on purpose")
 ap.add_argument("specs", nargs="*", default=["base"])
 a = ap.parse_args()
 fp, vp, i32, i64 = C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int64
@@ -85,7 +83,7 @@ for r in range(a.rounds):
         if r == 0:
             c = sum(float(o.view(-1)[::97].double().sum().item()) for o in outs)
             chk = c if chk is None else chk
-            assert a.no_check or c == chk, (spec, c, chk)
+            assert c == chk, (spec, c, chk)
         if r >= 2:
             res[spec].append(ms)
         for e in kv:

@@ -52,11 +52,6 @@ for name, (h, w), nfr in (("1080p", (1080, 1920), 24), ("4K", (2160, 3840), 8), 
     os.environ.pop("MV_DW3X3_ROWS", None)
     t = block_us(run, 4 * nfr)
     line += f"  tile {t:6.1f} us ({3 * h * w * 8 / t / 1e6:5.2f} TB/s)"
-    for rpt, th in ((2, 8), (8, 32)):
-        os.environ["MV_TILE_RPT_SIZED"] = str(rpt)
-        t = block_us(run, 4 * nfr)
-        line += f"  tile/{th} {t:6.1f} us ({3 * h * w * 8 / t / 1e6:5.2f} TB/s)"
-    os.environ.pop("MV_TILE_RPT_SIZED", None)
     os.environ["MV_FORCE_REG3X3"] = "1"
     for rows in (4, 8, 16, 32):
         os.environ["MV_DW3X3_ROWS"] = str(rows)
