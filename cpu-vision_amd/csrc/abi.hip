@@ -78,11 +78,48 @@ static int check_kernel_size(int ky, int kx, int h, int w, int border) {
   return MV_OK;
 }
 
-static int check_taps1d(const float* k1d_x, int kx, const float* k1d_y, int ky) {
+// hint: appended to the tap-count message
+static int check_taps1d(const void* k1d_x, int kx, const void* k1d_y, int ky, const char* hint = "") {
   if (!k1d_x || !k1d_y) return set_error(MV_ERR_INVALID_ARGUMENT, "null tap pointer");
   if (kx > kMaxTaps1D || ky > kMaxTaps1D)
-    return set_error(MV_ERR_UNSUPPORTED, "1-D kernels up to %d taps are supported, got (%d, %d)", kMaxTaps1D, ky, kx);
+    return set_error(MV_ERR_UNSUPPORTED, "1-D kernels up to %d taps are supported, got (%d, %d)%s", kMaxTaps1D, ky, kx, hint);
   return MV_OK;
+}
+
+// The argument checks of the single-output entry points that take a pair of 1-D kernels (reflect border), in the order the
+// ABI reports them.  An empty image passes: the caller returns MV_OK before dispatching.
+static int check_blur1d(const void* x, const void* y, int64_t planes, int h, int w, const void* k1d_x, int kx, const void* k1d_y,
+                        int ky, const char* hint = "") {
+  if (int rc = check_image(x, y, planes, h, w)) return rc;
+  if (planes == 0 || h == 0 || w == 0) return MV_OK;
+  if (int rc = check_kernel_size(ky, kx, h, w, MV_BORDER_REFLECT)) return rc;
+  return check_taps1d(k1d_x, kx, k1d_y, ky, hint);
+}
+
+// Kernel sides up to 11 of a size no specialised tile kernel is built for (1x5, 7x3, 9x1, ...) are zero-padded (centred) to
+// one that is: a zero tap is an exact no-op of the fma chain, and static fmas beat taps read from LDS one by one by 3x (7x5 on
+// 32 x 4K: 3.1 -> 1.5 ms).  Each side rounds up to 3 / 5 / 7 / 9 / 11.
+static int tile_side(int k) { return k <= 3 ? 3 : (k <= 5 ? 5 : (k <= 7 ? 7 : (k <= 9 ? 9 : 11))); }
+
+// The padded sides (ty, tx) of a ky x kx kernel: the tile kernels are built for equal sides and 5x3 / 3x5, the uint8 16-pixel
+// kernels for any mix of 3 / 5 / 7; any other pair is squared up to its larger side.  False when the kernel stays as it is:
+// a side above 11, a size that is built already, or a padded half-size that would reach past the image.
+static bool fit_tile(int ky, int kx, bool u8, int h, int w, int& ty, int& tx) {
+  if (ky > 11 || kx > 11) return false;
+  ty = tile_side(ky), tx = tile_side(kx);
+  const bool pair_ok = ty == tx || (ty <= 5 && tx <= 5) || (u8 && ty <= 7 && tx <= 7);
+  if (!pair_ok) ty = tx = (ty > tx ? ty : tx);
+  return (ty != ky || tx != kx) && ty / 2 < h && tx / 2 < w;
+}
+
+// fit_tile for a pair of 1-D kernels: on a fit, k1d_x / k1d_y point at the padded copies in pad_x / pad_y
+static void fit_taps1d(bool u8, int h, int w, const float*& k1d_x, int& kx, const float*& k1d_y, int& ky, float (&pad_x)[11],
+                       float (&pad_y)[11]) {
+  int ty, tx;
+  if (!fit_tile(ky, kx, u8, h, w, ty, tx)) return;
+  center_pad(k1d_x, kx, pad_x, tx);
+  center_pad(k1d_y, ky, pad_y, ty);
+  k1d_x = pad_x, k1d_y = pad_y, kx = tx, ky = ty;
 }
 
 template <typename T>
@@ -96,21 +133,12 @@ static int depthwise(const T* x, T* y, const float* w, int w_on_device, int64_t 
     return set_error(MV_ERR_UNSUPPORTED, "%d host taps exceed MV_MAX_HOST_TAPS_2D=%d: pass a device pointer", ky * kx,
                      kMaxTaps2D);
   constexpr bool u8 = sizeof(T) == 1;
-  // Host taps up to 11x11 of a size no specialised kernel is built for (7x5, 1x7, 3x9, ...) are zero-padded (centred) to
-  // the next one that is: a zero tap is an exact no-op of the fma chain, and static fmas beat taps read from LDS one by one
-  // by 3x (7x5 on 32 x 4K: 3.1 -> 1.5 ms).  Not for VALID borders (the output size follows the kernel size).
+  // host taps are zero-padded to a specialised size (fit_tile); not for VALID borders (the output size follows the kernel size)
   float padded[121];
-  if (!w_on_device && border != MV_BORDER_VALID && ky <= 11 && kx <= 11) {
-    auto up = [](int k) { return k <= 3 ? 3 : (k <= 5 ? 5 : (k <= 7 ? 7 : (k <= 9 ? 9 : 11))); };
-    int ty = up(ky), tx = up(kx);
-    const bool pair_ok = (ty == tx) || (ty == 5 && tx == 3) || (ty == 3 && tx == 5) || (u8 && ty <= 7 && tx <= 7);
-    if (!pair_ok) ty = tx = (ty > tx ? ty : tx);  // the tile kernels beyond 5x3 / 3x5 are square
-    if ((ty != ky || tx != kx) && ty / 2 < h && tx / 2 < wdt) {
-      for (int i = 0; i < ty * tx; ++i) padded[i] = 0.f;
-      for (int j = 0; j < ky; ++j)
-        for (int i = 0; i < kx; ++i) padded[((ty - ky) / 2 + j) * tx + (tx - kx) / 2 + i] = w[j * kx + i];
-      w = padded, ky = ty, kx = tx;
-    }
+  int ty, tx;
+  if (!w_on_device && border != MV_BORDER_VALID && fit_tile(ky, kx, u8, h, wdt, ty, tx)) {
+    center_pad2d(w, ky, kx, padded, ty, tx);
+    w = padded, ky = ty, kx = tx;
   }
   if constexpr (u8) {
     // the 16-pixel kernels narrow with a saturating pack; the reference's .to(uint8) of an out-of-range float is not
@@ -139,28 +167,12 @@ static int depthwise(const T* x, T* y, const float* w, int w_on_device, int64_t 
 template <typename T>
 static int gaussian(const T* x, T* y, int64_t planes, int h, int wdt, const float* k1d_x, int kx, const float* k1d_y,
                     int ky, hipStream_t s) {
-  if (int rc = check_image(x, y, planes, h, wdt)) return rc;
+  if (int rc = check_blur1d(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky)) return rc;
   if (planes == 0 || h == 0 || wdt == 0) return MV_OK;
-  if (int rc = check_kernel_size(ky, kx, h, wdt, MV_BORDER_REFLECT)) return rc;
-  if (int rc = check_taps1d(k1d_x, kx, k1d_y, ky)) return rc;
   constexpr bool u8 = sizeof(T) == 1;
-  // Sides are zero-padded up to the next size the specialised kernels are built for (3 / 5 / 7 / 9 / 11; see the pairs
-  // below): the padded outer product has exact zeros there, and a zero tap is an
-  // exact no-op of the fma chain, so e.g. kernel_size = (1, 5) runs on the 3x5 kernel with the same bits.
+  // the padded outer product has exact zeros, so e.g. kernel_size = (1, 5) runs on the 3x5 kernel with the same bits
   float pad_x[11], pad_y[11];
-  if (kx <= 11 && ky <= 11) {
-    auto up = [](int k) { return k <= 3 ? 3 : (k <= 5 ? 5 : (k <= 7 ? 7 : (k <= 9 ? 9 : 11))); };
-    int tx = up(kx), ty = up(ky);
-    // uint8 16-pixel kernels: any mix of 3 / 5 / 7; fp32 tile kernels: 3x3, 5x5, 5x3, 3x5, then squares 7 / 9 / 11
-    const bool pair_ok = (tx == ty) || (tx <= 5 && ty <= 5) || (u8 && tx <= 7 && ty <= 7);
-    if (!pair_ok) tx = ty = (tx > ty ? tx : ty);
-    if ((tx != kx || ty != ky) && tx / 2 < wdt && ty / 2 < h) {
-      for (int i = 0; i < 11; ++i) pad_x[i] = 0.f, pad_y[i] = 0.f;
-      for (int i = 0; i < kx; ++i) pad_x[(tx - kx) / 2 + i] = k1d_x[i];
-      for (int i = 0; i < ky; ++i) pad_y[(ty - ky) / 2 + i] = k1d_y[i];
-      k1d_x = pad_x, k1d_y = pad_y, kx = tx, ky = ty;
-    }
-  }
+  fit_taps1d(u8, h, wdt, k1d_x, kx, k1d_y, ky, pad_x, pad_y);
   bool u8x16 = false;
   if constexpr (u8) u8x16 = (ky == 3 && kx == 3) && dw3x3_u8x16_supported(x, y, h, wdt);
   if (ky == 3 && kx == 3 && (use_reg3x3(wdt) || u8x16)) {
@@ -277,16 +289,13 @@ static bool taps_are_an_average(const float* k, int n) {
 int64_t mv_gaussian_blur_u8_workspace_bytes(int64_t planes, int h, int wdt, int kx, int ky) {
   if (planes <= 0 || h <= 0 || wdt <= 0 || kx < 1 || ky < 1 || !(kx & 1) || !(ky & 1)) return 0;
   if (kx / 2 >= wdt || ky / 2 >= h || !gaussian_blur_u8_hybrid_supported(h, wdt, kx, ky)) return 0;
-  const bool small = (kx <= 7 && ky <= 7) || (kx == 9 && (ky == 7 || ky == 9)) || (kx == 7 && ky == 9);
-  return u8_tie_workspace_bytes(planes, h, wdt, small ? 16 : sepstream_u8_pixels_per_lane(kx, ky));
+  return u8_tie_workspace_bytes(planes, h, wdt, hybrid_npx(kx, ky));
 }
 
 int mv_gaussian_blur_u8_ws(const uint8_t* x, uint8_t* y, int64_t planes, int h, int wdt, const float* k1d_x, int kx,
                            const float* k1d_y, int ky, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = check_image(x, y, planes, h, wdt)) return rc;
+  if (int rc = check_blur1d(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky)) return rc;
   if (planes == 0 || h == 0 || wdt == 0) return MV_OK;
-  if (int rc = check_kernel_size(ky, kx, h, wdt, MV_BORDER_REFLECT)) return rc;
-  if (int rc = check_taps1d(k1d_x, kx, k1d_y, ky)) return rc;
   const bool fast = workspace != nullptr && workspace_bytes > 0 && gaussian_blur_u8_hybrid_supported(h, wdt, kx, ky) &&
                     taps_are_an_average(k1d_x, kx) && taps_are_an_average(k1d_y, ky);
   if (!fast) return gaussian<uint8_t>(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky, (hipStream_t)stream);
@@ -310,13 +319,10 @@ int mv_gaussian_blur_u8_v(const uint8_t* const* xs, uint8_t* const* ys, int nfra
 // float64 images: the reference computes them in float64 (taps, padding and conv2d all in the image dtype)
 int mv_gaussian_blur_f64(const double* x, double* y, int64_t planes, int h, int wdt, const double* k1d_x, int kx,
                          const double* k1d_y, int ky, void* stream) {
-  if (int rc = check_image(x, y, planes, h, wdt)) return rc;
+  if (int rc = check_blur1d(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky,
+                            ": pass the 2-D kernel to mv_depthwise_conv2d_f64 as a device array"))
+    return rc;
   if (planes == 0 || h == 0 || wdt == 0) return MV_OK;
-  if (int rc = check_kernel_size(ky, kx, h, wdt, MV_BORDER_REFLECT)) return rc;
-  if (!k1d_x || !k1d_y) return set_error(MV_ERR_INVALID_ARGUMENT, "null tap pointer");
-  if (kx > kMaxTaps1D || ky > kMaxTaps1D)
-    return set_error(MV_ERR_UNSUPPORTED, "1-D kernels up to %d taps are supported, got (%d, %d): pass the 2-D kernel to "
-                     "mv_depthwise_conv2d_f64 as a device array", kMaxTaps1D, ky, kx);
   return launch_dwf64(x, y, nullptr, k1d_x, k1d_y, planes, h, wdt, ky, kx, MV_BORDER_REFLECT, (hipStream_t)stream);
 }
 
@@ -348,21 +354,11 @@ int mv_sharpness_f64(const double* x, double* y, int64_t planes, int h, int wdt,
 // converts to fp32 around mv_separable_blur_f32.
 static int gaussian_half(const void* x, void* y, int dtype, int64_t planes, int h, int wdt, const float* k1d_x, int kx,
                          const float* k1d_y, int ky, hipStream_t s) {
-  if (int rc = check_image(x, y, planes, h, wdt)) return rc;
+  if (int rc = check_blur1d(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky)) return rc;
   if (planes == 0 || h == 0 || wdt == 0) return MV_OK;
-  if (int rc = check_kernel_size(ky, kx, h, wdt, MV_BORDER_REFLECT)) return rc;
-  if (int rc = check_taps1d(k1d_x, kx, k1d_y, ky)) return rc;
   if (kx > 11 || ky > 11) return set_error(MV_ERR_UNSUPPORTED, "half-precision storage: kernel sides up to 11, got (%d, %d)", ky, kx);
   float pad_x[11], pad_y[11];
-  auto up = [](int k) { return k <= 3 ? 3 : (k <= 5 ? 5 : (k <= 7 ? 7 : (k <= 9 ? 9 : 11))); };
-  int tx = up(kx), ty = up(ky);
-  if (!((tx == ty) || (tx <= 5 && ty <= 5))) tx = ty = (tx > ty ? tx : ty);
-  if ((tx != kx || ty != ky) && tx / 2 < wdt && ty / 2 < h) {
-    for (int i = 0; i < 11; ++i) pad_x[i] = 0.f, pad_y[i] = 0.f;
-    for (int i = 0; i < kx; ++i) pad_x[(tx - kx) / 2 + i] = k1d_x[i];
-    for (int i = 0; i < ky; ++i) pad_y[(ty - ky) / 2 + i] = k1d_y[i];
-    k1d_x = pad_x, k1d_y = pad_y, kx = tx, ky = ty;
-  }
+  fit_taps1d(false, h, wdt, k1d_x, kx, k1d_y, ky, pad_x, pad_y);
   return launch_dwtile(x, y, dtype, nullptr, nullptr, k1d_x, k1d_y, planes, h, wdt, ky, kx, MV_BORDER_REFLECT, s);
 }
 
@@ -387,18 +383,15 @@ static bool pad_small_taps(const float* k1d_x, int kx, const float* k1d_y, int k
   if (kx > 7 || ky > 7 || kx < 1 || ky < 1) return false;
   p.k = kx > ky ? kx : ky;
   if (p.k < 3) p.k = 3;
-  for (int i = 0; i < 7; ++i) p.x[i] = 0.f, p.y[i] = 0.f;
-  for (int i = 0; i < kx; ++i) p.x[(p.k - kx) / 2 + i] = k1d_x[i];
-  for (int i = 0; i < ky; ++i) p.y[(p.k - ky) / 2 + i] = k1d_y[i];
+  center_pad(k1d_x, kx, p.x, p.k);
+  center_pad(k1d_y, ky, p.y, p.k);
   return true;
 }
 
 int mv_separable_blur_f32(const float* x, float* y, int64_t planes, int h, int wdt, const float* k1d_x, int kx,
                           const float* k1d_y, int ky, void* stream) {
-  if (int rc = check_image(x, y, planes, h, wdt)) return rc;
+  if (int rc = check_blur1d(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky)) return rc;
   if (planes == 0 || h == 0 || wdt == 0) return MV_OK;
-  if (int rc = check_kernel_size(ky, kx, h, wdt, MV_BORDER_REFLECT)) return rc;
-  if (int rc = check_taps1d(k1d_x, kx, k1d_y, ky)) return rc;
   PaddedTaps pt;
   if (pad_small_taps(k1d_x, kx, k1d_y, ky, pt) && sepfast_supported(x, y, nullptr, h, wdt, pt.k, pt.k, false))
     return launch_sepfast(x, y, nullptr, nullptr, false, planes, h, wdt, pt.x, pt.y, pt.k, (hipStream_t)stream);
@@ -409,23 +402,12 @@ int mv_separable_blur_f32(const float* x, float* y, int64_t planes, int h, int w
 
 int mv_separable_blur_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int wdt, const float* k1d_x, int kx,
                          const float* k1d_y, int ky, void* stream) {
-  if (int rc = check_image(x, y, planes, h, wdt)) return rc;
+  if (int rc = check_blur1d(x, y, planes, h, wdt, k1d_x, kx, k1d_y, ky)) return rc;
   if (planes == 0 || h == 0 || wdt == 0) return MV_OK;
-  if (int rc = check_kernel_size(ky, kx, h, wdt, MV_BORDER_REFLECT)) return rc;
-  if (int rc = check_taps1d(k1d_x, kx, k1d_y, ky)) return rc;
-  const bool nine = (kx == 9 && (ky == 7 || ky == 9)) || (kx == 7 && ky == 9);
-  if ((kx <= 7 && ky <= 7) || (nine && wdt >= 16)) {
-    // small kernels: the 16-pixel-per-lane register kernel in its separable form; sides of 1 are zero-padded to 3 (an exact
-    // no-op of both fma chains)
-    float px[9], py[9];
-    int tx = kx < 3 ? 3 : kx, ty = ky < 3 ? 3 : ky;
-    for (int i = 0; i < 9; ++i) px[i] = 0.f, py[i] = 0.f;
-    for (int i = 0; i < kx; ++i) px[(tx - kx) / 2 + i] = k1d_x[i];
-    for (int i = 0; i < ky; ++i) py[(ty - ky) / 2 + i] = k1d_y[i];
-    if (!sep_u8x16_supported(h, wdt, ty, tx))
-      return set_error(MV_ERR_UNSUPPORTED, "separable uint8 blur with kernel sides <= 7 needs W >= 16 (got %d): use mv_gaussian_blur_u8", wdt);
-    return launch_sep_u8x16(x, y, px, py, planes, h, wdt, ty, tx, (hipStream_t)stream);
-  }
+  // small kernels: the 16-pixel-per-lane register kernel in its separable form; 9-tap sides below W = 16 take k_sepstream
+  if (sep_u8x16_supported(h, wdt, ky, kx)) return launch_sep_u8x16(x, y, k1d_x, k1d_y, planes, h, wdt, ky, kx, (hipStream_t)stream);
+  if (kx <= 7 && ky <= 7)
+    return set_error(MV_ERR_UNSUPPORTED, "separable uint8 blur with kernel sides <= 7 needs W >= 16 (got %d): use mv_gaussian_blur_u8", wdt);
   if (!sepstream_supported(x, y, true, h, wdt, kx, ky))
     return set_error(MV_ERR_UNSUPPORTED, "separable uint8 blur with a kernel side above 7 needs K <= 63 and W >= 8");
   return launch_sepstream(x, y, true, planes, h, wdt, k1d_x, kx, k1d_y, ky, (hipStream_t)stream);

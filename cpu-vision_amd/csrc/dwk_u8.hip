@@ -387,13 +387,18 @@ int launch_dwk_u8x16(const uint8_t* x, uint8_t* y, const float* w2d, const float
   return set_error(MV_ERR_UNSUPPORTED, "dwk_u8: kernel size (%d, %d)", ky, kx);
 }
 
-// Separable form: kernel sides in {3, 5, 7} (the caller zero-pads 1 -> 3: an exact no-op of the fma chains) and 9 x 9, 9 x 7, 7 x 9
-// (a lane's halo is the 4 bytes either side of its 16 pixels: sides up to 9), reflect border
-bool sep_u8x16_supported(int h, int w, int ky, int kx) {
+// Separable form: kernel sides in {3, 5, 7} (sides of 1 are zero-padded to 3: an exact no-op of the fma chains) and 9 x 9, 9 x 7,
+// 7 x 9 (a lane's halo is the 4 bytes either side of its 16 pixels: sides up to 9), reflect border
+static int sep_side(int k) { return k < 3 ? 3 : k; }
+
+bool sep_u8x16_sides(int ky, int kx) {
+  ky = sep_side(ky), kx = sep_side(kx);
   const bool small = (ky == 3 || ky == 5 || ky == 7) && (kx == 3 || kx == 5 || kx == 7);
-  const bool nine = (ky == 9 && (kx == 7 || kx == 9)) || (ky == 7 && kx == 9);
-  const bool ks = small || nine;
-  return ks && w >= 16 && h >= 1;  // sides may be zero-padded past the image: the reflect map is total and a zero tap is exact
+  return small || (ky == 9 && (kx == 7 || kx == 9)) || (ky == 7 && kx == 9);
+}
+
+bool sep_u8x16_supported(int h, int w, int ky, int kx) {
+  return sep_u8x16_sides(ky, kx) && w >= 16 && h >= 1;  // sides may be zero-padded past the image: the reflect map is total
 }
 
 bool sep_u8x16_ties_supported(int h, int w, int ky, int kx) {
@@ -409,8 +414,9 @@ int launch_sep_u8x16(const uint8_t* x, uint8_t* y, const float* k1d_x, const flo
   a.x = x, a.y = y, a.h = h, a.wdt = w;
   a.ties = ties, a.tie_thresh = tie_thresh;
   fill_frames(a.fp);
-  for (int i = 0; i < kx; ++i) a.w[i] = k1d_x[i];
-  for (int j = 0; j < ky; ++j) a.w[kSepY + j] = k1d_y[j];
+  center_pad(k1d_x, kx, a.w, sep_side(kx));
+  center_pad(k1d_y, ky, a.w + kSepY, sep_side(ky));
+  kx = sep_side(kx), ky = sep_side(ky);
   int rows = 64;
   if (ky >= 7 || kx >= 7) {
     // the 7-tap instantiations hold 3 waves per SIMD = 3 workgroups per CU: with so few in flight a partial last round of

@@ -96,6 +96,21 @@ __device__ inline unsigned xcd_remap(unsigned bid, unsigned nblocks) {
 // round-half-to-even to uint8, as torch.round_() followed by .to(torch.uint8) on in-range values
 __device__ inline unsigned char round_u8(float v) { return (unsigned char)(int)__builtin_rintf(v); }
 
+// ---- centred zero-padding of host taps to a larger odd size that has a specialised kernel ------------------------------------
+// A zero tap is an exact no-op of the fma chain: the padded kernel gives the same bits.
+inline void center_pad(const float* src, int k, float* dst, int n) {
+  for (int i = 0; i < n; ++i) dst[i] = 0.f;
+  for (int i = 0; i < k; ++i) dst[(n - k) / 2 + i] = src[i];
+}
+// row-major ky x kx taps into ty x tx
+inline void center_pad2d(const float* src, int ky, int kx, float* dst, int ty, int tx) {
+  const int top = (ty - ky) / 2;
+  for (int j = 0; j < ty; ++j) {
+    if (j >= top && j < top + ky) center_pad(src + (j - top) * kx, kx, dst + j * tx, tx);
+    else for (int i = 0; i < tx; ++i) dst[j * tx + i] = 0.f;
+  }
+}
+
 // ---- exact uint8 Gaussian blur at separable cost (tiefix_u8.hip) --------------------------------------------------------------
 // The reference rounds ONE 2-D fp32 chain per pixel (V2); the separable pair (V1) is another association of the same sum and
 // differs from it by at most M = (kx * ky + kx + ky + 2) * 2^-17 (proof in tiefix_u8.hip), so round(V1) == round(V2) whenever V1
@@ -152,6 +167,7 @@ inline float tie_threshold(int kx, int ky) {
   return 0.5f - (m * 1.0625f + 1e-6f);
 }
 int64_t u8_tie_workspace_bytes(int64_t planes, int h, int w, int npx);
+int hybrid_npx(int kx, int ky);  // pixels per tie-list entry: 16 on k_dwk_u8's separable form, else k_sepstream's
 bool gaussian_blur_u8_hybrid_supported(int h, int w, int kx, int ky);
 int launch_gaussian_blur_u8_hybrid(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, const float* k1d_x, int kx,
                                    const float* k1d_y, int ky, void* workspace, int64_t workspace_bytes, hipStream_t s);
@@ -168,7 +184,9 @@ int launch_sharpness(const void* x, void* y, bool u8, int64_t planes, int h, int
 bool dwk_u8x16_supported(const uint8_t* x, const uint8_t* y, int h, int w, int ky, int kx, int border);
 int launch_dwk_u8x16(const uint8_t* x, uint8_t* y, const float* w2d, const float* k1d_x, const float* k1d_y,
                      int64_t planes, int h, int w, int ky, int kx, int border, hipStream_t s);
-// the same lane layout, separable form (row pass then systolic column chain): kernel sides in {3, 5, 7}, reflect border
+// the same lane layout, separable form (row pass then systolic column chain), reflect border.  Sides of 1 count as 3 (the
+// launcher zero-pads them); the side pairs built are {3, 5, 7}^2 and 9 x 7, 7 x 9, 9 x 9.
+bool sep_u8x16_sides(int ky, int kx);
 bool sep_u8x16_supported(int h, int w, int ky, int kx);
 bool sep_u8x16_ties_supported(int h, int w, int ky, int kx);  // the instantiation with the tie check: full 64-lane rows, no byte path
 int launch_sep_u8x16(const uint8_t* x, uint8_t* y, const float* k1d_x, const float* k1d_y, int64_t planes, int h, int w, int ky,

@@ -201,10 +201,7 @@ __global__ __launch_bounds__(256, KXB <= 23 ? 4 : 2) void k_u8_tie_fixup(const T
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static int hybrid_npx(int kx, int ky) {
-  const bool small = (kx <= 7 && ky <= 7) || (kx == 9 && (ky == 7 || ky == 9)) || (kx == 7 && ky == 9);
-  return small ? 16 : sepstream_u8_pixels_per_lane(kx, ky);
-}
+int hybrid_npx(int kx, int ky) { return sep_u8x16_sides(ky, kx) ? 16 : sepstream_u8_pixels_per_lane(kx, ky); }
 
 bool gaussian_blur_u8_hybrid_supported(int h, int w, int kx, int ky) {
   // From 25 taps up pair + tie check + fix-up beats the plain 2-D pass (32 x 4K uint8, tools/ab_u8_hybrid_threshold.py, identical
@@ -218,10 +215,7 @@ bool gaussian_blur_u8_hybrid_supported(int h, int w, int kx, int ky) {
   if (const char* e = tune_env("MV_U8_HYBRID_MIN_TAPS")) min_taps = atoi(e);
   if (kx > 63 || ky > 63 || kx * ky <= min_taps || h < 1) return false;
   if (tune_env("MV_U8_NO_HYBRID")) return false;
-  if (hybrid_npx(kx, ky) == 16) {
-    const int tx = kx < 3 ? 3 : kx, ty = ky < 3 ? 3 : ky;
-    return ky > 1 && sep_u8x16_ties_supported(h, w, ty, tx);
-  }
+  if (hybrid_npx(kx, ky) == 16) return ky > 1 && sep_u8x16_ties_supported(h, w, ky, kx);
   return sepstream_supported(nullptr, nullptr, true, h, w, kx, ky);
 }
 
@@ -260,17 +254,8 @@ int launch_gaussian_blur_u8_hybrid(const uint8_t* x, uint8_t* y, int64_t planes,
   const int64_t seg_cap = cap / kTieSegs;  // entries per segment (0 for a tiny workspace: nothing fits, the fix-up recomputes every pixel)
   hipLaunchKernelGGL(k_u8_tie_reset, dim3(1), dim3(kTieSegs), 0, s, T, (unsigned)seg_cap, (unsigned)npx);
   const float thresh = tie_threshold(kx, ky);
-  int rc;
-  if (npx == 16) {
-    float px[9], py[9];
-    const int tx = kx < 3 ? 3 : kx, ty = ky < 3 ? 3 : ky;
-    for (int i = 0; i < 9; ++i) px[i] = 0.f, py[i] = 0.f;
-    for (int i = 0; i < kx; ++i) px[(tx - kx) / 2 + i] = k1d_x[i];
-    for (int i = 0; i < ky; ++i) py[(ty - ky) / 2 + i] = k1d_y[i];
-    rc = launch_sep_u8x16(x, y, px, py, planes, h, w, ty, tx, s, T, thresh);
-  } else {
-    rc = launch_sepstream(x, y, true, planes, h, w, k1d_x, kx, k1d_y, ky, s, T, thresh);
-  }
+  const int rc = npx == 16 ? launch_sep_u8x16(x, y, k1d_x, k1d_y, planes, h, w, ky, kx, s, T, thresh)
+                           : launch_sepstream(x, y, true, planes, h, w, k1d_x, kx, k1d_y, ky, s, T, thresh);
   if (rc) return rc;
   TieFixArgs a = {};
   a.x = x, a.y = y, a.ties = T, a.h = h, a.w = w, a.kx = kx, a.ky = ky;
