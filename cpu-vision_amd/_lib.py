@@ -83,6 +83,8 @@ SYMBOLS = {
     "mv_preset_classification_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _vp, _i64, _vp]),
     "mv_maxpool2x2_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "mv_adaptive_avgpool_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "mv_elastic_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _fp, _vp]),
+    "mv_elastic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -851,4 +851,32 @@ int mv_preset_classification_f32(const float* x, float* y, int64_t n, int c, int
                 workspace_bytes, stream);
 }
 
+static int elastic(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int wdt, const float* base_x,
+                   const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
+                   const float* fill, void* stream) {
+  if (planes <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "elastic: bad shape planes=%lld (%d, %d)", (long long)planes, h, wdt);
+  if (channels <= 0 || planes % channels)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "elastic: planes (%lld) must be a multiple of channels (%d)", (long long)planes, channels);
+  if (mode != 0 && mode != 1) return set_error(MV_ERR_INVALID_ARGUMENT, "elastic: unknown mode %d (0 bilinear, 1 nearest)", mode);
+  if (!x || !y || !base_x || !base_y || !disp) return set_error(MV_ERR_INVALID_ARGUMENT, "elastic: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if ((int64_t)h * wdt > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "elastic: planes of %d x %d pixels exceed 2^31 - 1", h, wdt);
+  return launch_elastic(x, y, u8, planes, channels, h, wdt, base_x, base_y, disp, disp_sh, disp_sw, disp_sc, mode, fill,
+                        (hipStream_t)stream);
+}
+
+int mv_elastic_f32(const float* x, float* y, int64_t planes, int channels, int h, int wdt, const float* base_x,
+                   const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
+                   const float* fill, void* stream) {
+  return elastic(x, y, false, planes, channels, h, wdt, base_x, base_y, disp, disp_sh, disp_sw, disp_sc, mode, fill, stream);
+}
+
+int mv_elastic_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, int h, int wdt, const float* base_x,
+                  const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
+                  const float* fill, void* stream) {
+  return elastic(x, y, true, planes, channels, h, wdt, base_x, base_y, disp, disp_sh, disp_sw, disp_sc, mode, fill, stream);
+}
+
 }  // extern "C"

@@ -276,4 +276,11 @@ int launch_resize(const void* x, void* y, bool u8, int64_t planes, int channels,
                   int cl, int ch, int cw, int preset, const float* mean, const float* stdv, void* workspace,
                   int64_t workspace_bytes, hipStream_t s);
 
+// F.elastic: grid_sample of every plane at identity grid + displacement (elastic.hip).  base_x / base_y: the reference's
+// linspace vectors (W and H floats, device); disp (1, H, W, 2) fp32 by strides; mode 0 bilinear, 1 nearest; fill: NULL or
+// `channels` host floats (plane p takes fill[p % channels]).
+int launch_elastic(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int w, const float* base_x,
+                   const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
+                   const float* fill, hipStream_t s);
+
 }  // namespace mv

@@ -9,6 +9,8 @@ New operators on the same primitive (BASELINE cfg1/cfg3; the reference has no bo
   depthwise_conv2d, box_filter, separable_gaussian_blur, sobel, gaussian_sobel
 First CNN layer (models/vgg.py:81-85, ops/misc.py:97-119):
   conv2d_bias_relu
+ElasticTransform's resampling:
+  elastic / elastic_image / elastic_mask / elastic_video      transforms/v2/functional/_geometry.py (elastic*, _apply_grid_transform)
 
 Tensors must live on a HIP device; there is no CPU fallback (see _lib.py).  Host-side work here is what
 the reference also does on the host: argument checking, the handful of Gaussian taps, reshapes.
@@ -967,6 +969,138 @@ def center_crop_image(image: torch.Tensor, output_size: List[int]) -> torch.Tens
     """center_crop_image (_geometry.py:1860-1880): a view when the box lies inside the image, zero padding otherwise."""
     from . import functional_v1
     return functional_v1.center_crop(image, output_size)
+
+
+# --------------------------------------------------------------------------------------------- elastic (v2 surface)
+def elastic(inpt: torch.Tensor, displacement: torch.Tensor, interpolation="bilinear", fill=None) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_geometry.py `elastic`: resample `inpt` at identity grid + displacement."""
+    kernel = _get_kernel(elastic, type(inpt))
+    return kernel(inpt, displacement=displacement, interpolation=interpolation, fill=fill)
+
+
+elastic_transform = elastic
+
+# Pillow's integer constants (transforms/functional.py `_interpolation_modes_from_int`)
+_PIL_INTERPOLATION = {0: "nearest", 2: "bilinear", 3: "bicubic", 4: "box", 5: "hamming", 1: "lanczos"}
+_ELASTIC_MODES = {"bilinear": 0, "nearest": 1}
+
+
+def _interpolation_name(interpolation) -> str:
+    """_check_interpolation (_geometry.py): an InterpolationMode, its string value or a Pillow integer constant -> the mode's
+    string value."""
+    if isinstance(interpolation, int) and not isinstance(interpolation, bool):
+        if interpolation not in _PIL_INTERPOLATION:
+            raise ValueError(f"Interpolation mode {interpolation} is not supported.")
+        return _PIL_INTERPOLATION[interpolation]
+    name = getattr(interpolation, "value", interpolation)
+    if not isinstance(name, str):
+        raise ValueError(f"Argument interpolation should be an `InterpolationMode` or a corresponding Pillow integer constant, "
+                         f"but got {interpolation}.")
+    return name
+
+
+@functools.lru_cache(maxsize=64)
+def _identity_grid_vectors(h: int, w: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two linspace vectors of the reference's `_create_identity_grid`, computed by torch on the host exactly as the
+    reference computes them (ATen's vectorised arange: its bits are not the closed form start + i * step) and kept on the
+    device: W + H floats per frame size."""
+    bx = torch.linspace((-w + 1) / w, (w - 1) / w, w, dtype=torch.float32)
+    by = torch.linspace((-h + 1) / h, (h - 1) / h, h, dtype=torch.float32)
+    return bx.to(device), by.to(device)
+
+
+def _elastic_fill(fill, c: int):
+    """(host float array, channels) of the fill blend, or (None, 1).  The reference builds
+    torch.tensor(fill_list, dtype=float32).view(1, -1, 1, 1) and broadcasts it against C channels."""
+    if fill is None:
+        return None, 1
+    values = [float(v) for v in fill] if isinstance(fill, (tuple, list)) else [float(fill)]
+    if len(values) not in (1, c):
+        raise RuntimeError(f"The size of tensor a ({c}) must match the size of tensor b ({len(values)}) at non-singleton "
+                           "dimension 1: fill needs one value or one per channel")
+    return _lib.taps(values), len(values)
+
+
+@_register_kernel_internal(elastic, torch.Tensor)
+@_register_kernel_internal(elastic, tv_tensors.Image)
+def elastic_image(image: torch.Tensor, displacement: torch.Tensor, interpolation="bilinear", fill=None) -> torch.Tensor:
+    """elastic_image (_geometry.py) on (..., C, H, W) float32 / uint8 images: grid_sample(image, identity grid +
+    displacement, mode, padding_mode="zeros", align_corners=False) with the fill blend of the reference's ones-mask, as ONE
+    launch (mv_elastic_*) over every plane -- the reference's per-pixel arithmetic, bit for bit.
+    The identity grid is never materialised: the kernel adds the displacement to the two cached linspace vectors."""
+    if not isinstance(displacement, torch.Tensor):
+        raise TypeError("Argument displacement should be a Tensor")
+    mode = _interpolation_name(interpolation)
+    if image.ndim < 3:
+        raise ValueError(f"Expected tensor to be a tensor image of size (..., C, H, W). Got {tuple(image.shape)}.")
+    h, w = int(image.shape[-2]), int(image.shape[-1])
+    expected_shape = (1, h, w, 2)
+    if expected_shape != displacement.shape:
+        raise ValueError(f"Argument displacement shape should be {expected_shape}, but given {displacement.shape}")
+    if mode not in _ELASTIC_MODES:
+        raise NotImplementedError(f"elastic: interpolation {mode!r} is not on the MI355X path (bilinear and nearest are)")
+    if image.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise NotImplementedError(f"elastic: {image.dtype} images are not on the MI355X path (float32 and uint8 are)")
+    c = int(image.shape[-3])
+    fill_arr, fill_channels = _elastic_fill(fill, c)
+    if image.numel() == 0:
+        return image
+    _lib.require_device(image)
+    _lib.require_device(displacement, "displacement")
+    lib = _lib.load()
+    planes = image.numel() // (h * w)
+    with _lib.on_device_of(image):
+        bx, by = _identity_grid_vectors(h, w, image.device)
+        d = displacement.detach().to(dtype=torch.float32, device=image.device)  # the reference's .to(dtype, device): no copy when it fits
+        x = image.contiguous() if image.dtype != torch.bool else image.to(torch.float32).contiguous()
+        y = torch.empty_like(x, memory_format=torch.contiguous_format)
+        fn = lib.mv_elastic_u8 if x.dtype == torch.uint8 else lib.mv_elastic_f32
+        _lib.check(fn(x.data_ptr(), y.data_ptr(), planes, fill_channels, h, w, bx.data_ptr(), by.data_ptr(), d.data_ptr(),
+                      d.stride(1), d.stride(2), d.stride(3), _ELASTIC_MODES[mode], fill_arr, _lib.stream_ptr(x)))
+    if image.dtype == torch.bool:  # the reference's integer tail: round_().to(dtype)
+        return y.round_().to(torch.bool)
+    if image.dtype == torch.float32:
+        return _lib.forward_only(y, "elastic", image, displacement)
+    return y
+
+
+def _elastic_image_pil(image, displacement: torch.Tensor, interpolation="bilinear", fill=None):
+    """_elastic_image_pil (_geometry.py): pil_to_tensor -> elastic_image -> to_pil_image(mode=image.mode), the tensor on the
+    current HIP device for the kernel."""
+    t_img = _pil.pil_to_tensor(image)
+    output = elastic_image(t_img.to(_pil.device_for_host_inputs()), displacement=displacement, interpolation=interpolation,
+                           fill=fill)
+    return _pil.to_pil_image(output.cpu(), mode=image.mode)
+
+
+if _pil.PIL is not None:
+    _register_kernel_internal(elastic, _pil.PIL.Image.Image)(_elastic_image_pil)
+
+
+def elastic_mask(mask: torch.Tensor, displacement: torch.Tensor, fill=None) -> torch.Tensor:
+    """elastic_mask (_geometry.py): nearest, with a channel dimension added below 3-D."""
+    needs_squeeze = mask.ndim < 3
+    if needs_squeeze:
+        mask = mask.unsqueeze(0)
+    output = elastic_image(mask, displacement=displacement, interpolation="nearest", fill=fill)
+    return output.squeeze(0) if needs_squeeze else output
+
+
+@_register_kernel_internal(elastic, tv_tensors.Mask, tv_tensor_wrapper=False)
+def _elastic_mask_dispatch(inpt: torch.Tensor, displacement: torch.Tensor, fill=None, **kwargs) -> torch.Tensor:
+    output = elastic_mask(inpt.as_subclass(torch.Tensor), displacement=displacement, fill=fill)
+    return tv_tensors.wrap(output, like=inpt)
+
+
+@_register_kernel_internal(elastic, tv_tensors.BoundingBoxes, tv_tensor_wrapper=False)
+def _elastic_bounding_boxes_dispatch(inpt: torch.Tensor, displacement: torch.Tensor, **kwargs) -> torch.Tensor:
+    """Boxes are not warped here: passed through, they would come back unmoved -- silently wrong -- so they raise."""
+    raise NotImplementedError("elastic: warping BoundingBoxes (elastic_bounding_boxes) is not implemented on the MI355X path")
+
+
+@_register_kernel_internal(elastic, tv_tensors.Video)
+def elastic_video(video: torch.Tensor, displacement: torch.Tensor, interpolation="bilinear", fill=None) -> torch.Tensor:
+    return elastic_image(video, displacement, interpolation=interpolation, fill=fill)
 
 
 def to_dtype(inpt: torch.Tensor, dtype: torch.dtype = torch.float, scale: bool = False) -> torch.Tensor:

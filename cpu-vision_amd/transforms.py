@@ -4,7 +4,8 @@
   GaussianBlur (v2)                       transforms/v2/_misc.py:168-205
   RandomAdjustSharpness (v2)              transforms/v2/_color.py:356-376 (+ _RandomApplyTransform, _transform.py:~150-190)
   GaussianBlurV1                          transforms/transforms.py:1753-1812
-  ElasticTransform._get_params            transforms/v2/_geometry.py:1054-1075 (noise field -> gaussian_blur -> displacement)
+  ElasticTransform                        transforms/v2/_geometry.py:1003-1085 (noise field -> gaussian_blur -> displacement
+                                          -> F.elastic)
   Resize / CenterCrop / ToDtype / Normalize / Compose   v2/_geometry.py:76-193, v2/_misc.py:134-304, v2/_container.py:10-64
 
 Parameter sampling stays on the host RNG exactly like the reference (torch.empty(1).uniform_ / torch.rand(1)).
@@ -327,25 +328,85 @@ class Compose(Transform):
         return "\n".join(f"    {t}" for t in self.transforms)
 
 
+def _check_fill_arg(fill) -> None:
+    """transforms/v2/_utils.py `_check_fill_arg`."""
+    if isinstance(fill, dict):
+        for value in fill.values():
+            _check_fill_arg(value)
+    elif fill is not None and not isinstance(fill, (numbers.Number, tuple, list)):
+        raise TypeError("Got inappropriate fill arg, only Numbers, tuples, lists and dicts are allowed.")
+
+
+def _convert_fill_arg(fill):
+    """transforms/v2/_utils.py `_convert_fill_arg`: fill = 0 is not fill = None (None skips the blend)."""
+    if fill is None:
+        return fill
+    if not isinstance(fill, (int, float)):
+        fill = [float(v) for v in list(fill)]
+    return fill
+
+
+def _setup_fill_arg(fill):
+    """transforms/v2/_utils.py `_setup_fill_arg`: a {type: fill} dict, or one fill for every type."""
+    _check_fill_arg(fill)
+    if isinstance(fill, dict):
+        for k, v in fill.items():
+            fill[k] = _convert_fill_arg(v)
+        return fill
+    return {"others": _convert_fill_arg(fill)}
+
+
+def _get_fill(fill_dict, inpt_type):
+    """transforms/v2/_utils.py `_get_fill` (a dict with neither the type nor "others" gives None, as the reference's does)."""
+    if inpt_type in fill_dict:
+        return fill_dict[inpt_type]
+    if "others" in fill_dict:
+        return fill_dict["others"]
+    return None
+
+
+_PIL_INTERPOLATION_MODES = {0: InterpolationMode.NEAREST, 2: InterpolationMode.BILINEAR, 3: InterpolationMode.BICUBIC,
+                            4: InterpolationMode.BOX, 5: InterpolationMode.HAMMING, 1: InterpolationMode.LANCZOS}
+
+
+def _check_interpolation(interpolation) -> InterpolationMode:
+    """transforms/v2/functional/_geometry.py `_check_interpolation`: an InterpolationMode or a Pillow integer constant; its
+    string value ("bilinear") is accepted as well."""
+    if isinstance(interpolation, int) and not isinstance(interpolation, bool):
+        if interpolation not in _PIL_INTERPOLATION_MODES:
+            raise ValueError(f"Interpolation mode {interpolation} is not supported.")
+        return _PIL_INTERPOLATION_MODES[interpolation]
+    if isinstance(interpolation, str):
+        try:
+            return InterpolationMode(interpolation)
+        except ValueError:
+            pass
+    elif isinstance(interpolation, InterpolationMode):
+        return interpolation
+    raise ValueError(f"Argument interpolation should be an `InterpolationMode` or a corresponding Pillow integer constant, "
+                     f"but got {interpolation}.")
+
+
 class ElasticTransform(Transform):
-    """v2.ElasticTransform(alpha=50.0, sigma=5.0, ...) -- transforms/v2/_geometry.py:1003-1085.
+    """v2.ElasticTransform(alpha=50.0, sigma=5.0, interpolation=BILINEAR, fill=0) -- transforms/v2/_geometry.py:1003-1085.
 
-    `_get_params` is the caller of the hot path mirrored here (row a9): a U(-1, 1) noise field per axis, blurred with a
-    Gaussian of `k = int(8 * sigma + 1) | 1` taps per side, scaled by `alpha / size`.  The noise is drawn from the HOST
-    generator with the reference's calls in the reference's order (`torch.rand([1, 1, H, W]) * 2 - 1`, dx then dy), so a
-    seeded pipeline samples the same displacement field; the blur -- the expensive part: 41 x 41 taps at the default
-    sigma = 5 -- runs on the MI355X and the field stays there (`displacement.device` is the HIP device).
+    `_get_params` (row a9): a U(-1, 1) noise field per axis, blurred with a Gaussian of `k = int(8 * sigma + 1) | 1` taps per
+    side, scaled by `alpha / size`.  The noise is drawn from the HOST generator with the reference's calls in the reference's
+    order (`torch.rand([1, 1, H, W]) * 2 - 1`, dx then dy), so a seeded pipeline samples the same displacement field; the
+    blur -- 41 x 41 taps at the default sigma = 5 -- runs on the MI355X and the field stays there.
 
-    Applying the field (`F.elastic` = grid_sample, _geometry.py:1077-1085) is a geometric resampling outside this
-    library's path: `_transform` says so; pass `params["displacement"]` to the resampler you use."""
+    `_transform` applies the field with `F.elastic` (one mv_elastic_* launch per image, video or mask: grid_sample at
+    identity grid + displacement and the fill blend, the reference's bits).  `fill` is the reference's: a number, a
+    sequence, None (no blend) or a {type: fill} dict; masks are resampled with nearest; BoundingBoxes raise (not warped)."""
 
     def __init__(self, alpha: Union[float, Sequence[float]] = 50.0, sigma: Union[float, Sequence[float]] = 5.0,
-                 interpolation="bilinear", fill=0) -> None:
+                 interpolation: Union[InterpolationMode, str, int] = InterpolationMode.BILINEAR, fill=0) -> None:
         super().__init__()
         self.alpha = _setup_number_or_seq(alpha, "alpha")
         self.sigma = _setup_number_or_seq(sigma, "sigma")
-        self.interpolation = interpolation
+        self.interpolation = _check_interpolation(interpolation)
         self.fill = fill
+        self._fill = _setup_fill_arg(fill)
 
     def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
         size = list(query_size(flat_inputs))
@@ -376,10 +437,12 @@ class ElasticTransform(Transform):
         return self._get_params(flat_inputs)
 
     def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
-        raise NotImplementedError(
-            "ElasticTransform: applying the displacement field (F.elastic = grid_sample) is a geometric resampling outside "
-            "this library's filtering path; use get_params(sample)['displacement'] (sampled and blurred on the MI355X) with "
-            "your resampler.")
+        if "displacement" not in params:
+            raise NotImplementedError(
+                "ElasticTransform: the params hold no displacement field to resample with grid_sample (F.elastic); use "
+                "forward() or get_params(sample).")
+        fill = _get_fill(self._fill, type(inpt))
+        return self._call_kernel(F.elastic, inpt, **params, fill=fill, interpolation=self.interpolation)
 
 
 class GaussianBlurV1(nn.Module):

@@ -337,6 +337,22 @@ int mv_preset_classification_u8(const uint8_t* x, float* y, int64_t n, int c, in
 int mv_preset_classification_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int oh, int ow, int crop_top,
                                  int crop_left, int crop_h, int crop_w, const float* mean, const float* stdv,
                                  void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- ElasticTransform's resampling: F.elastic (transforms/v2/functional/_geometry.py elastic_image /
+ * _apply_grid_transform) = grid_sample(image, identity grid + displacement, mode, padding_mode="zeros",
+ * align_corners=False), then the fill blend of the resampled ones-mask (bilinear: ((v - fill) * m) + fill; nearest:
+ * fill where the sample left the frame), then round half to even for uint8.  x, y are (planes, h, w); every plane is
+ * resampled with the same field.  base_x / base_y are DEVICE arrays of w / h floats: the identity grid's
+ * torch.linspace((1 - n) / n, (n - 1) / n, n) vectors as the caller's torch computed them (their bits are ATen's
+ * vectorised arange, not a closed form).  disp is the DEVICE (1, h, w, 2) fp32 field, element (i, j, c) at
+ * disp[i * disp_sh + j * disp_sw + c * disp_sc] (any strides: interleaved or the dx-plane / dy-plane permute of
+ * ElasticTransform._get_params).  mode: 0 bilinear, 1 nearest.  fill: NULL (no blend) or a HOST array of `channels`
+ * floats (plane p takes fill[p % channels]; at most 16); planes must be a multiple of channels.  h * w < 2^31. */
+int mv_elastic_f32(const float* x, float* y, int64_t planes, int channels, int h, int wdt, const float* base_x,
+                   const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
+                   const float* fill, void* stream);
+int mv_elastic_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, int h, int wdt, const float* base_x,
+                  const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
+                  const float* fill, void* stream);
 /* The same convolution with K SLICES ACROSS WORKGROUPS for launches too small to fill the chip with one chain per output (VGG's
  * 512 -> 512 layers at batch 1: ~50 workgroups walking 128 K chunks each).  mv_conv3x3_k_slices() states the summation order for a
  * shape -- 1: the single chain of mv_conv3x3_bias_relu_f32; otherwise that many chains over `slice_channels` input channels each
