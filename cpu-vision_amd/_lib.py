@@ -85,6 +85,8 @@ SYMBOLS = {
     "mv_adaptive_avgpool_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_elastic_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _fp, _vp]),
     "mv_elastic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _fp, _vp]),
+    "mv_warp_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _fp, _vp]),
+    "mv_warp_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

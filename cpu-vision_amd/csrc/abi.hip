@@ -879,4 +879,32 @@ int mv_elastic_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, in
   return elastic(x, y, true, planes, channels, h, wdt, base_x, base_y, disp, disp_sh, disp_sw, disp_sc, mode, fill, stream);
 }
 
+static int warp(const void* x, void* y, bool u8, int64_t planes, int channels, int ih, int iw, int oh, int ow,
+                const float* coeffs, int kind, int order, int mode, const float* fill, void* stream) {
+  if (planes <= 0 || ih <= 0 || iw <= 0 || oh <= 0 || ow <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "warp: bad shape planes=%lld (%d, %d) -> (%d, %d)", (long long)planes, ih, iw, oh,
+                     ow);
+  if (channels <= 0 || planes % channels)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "warp: planes (%lld) must be a multiple of channels (%d)", (long long)planes, channels);
+  if (kind != 0 && kind != 1) return set_error(MV_ERR_INVALID_ARGUMENT, "warp: unknown kind %d (0 affine, 1 perspective)", kind);
+  if (order != 0 && order != 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "warp: unknown grid order %d (0 plain sum, 1 fma chain)", order);
+  if (mode != 0 && mode != 1) return set_error(MV_ERR_INVALID_ARGUMENT, "warp: unknown mode %d (0 bilinear, 1 nearest)", mode);
+  if (!x || !y || !coeffs) return set_error(MV_ERR_INVALID_ARGUMENT, "warp: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if ((int64_t)ih * iw > 0x7fffffffLL || (int64_t)oh * ow > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "warp: planes of %d x %d -> %d x %d pixels exceed 2^31 - 1", ih, iw, oh, ow);
+  return launch_warp(x, y, u8, planes, channels, ih, iw, oh, ow, coeffs, kind, order, mode, fill, (hipStream_t)stream);
+}
+
+int mv_warp_f32(const float* x, float* y, int64_t planes, int channels, int ih, int iw, int oh, int ow, const float* coeffs,
+                int kind, int order, int mode, const float* fill, void* stream) {
+  return warp(x, y, false, planes, channels, ih, iw, oh, ow, coeffs, kind, order, mode, fill, stream);
+}
+
+int mv_warp_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, int ih, int iw, int oh, int ow, const float* coeffs,
+               int kind, int order, int mode, const float* fill, void* stream) {
+  return warp(x, y, true, planes, channels, ih, iw, oh, ow, coeffs, kind, order, mode, fill, stream);
+}
+
 }  // extern "C"

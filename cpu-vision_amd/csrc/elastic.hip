@@ -2,7 +2,7 @@
 // _geometry.py `elastic_image` / `_apply_grid_transform`): grid = identity grid + displacement, then grid_sample(mode,
 // padding_mode="zeros", align_corners=False), with the optional fill blended through a resampled ones-mask.  The reference
 // runs these ops on torch-CPU; the arithmetic below is ATen's vectorised CPU grid_sampler per pixel, so the results are its
-// bits:
+// bits (the per-pixel sampling core lives in mv_gridsample.h, shared with warp.hip):
 //   gx = base_x[j] + dx,  x = fma(gx + 1, W / 2, -0.5)        (the same for y; base_* = the reference's own linspace)
 //   bilinear  x0 = floor(x), w = x - x0, e = 1 - w (n, s for y);  nw = s*e, ne = s*w, sw = n*e, se = n*w
 //             acc = v_nw*nw; acc = fma(v_ne, ne, acc); acc = fma(v_sw, sw, acc); acc = fma(v_se, se, acc)
@@ -20,37 +20,18 @@
 // 4-row tile (one row segment per wave); tiles are dealt to the XCDs in contiguous runs (xcd_remap) so the neighbouring rows
 // every bilinear tap reads meet in one L2.  Small frames split the planes over several workgroups per tile (each re-reads the
 // 8 B/pixel field) so the grid still fills the chip.
-#include "mv_common.h"
+#include "mv_gridsample.h"
 
 namespace mv {
 
 namespace {
 
-constexpr int kElasticMaxFill = 16;  // fill values by value in the kernel arguments (per channel; a scalar fill is 1 channel)
+constexpr int kElasticMaxFill = gs::kMaxFill;
 constexpr int kTileW = 256;          // pixels per wave row segment (64 lanes x 4)
 constexpr int kTileH = 4;            // rows per workgroup (one wave each)
 
-struct Fill {
-  float v[kElasticMaxFill];
-};
-
-template <typename T>
-__device__ inline float load_f(const T* p) { return (float)*p; }
-
-template <typename T>
-__device__ inline T narrow(float v);
-template <>
-__device__ inline float narrow<float>(float v) { return v; }
-template <>
-__device__ inline uint8_t narrow<uint8_t>(float v) { return round_u8(v); }
-
-// the 2-element corner pair at p[0], p[1] (x0 and x0 + 1 of one row) as one load where the target allows it
-template <typename T>
-__device__ inline void load_pair(const T* p, float& a, float& b) {
-  struct alignas(sizeof(T)) Pair { T v[2]; } q;
-  __builtin_memcpy(&q, p, sizeof(q));
-  a = (float)q.v[0], b = (float)q.v[1];
-}
+using gs::Fill;
+using gs::narrow;
 
 // T: float or uint8_t.  NEAREST: mode.  FILL: blend with fill.v[plane % channels].  VEC (uint8): the lane's 4 pixels are one
 // aligned dword store; otherwise pixel-wise stores that stop at the end of the row.  PAIR (bilinear, w >= 2): corner pairs.
@@ -71,10 +52,8 @@ __global__ __launch_bounds__(256) void k_elastic(const T* __restrict__ x, T* __r
   const long long p1 = p0 + chunk_planes < planes ? p0 + chunk_planes : planes;
 
   const float hw_x = (float)w * 0.5f, hw_y = (float)h * 0.5f;
-  const float fw = (float)w, fh = (float)h;
   const float gy0 = base_y[i];
-  // per pixel: corner offsets in the plane (clamped: always a legal address) and weights with the out-of-bounds corners zeroed
-  // through the in-bounds flags (bit 0..3 = nw, ne, sw, se; nearest: bit 0)
+  // per pixel: corner offsets, weights and in-bounds bits (gs::setup)
   int off[4][4];
   float wt[4][4];
   unsigned inb[4];
@@ -86,45 +65,13 @@ __global__ __launch_bounds__(256) void k_elastic(const T* __restrict__ x, T* __r
     const float gy = gy0 + d[ds_c];
     const float xs = __builtin_fmaf(gx + 1.f, hw_x, -0.5f);
     const float ys = __builtin_fmaf(gy + 1.f, hw_y, -0.5f);
-    if (NEAREST) {
-      // clamp before the int conversion: far-out samples (and NaN) become out-of-bounds indices, never UB
-      const int ix = (int)__builtin_fminf(__builtin_fmaxf(__builtin_rintf(xs), -1.f), fw);
-      const int iy = (int)__builtin_fminf(__builtin_fmaxf(__builtin_rintf(ys), -1.f), fh);
-      inb[k] = (ix >= 0 && ix < w && iy >= 0 && iy < h) ? 1u : 0u;
-      const int cx = ix < 0 ? 0 : (ix >= w ? w - 1 : ix), cy = iy < 0 ? 0 : (iy >= h ? h - 1 : iy);
-      off[k][0] = cy * w + cx;
-    } else {
-      const float x0 = __builtin_floorf(xs), y0 = __builtin_floorf(ys);
-      const float ww = xs - x0, ee = 1.f - ww, nn = ys - y0, ss = 1.f - nn;
-      wt[k][0] = ss * ee, wt[k][1] = ss * ww, wt[k][2] = nn * ee, wt[k][3] = nn * ww;
-      const int ix = (int)__builtin_fminf(__builtin_fmaxf(x0, -2.f), fw);
-      const int iy = (int)__builtin_fminf(__builtin_fmaxf(y0, -2.f), fh);
-      const bool in_x0 = ix >= 0 && ix < w, in_x1 = ix + 1 >= 0 && ix + 1 < w;
-      const bool in_y0 = iy >= 0 && iy < h, in_y1 = iy + 1 >= 0 && iy + 1 < h;
-      inb[k] = (in_y0 && in_x0 ? 1u : 0u) | (in_y0 && in_x1 ? 2u : 0u) | (in_y1 && in_x0 ? 4u : 0u) | (in_y1 && in_x1 ? 8u : 0u);
-      const int cx0 = ix < 0 ? 0 : (ix >= w ? w - 1 : ix), cx1 = ix + 1 < 0 ? 0 : (ix + 1 >= w ? w - 1 : ix + 1);
-      const int cy0 = iy < 0 ? 0 : (iy >= h ? h - 1 : iy), cy1 = iy + 1 < 0 ? 0 : (iy + 1 >= h ? h - 1 : iy + 1);
-      if (PAIR) {
-        // pair start px in [0, w - 2]: ix == px -> (nw, ne) = (a, b); ix == -1 -> ne = a; ix == w - 1 -> nw = b (the corner
-        // outside the row is masked out anyway).  Bits 4 / 5: take a for nw / ne.
-        const int px = ix < 0 ? 0 : (ix > w - 2 ? w - 2 : ix);
-        inb[k] |= (ix == px ? 16u : 0u) | (ix + 1 == px ? 32u : 0u);
-        off[k][0] = cy0 * w + px, off[k][2] = cy1 * w + px;
-      } else {
-        off[k][0] = cy0 * w + cx0, off[k][1] = cy0 * w + cx1, off[k][2] = cy1 * w + cx0, off[k][3] = cy1 * w + cx1;
-      }
-    }
+    gs::setup<NEAREST, PAIR>(xs, ys, h, w, off[k], wt[k], inb[k]);
   }
   // the fill mask: the resampled ones-channel of the reference, per pixel (independent of the plane)
-  float msk[4];
+  float msk[4] = {};
   if (FILL && !NEAREST) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float m = (inb[k] & 1u ? 1.f : 0.f) * wt[k][0];
-      m = __builtin_fmaf(inb[k] & 2u ? 1.f : 0.f, wt[k][1], m);
-      m = __builtin_fmaf(inb[k] & 4u ? 1.f : 0.f, wt[k][2], m);
-      msk[k] = __builtin_fmaf(inb[k] & 8u ? 1.f : 0.f, wt[k][3], m);
-    }
+    for (int k = 0; k < 4; ++k) msk[k] = gs::fill_mask(wt[k], inb[k]);
   }
 
   const size_t plane_elems = (size_t)h * w;
@@ -135,35 +82,8 @@ __global__ __launch_bounds__(256) void k_elastic(const T* __restrict__ x, T* __r
     const T* src = x + (size_t)p * plane_elems;
     float out[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float r;
-      if (NEAREST) {
-        const float v = load_f(src + off[k][0]);
-        r = FILL ? (inb[k] ? v : fill.v[c]) : (inb[k] ? v : 0.f);
-      } else {
-        float v0, v1, v2, v3;
-        if (PAIR) {
-          float a0, b0, a1, b1;
-          load_pair(src + off[k][0], a0, b0);
-          load_pair(src + off[k][2], a1, b1);
-          v0 = inb[k] & 16u ? a0 : b0, v1 = inb[k] & 32u ? a0 : b0;
-          v2 = inb[k] & 16u ? a1 : b1, v3 = inb[k] & 32u ? a1 : b1;
-        } else {
-          v0 = load_f(src + off[k][0]), v1 = load_f(src + off[k][1]);
-          v2 = load_f(src + off[k][2]), v3 = load_f(src + off[k][3]);
-        }
-        float acc = (inb[k] & 1u ? v0 : 0.f) * wt[k][0];
-        acc = __builtin_fmaf(inb[k] & 2u ? v1 : 0.f, wt[k][1], acc);
-        acc = __builtin_fmaf(inb[k] & 4u ? v2 : 0.f, wt[k][2], acc);
-        acc = __builtin_fmaf(inb[k] & 8u ? v3 : 0.f, wt[k][3], acc);
-        if (FILL) {
-          const float f = fill.v[c];
-          acc = ((acc - f) * msk[k]) + f;  // three roundings (sub_, mul_, add_): -ffp-contract=off keeps them apart
-        }
-        r = acc;
-      }
-      out[k] = r;
-    }
+    for (int k = 0; k < 4; ++k)
+      out[k] = gs::sample<T, NEAREST, FILL, PAIR>(src, off[k], wt[k], inb[k], msk[k], FILL ? fill.v[c] : 0.f);
     T* dst = y + (size_t)p * plane_elems + row;
     if (VEC && !kStrided) {
       const unsigned o = (unsigned)narrow<T>(out[0]) | ((unsigned)narrow<T>(out[1]) << 8) |
@@ -212,13 +132,8 @@ int launch(const T* x, T* y, int64_t planes, int channels, int h, int w, const f
     for (int k = 0; k < channels; ++k) fill.v[k] = fill_host[k];
   const int tiles_x = (w + kTileW - 1) / kTileW, tiles_y = (h + kTileH - 1) / kTileH;
   const long long tiles = (long long)tiles_x * tiles_y;
-  // at least ~2048 workgroups (8 per CU) when the frame alone gives fewer: the planes go to several workgroups per tile
-  long long chunks = (2048 + tiles - 1) / tiles;
-  if (chunks > planes) chunks = planes;
-  if (chunks < 1) chunks = 1;
-  const long long chunk_planes = (planes + chunks - 1) / chunks;
-  chunks = (planes + chunk_planes - 1) / chunk_planes;
-  if (tiles * chunks > 0x7fffffffLL || chunk_planes > 0x7fffffffLL)
+  long long chunks, chunk_planes;
+  if (!gs::plan_chunks(tiles, planes, chunks, chunk_planes))
     return set_error(MV_ERR_UNSUPPORTED, "elastic: grid of %lld tiles x %lld plane chunks is too large", tiles, chunks);
   const dim3 grid((unsigned)(tiles * chunks));
   const bool vec = sizeof(T) == 1 && w % 4 == 0 && ((uintptr_t)y % 4) == 0;  // float stores are per pixel (coalesced)

@@ -283,4 +283,10 @@ int launch_elastic(const void* x, void* y, bool u8, int64_t planes, int channels
                    const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
                    const float* fill, hipStream_t s);
 
+// F.affine / F.rotate / F.perspective: grid_sample of every (ih, iw) plane at a grid computed per (oh, ow) output pixel from 8
+// host floats (warp.hip; layout and arithmetic in mi355vision.h mv_warp_f32).  kind 0 affine, 1 perspective; order 1 the fma
+// chain, 0 the plain sum (the rounding of the reference's CPU bmm); mode 0 bilinear, 1 nearest; fill as launch_elastic.
+int launch_warp(const void* x, void* y, bool u8, int64_t planes, int channels, int ih, int iw, int oh, int ow, const float* coeffs,
+                int kind, int order, int mode, const float* fill, hipStream_t s);
+
 }  // namespace mv

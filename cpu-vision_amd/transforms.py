@@ -6,6 +6,7 @@
   GaussianBlurV1                          transforms/transforms.py:1753-1812
   ElasticTransform                        transforms/v2/_geometry.py:1003-1085 (noise field -> gaussian_blur -> displacement
                                           -> F.elastic)
+  RandomRotation / RandomAffine / RandomPerspective   transforms/v2/_geometry.py (-> F.rotate / F.affine / F.perspective)
   Resize / CenterCrop / ToDtype / Normalize / Compose   v2/_geometry.py:76-193, v2/_misc.py:134-304, v2/_container.py:10-64
 
 Parameter sampling stays on the host RNG exactly like the reference (torch.empty(1).uniform_ / torch.rand(1)).
@@ -13,7 +14,7 @@ Parameter sampling stays on the host RNG exactly like the reference (torch.empty
 from __future__ import annotations
 
 import numbers
-from typing import Any, Callable, Dict, List, Sequence, Union
+from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import torch
 from torch import nn
@@ -443,6 +444,165 @@ class ElasticTransform(Transform):
                 "forward() or get_params(sample).")
         fill = _get_fill(self._fill, type(inpt))
         return self._call_kernel(F.elastic, inpt, **params, fill=fill, interpolation=self.interpolation)
+
+
+def _check_sequence_input(x, name: str, req_sizes) -> None:
+    """transforms/v2/_utils.py `_check_sequence_input`."""
+    msg = req_sizes[0] if len(req_sizes) < 2 else " or ".join([str(s) for s in req_sizes])
+    if not isinstance(x, Sequence):
+        raise TypeError(f"{name} should be a sequence of length {msg}.")
+    if len(x) not in req_sizes:
+        raise ValueError(f"{name} should be a sequence of length {msg}.")
+
+
+def _setup_angle(x, name: str, req_sizes=(2,)) -> List[float]:
+    """transforms/v2/_utils.py `_setup_angle`: a number d gives [-d, d]."""
+    if isinstance(x, numbers.Number):
+        if x < 0:
+            raise ValueError(f"If {name} is a single number, it must be positive.")
+        x = [-x, x]
+    else:
+        _check_sequence_input(x, name, req_sizes)
+    return [float(d) for d in x]
+
+
+class RandomRotation(Transform):
+    """v2.RandomRotation(degrees, interpolation=NEAREST, expand=False, center=None, fill=0) -- transforms/v2/_geometry.py.
+
+    The angle is drawn from the host generator as the reference draws it (`torch.empty(1).uniform_`); `F.rotate` resamples
+    images, videos and masks (nearest) in one mv_warp_* launch each.  The default fill = 0 runs the fill blend, which for
+    bilinear is not the same as fill=None."""
+
+    def __init__(self, degrees: Union[numbers.Number, Sequence], interpolation=InterpolationMode.NEAREST, expand: bool = False,
+                 center: Optional[List[float]] = None, fill=0) -> None:
+        super().__init__()
+        self.degrees = _setup_angle(degrees, name="degrees", req_sizes=(2,))
+        self.interpolation = _check_interpolation(interpolation)
+        self.expand = expand
+        self.fill = fill
+        self._fill = _setup_fill_arg(fill)
+        if center is not None:
+            _check_sequence_input(center, "center", req_sizes=(2,))
+        self.center = center
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        angle = torch.empty(1).uniform_(self.degrees[0], self.degrees[1]).item()
+        return dict(angle=angle)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        fill = _get_fill(self._fill, type(inpt))
+        return self._call_kernel(F.rotate, inpt, **params, interpolation=self.interpolation, expand=self.expand,
+                                 center=self.center, fill=fill)
+
+
+class RandomAffine(Transform):
+    """v2.RandomAffine(degrees, translate=None, scale=None, shear=None, interpolation=NEAREST, fill=0, center=None) --
+    transforms/v2/_geometry.py.  `_get_params` draws angle, translation, scale and shear from the host generator with the
+    reference's calls in the reference's order; `F.affine` resamples in one mv_warp_* launch per image, video or mask."""
+
+    def __init__(self, degrees: Union[numbers.Number, Sequence], translate: Optional[Sequence[float]] = None,
+                 scale: Optional[Sequence[float]] = None, shear: Optional[Union[int, float, Sequence[float]]] = None,
+                 interpolation=InterpolationMode.NEAREST, fill=0, center: Optional[List[float]] = None) -> None:
+        super().__init__()
+        self.degrees = _setup_angle(degrees, name="degrees", req_sizes=(2,))
+        if translate is not None:
+            _check_sequence_input(translate, "translate", req_sizes=(2,))
+            for t in translate:
+                if not (0.0 <= t <= 1.0):
+                    raise ValueError("translation values should be between 0 and 1")
+        self.translate = translate
+        if scale is not None:
+            _check_sequence_input(scale, "scale", req_sizes=(2,))
+            for s in scale:
+                if s <= 0:
+                    raise ValueError("scale values should be positive")
+        self.scale = scale
+        if shear is not None:
+            self.shear = _setup_angle(shear, name="shear", req_sizes=(2, 4))
+        else:
+            self.shear = shear
+        self.interpolation = _check_interpolation(interpolation)
+        self.fill = fill
+        self._fill = _setup_fill_arg(fill)
+        if center is not None:
+            _check_sequence_input(center, "center", req_sizes=(2,))
+        self.center = center
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        height, width = query_size(flat_inputs)
+        angle = torch.empty(1).uniform_(self.degrees[0], self.degrees[1]).item()
+        if self.translate is not None:
+            max_dx = float(self.translate[0] * width)
+            max_dy = float(self.translate[1] * height)
+            tx = int(round(torch.empty(1).uniform_(-max_dx, max_dx).item()))
+            ty = int(round(torch.empty(1).uniform_(-max_dy, max_dy).item()))
+            translate = (tx, ty)
+        else:
+            translate = (0, 0)
+        if self.scale is not None:
+            scale = torch.empty(1).uniform_(self.scale[0], self.scale[1]).item()
+        else:
+            scale = 1.0
+        shear_x = shear_y = 0.0
+        if self.shear is not None:
+            shear_x = torch.empty(1).uniform_(self.shear[0], self.shear[1]).item()
+            if len(self.shear) == 4:
+                shear_y = torch.empty(1).uniform_(self.shear[2], self.shear[3]).item()
+        shear = (shear_x, shear_y)
+        return dict(angle=angle, translate=translate, scale=scale, shear=shear)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        fill = _get_fill(self._fill, type(inpt))
+        return self._call_kernel(F.affine, inpt, **params, interpolation=self.interpolation, fill=fill, center=self.center)
+
+
+class RandomPerspective(_RandomApplyTransform):
+    """v2.RandomPerspective(distortion_scale=0.5, p=0.5, interpolation=BILINEAR, fill=0) -- transforms/v2/_geometry.py.
+    `_get_params` draws the four displaced corners with the reference's `torch.randint` calls in its order and solves the 8
+    coefficients on the host (float64 least squares); `F.perspective` resamples in one mv_warp_* launch."""
+
+    def __init__(self, distortion_scale: float = 0.5, p: float = 0.5, interpolation=InterpolationMode.BILINEAR,
+                 fill=0) -> None:
+        super().__init__(p=p)
+        if not (0 <= distortion_scale <= 1):
+            raise ValueError("Argument distortion_scale value should be between 0 and 1")
+        self.distortion_scale = distortion_scale
+        self.interpolation = _check_interpolation(interpolation)
+        self.fill = fill
+        self._fill = _setup_fill_arg(fill)
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        height, width = query_size(flat_inputs)
+        distortion_scale = self.distortion_scale
+        half_height = height // 2
+        half_width = width // 2
+        bound_height = int(distortion_scale * half_height) + 1
+        bound_width = int(distortion_scale * half_width) + 1
+        topleft = [
+            int(torch.randint(0, bound_width, size=(1,))),
+            int(torch.randint(0, bound_height, size=(1,))),
+        ]
+        topright = [
+            int(torch.randint(width - bound_width, width, size=(1,))),
+            int(torch.randint(0, bound_height, size=(1,))),
+        ]
+        botright = [
+            int(torch.randint(width - bound_width, width, size=(1,))),
+            int(torch.randint(height - bound_height, height, size=(1,))),
+        ]
+        botleft = [
+            int(torch.randint(0, bound_width, size=(1,))),
+            int(torch.randint(height - bound_height, height, size=(1,))),
+        ]
+        startpoints = [[0, 0], [width - 1, 0], [width - 1, height - 1], [0, height - 1]]
+        endpoints = [topleft, topright, botright, botleft]
+        perspective_coeffs = F._get_perspective_coeffs(startpoints, endpoints)
+        return dict(coefficients=perspective_coeffs)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        fill = _get_fill(self._fill, type(inpt))
+        return self._call_kernel(F.perspective, inpt, startpoints=None, endpoints=None, fill=fill,
+                                 interpolation=self.interpolation, **params)
 
 
 class GaussianBlurV1(nn.Module):

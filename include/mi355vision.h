@@ -353,6 +353,21 @@ int mv_elastic_f32(const float* x, float* y, int64_t planes, int channels, int h
 int mv_elastic_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, int h, int wdt, const float* base_x,
                   const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
                   const float* fill, void* stream);
+/* ---- F.affine / F.rotate / F.perspective (transforms/v2/functional/_geometry.py affine_image, rotate_image,
+ * perspective_image / _apply_grid_transform) = grid_sample(image, grid, mode, padding_mode="zeros", align_corners=False), the
+ * fill blend as mv_elastic_*, round half to even for uint8.  x is (planes, ih, iw), y is (planes, oh, ow); every plane is
+ * resampled with the same grid, which is never materialised: output pixel (i, j) computes it from coeffs, a HOST array of 8
+ * floats (ax, bx, cx, ay, by, cy, c6, c7) -- (a, b, c) of each axis = one column of the reference's rescaled theta:
+ *   kind 0 (affine):      x = j - (ow - 1) / 2, y = i - (oh - 1) / 2, g = x * a + y * b + c              (c6, c7 unused)
+ *   kind 1 (perspective): x = j + 0.5, y = i + 0.5, g = (x * a + y * b + c) / (x * c6 + y * c7 + 1) - 1
+ * with the rounding of the reference's CPU bmm: order 1 = fma(y, b, x * a) + c (a blocked BLAS path that fuses), order 0 =
+ * (x * a + y * b) + c (ATen's naive loop, taken when oh * ow * 3 * 2 < 400, or a blocked path that does not fuse).  mode: 0 bilinear, 1 nearest.  fill: NULL (no blend) or a HOST array
+ * of `channels` floats (plane p takes fill[p % channels]; at most 16); planes must be a multiple of channels.  ih * iw and
+ * oh * ow < 2^31. */
+int mv_warp_f32(const float* x, float* y, int64_t planes, int channels, int ih, int iw, int oh, int ow, const float* coeffs,
+                int kind, int order, int mode, const float* fill, void* stream);
+int mv_warp_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, int ih, int iw, int oh, int ow, const float* coeffs,
+               int kind, int order, int mode, const float* fill, void* stream);
 /* The same convolution with K SLICES ACROSS WORKGROUPS for launches too small to fill the chip with one chain per output (VGG's
  * 512 -> 512 layers at batch 1: ~50 workgroups walking 128 K chunks each).  mv_conv3x3_k_slices() states the summation order for a
  * shape -- 1: the single chain of mv_conv3x3_bias_relu_f32; otherwise that many chains over `slice_channels` input channels each
