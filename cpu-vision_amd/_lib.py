@@ -87,6 +87,11 @@ SYMBOLS = {
     "mv_elastic_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _fp, _vp]),
     "mv_warp_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _fp, _vp]),
     "mv_warp_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _fp, _vp]),
+    "mv_color_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "mv_color_chain_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_double), _i, _i, _vp, _i64, _vp]),
+    "mv_color_chain_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_double), _i, _i, _vp, _i64, _vp]),
+    "mv_rgb_to_grayscale_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "mv_rgb_to_grayscale_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

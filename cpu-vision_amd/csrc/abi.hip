@@ -907,4 +907,77 @@ int mv_warp_u8(const uint8_t* x, uint8_t* y, int64_t planes, int channels, int i
   return warp(x, y, true, planes, channels, ih, iw, oh, ow, coeffs, kind, order, mode, fill, stream);
 }
 
+int64_t mv_color_workspace_bytes(int64_t images, int h, int w, int u8) {
+  if (images <= 0 || h <= 0 || w <= 0) return 0;
+  return color_workspace_bytes(images, h, w, u8 != 0);
+}
+
+static int color_chain(const void* x, void* y, bool u8, int64_t images, int channels, int h, int w, const int* ops,
+                       const double* factors, int n_ops, int form, void* ws, int64_t ws_bytes, void* stream) {
+  if (images <= 0 || h <= 0 || w <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "color: bad shape images=%lld (%d, %d)", (long long)images, h, w);
+  if (channels != 1 && channels != 3)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "color: channels must be 1 or 3, got %d", channels);
+  if (n_ops < 1 || n_ops > 4) return set_error(MV_ERR_INVALID_ARGUMENT, "color: a chain has 1 to 4 ops, got %d", n_ops);
+  if (!x || !y || !ops || !factors) return set_error(MV_ERR_INVALID_ARGUMENT, "color: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (form != 0 && form != 1) return set_error(MV_ERR_INVALID_ARGUMENT, "color: unknown blend form %d (0 plain, 1 fma)", form);
+  int contrasts = 0;
+  for (int k = 0; k < n_ops; ++k) {
+    if (ops[k] < MV_COLOR_BRIGHTNESS || ops[k] > MV_COLOR_HUE)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "color: unknown op code %d at position %d", ops[k], k);
+    const double f = factors[k];
+    if (ops[k] == MV_COLOR_HUE ? !(f >= -0.5 && f <= 0.5) : !(f >= 0.0))
+      return set_error(MV_ERR_INVALID_ARGUMENT, "color: factor %g of op %d is out of range", f, ops[k]);
+    contrasts += ops[k] == MV_COLOR_CONTRAST;
+  }
+  if (contrasts > 1) return set_error(MV_ERR_INVALID_ARGUMENT, "color: a chain holds at most one contrast op, got %d", contrasts);
+  if (contrasts) {
+    const int64_t need = color_workspace_bytes(images, h, w, u8);
+    if (!ws) return set_error(MV_ERR_INVALID_ARGUMENT, "color: a chain with contrast needs a workspace");
+    if (ws_bytes < need)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "color: workspace of %lld bytes, need %lld", (long long)ws_bytes, (long long)need);
+    if ((uintptr_t)ws % 16)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "color: the workspace must be 16-byte aligned");
+  }
+  if (!color_grid_fits(images, h, w, u8))
+    return set_error(MV_ERR_UNSUPPORTED, "color: %lld images of %d x %d pixels exceed the launch grid", (long long)images, h, w);
+  return launch_color_chain(x, y, u8, images, channels, h, w, ops, factors, n_ops, form, ws, (hipStream_t)stream);
+}
+
+int mv_color_chain_f32(const float* x, float* y, int64_t images, int channels, int h, int w, const int* ops,
+                       const double* factors, int n_ops, int form, void* workspace, int64_t workspace_bytes, void* stream) {
+  return color_chain(x, y, false, images, channels, h, w, ops, factors, n_ops, form, workspace, workspace_bytes, stream);
+}
+
+int mv_color_chain_u8(const uint8_t* x, uint8_t* y, int64_t images, int channels, int h, int w, const int* ops,
+                      const double* factors, int n_ops, int form, void* workspace, int64_t workspace_bytes, void* stream) {
+  return color_chain(x, y, true, images, channels, h, w, ops, factors, n_ops, form, workspace, workspace_bytes, stream);
+}
+
+static int rgb_to_grayscale(const void* x, void* y, bool u8, int64_t images, int h, int w, int out_channels, int form,
+                            void* stream) {
+  if (images <= 0 || h <= 0 || w <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "rgb_to_grayscale: bad shape images=%lld (%d, %d)", (long long)images, h, w);
+  if (out_channels != 1 && out_channels != 3)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "rgb_to_grayscale: out_channels must be 1 or 3, got %d", out_channels);
+  if (form != 0 && form != 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "rgb_to_grayscale: unknown form %d (0 plain, 1 fma)", form);
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "rgb_to_grayscale: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (!color_grid_fits(images, h, w, u8))
+    return set_error(MV_ERR_UNSUPPORTED, "rgb_to_grayscale: %lld images of %d x %d pixels exceed the launch grid",
+                     (long long)images, h, w);
+  return launch_rgb_to_grayscale(x, y, u8, images, h, w, out_channels, form, (hipStream_t)stream);
+}
+
+int mv_rgb_to_grayscale_f32(const float* x, float* y, int64_t images, int h, int w, int out_channels, int form, void* stream) {
+  return rgb_to_grayscale(x, y, false, images, h, w, out_channels, form, stream);
+}
+
+int mv_rgb_to_grayscale_u8(const uint8_t* x, uint8_t* y, int64_t images, int h, int w, int out_channels, int form,
+                           void* stream) {
+  return rgb_to_grayscale(x, y, true, images, h, w, out_channels, form, stream);
+}
+
 }  // extern "C"

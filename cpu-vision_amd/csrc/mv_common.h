@@ -17,6 +17,15 @@
 #else
 namespace mv {
 constexpr const char* tune_env(const char*) { return nullptr; }
+// The v2 colour ops (color.hip; layout and arithmetic in mi355vision.h mv_color_chain_f32).  The entry points have checked
+// the arguments, the workspace size (color_workspace_bytes) and the grid (color_grid_fits).
+int64_t color_workspace_bytes(int64_t images, int h, int w, bool u8);
+bool color_grid_fits(int64_t images, int h, int w, bool u8);
+int launch_color_chain(const void* x, void* y, bool u8, int64_t images, int channels, int h, int w, const int* ops,
+                       const double* factors, int n_ops, int form, void* ws, hipStream_t s);
+int launch_rgb_to_grayscale(const void* x, void* y, bool u8, int64_t images, int h, int w, int out_channels, int form,
+                            hipStream_t s);
+
 }  // namespace mv
 #endif
 
@@ -288,5 +297,14 @@ int launch_elastic(const void* x, void* y, bool u8, int64_t planes, int channels
 // chain, 0 the plain sum (the rounding of the reference's CPU bmm); mode 0 bilinear, 1 nearest; fill as launch_elastic.
 int launch_warp(const void* x, void* y, bool u8, int64_t planes, int channels, int ih, int iw, int oh, int ow, const float* coeffs,
                 int kind, int order, int mode, const float* fill, hipStream_t s);
+
+// The v2 colour ops (color.hip; layout and arithmetic in mi355vision.h mv_color_chain_f32).  The entry points have checked
+// the arguments, the workspace size (color_workspace_bytes) and the grid (color_grid_fits).
+int64_t color_workspace_bytes(int64_t images, int h, int w, bool u8);
+bool color_grid_fits(int64_t images, int h, int w, bool u8);
+int launch_color_chain(const void* x, void* y, bool u8, int64_t images, int channels, int h, int w, const int* ops,
+                       const double* factors, int n_ops, int form, void* ws, hipStream_t s);
+int launch_rgb_to_grayscale(const void* x, void* y, bool u8, int64_t images, int h, int w, int out_channels, int form,
+                            hipStream_t s);
 
 }  // namespace mv

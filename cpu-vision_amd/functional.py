@@ -13,6 +13,9 @@ ElasticTransform's resampling:
   elastic / elastic_image / elastic_mask / elastic_video      transforms/v2/functional/_geometry.py (elastic*, _apply_grid_transform)
 The other grid transforms (same file, same _apply_grid_transform):
   affine / rotate / perspective and their _image / _mask / _video kernels
+The colour ops (transforms/v2/functional/_color.py):
+  adjust_brightness / adjust_contrast / adjust_saturation / adjust_hue and their _image / _video kernels,
+  rgb_to_grayscale / rgb_to_grayscale_image
 
 Tensors must live on a HIP device; there is no CPU fallback (see _lib.py).  Host-side work here is what
 the reference also does on the host: argument checking, the handful of Gaussian taps, reshapes.
@@ -1474,6 +1477,251 @@ for _f in (affine, rotate, perspective):
     _register_kernel_internal(_f, tv_tensors.BoundingBoxes, tv_tensor_wrapper=False)(_warp_boxes_unsupported(_f.__name__))
     if _pil.PIL is not None:
         _register_kernel_internal(_f, _pil.PIL.Image.Image)(_warp_pil_unsupported(_f.__name__))
+del _f
+
+
+# --------------------------------------------------------------------------------------------- colour (v2 surface)
+# transforms/v2/functional/_color.py: argument checks and special cases here, with the reference's error text; the pixel
+# arithmetic is one chain of ops per call in k_color (csrc/color.hip).
+_COLOR_OPS = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}
+
+
+@functools.lru_cache(maxsize=None)
+def _add_alpha_fuses() -> bool:
+    """Whether this host's `a.add_(b, alpha=s)` on float32 rounds as fma(b, s, a) (True: ATen's vectorised kernel on a host
+    with FMA) or as a + b * s (False).  The reference's grey value and its `_blend` are such adds, so their rounding is probed
+    once, on 4096 random pairs, and passed to the kernel as its blend form."""
+    g = torch.Generator().manual_seed(0)
+    a = torch.rand(4096, generator=g) * 255.0
+    b = torch.rand(4096, generator=g) * 255.0
+    got = a.clone().add_(b, alpha=0.587)
+    plain = a + b * torch.tensor(0.587, dtype=torch.float32)  # two separately rounded ops
+    return not torch.equal(got, plain)
+
+
+def _blend_form() -> int:
+    return 1 if _add_alpha_fuses() else 0
+
+
+def _check_color_channels(image: torch.Tensor) -> int:
+    c = image.shape[-3]
+    if c not in [1, 3]:
+        raise TypeError(f"Input image tensor permitted channel values are 1 or 3, but found {c}")
+    return int(c)
+
+
+def _check_color_dtype(image: torch.Tensor, name: str) -> None:
+    if image.dtype not in (torch.float32, torch.uint8):
+        raise NotImplementedError(f"{name}: {image.dtype} images are not on the MI355X path (float32 and uint8 are)")
+
+
+def _check_color_factor(name: str, factor: float) -> None:
+    if name == "hue":
+        if not (-0.5 <= factor <= 0.5):
+            raise ValueError(f"hue_factor ({factor}) is not in [-0.5, 0.5].")
+    elif factor < 0:
+        raise ValueError(f"{name}_factor ({factor}) is not non-negative.")
+
+
+def _color_chain(image: torch.Tensor, ops: Sequence[Tuple[str, float]]) -> torch.Tensor:
+    """The ops, in order, on a non-empty float32 / uint8 (..., C, H, W) image with C in {1, 3}: ONE mv_color_chain_* call (a
+    chain with contrast runs its mean reduction on the stream first).  The caller has checked the arguments and dropped
+    saturation and hue from 1-channel chains."""
+    c, h, w = (int(s) for s in image.shape[-3:])
+    images = image.numel() // (c * h * w)
+    _lib.require_device(image)
+    lib = _lib.load()
+    u8 = image.dtype == torch.uint8
+    n = len(ops)
+    codes = (C.c_int * n)(*[_COLOR_OPS[name] for name, _ in ops])
+    factors = (C.c_double * n)(*[float(f) for _, f in ops])
+    with _lib.on_device_of(image):
+        x = image.contiguous()
+        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        ws, ws_bytes = None, 0
+        if any(name == "contrast" for name, _ in ops):
+            ws_bytes = int(lib.mv_color_workspace_bytes(images, h, w, int(u8)))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        fn = lib.mv_color_chain_u8 if u8 else lib.mv_color_chain_f32
+        _lib.check(fn(x.data_ptr(), y.data_ptr(), images, c, h, w, codes, factors, n, _blend_form(),
+                      None if ws is None else ws.data_ptr(), ws_bytes, _lib.stream_ptr(x)))
+    if not u8:
+        return _lib.forward_only(y, "adjust_" + ops[0][0] if n == 1 else "color_jitter", image)
+    return y
+
+
+def _color_pil_unsupported(name: str):
+    def kernel(image, *args, **kwargs):
+        raise NotImplementedError(f"{name}: PIL images go through Pillow's ImageEnhance in the reference, whose results the "
+                                  "tensor formula does not reproduce; convert with pil_to_tensor and move the tensor to the MI355X")
+    return kernel
+
+
+def adjust_brightness(inpt: torch.Tensor, brightness_factor: float) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `adjust_brightness`."""
+    kernel = _get_kernel(adjust_brightness, type(inpt))
+    return kernel(inpt, brightness_factor=brightness_factor)
+
+
+@_register_kernel_internal(adjust_brightness, torch.Tensor)
+@_register_kernel_internal(adjust_brightness, tv_tensors.Image)
+def adjust_brightness_image(image: torch.Tensor, brightness_factor: float) -> torch.Tensor:
+    """adjust_brightness_image (_color.py): image.mul(factor).clamp_(0, bound), truncated back to uint8."""
+    _check_color_factor("brightness", brightness_factor)
+    _check_color_channels(image)
+    _check_color_dtype(image, "adjust_brightness")
+    if image.dtype == torch.uint8 and isinstance(brightness_factor, int) and brightness_factor > 1:
+        # image.mul(int) stays uint8 in the reference and wraps modulo 256 before the clamp
+        raise NotImplementedError(f"adjust_brightness: an integer factor ({brightness_factor}) on a uint8 image multiplies "
+                                  "modulo 256 in the reference, which is not on the MI355X path; pass a float factor")
+    if image.numel() == 0:
+        return torch.empty_like(image)
+    return _color_chain(image, [("brightness", brightness_factor)])
+
+
+@_register_kernel_internal(adjust_brightness, tv_tensors.Video)
+def adjust_brightness_video(video: torch.Tensor, brightness_factor: float) -> torch.Tensor:
+    return adjust_brightness_image(video, brightness_factor=brightness_factor)
+
+
+def adjust_saturation(inpt: torch.Tensor, saturation_factor: float) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `adjust_saturation`."""
+    kernel = _get_kernel(adjust_saturation, type(inpt))
+    return kernel(inpt, saturation_factor=saturation_factor)
+
+
+@_register_kernel_internal(adjust_saturation, torch.Tensor)
+@_register_kernel_internal(adjust_saturation, tv_tensors.Image)
+def adjust_saturation_image(image: torch.Tensor, saturation_factor: float) -> torch.Tensor:
+    """adjust_saturation_image (_color.py): _blend with the per-pixel grey value (floored for uint8); 1-channel images are
+    returned as they are."""
+    _check_color_factor("saturation", saturation_factor)
+    c = _check_color_channels(image)
+    if c == 1:  # the reference matches PIL here
+        return image
+    _check_color_dtype(image, "adjust_saturation")
+    if image.numel() == 0:
+        return torch.empty_like(image)
+    return _color_chain(image, [("saturation", saturation_factor)])
+
+
+@_register_kernel_internal(adjust_saturation, tv_tensors.Video)
+def adjust_saturation_video(video: torch.Tensor, saturation_factor: float) -> torch.Tensor:
+    return adjust_saturation_image(video, saturation_factor=saturation_factor)
+
+
+def adjust_contrast(inpt: torch.Tensor, contrast_factor: float) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `adjust_contrast`."""
+    kernel = _get_kernel(adjust_contrast, type(inpt))
+    return kernel(inpt, contrast_factor=contrast_factor)
+
+
+@_register_kernel_internal(adjust_contrast, torch.Tensor)
+@_register_kernel_internal(adjust_contrast, tv_tensors.Image)
+def adjust_contrast_image(image: torch.Tensor, contrast_factor: float) -> torch.Tensor:
+    """adjust_contrast_image (_color.py): _blend with the mean of the grey image over dims (-3, -2, -1) -- per image, per
+    frame of a video; a 1-channel image is its own grey image."""
+    _check_color_factor("contrast", contrast_factor)
+    _check_color_channels(image)
+    _check_color_dtype(image, "adjust_contrast")
+    if image.numel() == 0:
+        return torch.empty_like(image)
+    return _color_chain(image, [("contrast", contrast_factor)])
+
+
+@_register_kernel_internal(adjust_contrast, tv_tensors.Video)
+def adjust_contrast_video(video: torch.Tensor, contrast_factor: float) -> torch.Tensor:
+    return adjust_contrast_image(video, contrast_factor=contrast_factor)
+
+
+def adjust_hue(inpt: torch.Tensor, hue_factor: float) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `adjust_hue`."""
+    kernel = _get_kernel(adjust_hue, type(inpt))
+    return kernel(inpt, hue_factor=hue_factor)
+
+
+@_register_kernel_internal(adjust_hue, torch.Tensor)
+@_register_kernel_internal(adjust_hue, tv_tensors.Image)
+def adjust_hue_image(image: torch.Tensor, hue_factor: float) -> torch.Tensor:
+    """adjust_hue_image (_color.py): _rgb_to_hsv, h = (h + hue_factor) mod 1, _hsv_to_rgb, with uint8 scaled in and out as
+    to_dtype_image(scale=True) does; 1-channel and empty images are returned as they are."""
+    _check_color_factor("hue", hue_factor)
+    c = _check_color_channels(image)
+    if c == 1:  # the reference matches PIL here
+        return image
+    if image.numel() == 0:
+        return image
+    _check_color_dtype(image, "adjust_hue")
+    return _color_chain(image, [("hue", hue_factor)])
+
+
+@_register_kernel_internal(adjust_hue, tv_tensors.Video)
+def adjust_hue_video(video: torch.Tensor, hue_factor: float) -> torch.Tensor:
+    return adjust_hue_image(video, hue_factor=hue_factor)
+
+
+def color_jitter_image(image: torch.Tensor, ops: Sequence[Tuple[str, float]]) -> torch.Tensor:
+    """The reference's loop of single `adjust_*_image` calls (v2.ColorJitter._transform) over (name, factor) pairs, as ONE
+    mv_color_chain_* call on a non-empty float32 / uint8 image on the device: the same bits as the loop.  Names are
+    "brightness", "contrast", "saturation" and "hue"."""
+    for name, factor in ops:
+        if name not in _COLOR_OPS:
+            raise ValueError(f"unknown colour op {name!r}")
+        _check_color_factor(name, factor)
+    if not ops:
+        return image
+    c = _check_color_channels(image)
+    if c == 1:  # saturation and hue return 1-channel images unchanged
+        ops = [(name, f) for name, f in ops if name in ("brightness", "contrast")]
+        if not ops:
+            return image
+    _check_color_dtype(image, "ColorJitter")
+    if image.numel() == 0:
+        raise ValueError("color_jitter_image: empty images take the reference's loop of single calls")
+    return _color_chain(image, list(ops))
+
+
+def rgb_to_grayscale(inpt: torch.Tensor, num_output_channels: int = 1) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `rgb_to_grayscale`."""
+    kernel = _get_kernel(rgb_to_grayscale, type(inpt))
+    return kernel(inpt, num_output_channels=num_output_channels)
+
+
+@_register_kernel_internal(rgb_to_grayscale, torch.Tensor)
+@_register_kernel_internal(rgb_to_grayscale, tv_tensors.Image)
+def rgb_to_grayscale_image(image: torch.Tensor, num_output_channels: int = 1) -> torch.Tensor:
+    """rgb_to_grayscale_image (_color.py): the grey value r * 0.2989 + g * 0.587 + b * 0.114 (truncated for uint8) in 1 or 3
+    planes; a 1-channel image is cloned or repeated."""
+    if num_output_channels not in (1, 3):
+        raise ValueError(f"num_output_channels must be 1 or 3, got {num_output_channels}.")
+    c = _check_color_channels(image)
+    if c == 1:
+        if num_output_channels == 1:
+            return image.clone()
+        s = [1] * image.ndim
+        s[-3] = 3
+        return image.repeat(s)
+    _check_color_dtype(image, "rgb_to_grayscale")
+    h, w = (int(d) for d in image.shape[-2:])
+    out_shape = tuple(image.shape[:-3]) + (num_output_channels, h, w)
+    if image.numel() == 0:
+        return torch.empty(out_shape, dtype=image.dtype, device=image.device)
+    _lib.require_device(image)
+    lib = _lib.load()
+    images = image.numel() // (3 * h * w)
+    with _lib.on_device_of(image):
+        x = image.contiguous()
+        y = torch.empty(out_shape, dtype=x.dtype, device=x.device)
+        fn = lib.mv_rgb_to_grayscale_u8 if x.dtype == torch.uint8 else lib.mv_rgb_to_grayscale_f32
+        _lib.check(fn(x.data_ptr(), y.data_ptr(), images, h, w, num_output_channels, _blend_form(), _lib.stream_ptr(x)))
+    if image.dtype == torch.float32:
+        return _lib.forward_only(y, "rgb_to_grayscale", image)
+    return y
+
+
+for _f in (adjust_brightness, adjust_contrast, adjust_saturation, adjust_hue, rgb_to_grayscale):
+    if _pil.PIL is not None:
+        _register_kernel_internal(_f, _pil.PIL.Image.Image)(_color_pil_unsupported(_f.__name__))
 del _f
 
 

@@ -7,14 +7,16 @@
   ElasticTransform                        transforms/v2/_geometry.py:1003-1085 (noise field -> gaussian_blur -> displacement
                                           -> F.elastic)
   RandomRotation / RandomAffine / RandomPerspective   transforms/v2/_geometry.py (-> F.rotate / F.affine / F.perspective)
+  ColorJitter / Grayscale / RandomGrayscale           transforms/v2/_color.py (-> F.adjust_* / F.rgb_to_grayscale)
   Resize / CenterCrop / ToDtype / Normalize / Compose   v2/_geometry.py:76-193, v2/_misc.py:134-304, v2/_container.py:10-64
 
 Parameter sampling stays on the host RNG exactly like the reference (torch.empty(1).uniform_ / torch.rand(1)).
 """
 from __future__ import annotations
 
+import collections.abc
 import numbers
-from typing import Any, Callable, Dict, List, Optional, Sequence, Union
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import nn
@@ -90,6 +92,27 @@ def query_size(flat_inputs: List[Any]):
         raise ValueError(f"Found multiple HxW dimensions in the sample: {sorted(sizes)}")
     h, w = sizes.pop()
     return int(h), int(w)
+
+
+def query_chw(flat_inputs: List[Any]) -> Tuple[int, int, int]:
+    """transforms/v2/_utils.py `query_chw`: the one (C, H, W) of the images and videos of a sample."""
+    chws = set()
+    for inpt in flat_inputs:
+        if isinstance(inpt, (tv_tensors.Image, tv_tensors.Video)) or is_pure_tensor(inpt):
+            chw = list(inpt.shape[-3:])
+            if len(chw) == 2:
+                chw.insert(0, 1)
+            elif len(chw) != 3:
+                raise TypeError(f"Input tensor should have at least two dimensions, but got {len(chw)}")
+            chws.add(tuple(int(d) for d in chw))
+        elif isinstance(inpt, _PIL_TYPES):
+            chws.add((len(inpt.getbands()), inpt.size[1], inpt.size[0]))
+    if not chws:
+        raise TypeError("No image or video was found in the sample")
+    if len(chws) > 1:
+        raise ValueError(f"Found multiple CxHxW dimensions in the sample: {', '.join(str(c) for c in sorted(chws))}")
+    c, h, w = chws.pop()
+    return c, h, w
 
 
 class Transform(nn.Module):
@@ -603,6 +626,101 @@ class RandomPerspective(_RandomApplyTransform):
         fill = _get_fill(self._fill, type(inpt))
         return self._call_kernel(F.perspective, inpt, startpoints=None, endpoints=None, fill=fill,
                                  interpolation=self.interpolation, **params)
+
+
+_COLOR_JITTER_OPS = ("brightness", "contrast", "saturation", "hue")
+
+
+class ColorJitter(Transform):
+    """v2.ColorJitter(brightness=None, contrast=None, saturation=None, hue=None) -- transforms/v2/_color.py.
+
+    `_get_params` draws with the reference's host RNG calls in its order: torch.randperm(4), then one
+    torch.empty(1).uniform_ per configured factor (brightness, contrast, saturation, hue).  A float32 / uint8 tensor, Image or
+    Video on the device goes through the whole chain in ONE call (F.color_jitter_image: one pass, two with contrast); any
+    other input takes the reference's loop of single F.adjust_* calls.  Both give the same bits."""
+
+    def __init__(self, brightness=None, contrast=None, saturation=None, hue=None) -> None:
+        super().__init__()
+        self.brightness = self._check_input(brightness, "brightness")
+        self.contrast = self._check_input(contrast, "contrast")
+        self.saturation = self._check_input(saturation, "saturation")
+        self.hue = self._check_input(hue, "hue", center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+
+    def _check_input(self, value, name: str, center: float = 1.0, bound: Tuple[float, float] = (0, float("inf")),
+                     clip_first_on_zero: bool = True) -> Optional[Tuple[float, float]]:
+        if value is None:
+            return None
+        if isinstance(value, (int, float)):
+            if value < 0:
+                raise ValueError(f"If {name} is a single number, it must be non negative.")
+            value = [center - value, center + value]
+            if clip_first_on_zero:
+                value[0] = max(value[0], 0.0)
+        elif isinstance(value, collections.abc.Sequence) and len(value) == 2:
+            value = [float(v) for v in value]
+        else:
+            raise TypeError(f"{name}={value} should be a single number or a sequence with length 2.")
+        if not bound[0] <= value[0] <= value[1] <= bound[1]:
+            raise ValueError(f"{name} values should be between {bound}, but got {value}.")
+        return None if value[0] == value[1] == center else (float(value[0]), float(value[1]))
+
+    @staticmethod
+    def _generate_value(left: float, right: float) -> float:
+        return torch.empty(1).uniform_(left, right).item()
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        fn_idx = torch.randperm(4)
+        b = None if self.brightness is None else self._generate_value(self.brightness[0], self.brightness[1])
+        c = None if self.contrast is None else self._generate_value(self.contrast[0], self.contrast[1])
+        s = None if self.saturation is None else self._generate_value(self.saturation[0], self.saturation[1])
+        h = None if self.hue is None else self._generate_value(self.hue[0], self.hue[1])
+        return dict(fn_idx=fn_idx, brightness_factor=b, contrast_factor=c, saturation_factor=s, hue_factor=h)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        ops = []
+        for fn_id in params["fn_idx"]:
+            name = _COLOR_JITTER_OPS[int(fn_id)]
+            factor = params[name + "_factor"]
+            if factor is not None:
+                ops.append((name, factor))
+        if (ops and type(inpt) in (torch.Tensor, tv_tensors.Image, tv_tensors.Video) and inpt.is_cuda
+                and inpt.dtype in (torch.float32, torch.uint8) and inpt.numel() > 0):
+            plain = inpt.as_subclass(torch.Tensor)
+            out = F.color_jitter_image(plain, ops)
+            if out is plain:
+                return inpt  # saturation and hue alone leave a 1-channel image as it is
+            return tv_tensors.wrap(out, like=inpt) if isinstance(inpt, tv_tensors.TVTensor) else out
+        output = inpt
+        for name, factor in ops:
+            functional = getattr(F, "adjust_" + name)
+            output = self._call_kernel(functional, output, **{name + "_factor": factor})
+        return output
+
+
+class Grayscale(Transform):
+    """v2.Grayscale(num_output_channels=1) -- transforms/v2/_color.py (-> F.rgb_to_grayscale; masks, boxes and videos pass
+    through, as in the reference)."""
+
+    def __init__(self, num_output_channels: int = 1) -> None:
+        super().__init__()
+        self.num_output_channels = num_output_channels
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.rgb_to_grayscale, inpt, num_output_channels=self.num_output_channels)
+
+
+class RandomGrayscale(_RandomApplyTransform):
+    """v2.RandomGrayscale(p=0.1) -- transforms/v2/_color.py: grey with as many channels as the input has."""
+
+    def __init__(self, p: float = 0.1) -> None:
+        super().__init__(p=p)
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        num_input_channels, *_ = query_chw(flat_inputs)
+        return dict(num_input_channels=num_input_channels)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.rgb_to_grayscale, inpt, num_output_channels=params["num_input_channels"])
 
 
 class GaussianBlurV1(nn.Module):

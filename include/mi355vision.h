@@ -402,6 +402,33 @@ int64_t mv_linear_workspace_bytes(int64_t n, int k, int m);
 int mv_linear_bias_relu_ws_f32(const float* x, const float* w, const float* b, float* y, int64_t n, int k, int m, int relu,
                                void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The v2 colour ops (transforms/v2/functional/_color.py adjust_brightness_image, adjust_contrast_image,
+ * adjust_saturation_image, adjust_hue_image) and ColorJitter's chain of them.  x, y are (images, channels, h, w), channels
+ * 1 or 3, contiguous, not aliased.  ops / factors are HOST arrays of n_ops (1-4) op codes and their factors, applied in order
+ * to every pixel with the reference's rounding and its quantisation between ops (uint8: clamp, then truncation); at most one
+ * MV_COLOR_CONTRAST.  Saturation and hue leave 1-channel images unchanged.  form: the rounding of the reference's
+ * `add_(other, alpha=a)` -- 1 fma(other, a, self), 0 self + other * a -- for the grey value and the blends.  A chain with
+ * contrast needs `workspace`, a DEVICE buffer of mv_color_workspace_bytes(images, h, w, u8) bytes (any content; the call
+ * initialises what it uses): the per-image mean of the grey image of the chain so far is reduced there on the stream --
+ * uint8 as an exact integer sum S, mean (float)S / (float)(h * w); float32 as double partials summed in a fixed order, the
+ * mean rounded once to float32 -- so results are the same bits on every run and nothing is read back.  Without contrast,
+ * workspace may be NULL. */
+#define MV_COLOR_BRIGHTNESS 0
+#define MV_COLOR_CONTRAST 1
+#define MV_COLOR_SATURATION 2
+#define MV_COLOR_HUE 3
+int64_t mv_color_workspace_bytes(int64_t images, int h, int w, int u8);
+int mv_color_chain_f32(const float* x, float* y, int64_t images, int channels, int h, int w, const int* ops,
+                       const double* factors, int n_ops, int form, void* workspace, int64_t workspace_bytes, void* stream);
+int mv_color_chain_u8(const uint8_t* x, uint8_t* y, int64_t images, int channels, int h, int w, const int* ops,
+                      const double* factors, int n_ops, int form, void* workspace, int64_t workspace_bytes, void* stream);
+/* rgb_to_grayscale of (images, 3, h, w) into (images, out_channels, h, w), out_channels 1 or 3: the grey value of the
+ * reference's `r.mul(0.2989).add_(g, alpha=0.587).add_(b, alpha=0.114)` (form as above; uint8: truncated by .to(uint8)) in
+ * every output plane. */
+int mv_rgb_to_grayscale_f32(const float* x, float* y, int64_t images, int h, int w, int out_channels, int form, void* stream);
+int mv_rgb_to_grayscale_u8(const uint8_t* x, uint8_t* y, int64_t images, int h, int w, int out_channels, int form,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
