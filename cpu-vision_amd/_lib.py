@@ -92,6 +92,14 @@ SYMBOLS = {
     "mv_color_chain_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_double), _i, _i, _vp, _i64, _vp]),
     "mv_rgb_to_grayscale_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_rgb_to_grayscale_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "mv_pointwise_f32": (_i, [_vp, _vp, _i64, _i, _d, _vp]),
+    "mv_pointwise_u8": (_i, [_vp, _vp, _i64, _i, _d, _vp]),
+    "mv_autocontrast_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "mv_autocontrast_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "mv_autocontrast_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "mv_equalize_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "mv_equalize_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "mv_equalize_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

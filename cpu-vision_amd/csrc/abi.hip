@@ -980,4 +980,84 @@ int mv_rgb_to_grayscale_u8(const uint8_t* x, uint8_t* y, int64_t images, int h, 
   return rgb_to_grayscale(x, y, true, images, h, w, out_channels, form, stream);
 }
 
+static int pointwise(const void* x, void* y, bool u8, int64_t n, int op, double param, void* stream) {
+  if (n <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "pointwise: bad element count %lld", (long long)n);
+  if (op < MV_POINT_INVERT || op > MV_POINT_SOLARIZE) return set_error(MV_ERR_INVALID_ARGUMENT, "pointwise: unknown op code %d", op);
+  if (op == MV_POINT_POSTERIZE && !(param >= 0.0 && param <= 8.0 && param == (double)(int)param))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pointwise: posterize bits must be an integer in [0, 8], got %g", param);
+  if (op == MV_POINT_SOLARIZE && param != param) return set_error(MV_ERR_INVALID_ARGUMENT, "pointwise: solarize threshold is NaN");
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "pointwise: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  return launch_pointwise(x, y, u8, n, op, param, (hipStream_t)stream);
+}
+
+int mv_pointwise_f32(const float* x, float* y, int64_t n, int op, double param, void* stream) {
+  return pointwise(x, y, false, n, op, param, stream);
+}
+
+int mv_pointwise_u8(const uint8_t* x, uint8_t* y, int64_t n, int op, double param, void* stream) {
+  return pointwise(x, y, true, n, op, param, stream);
+}
+
+int64_t mv_autocontrast_workspace_bytes(int64_t planes, int h, int w, int u8) {
+  if (planes <= 0 || h <= 0 || w <= 0) return 0;
+  return autocontrast_workspace_bytes(planes, (int64_t)h * w, u8 != 0);
+}
+
+int64_t mv_equalize_workspace_bytes(int64_t planes, int h, int w, int u8) {
+  (void)u8;
+  if (planes <= 0 || h <= 0 || w <= 0) return 0;
+  return equalize_workspace_bytes(planes);
+}
+
+// the checks autocontrast and equalize share; need: the op's workspace size
+static int plane_op_args(const char* what, const void* x, void* y, bool u8, int64_t planes, int h, int w, const void* ws,
+                         int64_t ws_bytes, int64_t need) {
+  if (planes <= 0 || h <= 0 || w <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape planes=%lld (%d, %d)", what, (long long)planes, h, w);
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (!ws) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: needs a workspace", what);
+  if (ws_bytes < need)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: workspace of %lld bytes, need %lld", what, (long long)ws_bytes, (long long)need);
+  if ((uintptr_t)ws % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", what);
+  if (!autoaug_grid_fits(planes, (int64_t)h * w, u8))
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld planes of %d x %d pixels exceed the launch grid", what, (long long)planes, h, w);
+  return MV_OK;
+}
+
+static int autocontrast(const void* x, void* y, bool u8, int64_t planes, int h, int w, void* ws, int64_t ws_bytes,
+                        void* stream) {
+  const int64_t need = planes > 0 && h > 0 && w > 0 ? autocontrast_workspace_bytes(planes, (int64_t)h * w, u8) : 0;
+  if (int rc = plane_op_args("autocontrast", x, y, u8, planes, h, w, ws, ws_bytes, need)) return rc;
+  return launch_autocontrast(x, y, u8, planes, (int64_t)h * w, ws, (hipStream_t)stream);
+}
+
+int mv_autocontrast_f32(const float* x, float* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                        void* stream) {
+  return autocontrast(x, y, false, planes, h, w, workspace, workspace_bytes, stream);
+}
+
+int mv_autocontrast_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+  return autocontrast(x, y, true, planes, h, w, workspace, workspace_bytes, stream);
+}
+
+static int equalize(const void* x, void* y, bool u8, int64_t planes, int h, int w, void* ws, int64_t ws_bytes, void* stream) {
+  if (int rc = plane_op_args("equalize", x, y, u8, planes, h, w, ws, ws_bytes, equalize_workspace_bytes(planes))) return rc;
+  if ((int64_t)h * w >= (int64_t)1 << 31)
+    return set_error(MV_ERR_UNSUPPORTED, "equalize: planes of %d x %d pixels overflow the 32-bit histogram", h, w);
+  return launch_equalize(x, y, u8, planes, (int64_t)h * w, ws, (hipStream_t)stream);
+}
+
+int mv_equalize_f32(const float* x, float* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+  return equalize(x, y, false, planes, h, w, workspace, workspace_bytes, stream);
+}
+
+int mv_equalize_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                   void* stream) {
+  return equalize(x, y, true, planes, h, w, workspace, workspace_bytes, stream);
+}
+
 }  // extern "C"

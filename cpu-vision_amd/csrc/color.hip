@@ -25,6 +25,7 @@
 // partials, in index order, divided by N and rounded once.  Nothing goes back to the host; the results are the same bits on
 // every run.
 #include "mv_common.h"
+#include "mv_vec16.h"
 
 namespace mv {
 
@@ -152,64 +153,6 @@ __device__ inline void run_ops(const Chain& ch, int k0, int k1, int form, float 
   }
 }
 
-template <typename T>
-struct Vec;
-template <>
-struct Vec<float> {
-  static constexpr int V = 4;
-  using Raw = float4;
-  __device__ static void unpack(const Raw& w, float (&o)[V]) { o[0] = w.x, o[1] = w.y, o[2] = w.z, o[3] = w.w; }
-  __device__ static Raw pack(const float (&o)[V]) { return make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <>
-struct Vec<uint8_t> {
-  static constexpr int V = 16;
-  using Raw = uint4;
-  __device__ static void unpack(const Raw& w, float (&o)[V]) {
-    const unsigned d[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int j = 0; j < V; ++j) o[j] = (float)((d[j >> 2] >> (8 * (j & 3))) & 0xffu);
-  }
-  __device__ static Raw pack(const float (&o)[V]) {
-    unsigned d[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < V; ++j) d[j >> 2] |= (unsigned)o[j] << (8 * (j & 3));  // o[j] is an integer in [0, 255]
-    return make_uint4(d[0], d[1], d[2], d[3]);
-  }
-};
-
-// the lane's group of V pixels starting at pixel p0 of each plane (planes of hw elements from base); VEC: one 16-byte load
-template <typename T, int C, bool VEC>
-__device__ inline void load(const T* __restrict__ base, long long hw, long long p0, float (&v)[C][Vec<T>::V]) {
-  constexpr int V = Vec<T>::V;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const T* src = base + (size_t)c * hw + p0;
-    if (VEC) {
-      Vec<T>::unpack(*reinterpret_cast<const typename Vec<T>::Raw*>(src), v[c]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j) v[c][j] = p0 + j < hw ? (float)src[j] : 0.f;
-    }
-  }
-}
-
-template <typename T, int C, bool VEC>
-__device__ inline void store(T* __restrict__ base, long long hw, long long p0, const float (&v)[C][Vec<T>::V]) {
-  constexpr int V = Vec<T>::V;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    T* dst = base + (size_t)c * hw + p0;
-    if (VEC) {
-      *reinterpret_cast<typename Vec<T>::Raw*>(dst) = Vec<T>::pack(v[c]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        if (p0 + j < hw) dst[j] = (T)v[c][j];
-    }
-  }
-}
-
 // Pass 1 of a chain with contrast: the sum over one image of the grey values of the chain in front of contrast.  Workgroup b
 // covers chunk b % chunks of image b / chunks, kSumItems groups of V pixels per lane.
 template <typename T, int C, bool VEC>
@@ -327,10 +270,6 @@ long long sum_chunks(long long hw, bool u8) {
 }
 
 long long means_bytes(long long images) { return (images * 4 + 15) / 16 * 16; }
-
-bool vec_ok(const void* x, const void* y, long long hw, int v) {
-  return hw % v == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;
-}
 
 template <typename T, int C, bool VEC>
 int launch_chain(const T* x, T* y, long long images, long long hw, const Chain& ch, int form, void* ws, hipStream_t s) {

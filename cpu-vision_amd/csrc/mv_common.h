@@ -307,4 +307,13 @@ int launch_color_chain(const void* x, void* y, bool u8, int64_t images, int chan
 int launch_rgb_to_grayscale(const void* x, void* y, bool u8, int64_t images, int h, int w, int out_channels, int form,
                             hipStream_t s);
 
+// The automatic-augmentation colour ops (autoaug.hip; arithmetic in mi355vision.h mv_pointwise_f32 and below).  The entry
+// points have checked the arguments, the workspace size and the grid (autoaug_grid_fits).
+bool autoaug_grid_fits(int64_t planes, int64_t plane_elems, bool u8);
+int64_t autocontrast_workspace_bytes(int64_t planes, int64_t plane_elems, bool u8);
+int64_t equalize_workspace_bytes(int64_t planes);
+int launch_pointwise(const void* x, void* y, bool u8, int64_t n, int op, double param, hipStream_t s);
+int launch_autocontrast(const void* x, void* y, bool u8, int64_t planes, int64_t plane_elems, void* ws, hipStream_t s);
+int launch_equalize(const void* x, void* y, bool u8, int64_t planes, int64_t plane_elems, void* ws, hipStream_t s);
+
 }  // namespace mv

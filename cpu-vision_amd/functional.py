@@ -16,6 +16,7 @@ The other grid transforms (same file, same _apply_grid_transform):
 The colour ops (transforms/v2/functional/_color.py):
   adjust_brightness / adjust_contrast / adjust_saturation / adjust_hue and their _image / _video kernels,
   rgb_to_grayscale / rgb_to_grayscale_image
+  invert / posterize / solarize / autocontrast / equalize and their _image / _video kernels
 
 Tensors must live on a HIP device; there is no CPU fallback (see _lib.py).  Host-side work here is what
 the reference also does on the host: argument checking, the handful of Gaussian taps, reshapes.
@@ -1722,6 +1723,182 @@ def rgb_to_grayscale_image(image: torch.Tensor, num_output_channels: int = 1) ->
 for _f in (adjust_brightness, adjust_contrast, adjust_saturation, adjust_hue, rgb_to_grayscale):
     if _pil.PIL is not None:
         _register_kernel_internal(_f, _pil.PIL.Image.Image)(_color_pil_unsupported(_f.__name__))
+del _f
+
+
+# --------------------------------------------------------------------------------------------- automatic-augmentation ops
+# transforms/v2/functional/_color.py invert / posterize / solarize / autocontrast / equalize: what AutoAugment, RandAugment and
+# TrivialAugmentWide call besides the geometric and F.adjust_* ops.  Argument checks here, with the reference's error text;
+# the pixels go through csrc/autoaug.hip.  Nothing is read back to the host.
+_POINT_OPS = {"invert": 0, "posterize": 1, "solarize": 2}
+
+
+def _pointwise(image: torch.Tensor, op: str, param: float = 0.0) -> torch.Tensor:
+    """One mv_pointwise_* call over every element of a non-empty float32 / uint8 image."""
+    _lib.require_device(image)
+    lib = _lib.load()
+    u8 = image.dtype == torch.uint8
+    with _lib.on_device_of(image):
+        x = image.contiguous()
+        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        fn = lib.mv_pointwise_u8 if u8 else lib.mv_pointwise_f32
+        _lib.check(fn(x.data_ptr(), y.data_ptr(), x.numel(), _POINT_OPS[op], float(param), _lib.stream_ptr(x)))
+    if not u8:
+        return _lib.forward_only(y, op, image)
+    return y
+
+
+def _plane_op(image: torch.Tensor, name: str) -> torch.Tensor:
+    """mv_autocontrast_* / mv_equalize_* on the (H, W) planes of a non-empty float32 / uint8 image, with its workspace."""
+    h, w = (int(d) for d in image.shape[-2:])
+    planes = image.numel() // (h * w)
+    _lib.require_device(image)
+    lib = _lib.load()
+    u8 = image.dtype == torch.uint8
+    with _lib.on_device_of(image):
+        x = image.contiguous()
+        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        ws_bytes = int(getattr(lib, f"mv_{name}_workspace_bytes")(planes, h, w, int(u8)))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        fn = getattr(lib, f"mv_{name}_u8" if u8 else f"mv_{name}_f32")
+        _lib.check(fn(x.data_ptr(), y.data_ptr(), planes, h, w, ws.data_ptr(), ws_bytes, _lib.stream_ptr(x)))
+    if not u8:
+        return _lib.forward_only(y, name, image)
+    return y
+
+
+def _autoaug_pil_unsupported(name: str):
+    def kernel(image, *args, **kwargs):
+        raise NotImplementedError(f"{name}: PIL images go through Pillow's ImageOps in the reference, which this library does "
+                                  "not reproduce; convert with pil_to_tensor and move the tensor to the MI355X")
+    return kernel
+
+
+def invert(inpt: torch.Tensor) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `invert`."""
+    kernel = _get_kernel(invert, type(inpt))
+    return kernel(inpt)
+
+
+@_register_kernel_internal(invert, torch.Tensor)
+@_register_kernel_internal(invert, tv_tensors.Image)
+def invert_image(image: torch.Tensor) -> torch.Tensor:
+    """invert_image (_color.py): float 1.0 - x, uint8 bitwise_not; any number of channels."""
+    _check_color_dtype(image, "invert")
+    if image.numel() == 0:
+        return torch.empty_like(image)
+    return _pointwise(image, "invert")
+
+
+@_register_kernel_internal(invert, tv_tensors.Video)
+def invert_video(video: torch.Tensor) -> torch.Tensor:
+    return invert_image(video)
+
+
+def posterize(inpt: torch.Tensor, bits: int) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `posterize`."""
+    kernel = _get_kernel(posterize, type(inpt))
+    return kernel(inpt, bits=bits)
+
+
+@_register_kernel_internal(posterize, torch.Tensor)
+@_register_kernel_internal(posterize, tv_tensors.Image)
+def posterize_image(image: torch.Tensor, bits: int) -> torch.Tensor:
+    """posterize_image (_color.py): float x.mul(2^bits).floor_().clamp_(0, 2^bits - 1).mul_(2^-bits); uint8 keeps the top
+    `bits` bits, and bits >= 8 returns the image itself."""
+    if not isinstance(bits, int) or not 0 <= bits <= 8:
+        raise TypeError(f"bits must be a positive integer in the range [0, 8], got {bits} instead.")
+    _check_color_dtype(image, "posterize")
+    if image.dtype == torch.uint8 and bits >= 8:
+        return image
+    if image.numel() == 0:
+        return torch.empty_like(image)
+    return _pointwise(image, "posterize", bits)
+
+
+@_register_kernel_internal(posterize, tv_tensors.Video)
+def posterize_video(video: torch.Tensor, bits: int) -> torch.Tensor:
+    return posterize_image(video, bits=bits)
+
+
+def solarize(inpt: torch.Tensor, threshold: float) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `solarize`."""
+    kernel = _get_kernel(solarize, type(inpt))
+    return kernel(inpt, threshold=threshold)
+
+
+@_register_kernel_internal(solarize, torch.Tensor)
+@_register_kernel_internal(solarize, tv_tensors.Image)
+def solarize_image(image: torch.Tensor, threshold: float) -> torch.Tensor:
+    """solarize_image (_color.py): torch.where(image >= threshold, invert(image), image).  The comparison is torch's: a
+    float threshold is rounded to float32 (a uint8 image is promoted to float32 against it); an integer threshold against a
+    uint8 image is first wrapped to uint8."""
+    _check_color_dtype(image, "solarize")
+    if threshold > _max_value(image.dtype):
+        raise TypeError(f"Threshold should be less or equal the maximum value of the dtype, but got {threshold}")
+    if image.numel() == 0:
+        return torch.empty_like(image)
+    if image.dtype == torch.uint8 and isinstance(threshold, int) and not isinstance(threshold, bool):
+        threshold = threshold % 256
+    return _pointwise(image, "solarize", float(threshold))
+
+
+@_register_kernel_internal(solarize, tv_tensors.Video)
+def solarize_video(video: torch.Tensor, threshold: float) -> torch.Tensor:
+    return solarize_image(video, threshold=threshold)
+
+
+def autocontrast(inpt: torch.Tensor) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `autocontrast`."""
+    kernel = _get_kernel(autocontrast, type(inpt))
+    return kernel(inpt)
+
+
+@_register_kernel_internal(autocontrast, torch.Tensor)
+@_register_kernel_internal(autocontrast, tv_tensors.Image)
+def autocontrast_image(image: torch.Tensor) -> torch.Tensor:
+    """autocontrast_image (_color.py): per (image, channel) plane, (x - min) / ((max - min) * (1 / bound)) clamped to
+    [0, bound] (uint8 truncated), min = 0 and scale 1 on flat planes; a NaN makes its float plane NaN.  Empty images are
+    returned as they are."""
+    _check_color_channels(image)
+    _check_color_dtype(image, "autocontrast")
+    if image.numel() == 0:
+        return image
+    return _plane_op(image, "autocontrast")
+
+
+@_register_kernel_internal(autocontrast, tv_tensors.Video)
+def autocontrast_video(video: torch.Tensor) -> torch.Tensor:
+    return autocontrast_image(video)
+
+
+def equalize(inpt: torch.Tensor) -> torch.Tensor:
+    """Dispatcher, as transforms/v2/functional/_color.py `equalize`."""
+    kernel = _get_kernel(equalize, type(inpt))
+    return kernel(inpt)
+
+
+@_register_kernel_internal(equalize, torch.Tensor)
+@_register_kernel_internal(equalize, tv_tensors.Image)
+def equalize_image(image: torch.Tensor) -> torch.Tensor:
+    """equalize_image (_color.py): per (H, W) plane, the 256-bin histogram of the uint8 image (float32: of
+    to_dtype(scale=True)), PIL's LUT, planes with step == 0 unequalised; float32 comes back as the uint8 result / 255, so it
+    is always quantised to 256 levels.  Float values outside [0, 1] (and NaN), where the reference's float -> uint8 cast is
+    undefined, are saturated: below 0 and NaN bin as 0, above 1 as 255.  Empty images are returned as they are."""
+    _check_color_dtype(image, "equalize")
+    if image.numel() == 0:
+        return image
+    return _plane_op(image, "equalize")
+
+
+@_register_kernel_internal(equalize, tv_tensors.Video)
+def equalize_video(video: torch.Tensor) -> torch.Tensor:
+    return equalize_image(video)
+
+
+for _f in (invert, posterize, solarize, autocontrast, equalize):
+    if _pil.PIL is not None:
+        _register_kernel_internal(_f, _pil.PIL.Image.Image)(_autoaug_pil_unsupported(_f.__name__))
 del _f
 
 

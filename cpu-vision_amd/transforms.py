@@ -8,6 +8,9 @@
                                           -> F.elastic)
   RandomRotation / RandomAffine / RandomPerspective   transforms/v2/_geometry.py (-> F.rotate / F.affine / F.perspective)
   ColorJitter / Grayscale / RandomGrayscale           transforms/v2/_color.py (-> F.adjust_* / F.rgb_to_grayscale)
+  RandomInvert / RandomPosterize / RandomSolarize / RandomAutocontrast / RandomEqualize   transforms/v2/_color.py
+  AutoAugment / RandAugment / TrivialAugmentWide      transforms/v2/_auto_augment.py (-> F.affine / rotate / adjust_* /
+                                                      posterize / solarize / autocontrast / equalize / invert)
   Resize / CenterCrop / ToDtype / Normalize / Compose   v2/_geometry.py:76-193, v2/_misc.py:134-304, v2/_container.py:10-64
 
 Parameter sampling stays on the host RNG exactly like the reference (torch.empty(1).uniform_ / torch.rand(1)).
@@ -15,6 +18,7 @@ Parameter sampling stays on the host RNG exactly like the reference (torch.empty
 from __future__ import annotations
 
 import collections.abc
+import math
 import numbers
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -721,6 +725,385 @@ class RandomGrayscale(_RandomApplyTransform):
 
     def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
         return self._call_kernel(F.rgb_to_grayscale, inpt, num_output_channels=params["num_input_channels"])
+
+
+class RandomInvert(_RandomApplyTransform):
+    """v2.RandomInvert(p=0.5) -- transforms/v2/_color.py (-> F.invert)."""
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.invert, inpt)
+
+
+class RandomPosterize(_RandomApplyTransform):
+    """v2.RandomPosterize(bits, p=0.5) -- transforms/v2/_color.py (-> F.posterize)."""
+
+    def __init__(self, bits: int, p: float = 0.5) -> None:
+        super().__init__(p=p)
+        self.bits = bits
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.posterize, inpt, bits=self.bits)
+
+
+class RandomSolarize(_RandomApplyTransform):
+    """v2.RandomSolarize(threshold, p=0.5) -- transforms/v2/_color.py (-> F.solarize)."""
+
+    def __init__(self, threshold: float, p: float = 0.5) -> None:
+        super().__init__(p=p)
+        self.threshold = threshold
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.solarize, inpt, threshold=self.threshold)
+
+
+class RandomAutocontrast(_RandomApplyTransform):
+    """v2.RandomAutocontrast(p=0.5) -- transforms/v2/_color.py (-> F.autocontrast)."""
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.autocontrast, inpt)
+
+
+class RandomEqualize(_RandomApplyTransform):
+    """v2.RandomEqualize(p=0.5) -- transforms/v2/_color.py (-> F.equalize)."""
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.equalize, inpt)
+
+
+class AutoAugmentPolicy(_enum.Enum):
+    """transforms/autoaugment.py `AutoAugmentPolicy`: the policies learned on these datasets."""
+
+    IMAGENET = "imagenet"
+    CIFAR10 = "cifar10"
+    SVHN = "svhn"
+
+
+class _AutoAugmentBase(Transform):
+    """transforms/v2/_auto_augment.py `_AutoAugmentBase`: one image or video per sample, ops applied one by one through the
+    F.* dispatchers.  The draws are the reference's host RNG calls in its order; PIL images raise NotImplementedError before
+    any draw."""
+
+    _AUGMENTATION_SPACE: Dict[str, Tuple[Callable[[int, int, int], Optional[torch.Tensor]], bool]] = {}
+
+    def __init__(self, *, interpolation=InterpolationMode.NEAREST, fill=None) -> None:
+        super().__init__()
+        self.interpolation = _check_interpolation(interpolation)
+        self.fill = fill
+        self._fill = _setup_fill_arg(fill)
+
+    def _get_random_item(self, dct: Dict[str, Any]) -> Tuple[str, Any]:
+        keys = tuple(dct.keys())
+        key = keys[int(torch.randint(len(keys), ()))]
+        return key, dct[key]
+
+    def _flatten_and_extract_image_or_video(self, inputs: Any, unsupported_types=(tv_tensors.BoundingBoxes, tv_tensors.Mask)):
+        flat_inputs, spec = tree_flatten(inputs if len(inputs) > 1 else inputs[0])
+        needs_transform_list = self._needs_transform_list(flat_inputs)
+        image_or_videos = []
+        for idx, (inpt, needs_transform) in enumerate(zip(flat_inputs, needs_transform_list)):
+            if needs_transform and (isinstance(inpt, (tv_tensors.Image, tv_tensors.Video) + _PIL_TYPES)
+                                    or is_pure_tensor(inpt)):
+                image_or_videos.append((idx, inpt))
+            elif isinstance(inpt, unsupported_types):
+                raise TypeError(f"Inputs of type {type(inpt).__name__} are not supported by {type(self).__name__}()")
+        if not image_or_videos:
+            raise TypeError("Found no image in the sample.")
+        if len(image_or_videos) > 1:
+            raise TypeError(f"Auto augment transformations are only properly defined for a single image or video, "
+                            f"but found {len(image_or_videos)}.")
+        idx, image_or_video = image_or_videos[0]
+        if isinstance(image_or_video, _PIL_TYPES):
+            raise NotImplementedError(f"{type(self).__name__}: PIL images go through Pillow's ImageOps / ImageEnhance in "
+                                      "the reference, which this library does not reproduce; convert with pil_to_tensor")
+        return (flat_inputs, spec, idx), image_or_video
+
+    def _unflatten_and_insert_image_or_video(self, flat_inputs_with_spec, image_or_video: Any) -> Any:
+        flat_inputs, spec, idx = flat_inputs_with_spec
+        flat_inputs[idx] = image_or_video
+        return tree_unflatten(flat_inputs, spec)
+
+    def _apply_image_or_video_transform(self, image: Any, transform_id: str, magnitude: float, interpolation, fill) -> Any:
+        fill_ = _get_fill(fill, type(image))
+        if transform_id == "Identity":
+            return image
+        elif transform_id == "ShearX":
+            # tan of the shear angle is the magnitude (the official AutoAugment's (1, level, 0, 0, 1, 0))
+            return F.affine(image, angle=0.0, translate=[0, 0], scale=1.0, shear=[math.degrees(math.atan(magnitude)), 0.0],
+                            interpolation=interpolation, fill=fill_, center=[0, 0])
+        elif transform_id == "ShearY":
+            return F.affine(image, angle=0.0, translate=[0, 0], scale=1.0, shear=[0.0, math.degrees(math.atan(magnitude))],
+                            interpolation=interpolation, fill=fill_, center=[0, 0])
+        elif transform_id == "TranslateX":
+            return F.affine(image, angle=0.0, translate=[int(magnitude), 0], scale=1.0, interpolation=interpolation,
+                            shear=[0.0, 0.0], fill=fill_)
+        elif transform_id == "TranslateY":
+            return F.affine(image, angle=0.0, translate=[0, int(magnitude)], scale=1.0, interpolation=interpolation,
+                            shear=[0.0, 0.0], fill=fill_)
+        elif transform_id == "Rotate":
+            return F.rotate(image, angle=magnitude, interpolation=interpolation, fill=fill_)
+        elif transform_id == "Brightness":
+            return F.adjust_brightness(image, brightness_factor=1.0 + magnitude)
+        elif transform_id == "Color":
+            return F.adjust_saturation(image, saturation_factor=1.0 + magnitude)
+        elif transform_id == "Contrast":
+            return F.adjust_contrast(image, contrast_factor=1.0 + magnitude)
+        elif transform_id == "Sharpness":
+            return F.adjust_sharpness(image, sharpness_factor=1.0 + magnitude)
+        elif transform_id == "Posterize":
+            return F.posterize(image, bits=int(magnitude))
+        elif transform_id == "Solarize":
+            bound = F._max_value(image.dtype)
+            return F.solarize(image, threshold=bound * magnitude)
+        elif transform_id == "AutoContrast":
+            return F.autocontrast(image)
+        elif transform_id == "Equalize":
+            return F.equalize(image)
+        elif transform_id == "Invert":
+            return F.invert(image)
+        else:
+            raise ValueError(f"No transform available for {transform_id}")
+
+    def _apply(self, image_or_video: Any, transform_id: str, magnitude: float) -> Any:
+        return self._apply_image_or_video_transform(image_or_video, transform_id, magnitude,
+                                                    interpolation=self.interpolation, fill=self._fill)
+
+    @staticmethod
+    def _size(image_or_video: Any) -> Tuple[int, int]:
+        h, w = image_or_video.shape[-2:]
+        return int(h), int(w)
+
+
+def _linspace(start: float, end: float):
+    return lambda num_bins, height, width: torch.linspace(start, end, num_bins)
+
+
+def _posterize_bits(levels: int):
+    return lambda num_bins, height, width: (8 - (torch.arange(num_bins) / ((num_bins - 1) / levels))).round().int()
+
+
+def _none(num_bins, height, width):
+    return None
+
+
+class AutoAugment(_AutoAugmentBase):
+    """v2.AutoAugment(policy=IMAGENET, interpolation=NEAREST, fill=None) -- transforms/v2/_auto_augment.py: one of the
+    policy's 25 sub-policies per sample (torch.randint), each of its two ops applied when torch.rand(()) <= its probability,
+    signed magnitudes negated when torch.rand(()) <= 0.5."""
+
+    _AUGMENTATION_SPACE = {
+        "ShearX": (_linspace(0.0, 0.3), True),
+        "ShearY": (_linspace(0.0, 0.3), True),
+        "TranslateX": (lambda num_bins, height, width: torch.linspace(0.0, 150.0 / 331.0 * width, num_bins), True),
+        "TranslateY": (lambda num_bins, height, width: torch.linspace(0.0, 150.0 / 331.0 * height, num_bins), True),
+        "Rotate": (_linspace(0.0, 30.0), True),
+        "Brightness": (_linspace(0.0, 0.9), True),
+        "Color": (_linspace(0.0, 0.9), True),
+        "Contrast": (_linspace(0.0, 0.9), True),
+        "Sharpness": (_linspace(0.0, 0.9), True),
+        "Posterize": (_posterize_bits(4), False),
+        "Solarize": (_linspace(1.0, 0.0), False),
+        "AutoContrast": (_none, False),
+        "Equalize": (_none, False),
+        "Invert": (_none, False),
+    }
+
+    def __init__(self, policy: AutoAugmentPolicy = AutoAugmentPolicy.IMAGENET, interpolation=InterpolationMode.NEAREST,
+                 fill=None) -> None:
+        super().__init__(interpolation=interpolation, fill=fill)
+        self.policy = policy
+        self._policies = self._get_policies(policy)
+
+    def _get_policies(self, policy: AutoAugmentPolicy):
+        if policy == AutoAugmentPolicy.IMAGENET:
+            return [
+                (("Posterize", 0.4, 8), ("Rotate", 0.6, 9)),
+                (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+                (("Equalize", 0.8, None), ("Equalize", 0.6, None)),
+                (("Posterize", 0.6, 7), ("Posterize", 0.6, 6)),
+                (("Equalize", 0.4, None), ("Solarize", 0.2, 4)),
+                (("Equalize", 0.4, None), ("Rotate", 0.8, 8)),
+                (("Solarize", 0.6, 3), ("Equalize", 0.6, None)),
+                (("Posterize", 0.8, 5), ("Equalize", 1.0, None)),
+                (("Rotate", 0.2, 3), ("Solarize", 0.6, 8)),
+                (("Equalize", 0.6, None), ("Posterize", 0.4, 6)),
+                (("Rotate", 0.8, 8), ("Color", 0.4, 0)),
+                (("Rotate", 0.4, 9), ("Equalize", 0.6, None)),
+                (("Equalize", 0.0, None), ("Equalize", 0.8, None)),
+                (("Invert", 0.6, None), ("Equalize", 1.0, None)),
+                (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+                (("Rotate", 0.8, 8), ("Color", 1.0, 2)),
+                (("Color", 0.8, 8), ("Solarize", 0.8, 7)),
+                (("Sharpness", 0.4, 7), ("Invert", 0.6, None)),
+                (("ShearX", 0.6, 5), ("Equalize", 1.0, None)),
+                (("Color", 0.4, 0), ("Equalize", 0.6, None)),
+                (("Equalize", 0.4, None), ("Solarize", 0.2, 4)),
+                (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+                (("Invert", 0.6, None), ("Equalize", 1.0, None)),
+                (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+                (("Equalize", 0.8, None), ("Equalize", 0.6, None)),
+            ]
+        elif policy == AutoAugmentPolicy.CIFAR10:
+            return [
+                (("Invert", 0.1, None), ("Contrast", 0.2, 6)),
+                (("Rotate", 0.7, 2), ("TranslateX", 0.3, 9)),
+                (("Sharpness", 0.8, 1), ("Sharpness", 0.9, 3)),
+                (("ShearY", 0.5, 8), ("TranslateY", 0.7, 9)),
+                (("AutoContrast", 0.5, None), ("Equalize", 0.9, None)),
+                (("ShearY", 0.2, 7), ("Posterize", 0.3, 7)),
+                (("Color", 0.4, 3), ("Brightness", 0.6, 7)),
+                (("Sharpness", 0.3, 9), ("Brightness", 0.7, 9)),
+                (("Equalize", 0.6, None), ("Equalize", 0.5, None)),
+                (("Contrast", 0.6, 7), ("Sharpness", 0.6, 5)),
+                (("Color", 0.7, 7), ("TranslateX", 0.5, 8)),
+                (("Equalize", 0.3, None), ("AutoContrast", 0.4, None)),
+                (("TranslateY", 0.4, 3), ("Sharpness", 0.2, 6)),
+                (("Brightness", 0.9, 6), ("Color", 0.2, 8)),
+                (("Solarize", 0.5, 2), ("Invert", 0.0, None)),
+                (("Equalize", 0.2, None), ("AutoContrast", 0.6, None)),
+                (("Equalize", 0.2, None), ("Equalize", 0.6, None)),
+                (("Color", 0.9, 9), ("Equalize", 0.6, None)),
+                (("AutoContrast", 0.8, None), ("Solarize", 0.2, 8)),
+                (("Brightness", 0.1, 3), ("Color", 0.7, 0)),
+                (("Solarize", 0.4, 5), ("AutoContrast", 0.9, None)),
+                (("TranslateY", 0.9, 9), ("TranslateY", 0.7, 9)),
+                (("AutoContrast", 0.9, None), ("Solarize", 0.8, 3)),
+                (("Equalize", 0.8, None), ("Invert", 0.1, None)),
+                (("TranslateY", 0.7, 9), ("AutoContrast", 0.9, None)),
+            ]
+        elif policy == AutoAugmentPolicy.SVHN:
+            return [
+                (("ShearX", 0.9, 4), ("Invert", 0.2, None)),
+                (("ShearY", 0.9, 8), ("Invert", 0.7, None)),
+                (("Equalize", 0.6, None), ("Solarize", 0.6, 6)),
+                (("Invert", 0.9, None), ("Equalize", 0.6, None)),
+                (("Equalize", 0.6, None), ("Rotate", 0.9, 3)),
+                (("ShearX", 0.9, 4), ("AutoContrast", 0.8, None)),
+                (("ShearY", 0.9, 8), ("Invert", 0.4, None)),
+                (("ShearY", 0.9, 5), ("Solarize", 0.2, 6)),
+                (("Invert", 0.9, None), ("AutoContrast", 0.8, None)),
+                (("Equalize", 0.6, None), ("Rotate", 0.9, 3)),
+                (("ShearX", 0.9, 4), ("Solarize", 0.3, 3)),
+                (("ShearY", 0.8, 8), ("Invert", 0.7, None)),
+                (("Equalize", 0.9, None), ("TranslateY", 0.6, 6)),
+                (("Invert", 0.9, None), ("Equalize", 0.6, None)),
+                (("Contrast", 0.3, 3), ("Rotate", 0.8, 4)),
+                (("Invert", 0.8, None), ("TranslateY", 0.0, 2)),
+                (("ShearY", 0.7, 6), ("Solarize", 0.4, 8)),
+                (("Invert", 0.6, None), ("Rotate", 0.8, 4)),
+                (("ShearY", 0.3, 7), ("TranslateX", 0.9, 3)),
+                (("ShearX", 0.1, 6), ("Invert", 0.6, None)),
+                (("Solarize", 0.7, 2), ("TranslateY", 0.6, 7)),
+                (("ShearY", 0.8, 4), ("Invert", 0.8, None)),
+                (("ShearX", 0.7, 9), ("TranslateY", 0.8, 3)),
+                (("ShearY", 0.8, 5), ("AutoContrast", 0.7, None)),
+                (("ShearX", 0.7, 2), ("Invert", 0.1, None)),
+            ]
+        else:
+            raise ValueError(f"The provided policy {policy} is not recognized.")
+
+    def forward(self, *inputs: Any) -> Any:
+        flat_inputs_with_spec, image_or_video = self._flatten_and_extract_image_or_video(inputs)
+        height, width = self._size(image_or_video)
+        policy = self._policies[int(torch.randint(len(self._policies), ()))]
+        for transform_id, probability, magnitude_idx in policy:
+            if not torch.rand(()) <= probability:
+                continue
+            magnitudes_fn, signed = self._AUGMENTATION_SPACE[transform_id]
+            magnitudes = magnitudes_fn(10, height, width)
+            if magnitudes is not None:
+                magnitude = float(magnitudes[magnitude_idx])
+                if signed and torch.rand(()) <= 0.5:
+                    magnitude *= -1
+            else:
+                magnitude = 0.0
+            image_or_video = self._apply(image_or_video, transform_id, magnitude)
+        return self._unflatten_and_insert_image_or_video(flat_inputs_with_spec, image_or_video)
+
+
+class RandAugment(_AutoAugmentBase):
+    """v2.RandAugment(num_ops=2, magnitude=9, num_magnitude_bins=31, interpolation=NEAREST, fill=None) --
+    transforms/v2/_auto_augment.py: num_ops ops drawn uniformly from the space (torch.randint), each at the fixed magnitude
+    bin, signed magnitudes negated when torch.rand(()) <= 0.5."""
+
+    _AUGMENTATION_SPACE = {
+        "Identity": (_none, False),
+        "ShearX": (_linspace(0.0, 0.3), True),
+        "ShearY": (_linspace(0.0, 0.3), True),
+        "TranslateX": (lambda num_bins, height, width: torch.linspace(0.0, 150.0 / 331.0 * width, num_bins), True),
+        "TranslateY": (lambda num_bins, height, width: torch.linspace(0.0, 150.0 / 331.0 * height, num_bins), True),
+        "Rotate": (_linspace(0.0, 30.0), True),
+        "Brightness": (_linspace(0.0, 0.9), True),
+        "Color": (_linspace(0.0, 0.9), True),
+        "Contrast": (_linspace(0.0, 0.9), True),
+        "Sharpness": (_linspace(0.0, 0.9), True),
+        "Posterize": (_posterize_bits(4), False),
+        "Solarize": (_linspace(1.0, 0.0), False),
+        "AutoContrast": (_none, False),
+        "Equalize": (_none, False),
+    }
+
+    def __init__(self, num_ops: int = 2, magnitude: int = 9, num_magnitude_bins: int = 31,
+                 interpolation=InterpolationMode.NEAREST, fill=None) -> None:
+        super().__init__(interpolation=interpolation, fill=fill)
+        self.num_ops = num_ops
+        self.magnitude = magnitude
+        self.num_magnitude_bins = num_magnitude_bins
+
+    def forward(self, *inputs: Any) -> Any:
+        flat_inputs_with_spec, image_or_video = self._flatten_and_extract_image_or_video(inputs)
+        height, width = self._size(image_or_video)
+        for _ in range(self.num_ops):
+            transform_id, (magnitudes_fn, signed) = self._get_random_item(self._AUGMENTATION_SPACE)
+            magnitudes = magnitudes_fn(self.num_magnitude_bins, height, width)
+            if magnitudes is not None:
+                magnitude = float(magnitudes[self.magnitude])
+                if signed and torch.rand(()) <= 0.5:
+                    magnitude *= -1
+            else:
+                magnitude = 0.0
+            image_or_video = self._apply(image_or_video, transform_id, magnitude)
+        return self._unflatten_and_insert_image_or_video(flat_inputs_with_spec, image_or_video)
+
+
+class TrivialAugmentWide(_AutoAugmentBase):
+    """v2.TrivialAugmentWide(num_magnitude_bins=31, interpolation=NEAREST, fill=None) -- transforms/v2/_auto_augment.py: one
+    op drawn uniformly from the space (torch.randint), a magnitude bin drawn uniformly (torch.randint, only for ops with
+    magnitudes), signed magnitudes negated when torch.rand(()) <= 0.5."""
+
+    _AUGMENTATION_SPACE = {
+        "Identity": (_none, False),
+        "ShearX": (_linspace(0.0, 0.99), True),
+        "ShearY": (_linspace(0.0, 0.99), True),
+        "TranslateX": (_linspace(0.0, 32.0), True),
+        "TranslateY": (_linspace(0.0, 32.0), True),
+        "Rotate": (_linspace(0.0, 135.0), True),
+        "Brightness": (_linspace(0.0, 0.99), True),
+        "Color": (_linspace(0.0, 0.99), True),
+        "Contrast": (_linspace(0.0, 0.99), True),
+        "Sharpness": (_linspace(0.0, 0.99), True),
+        "Posterize": (_posterize_bits(6), False),
+        "Solarize": (_linspace(1.0, 0.0), False),
+        "AutoContrast": (_none, False),
+        "Equalize": (_none, False),
+    }
+
+    def __init__(self, num_magnitude_bins: int = 31, interpolation=InterpolationMode.NEAREST, fill=None) -> None:
+        super().__init__(interpolation=interpolation, fill=fill)
+        self.num_magnitude_bins = num_magnitude_bins
+
+    def forward(self, *inputs: Any) -> Any:
+        flat_inputs_with_spec, image_or_video = self._flatten_and_extract_image_or_video(inputs)
+        height, width = self._size(image_or_video)
+        transform_id, (magnitudes_fn, signed) = self._get_random_item(self._AUGMENTATION_SPACE)
+        magnitudes = magnitudes_fn(self.num_magnitude_bins, height, width)
+        if magnitudes is not None:
+            magnitude = float(magnitudes[int(torch.randint(self.num_magnitude_bins, ()))])
+            if signed and torch.rand(()) <= 0.5:
+                magnitude *= -1
+        else:
+            magnitude = 0.0
+        image_or_video = self._apply(image_or_video, transform_id, magnitude)
+        return self._unflatten_and_insert_image_or_video(flat_inputs_with_spec, image_or_video)
 
 
 class GaussianBlurV1(nn.Module):

@@ -429,6 +429,43 @@ int mv_rgb_to_grayscale_f32(const float* x, float* y, int64_t images, int h, int
 int mv_rgb_to_grayscale_u8(const uint8_t* x, uint8_t* y, int64_t images, int h, int w, int out_channels, int form,
                            void* stream);
 
+/* ---- The automatic-augmentation colour ops (transforms/v2/functional/_color.py invert_image, posterize_image,
+ * solarize_image, autocontrast_image, equalize_image): what AutoAugment / RandAugment / TrivialAugmentWide call besides the
+ * geometric and F.adjust_* ops.  x, y are contiguous and not aliased.
+ *
+ * mv_pointwise_*: n elements of any layout, op applied to each.  MV_POINT_INVERT: float 1.0f - x, uint8 ~x (param unused).
+ * MV_POINT_POSTERIZE, param = bits in [0, 8]: float floor(x * 2^bits) clamped to [0, 2^bits - 1], times 2^-bits (NaN stays
+ * NaN); uint8 x & (((1 << bits) - 1) << (8 - bits)).  MV_POINT_SOLARIZE, param = threshold: (float)x >= (float)threshold ?
+ * invert(x) : x -- the comparison of a uint8 image against a float threshold, which torch promotes to float32 (a host with an
+ * integer threshold passes the uint8 value it wraps to). */
+#define MV_POINT_INVERT 0
+#define MV_POINT_POSTERIZE 1
+#define MV_POINT_SOLARIZE 2
+int mv_pointwise_f32(const float* x, float* y, int64_t n, int op, double param, void* stream);
+int mv_pointwise_u8(const uint8_t* x, uint8_t* y, int64_t n, int op, double param, void* stream);
+/* autocontrast on (planes, h, w): per plane, min and max in float32 (uint8 as its integer values), inv_scale =
+ * (max - min) * (float)(1 / bound); a plane with max == min takes min = 0, inv_scale = 1; then (x - min) / inv_scale (a
+ * correctly rounded division) clamped to [0, bound], uint8 truncated.  A NaN anywhere in a float32 plane makes the whole
+ * plane NaN, as amin / amax propagate it.  Two launches: per-workgroup (min, max, NaN) partials in `workspace` (a DEVICE
+ * buffer of mv_autocontrast_workspace_bytes bytes, any content), then the map, each workgroup reducing its plane's partials
+ * in index order.  Nothing is read back. */
+int64_t mv_autocontrast_workspace_bytes(int64_t planes, int h, int w, int u8);
+int mv_autocontrast_f32(const float* x, float* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int mv_autocontrast_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+/* equalize on (planes, h, w), h * w < 2^31: per plane the 256-bin histogram of the uint8 image (float32: of
+ * (uint8)(x * 255.999f), with values outside [0, 1] and NaN saturated to bins 0 and 255), num_non_max = h * w - hist[max value],
+ * step = num_non_max / 255, lut[0] = 0, lut[k] = min((cum_hist[k - 1] + step / 2) / step, 255); planes with step == 0 keep
+ * their (quantised) values.  float32 output: (float)v * (float)(1 / 255.0).  The histogram is built per workgroup in LDS and
+ * added with integer atomics into `workspace` (mv_equalize_workspace_bytes bytes: planes x 256 uint32, zeroed on the stream
+ * by the call's first kernel); the map's workgroups each rebuild their plane's LUT from it.  Nothing is read back. */
+int64_t mv_equalize_workspace_bytes(int64_t planes, int h, int w, int u8);
+int mv_equalize_f32(const float* x, float* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+int mv_equalize_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
