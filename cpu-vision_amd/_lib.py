@@ -183,6 +183,19 @@ def require_device(t: torch.Tensor, what: str = "input") -> None:
             "fallback -- move the tensor to a HIP device (tensor.cuda()).")
 
 
+def require_f32_u8(image: torch.Tensor, name: str, allow_bool: bool = False) -> None:
+    """The dtype gate of the image ops whose kernels exist for float32 and uint8 storage (launch_image_op)."""
+    dtype = image.dtype
+    if not (dtype is torch.uint8 or dtype is torch.float32 or (allow_bool and dtype is torch.bool)):
+        raise NotImplementedError(f"{name}: {image.dtype} images are not on the MI355X path (float32 and uint8 are)")
+
+
+def max_value(dtype: torch.dtype) -> int:
+    """transforms/_functional_tensor.py:41-57"""
+    return {torch.uint8: 255, torch.int8: 127, torch.int16: 32767, torch.uint16: 65535, torch.int32: 2147483647,
+            torch.int64: 9223372036854775807}.get(dtype, 1)
+
+
 class _ForwardOnly(torch.autograd.Function):
     """Marks the output of a forward-only kernel: it takes part in autograd (so that nothing downstream silently trains on
     missing gradients) and raises as soon as a backward pass reaches it."""
@@ -233,6 +246,42 @@ def on_device_of(t: torch.Tensor) -> _DeviceOf:
 
 def stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def launch_image_op(name: str, image: torch.Tensor, args, *, out_shape=None, workspace=None, allow_bool: bool = False,
+                    what: Optional[str] = None, deps=()) -> torch.Tensor:
+    """ONE call of mv_<name>_u8 / mv_<name>_f32 (chosen by the storage type) on a non-empty float32 / uint8 image:
+    fn(x, y, *args[, workspace, workspace_bytes], stream), x the contiguous image and y a fresh output of `out_shape` (default:
+    x's shape).  The caller has checked its arguments and the dtype (require_f32_u8).
+
+      args        the tuple of what the entry point takes between y and the workspace / stream; a device tensor whose pointer is
+                  in it lives on the image's device, and the caller keeps it alive over this call
+      workspace   (base, dims): a device buffer of mv_<base>_workspace_bytes(*dims, is_u8) bytes, passed with its size
+      allow_bool  bool images are computed as float32 and come back through the reference's integer tail, round_().to(bool)
+      what, deps  float32 results are forward-only (forward_only) under the name `what` (default: `name`), computed from
+                  the image and `deps`
+
+    The filters and the CNN layers do not come through here: they widen dtypes, return pairs or take pointer tables."""
+    require_device(image)
+    lib = load()
+    u8 = image.dtype is torch.uint8
+    as_f32 = allow_bool and image.dtype is torch.bool
+    with on_device_of(image):
+        x = image.to(torch.float32).contiguous() if as_f32 else image.contiguous()
+        # each case's cheapest binding of the same allocation: torch.empty(shape, dtype=, device=) costs 1-2 us more host time
+        y = torch.empty_like(x, memory_format=torch.contiguous_format) if out_shape is None else x.new_empty(out_shape)
+        if workspace is not None:
+            base, dims = workspace
+            ws_bytes = int(getattr(lib, f"mv_{base}_workspace_bytes")(*dims, int(u8)))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+            args += (ws.data_ptr(), ws_bytes)
+        fn = getattr(lib, f"mv_{name}_u8" if u8 else f"mv_{name}_f32")
+        check(fn(x.data_ptr(), y.data_ptr(), *args, stream_ptr(x)))
+    if as_f32:
+        return y.round_().to(torch.bool)
+    if u8:
+        return y
+    return forward_only(y, what or name, image, *deps)
 
 
 def taps(values: Sequence[float]):

@@ -88,6 +88,42 @@ def _register_kernel_internal(functional, input_type, *, tv_tensor_wrapper=True)
     return decorator
 
 
+def _register_image_and_video(functional):
+    """Decorator: the image kernel serves plain tensors, Image and Video alike (it takes any leading dimensions, so the
+    reference's `*_video` kernels, which only call `*_image`, are the same function here)."""
+
+    def decorator(image_kernel):
+        for input_type in (tv_tensors.Image, torch.Tensor, tv_tensors.Video):  # _get_kernel's TypeError lists them in this order
+            _register_kernel_internal(functional, input_type)(image_kernel)
+        return image_kernel
+
+    return decorator
+
+
+def _register_mask(functional):
+    """Decorator for the `*_mask` kernel of a grid transform: the dispatcher hands every kernel the images' `interpolation`,
+    which a mask (always nearest) does not take."""
+
+    def decorator(mask_kernel):
+        def from_dispatcher(mask, *args, interpolation=None, **kwargs):
+            return mask_kernel(mask, *args, **kwargs)
+
+        _register_kernel_internal(functional, tv_tensors.Mask)(from_dispatcher)
+        return mask_kernel
+
+    return decorator
+
+
+def _unsupported(functional, input_type, reason: str) -> None:
+    """Inputs of `input_type` raise "<functional>: <reason>": passed through they would come back untransformed, silently
+    wrong."""
+
+    def kernel(inpt, *args, **kwargs):
+        raise NotImplementedError(f"{functional.__name__}: {reason}")
+
+    _register_kernel_internal(functional, input_type, tv_tensor_wrapper=False)(kernel)
+
+
 def _functional_by_name(name: str):
     from . import functional as F
 

@@ -9,14 +9,12 @@ New operators on the same primitive (BASELINE cfg1/cfg3; the reference has no bo
   depthwise_conv2d, box_filter, separable_gaussian_blur, sobel, gaussian_sobel
 First CNN layer (models/vgg.py:81-85, ops/misc.py:97-119):
   conv2d_bias_relu
-ElasticTransform's resampling:
-  elastic / elastic_image / elastic_mask / elastic_video      transforms/v2/functional/_geometry.py (elastic*, _apply_grid_transform)
-The other grid transforms (same file, same _apply_grid_transform):
-  affine / rotate / perspective and their _image / _mask / _video kernels
-The colour ops (transforms/v2/functional/_color.py):
-  adjust_brightness / adjust_contrast / adjust_saturation / adjust_hue and their _image / _video kernels,
-  rgb_to_grayscale / rgb_to_grayscale_image
+Defined in _geometry.py and _color.py, as in the reference (transforms/v2/functional/_geometry.py, _color.py), and re-exported
+here under the same names, private helpers included -- this module stays the one namespace the package, the tests and tools/ use:
+  elastic / affine / rotate / perspective and their _image / _mask / _video kernels
+  adjust_brightness / adjust_contrast / adjust_saturation / adjust_hue, rgb_to_grayscale,
   invert / posterize / solarize / autocontrast / equalize and their _image / _video kernels
+The module-level switches below (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION, CONV2D_*) are set and read on this module only.
 
 Tensors must live on a HIP device; there is no CPU fallback (see _lib.py).  Host-side work here is what
 the reference also does on the host: argument checking, the handful of Gaussian taps, reshapes.
@@ -25,7 +23,6 @@ from __future__ import annotations
 
 import functools
 import math
-import numbers
 from typing import List, Optional, Sequence, Tuple, Union
 
 import ctypes as C
@@ -33,6 +30,25 @@ import ctypes as C
 import torch
 
 from . import _lib, _pil, tv_tensors
+# moved code, same objects: everything _color and _geometry define is reached through this module
+from ._color import (_add_alpha_fuses, adjust_brightness, adjust_brightness_image, adjust_brightness_video,  # noqa: F401
+                     adjust_contrast, adjust_contrast_image, adjust_contrast_video, adjust_hue, adjust_hue_image,
+                     adjust_hue_video, adjust_saturation, adjust_saturation_image, adjust_saturation_video,
+                     autocontrast, autocontrast_image, autocontrast_video, _blend_form, _check_color_channels,
+                     _check_color_factor, _color_chain, color_jitter_image, _COLOR_OPS, equalize, equalize_image,
+                     equalize_video, invert, invert_image, invert_video, _plane_op, _POINT_OPS, _pointwise,
+                     posterize, posterize_image, posterize_video, rgb_to_grayscale, rgb_to_grayscale_image,
+                     solarize, solarize_image, solarize_video)
+from ._geometry import (affine, _affine_coeffs, affine_image, affine_mask, _affine_parse_args, affine_video,  # noqa: F401
+                        _assert_grid_transform_inputs, _blocked_bmm_fuses, _BMM_NAIVE_LIMIT,
+                        _compute_affine_output_size, elastic, _elastic_bounding_boxes_dispatch, _elastic_fill,
+                        elastic_image, _elastic_image_pil, elastic_mask, _ELASTIC_MODES, elastic_transform,
+                        elastic_video, _get_inverse_affine_matrix, _get_perspective_coeffs, _grid_order,
+                        _identity_grid_vectors, _interpolation_name, _nearest_on_mask, perspective,
+                        _perspective_coefficients, _perspective_grid_coeffs, perspective_image, perspective_mask,
+                        perspective_video, _PIL_INTERPOLATION, rotate, rotate_image, rotate_mask, rotate_video,
+                        _warp, _WARP_KINDS)
+from ._lib import max_value as _max_value
 from ._registry import _get_kernel, _register_kernel_internal
 
 # direct 2-D evaluation (the reference's own formulation) up to this many taps; larger float kernels
@@ -59,12 +75,6 @@ INTEGER_BLUR_EXACT_FAST = True
 # slices (mv_inverted_residual_k_slices) then runs as three launches.  (MobileNet's pointwise convs slice K inside the
 # workgroup, mv_conv1x1_k_slices: that plan is part of the kernel and is not switched by this flag.)
 BATCH_INVARIANT_SUMMATION = False
-
-
-def _max_value(dtype: torch.dtype) -> int:
-    """transforms/_functional_tensor.py:41-57"""
-    return {torch.uint8: 255, torch.int8: 127, torch.int16: 32767, torch.uint16: 65535, torch.int32: 2147483647,
-            torch.int64: 9223372036854775807}.get(dtype, 1)
 
 
 # --------------------------------------------------------------------------------------------- taps
@@ -976,930 +986,6 @@ def center_crop_image(image: torch.Tensor, output_size: List[int]) -> torch.Tens
     """center_crop_image (_geometry.py:1860-1880): a view when the box lies inside the image, zero padding otherwise."""
     from . import functional_v1
     return functional_v1.center_crop(image, output_size)
-
-
-# --------------------------------------------------------------------------------------------- elastic (v2 surface)
-def elastic(inpt: torch.Tensor, displacement: torch.Tensor, interpolation="bilinear", fill=None) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_geometry.py `elastic`: resample `inpt` at identity grid + displacement."""
-    kernel = _get_kernel(elastic, type(inpt))
-    return kernel(inpt, displacement=displacement, interpolation=interpolation, fill=fill)
-
-
-elastic_transform = elastic
-
-# Pillow's integer constants (transforms/functional.py `_interpolation_modes_from_int`)
-_PIL_INTERPOLATION = {0: "nearest", 2: "bilinear", 3: "bicubic", 4: "box", 5: "hamming", 1: "lanczos"}
-_ELASTIC_MODES = {"bilinear": 0, "nearest": 1}
-
-
-def _interpolation_name(interpolation) -> str:
-    """_check_interpolation (_geometry.py): an InterpolationMode, its string value or a Pillow integer constant -> the mode's
-    string value."""
-    if isinstance(interpolation, int) and not isinstance(interpolation, bool):
-        if interpolation not in _PIL_INTERPOLATION:
-            raise ValueError(f"Interpolation mode {interpolation} is not supported.")
-        return _PIL_INTERPOLATION[interpolation]
-    name = getattr(interpolation, "value", interpolation)
-    if not isinstance(name, str):
-        raise ValueError(f"Argument interpolation should be an `InterpolationMode` or a corresponding Pillow integer constant, "
-                         f"but got {interpolation}.")
-    return name
-
-
-@functools.lru_cache(maxsize=64)
-def _identity_grid_vectors(h: int, w: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The two linspace vectors of the reference's `_create_identity_grid`, computed by torch on the host exactly as the
-    reference computes them (ATen's vectorised arange: its bits are not the closed form start + i * step) and kept on the
-    device: W + H floats per frame size."""
-    bx = torch.linspace((-w + 1) / w, (w - 1) / w, w, dtype=torch.float32)
-    by = torch.linspace((-h + 1) / h, (h - 1) / h, h, dtype=torch.float32)
-    return bx.to(device), by.to(device)
-
-
-def _elastic_fill(fill, c: int):
-    """(host float array, channels) of the fill blend, or (None, 1).  The reference builds
-    torch.tensor(fill_list, dtype=float32).view(1, -1, 1, 1) and broadcasts it against C channels."""
-    if fill is None:
-        return None, 1
-    values = [float(v) for v in fill] if isinstance(fill, (tuple, list)) else [float(fill)]
-    if len(values) not in (1, c):
-        raise RuntimeError(f"The size of tensor a ({c}) must match the size of tensor b ({len(values)}) at non-singleton "
-                           "dimension 1: fill needs one value or one per channel")
-    return _lib.taps(values), len(values)
-
-
-@_register_kernel_internal(elastic, torch.Tensor)
-@_register_kernel_internal(elastic, tv_tensors.Image)
-def elastic_image(image: torch.Tensor, displacement: torch.Tensor, interpolation="bilinear", fill=None) -> torch.Tensor:
-    """elastic_image (_geometry.py) on (..., C, H, W) float32 / uint8 images: grid_sample(image, identity grid +
-    displacement, mode, padding_mode="zeros", align_corners=False) with the fill blend of the reference's ones-mask, as ONE
-    launch (mv_elastic_*) over every plane -- the reference's per-pixel arithmetic, bit for bit.
-    The identity grid is never materialised: the kernel adds the displacement to the two cached linspace vectors."""
-    if not isinstance(displacement, torch.Tensor):
-        raise TypeError("Argument displacement should be a Tensor")
-    mode = _interpolation_name(interpolation)
-    if image.ndim < 3:
-        raise ValueError(f"Expected tensor to be a tensor image of size (..., C, H, W). Got {tuple(image.shape)}.")
-    h, w = int(image.shape[-2]), int(image.shape[-1])
-    expected_shape = (1, h, w, 2)
-    if expected_shape != displacement.shape:
-        raise ValueError(f"Argument displacement shape should be {expected_shape}, but given {displacement.shape}")
-    if mode not in _ELASTIC_MODES:
-        raise NotImplementedError(f"elastic: interpolation {mode!r} is not on the MI355X path (bilinear and nearest are)")
-    if image.dtype not in (torch.float32, torch.uint8, torch.bool):
-        raise NotImplementedError(f"elastic: {image.dtype} images are not on the MI355X path (float32 and uint8 are)")
-    c = int(image.shape[-3])
-    fill_arr, fill_channels = _elastic_fill(fill, c)
-    if image.numel() == 0:
-        return image
-    _lib.require_device(image)
-    _lib.require_device(displacement, "displacement")
-    lib = _lib.load()
-    planes = image.numel() // (h * w)
-    with _lib.on_device_of(image):
-        bx, by = _identity_grid_vectors(h, w, image.device)
-        d = displacement.detach().to(dtype=torch.float32, device=image.device)  # the reference's .to(dtype, device): no copy when it fits
-        x = image.contiguous() if image.dtype != torch.bool else image.to(torch.float32).contiguous()
-        y = torch.empty_like(x, memory_format=torch.contiguous_format)
-        fn = lib.mv_elastic_u8 if x.dtype == torch.uint8 else lib.mv_elastic_f32
-        _lib.check(fn(x.data_ptr(), y.data_ptr(), planes, fill_channels, h, w, bx.data_ptr(), by.data_ptr(), d.data_ptr(),
-                      d.stride(1), d.stride(2), d.stride(3), _ELASTIC_MODES[mode], fill_arr, _lib.stream_ptr(x)))
-    if image.dtype == torch.bool:  # the reference's integer tail: round_().to(dtype)
-        return y.round_().to(torch.bool)
-    if image.dtype == torch.float32:
-        return _lib.forward_only(y, "elastic", image, displacement)
-    return y
-
-
-def _elastic_image_pil(image, displacement: torch.Tensor, interpolation="bilinear", fill=None):
-    """_elastic_image_pil (_geometry.py): pil_to_tensor -> elastic_image -> to_pil_image(mode=image.mode), the tensor on the
-    current HIP device for the kernel."""
-    t_img = _pil.pil_to_tensor(image)
-    output = elastic_image(t_img.to(_pil.device_for_host_inputs()), displacement=displacement, interpolation=interpolation,
-                           fill=fill)
-    return _pil.to_pil_image(output.cpu(), mode=image.mode)
-
-
-if _pil.PIL is not None:
-    _register_kernel_internal(elastic, _pil.PIL.Image.Image)(_elastic_image_pil)
-
-
-def elastic_mask(mask: torch.Tensor, displacement: torch.Tensor, fill=None) -> torch.Tensor:
-    """elastic_mask (_geometry.py): nearest, with a channel dimension added below 3-D."""
-    needs_squeeze = mask.ndim < 3
-    if needs_squeeze:
-        mask = mask.unsqueeze(0)
-    output = elastic_image(mask, displacement=displacement, interpolation="nearest", fill=fill)
-    return output.squeeze(0) if needs_squeeze else output
-
-
-@_register_kernel_internal(elastic, tv_tensors.Mask, tv_tensor_wrapper=False)
-def _elastic_mask_dispatch(inpt: torch.Tensor, displacement: torch.Tensor, fill=None, **kwargs) -> torch.Tensor:
-    output = elastic_mask(inpt.as_subclass(torch.Tensor), displacement=displacement, fill=fill)
-    return tv_tensors.wrap(output, like=inpt)
-
-
-@_register_kernel_internal(elastic, tv_tensors.BoundingBoxes, tv_tensor_wrapper=False)
-def _elastic_bounding_boxes_dispatch(inpt: torch.Tensor, displacement: torch.Tensor, **kwargs) -> torch.Tensor:
-    """Boxes are not warped here: passed through, they would come back unmoved -- silently wrong -- so they raise."""
-    raise NotImplementedError("elastic: warping BoundingBoxes (elastic_bounding_boxes) is not implemented on the MI355X path")
-
-
-@_register_kernel_internal(elastic, tv_tensors.Video)
-def elastic_video(video: torch.Tensor, displacement: torch.Tensor, interpolation="bilinear", fill=None) -> torch.Tensor:
-    return elastic_image(video, displacement, interpolation=interpolation, fill=fill)
-
-
-# --------------------------------------------------------------------------------------------- affine / rotate / perspective
-# (v2 surface).  The host math below is the reference's, with its own ops on the CPU (transforms/functional.py
-# _get_inverse_affine_matrix / _get_perspective_coeffs, v2/functional/_geometry.py _affine_parse_args /
-# _compute_affine_output_size / _perspective_coefficients / _assert_grid_transform_inputs / _affine_grid / _perspective_grid);
-# the grid itself is computed per pixel by k_warp (csrc/warp.hip, DESIGN.md section 3.14).
-_WARP_KINDS = {"affine": 0, "perspective": 1}
-# ATen's bmm takes its naive loop -- plain sums, no fma -- below this many multiply-adds (contraction 3 x oh*ow x 2); above
-# it the rounding is the BLAS kernel's (_blocked_bmm_fuses)
-_BMM_NAIVE_LIMIT = 400
-
-
-def _affine_parse_args(angle, translate, scale, shear, center=None):
-    """_affine_parse_args (_geometry.py); the interpolation is checked by the caller."""
-    if not isinstance(angle, (int, float)):
-        raise TypeError("Argument angle should be int or float")
-    if not isinstance(translate, (list, tuple)):
-        raise TypeError("Argument translate should be a sequence")
-    if len(translate) != 2:
-        raise ValueError("Argument translate should be a sequence of length 2")
-    if scale <= 0.0:
-        raise ValueError("Argument scale should be positive")
-    if not isinstance(shear, (numbers.Number, (list, tuple))):
-        raise TypeError("Shear should be either a single value or a sequence of two values")
-    if isinstance(angle, int):
-        angle = float(angle)
-    if isinstance(translate, tuple):
-        translate = list(translate)
-    if isinstance(shear, numbers.Number):
-        shear = [shear, 0.0]
-    if isinstance(shear, tuple):
-        shear = list(shear)
-    if len(shear) == 1:
-        shear = [shear[0], shear[0]]
-    if len(shear) != 2:
-        raise ValueError(f"Shear should be a sequence containing two values. Got {shear}")
-    if center is not None:
-        if not isinstance(center, (list, tuple)):
-            raise TypeError("Argument center should be a sequence")
-        center = [float(c) for c in center]
-    return angle, translate, shear, center
-
-
-def _get_inverse_affine_matrix(center: List[float], angle: float, translate: List[float], scale: float,
-                               shear: List[float]) -> List[float]:
-    """transforms/functional.py `_get_inverse_affine_matrix` (inverted=True): RSS^-1 * C^-1 * T^-1, then C."""
-    rot = math.radians(angle)
-    sx = math.radians(shear[0])
-    sy = math.radians(shear[1])
-    cx, cy = center
-    tx, ty = translate
-    a = math.cos(rot - sy) / math.cos(sy)
-    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
-    c = math.sin(rot - sy) / math.cos(sy)
-    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
-    matrix = [d, -b, 0.0, -c, a, 0.0]
-    matrix = [x / scale for x in matrix]
-    matrix[2] += matrix[0] * (-cx - tx) + matrix[1] * (-cy - ty)
-    matrix[5] += matrix[3] * (-cx - tx) + matrix[4] * (-cy - ty)
-    matrix[2] += cx
-    matrix[5] += cy
-    return matrix
-
-
-def _compute_affine_output_size(matrix: List[float], w: int, h: int) -> Tuple[int, int]:
-    """_compute_affine_output_size (_geometry.py, tensor form): the (w, h) of rotate's `expand` canvas."""
-    half_w = 0.5 * w
-    half_h = 0.5 * h
-    pts = torch.tensor([[-half_w, -half_h, 1.0], [-half_w, half_h, 1.0], [half_w, half_h, 1.0], [half_w, -half_h, 1.0]])
-    theta = torch.tensor(matrix, dtype=torch.float).view(2, 3)
-    new_pts = torch.matmul(pts, theta.T)
-    min_vals, max_vals = new_pts.aminmax(dim=0)
-    halfs = torch.tensor((half_w, half_h))
-    min_vals.add_(halfs)
-    max_vals.add_(halfs)
-    tol = 1e-4  # truncate to 1e-4 so that ceil does not turn X.00000000001 into X + 1
-    inv_tol = 1.0 / tol
-    cmax = max_vals.mul_(inv_tol).trunc_().mul_(tol).ceil_()
-    cmin = min_vals.mul_(inv_tol).trunc_().mul_(tol).floor_()
-    size = cmax.sub_(cmin)
-    return int(size[0]), int(size[1])
-
-
-def _get_perspective_coeffs(startpoints: List[List[int]], endpoints: List[List[int]]) -> List[float]:
-    """transforms/functional.py `_get_perspective_coeffs`: the 8 coefficients mapping endpoints to startpoints, by least
-    squares in float64, rounded to float32."""
-    if len(startpoints) != 4 or len(endpoints) != 4:
-        raise ValueError(
-            f"Please provide exactly four corners, got {len(startpoints)} startpoints and {len(endpoints)} endpoints.")
-    a_matrix = torch.zeros(2 * len(startpoints), 8, dtype=torch.float64)
-    for i, (p1, p2) in enumerate(zip(endpoints, startpoints)):
-        a_matrix[2 * i, :] = torch.tensor([p1[0], p1[1], 1, 0, 0, 0, -p2[0] * p1[0], -p2[0] * p1[1]])
-        a_matrix[2 * i + 1, :] = torch.tensor([0, 0, 0, p1[0], p1[1], 1, -p2[1] * p1[0], -p2[1] * p1[1]])
-    b_matrix = torch.tensor(startpoints, dtype=torch.float64).view(8)
-    res = torch.linalg.lstsq(a_matrix, b_matrix, driver="gels").solution.to(torch.float32)
-    return res.tolist()
-
-
-def _perspective_coefficients(startpoints, endpoints, coefficients) -> List[float]:
-    """_perspective_coefficients (_geometry.py)."""
-    if coefficients is not None:
-        if startpoints is not None and endpoints is not None:
-            raise ValueError("The startpoints/endpoints and the coefficients shouldn't be defined concurrently.")
-        elif len(coefficients) != 8:
-            raise ValueError("Argument coefficients should have 8 float values")
-        return coefficients
-    elif startpoints is not None and endpoints is not None:
-        return _get_perspective_coeffs(startpoints, endpoints)
-    raise ValueError("Either the startpoints/endpoints or the coefficients must have non `None` values.")
-
-
-def _assert_grid_transform_inputs(image: torch.Tensor, matrix: Optional[List[float]], interpolation: str, fill,
-                                  supported_interpolation_modes: List[str], coeffs: Optional[List[float]] = None) -> None:
-    """_assert_grid_transform_inputs (_geometry.py)."""
-    if matrix is not None:
-        if not isinstance(matrix, list):
-            raise TypeError("Argument matrix should be a list")
-        elif len(matrix) != 6:
-            raise ValueError("Argument matrix should have 6 float values")
-    if coeffs is not None and len(coeffs) != 8:
-        raise ValueError("Argument coeffs should have 8 float values")
-    if fill is not None:
-        if isinstance(fill, (tuple, list)):
-            length = len(fill)
-            num_channels = image.shape[-3]
-            if length > 1 and length != num_channels:
-                raise ValueError("The number of elements in 'fill' cannot broadcast to match the number of "
-                                 f"channels of the image: {length} != {num_channels}")
-        elif not isinstance(fill, (int, float)):
-            raise ValueError("Argument fill should be either int, float, tuple or list")
-    if interpolation not in supported_interpolation_modes:
-        raise ValueError(f"Interpolation mode '{interpolation}' is unsupported with Tensor input")
-
-
-def _affine_coeffs(matrix: List[float], w: int, h: int) -> List[float]:
-    """The 8 kernel coefficients of `_affine_grid`: rescaled_theta = theta.transpose(1, 2).div_([0.5 * w, 0.5 * h]) in
-    float32 with torch, column x then column y (the denominator's two are unused)."""
-    theta = torch.tensor(matrix, dtype=torch.float32).reshape(1, 2, 3)
-    rescaled = theta.transpose(1, 2).div_(torch.tensor([0.5 * w, 0.5 * h], dtype=torch.float32))
-    return rescaled[0].t().reshape(6).tolist() + [0.0, 0.0]
-
-
-def _perspective_grid_coeffs(coeffs: List[float], ow: int, oh: int) -> List[float]:
-    """The 8 kernel coefficients of `_perspective_grid`: theta1 rescaled by (0.5 * ow, 0.5 * oh) in float32, then theta2's
-    (coeffs[6], coeffs[7]) as float32."""
-    theta1 = torch.tensor([[[coeffs[0], coeffs[1], coeffs[2]], [coeffs[3], coeffs[4], coeffs[5]]]], dtype=torch.float32)
-    rescaled = theta1.transpose(1, 2).div_(torch.tensor([0.5 * ow, 0.5 * oh], dtype=torch.float32))
-    theta2 = torch.tensor([coeffs[6], coeffs[7]], dtype=torch.float32)
-    return rescaled[0].t().reshape(6).tolist() + theta2.tolist()
-
-
-@functools.lru_cache(maxsize=None)
-def _blocked_bmm_fuses() -> bool:
-    """Whether this host's CPU bmm, past ATen's naive loop, rounds the grid as fma(y, b, x * a) + c (True) or as the plain
-    sum (x * a + y * b) + c (False).  The BLAS kernel behind it differs between CPUs of one torch build (both forms have been
-    seen on AVX-512 hosts), so the reference's rounding is probed once, on a 64 x 64 rotation grid."""
-    n = 64
-    matrix = _get_inverse_affine_matrix([0.0, 0.0], 30.0, [0.0, 0.0], 1.0, [0.0, 0.0])
-    theta = torch.tensor(matrix, dtype=torch.float32).reshape(1, 2, 3)
-    rt = theta.transpose(1, 2).div_(torch.tensor([0.5 * n, 0.5 * n], dtype=torch.float32))[0]
-    v = torch.linspace((1.0 - n) * 0.5, (n - 1.0) * 0.5, steps=n)
-    base = torch.stack([v.expand(n, n), v.unsqueeze(-1).expand(n, n), torch.ones(n, n)], -1).reshape(1, n * n, 3)
-    got = base.bmm(rt.unsqueeze(0))[0]
-    x, y = base[0, :, :1], base[0, :, 1:2]
-    plain = (x * rt[0] + y * rt[1]) + rt[2]  # separate elementwise ops: each rounded once
-    return not torch.equal(got, plain)
-
-
-def _grid_order(oh: int, ow: int) -> int:
-    """1: the grid carries the fma chain (this host's blocked CPU bmm fuses); 0: plain sums (ATen's naive small-bmm loop,
-    or a blocked bmm that does not fuse)."""
-    return 0 if oh * ow * 3 * 2 < _BMM_NAIVE_LIMIT or not _blocked_bmm_fuses() else 1
-
-
-def _warp(image: torch.Tensor, oh: int, ow: int, coeffs: List[float], kind: str, mode: str, fill) -> torch.Tensor:
-    """`_apply_grid_transform` of the (..., C, H, W) image at the k_warp grid given by the 8 float32 `coeffs`: ONE launch
-    (mv_warp_*) over every plane.  The caller has run `_assert_grid_transform_inputs`."""
-    if image.dtype not in (torch.float32, torch.uint8, torch.bool):
-        raise NotImplementedError(f"{kind}: {image.dtype} images are not on the MI355X path (float32 and uint8 are)")
-    c, ih, iw = (int(s) for s in image.shape[-3:])
-    out_shape = tuple(image.shape[:-2]) + (oh, ow)
-    fill_arr, fill_channels = _elastic_fill(fill, c)
-    if image.numel() == 0:
-        return image.reshape(out_shape)
-    _lib.require_device(image)
-    lib = _lib.load()
-    planes = image.numel() // (ih * iw)
-    with _lib.on_device_of(image):
-        x = image.contiguous() if image.dtype != torch.bool else image.to(torch.float32).contiguous()
-        y = torch.empty(out_shape, dtype=x.dtype, device=x.device)
-        fn = lib.mv_warp_u8 if x.dtype == torch.uint8 else lib.mv_warp_f32
-        _lib.check(fn(x.data_ptr(), y.data_ptr(), planes, fill_channels, ih, iw, oh, ow, _lib.taps(coeffs), _WARP_KINDS[kind],
-                      _grid_order(oh, ow), _ELASTIC_MODES[mode], fill_arr, _lib.stream_ptr(x)))
-    if image.dtype == torch.bool:  # the reference's integer tail: round_().to(dtype)
-        return y.round_().to(torch.bool)
-    if image.dtype == torch.float32:
-        return _lib.forward_only(y, kind, image)
-    return y
-
-
-def _warp_pil_unsupported(name: str):
-    def kernel(image, *args, **kwargs):
-        raise NotImplementedError(f"{name}: PIL images are resampled by Pillow's own C code in the reference, not by grid_sample; "
-                                  "convert with pil_to_tensor and move the tensor to the MI355X")
-    return kernel
-
-
-def _warp_boxes_unsupported(name: str):
-    def kernel(inpt, *args, **kwargs):
-        raise NotImplementedError(f"{name}: BoundingBoxes are not transformed on the MI355X path (the local BoundingBoxes "
-                                  "carries no format or canvas size)")
-    return kernel
-
-
-def affine(inpt: torch.Tensor, angle, translate, scale, shear, interpolation="nearest", fill=None,
-           center: Optional[List[float]] = None) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_geometry.py `affine`."""
-    kernel = _get_kernel(affine, type(inpt))
-    return kernel(inpt, angle=angle, translate=translate, scale=scale, shear=shear, interpolation=interpolation, fill=fill,
-                  center=center)
-
-
-@_register_kernel_internal(affine, torch.Tensor)
-@_register_kernel_internal(affine, tv_tensors.Image)
-def affine_image(image: torch.Tensor, angle, translate, scale, shear, interpolation="nearest", fill=None,
-                 center: Optional[List[float]] = None) -> torch.Tensor:
-    """affine_image (_geometry.py) on (..., C, H, W) float32 / uint8 / bool images: the inverse affine matrix about the image
-    centre (or `center`), then grid_sample at its grid with the fill blend, in one mv_warp_* launch."""
-    mode = _interpolation_name(interpolation)
-    angle, translate, shear, center = _affine_parse_args(angle, translate, scale, shear, center)
-    height, width = image.shape[-2:]
-    center_f = [0.0, 0.0]
-    if center is not None:  # pixel coordinates, shifted so that (0, 0) is the image centre
-        center_f = [(c - s * 0.5) for c, s in zip(center, [width, height])]
-    translate_f = [float(t) for t in translate]
-    matrix = _get_inverse_affine_matrix(center_f, angle, translate_f, scale, shear)
-    _assert_grid_transform_inputs(image, matrix, mode, fill, ["nearest", "bilinear"])
-    return _warp(image, height, width, _affine_coeffs(matrix, width, height), "affine", mode, fill)
-
-
-@_register_kernel_internal(affine, tv_tensors.Video)
-def affine_video(video: torch.Tensor, angle, translate, scale, shear, interpolation="nearest", fill=None,
-                 center: Optional[List[float]] = None) -> torch.Tensor:
-    return affine_image(video, angle, translate, scale, shear, interpolation=interpolation, fill=fill, center=center)
-
-
-def affine_mask(mask: torch.Tensor, angle, translate, scale, shear, fill=None,
-                center: Optional[List[float]] = None) -> torch.Tensor:
-    """affine_mask (_geometry.py): nearest, with a channel dimension added below 3-D."""
-    needs_squeeze = mask.ndim < 3
-    if needs_squeeze:
-        mask = mask.unsqueeze(0)
-    output = affine_image(mask, angle, translate, scale, shear, interpolation="nearest", fill=fill, center=center)
-    return output.squeeze(0) if needs_squeeze else output
-
-
-@_register_kernel_internal(affine, tv_tensors.Mask, tv_tensor_wrapper=False)
-def _affine_mask_dispatch(inpt: torch.Tensor, angle, translate, scale, shear, fill=None, center=None, **kwargs) -> torch.Tensor:
-    output = affine_mask(inpt.as_subclass(torch.Tensor), angle, translate, scale, shear, fill=fill, center=center)
-    return tv_tensors.wrap(output, like=inpt)
-
-
-def rotate(inpt: torch.Tensor, angle: float, interpolation="nearest", expand: bool = False,
-           center: Optional[List[float]] = None, fill=None) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_geometry.py `rotate`."""
-    kernel = _get_kernel(rotate, type(inpt))
-    return kernel(inpt, angle=angle, interpolation=interpolation, expand=expand, fill=fill, center=center)
-
-
-@_register_kernel_internal(rotate, torch.Tensor)
-@_register_kernel_internal(rotate, tv_tensors.Image)
-def rotate_image(image: torch.Tensor, angle: float, interpolation="nearest", expand: bool = False,
-                 center: Optional[List[float]] = None, fill=None) -> torch.Tensor:
-    """rotate_image (_geometry.py): the inverse affine matrix of -angle about the centre; `expand` sizes the output to the
-    rotated frame (_compute_affine_output_size), whose grid is still normalised by the input size."""
-    mode = _interpolation_name(interpolation)
-    shape = image.shape
-    num_channels, height, width = shape[-3:]
-    center_f = [0.0, 0.0]
-    if center is not None:
-        center_f = [(c - s * 0.5) for c, s in zip(center, [width, height])]
-    # rotate and affine turn in opposite directions: -angle
-    matrix = _get_inverse_affine_matrix(center_f, -angle, [0.0, 0.0], 1.0, [0.0, 0.0])
-    if image.numel() > 0:
-        image = image.reshape(-1, num_channels, height, width)
-        _assert_grid_transform_inputs(image, matrix, mode, fill, ["nearest", "bilinear"])
-        ow, oh = _compute_affine_output_size(matrix, width, height) if expand else (width, height)
-        output = _warp(image, oh, ow, _affine_coeffs(matrix, width, height), "affine", mode, fill)
-        new_height, new_width = output.shape[-2:]
-    else:
-        output = image
-        new_width, new_height = _compute_affine_output_size(matrix, width, height) if expand else (width, height)
-    return output.reshape(shape[:-3] + (num_channels, new_height, new_width))
-
-
-@_register_kernel_internal(rotate, tv_tensors.Video)
-def rotate_video(video: torch.Tensor, angle: float, interpolation="nearest", expand: bool = False,
-                 center: Optional[List[float]] = None, fill=None) -> torch.Tensor:
-    return rotate_image(video, angle, interpolation=interpolation, expand=expand, fill=fill, center=center)
-
-
-def rotate_mask(mask: torch.Tensor, angle: float, expand: bool = False, center: Optional[List[float]] = None,
-                fill=None) -> torch.Tensor:
-    """rotate_mask (_geometry.py): nearest, with a channel dimension added below 3-D."""
-    needs_squeeze = mask.ndim < 3
-    if needs_squeeze:
-        mask = mask.unsqueeze(0)
-    output = rotate_image(mask, angle, expand=expand, interpolation="nearest", fill=fill, center=center)
-    return output.squeeze(0) if needs_squeeze else output
-
-
-@_register_kernel_internal(rotate, tv_tensors.Mask, tv_tensor_wrapper=False)
-def _rotate_mask_dispatch(inpt: torch.Tensor, angle: float, expand: bool = False, center=None, fill=None,
-                          **kwargs) -> torch.Tensor:
-    output = rotate_mask(inpt.as_subclass(torch.Tensor), angle=angle, expand=expand, fill=fill, center=center)
-    return tv_tensors.wrap(output, like=inpt)
-
-
-def perspective(inpt: torch.Tensor, startpoints: Optional[List[List[int]]], endpoints: Optional[List[List[int]]],
-                interpolation="bilinear", fill=None, coefficients: Optional[List[float]] = None) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_geometry.py `perspective`."""
-    kernel = _get_kernel(perspective, type(inpt))
-    return kernel(inpt, startpoints=startpoints, endpoints=endpoints, interpolation=interpolation, fill=fill,
-                  coefficients=coefficients)
-
-
-@_register_kernel_internal(perspective, torch.Tensor)
-@_register_kernel_internal(perspective, tv_tensors.Image)
-def perspective_image(image: torch.Tensor, startpoints: Optional[List[List[int]]], endpoints: Optional[List[List[int]]],
-                      interpolation="bilinear", fill=None, coefficients: Optional[List[float]] = None) -> torch.Tensor:
-    """perspective_image (_geometry.py): the 8 perspective coefficients (given, or solved from the corners), then
-    grid_sample at `_perspective_grid` with the fill blend, in one mv_warp_* launch."""
-    perspective_coeffs = _perspective_coefficients(startpoints, endpoints, coefficients)
-    mode = _interpolation_name(interpolation)
-    if image.numel() == 0:
-        return image
-    _assert_grid_transform_inputs(image, matrix=None, interpolation=mode, fill=fill,
-                                  supported_interpolation_modes=["nearest", "bilinear"], coeffs=perspective_coeffs)
-    oh, ow = image.shape[-2:]
-    return _warp(image, oh, ow, _perspective_grid_coeffs(perspective_coeffs, ow, oh), "perspective", mode, fill)
-
-
-@_register_kernel_internal(perspective, tv_tensors.Video)
-def perspective_video(video: torch.Tensor, startpoints: Optional[List[List[int]]], endpoints: Optional[List[List[int]]],
-                      interpolation="bilinear", fill=None, coefficients: Optional[List[float]] = None) -> torch.Tensor:
-    return perspective_image(video, startpoints, endpoints, interpolation=interpolation, fill=fill, coefficients=coefficients)
-
-
-def perspective_mask(mask: torch.Tensor, startpoints: Optional[List[List[int]]], endpoints: Optional[List[List[int]]],
-                     fill=None, coefficients: Optional[List[float]] = None) -> torch.Tensor:
-    """perspective_mask (_geometry.py): nearest, with a channel dimension added below 3-D."""
-    needs_squeeze = mask.ndim < 3
-    if needs_squeeze:
-        mask = mask.unsqueeze(0)
-    output = perspective_image(mask, startpoints, endpoints, interpolation="nearest", fill=fill, coefficients=coefficients)
-    return output.squeeze(0) if needs_squeeze else output
-
-
-@_register_kernel_internal(perspective, tv_tensors.Mask, tv_tensor_wrapper=False)
-def _perspective_mask_dispatch(inpt: torch.Tensor, startpoints, endpoints, fill=None, coefficients=None,
-                               **kwargs) -> torch.Tensor:
-    output = perspective_mask(inpt.as_subclass(torch.Tensor), startpoints, endpoints, fill=fill, coefficients=coefficients)
-    return tv_tensors.wrap(output, like=inpt)
-
-
-for _f in (affine, rotate, perspective):
-    _register_kernel_internal(_f, tv_tensors.BoundingBoxes, tv_tensor_wrapper=False)(_warp_boxes_unsupported(_f.__name__))
-    if _pil.PIL is not None:
-        _register_kernel_internal(_f, _pil.PIL.Image.Image)(_warp_pil_unsupported(_f.__name__))
-del _f
-
-
-# --------------------------------------------------------------------------------------------- colour (v2 surface)
-# transforms/v2/functional/_color.py: argument checks and special cases here, with the reference's error text; the pixel
-# arithmetic is one chain of ops per call in k_color (csrc/color.hip, DESIGN.md section 3.15).
-_COLOR_OPS = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}
-
-
-@functools.lru_cache(maxsize=None)
-def _add_alpha_fuses() -> bool:
-    """Whether this host's `a.add_(b, alpha=s)` on float32 rounds as fma(b, s, a) (True: ATen's vectorised kernel on a host
-    with FMA) or as a + b * s (False).  The reference's grey value and its `_blend` are such adds, so their rounding is probed
-    once, on 4096 random pairs, and passed to the kernel as its blend form."""
-    g = torch.Generator().manual_seed(0)
-    a = torch.rand(4096, generator=g) * 255.0
-    b = torch.rand(4096, generator=g) * 255.0
-    got = a.clone().add_(b, alpha=0.587)
-    plain = a + b * torch.tensor(0.587, dtype=torch.float32)  # two separately rounded ops
-    return not torch.equal(got, plain)
-
-
-def _blend_form() -> int:
-    return 1 if _add_alpha_fuses() else 0
-
-
-def _check_color_channels(image: torch.Tensor) -> int:
-    c = image.shape[-3]
-    if c not in [1, 3]:
-        raise TypeError(f"Input image tensor permitted channel values are 1 or 3, but found {c}")
-    return int(c)
-
-
-def _check_color_dtype(image: torch.Tensor, name: str) -> None:
-    if image.dtype not in (torch.float32, torch.uint8):
-        raise NotImplementedError(f"{name}: {image.dtype} images are not on the MI355X path (float32 and uint8 are)")
-
-
-def _check_color_factor(name: str, factor: float) -> None:
-    if name == "hue":
-        if not (-0.5 <= factor <= 0.5):
-            raise ValueError(f"hue_factor ({factor}) is not in [-0.5, 0.5].")
-    elif factor < 0:
-        raise ValueError(f"{name}_factor ({factor}) is not non-negative.")
-
-
-def _color_chain(image: torch.Tensor, ops: Sequence[Tuple[str, float]]) -> torch.Tensor:
-    """The ops, in order, on a non-empty float32 / uint8 (..., C, H, W) image with C in {1, 3}: ONE mv_color_chain_* call (a
-    chain with contrast runs its mean reduction on the stream first).  The caller has checked the arguments and dropped
-    saturation and hue from 1-channel chains."""
-    c, h, w = (int(s) for s in image.shape[-3:])
-    images = image.numel() // (c * h * w)
-    _lib.require_device(image)
-    lib = _lib.load()
-    u8 = image.dtype == torch.uint8
-    n = len(ops)
-    codes = (C.c_int * n)(*[_COLOR_OPS[name] for name, _ in ops])
-    factors = (C.c_double * n)(*[float(f) for _, f in ops])
-    with _lib.on_device_of(image):
-        x = image.contiguous()
-        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        ws, ws_bytes = None, 0
-        if any(name == "contrast" for name, _ in ops):
-            ws_bytes = int(lib.mv_color_workspace_bytes(images, h, w, int(u8)))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        fn = lib.mv_color_chain_u8 if u8 else lib.mv_color_chain_f32
-        _lib.check(fn(x.data_ptr(), y.data_ptr(), images, c, h, w, codes, factors, n, _blend_form(),
-                      None if ws is None else ws.data_ptr(), ws_bytes, _lib.stream_ptr(x)))
-    if not u8:
-        return _lib.forward_only(y, "adjust_" + ops[0][0] if n == 1 else "color_jitter", image)
-    return y
-
-
-def _color_pil_unsupported(name: str):
-    def kernel(image, *args, **kwargs):
-        raise NotImplementedError(f"{name}: PIL images go through Pillow's ImageEnhance in the reference, whose results the "
-                                  "tensor formula does not reproduce; convert with pil_to_tensor and move the tensor to the MI355X")
-    return kernel
-
-
-def adjust_brightness(inpt: torch.Tensor, brightness_factor: float) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `adjust_brightness`."""
-    kernel = _get_kernel(adjust_brightness, type(inpt))
-    return kernel(inpt, brightness_factor=brightness_factor)
-
-
-@_register_kernel_internal(adjust_brightness, torch.Tensor)
-@_register_kernel_internal(adjust_brightness, tv_tensors.Image)
-def adjust_brightness_image(image: torch.Tensor, brightness_factor: float) -> torch.Tensor:
-    """adjust_brightness_image (_color.py): image.mul(factor).clamp_(0, bound), truncated back to uint8."""
-    _check_color_factor("brightness", brightness_factor)
-    _check_color_channels(image)
-    _check_color_dtype(image, "adjust_brightness")
-    if image.dtype == torch.uint8 and isinstance(brightness_factor, int) and brightness_factor > 1:
-        # image.mul(int) stays uint8 in the reference and wraps modulo 256 before the clamp
-        raise NotImplementedError(f"adjust_brightness: an integer factor ({brightness_factor}) on a uint8 image multiplies "
-                                  "modulo 256 in the reference, which is not on the MI355X path; pass a float factor")
-    if image.numel() == 0:
-        return torch.empty_like(image)
-    return _color_chain(image, [("brightness", brightness_factor)])
-
-
-@_register_kernel_internal(adjust_brightness, tv_tensors.Video)
-def adjust_brightness_video(video: torch.Tensor, brightness_factor: float) -> torch.Tensor:
-    return adjust_brightness_image(video, brightness_factor=brightness_factor)
-
-
-def adjust_saturation(inpt: torch.Tensor, saturation_factor: float) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `adjust_saturation`."""
-    kernel = _get_kernel(adjust_saturation, type(inpt))
-    return kernel(inpt, saturation_factor=saturation_factor)
-
-
-@_register_kernel_internal(adjust_saturation, torch.Tensor)
-@_register_kernel_internal(adjust_saturation, tv_tensors.Image)
-def adjust_saturation_image(image: torch.Tensor, saturation_factor: float) -> torch.Tensor:
-    """adjust_saturation_image (_color.py): _blend with the per-pixel grey value (floored for uint8); 1-channel images are
-    returned as they are."""
-    _check_color_factor("saturation", saturation_factor)
-    c = _check_color_channels(image)
-    if c == 1:  # the reference matches PIL here
-        return image
-    _check_color_dtype(image, "adjust_saturation")
-    if image.numel() == 0:
-        return torch.empty_like(image)
-    return _color_chain(image, [("saturation", saturation_factor)])
-
-
-@_register_kernel_internal(adjust_saturation, tv_tensors.Video)
-def adjust_saturation_video(video: torch.Tensor, saturation_factor: float) -> torch.Tensor:
-    return adjust_saturation_image(video, saturation_factor=saturation_factor)
-
-
-def adjust_contrast(inpt: torch.Tensor, contrast_factor: float) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `adjust_contrast`."""
-    kernel = _get_kernel(adjust_contrast, type(inpt))
-    return kernel(inpt, contrast_factor=contrast_factor)
-
-
-@_register_kernel_internal(adjust_contrast, torch.Tensor)
-@_register_kernel_internal(adjust_contrast, tv_tensors.Image)
-def adjust_contrast_image(image: torch.Tensor, contrast_factor: float) -> torch.Tensor:
-    """adjust_contrast_image (_color.py): _blend with the mean of the grey image over dims (-3, -2, -1) -- per image, per
-    frame of a video; a 1-channel image is its own grey image."""
-    _check_color_factor("contrast", contrast_factor)
-    _check_color_channels(image)
-    _check_color_dtype(image, "adjust_contrast")
-    if image.numel() == 0:
-        return torch.empty_like(image)
-    return _color_chain(image, [("contrast", contrast_factor)])
-
-
-@_register_kernel_internal(adjust_contrast, tv_tensors.Video)
-def adjust_contrast_video(video: torch.Tensor, contrast_factor: float) -> torch.Tensor:
-    return adjust_contrast_image(video, contrast_factor=contrast_factor)
-
-
-def adjust_hue(inpt: torch.Tensor, hue_factor: float) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `adjust_hue`."""
-    kernel = _get_kernel(adjust_hue, type(inpt))
-    return kernel(inpt, hue_factor=hue_factor)
-
-
-@_register_kernel_internal(adjust_hue, torch.Tensor)
-@_register_kernel_internal(adjust_hue, tv_tensors.Image)
-def adjust_hue_image(image: torch.Tensor, hue_factor: float) -> torch.Tensor:
-    """adjust_hue_image (_color.py): _rgb_to_hsv, h = (h + hue_factor) mod 1, _hsv_to_rgb, with uint8 scaled in and out as
-    to_dtype_image(scale=True) does; 1-channel and empty images are returned as they are."""
-    _check_color_factor("hue", hue_factor)
-    c = _check_color_channels(image)
-    if c == 1:  # the reference matches PIL here
-        return image
-    if image.numel() == 0:
-        return image
-    _check_color_dtype(image, "adjust_hue")
-    return _color_chain(image, [("hue", hue_factor)])
-
-
-@_register_kernel_internal(adjust_hue, tv_tensors.Video)
-def adjust_hue_video(video: torch.Tensor, hue_factor: float) -> torch.Tensor:
-    return adjust_hue_image(video, hue_factor=hue_factor)
-
-
-def color_jitter_image(image: torch.Tensor, ops: Sequence[Tuple[str, float]]) -> torch.Tensor:
-    """The reference's loop of single `adjust_*_image` calls (v2.ColorJitter._transform) over (name, factor) pairs, as ONE
-    mv_color_chain_* call on a non-empty float32 / uint8 image on the device: the same bits as the loop.  Names are
-    "brightness", "contrast", "saturation" and "hue"."""
-    for name, factor in ops:
-        if name not in _COLOR_OPS:
-            raise ValueError(f"unknown colour op {name!r}")
-        _check_color_factor(name, factor)
-    if not ops:
-        return image
-    c = _check_color_channels(image)
-    if c == 1:  # saturation and hue return 1-channel images unchanged
-        ops = [(name, f) for name, f in ops if name in ("brightness", "contrast")]
-        if not ops:
-            return image
-    _check_color_dtype(image, "ColorJitter")
-    if image.numel() == 0:
-        raise ValueError("color_jitter_image: empty images take the reference's loop of single calls")
-    return _color_chain(image, list(ops))
-
-
-def rgb_to_grayscale(inpt: torch.Tensor, num_output_channels: int = 1) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `rgb_to_grayscale`."""
-    kernel = _get_kernel(rgb_to_grayscale, type(inpt))
-    return kernel(inpt, num_output_channels=num_output_channels)
-
-
-@_register_kernel_internal(rgb_to_grayscale, torch.Tensor)
-@_register_kernel_internal(rgb_to_grayscale, tv_tensors.Image)
-def rgb_to_grayscale_image(image: torch.Tensor, num_output_channels: int = 1) -> torch.Tensor:
-    """rgb_to_grayscale_image (_color.py): the grey value r * 0.2989 + g * 0.587 + b * 0.114 (truncated for uint8) in 1 or 3
-    planes; a 1-channel image is cloned or repeated."""
-    if num_output_channels not in (1, 3):
-        raise ValueError(f"num_output_channels must be 1 or 3, got {num_output_channels}.")
-    c = _check_color_channels(image)
-    if c == 1:
-        if num_output_channels == 1:
-            return image.clone()
-        s = [1] * image.ndim
-        s[-3] = 3
-        return image.repeat(s)
-    _check_color_dtype(image, "rgb_to_grayscale")
-    h, w = (int(d) for d in image.shape[-2:])
-    out_shape = tuple(image.shape[:-3]) + (num_output_channels, h, w)
-    if image.numel() == 0:
-        return torch.empty(out_shape, dtype=image.dtype, device=image.device)
-    _lib.require_device(image)
-    lib = _lib.load()
-    images = image.numel() // (3 * h * w)
-    with _lib.on_device_of(image):
-        x = image.contiguous()
-        y = torch.empty(out_shape, dtype=x.dtype, device=x.device)
-        fn = lib.mv_rgb_to_grayscale_u8 if x.dtype == torch.uint8 else lib.mv_rgb_to_grayscale_f32
-        _lib.check(fn(x.data_ptr(), y.data_ptr(), images, h, w, num_output_channels, _blend_form(), _lib.stream_ptr(x)))
-    if image.dtype == torch.float32:
-        return _lib.forward_only(y, "rgb_to_grayscale", image)
-    return y
-
-
-for _f in (adjust_brightness, adjust_contrast, adjust_saturation, adjust_hue, rgb_to_grayscale):
-    if _pil.PIL is not None:
-        _register_kernel_internal(_f, _pil.PIL.Image.Image)(_color_pil_unsupported(_f.__name__))
-del _f
-
-
-# --------------------------------------------------------------------------------------------- automatic-augmentation ops
-# transforms/v2/functional/_color.py invert / posterize / solarize / autocontrast / equalize: what AutoAugment, RandAugment and
-# TrivialAugmentWide call besides the geometric and F.adjust_* ops.  Argument checks here, with the reference's error text;
-# the pixels go through csrc/autoaug.hip (DESIGN.md section 3.16).  Nothing is read back to the host.
-_POINT_OPS = {"invert": 0, "posterize": 1, "solarize": 2}
-
-
-def _pointwise(image: torch.Tensor, op: str, param: float = 0.0) -> torch.Tensor:
-    """One mv_pointwise_* call over every element of a non-empty float32 / uint8 image."""
-    _lib.require_device(image)
-    lib = _lib.load()
-    u8 = image.dtype == torch.uint8
-    with _lib.on_device_of(image):
-        x = image.contiguous()
-        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        fn = lib.mv_pointwise_u8 if u8 else lib.mv_pointwise_f32
-        _lib.check(fn(x.data_ptr(), y.data_ptr(), x.numel(), _POINT_OPS[op], float(param), _lib.stream_ptr(x)))
-    if not u8:
-        return _lib.forward_only(y, op, image)
-    return y
-
-
-def _plane_op(image: torch.Tensor, name: str) -> torch.Tensor:
-    """mv_autocontrast_* / mv_equalize_* on the (H, W) planes of a non-empty float32 / uint8 image, with its workspace."""
-    h, w = (int(d) for d in image.shape[-2:])
-    planes = image.numel() // (h * w)
-    _lib.require_device(image)
-    lib = _lib.load()
-    u8 = image.dtype == torch.uint8
-    with _lib.on_device_of(image):
-        x = image.contiguous()
-        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        ws_bytes = int(getattr(lib, f"mv_{name}_workspace_bytes")(planes, h, w, int(u8)))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        fn = getattr(lib, f"mv_{name}_u8" if u8 else f"mv_{name}_f32")
-        _lib.check(fn(x.data_ptr(), y.data_ptr(), planes, h, w, ws.data_ptr(), ws_bytes, _lib.stream_ptr(x)))
-    if not u8:
-        return _lib.forward_only(y, name, image)
-    return y
-
-
-def _autoaug_pil_unsupported(name: str):
-    def kernel(image, *args, **kwargs):
-        raise NotImplementedError(f"{name}: PIL images go through Pillow's ImageOps in the reference, which this library does "
-                                  "not reproduce; convert with pil_to_tensor and move the tensor to the MI355X")
-    return kernel
-
-
-def invert(inpt: torch.Tensor) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `invert`."""
-    kernel = _get_kernel(invert, type(inpt))
-    return kernel(inpt)
-
-
-@_register_kernel_internal(invert, torch.Tensor)
-@_register_kernel_internal(invert, tv_tensors.Image)
-def invert_image(image: torch.Tensor) -> torch.Tensor:
-    """invert_image (_color.py): float 1.0 - x, uint8 bitwise_not; any number of channels."""
-    _check_color_dtype(image, "invert")
-    if image.numel() == 0:
-        return torch.empty_like(image)
-    return _pointwise(image, "invert")
-
-
-@_register_kernel_internal(invert, tv_tensors.Video)
-def invert_video(video: torch.Tensor) -> torch.Tensor:
-    return invert_image(video)
-
-
-def posterize(inpt: torch.Tensor, bits: int) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `posterize`."""
-    kernel = _get_kernel(posterize, type(inpt))
-    return kernel(inpt, bits=bits)
-
-
-@_register_kernel_internal(posterize, torch.Tensor)
-@_register_kernel_internal(posterize, tv_tensors.Image)
-def posterize_image(image: torch.Tensor, bits: int) -> torch.Tensor:
-    """posterize_image (_color.py): float x.mul(2^bits).floor_().clamp_(0, 2^bits - 1).mul_(2^-bits); uint8 keeps the top
-    `bits` bits, and bits >= 8 returns the image itself."""
-    if not isinstance(bits, int) or not 0 <= bits <= 8:
-        raise TypeError(f"bits must be a positive integer in the range [0, 8], got {bits} instead.")
-    _check_color_dtype(image, "posterize")
-    if image.dtype == torch.uint8 and bits >= 8:
-        return image
-    if image.numel() == 0:
-        return torch.empty_like(image)
-    return _pointwise(image, "posterize", bits)
-
-
-@_register_kernel_internal(posterize, tv_tensors.Video)
-def posterize_video(video: torch.Tensor, bits: int) -> torch.Tensor:
-    return posterize_image(video, bits=bits)
-
-
-def solarize(inpt: torch.Tensor, threshold: float) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `solarize`."""
-    kernel = _get_kernel(solarize, type(inpt))
-    return kernel(inpt, threshold=threshold)
-
-
-@_register_kernel_internal(solarize, torch.Tensor)
-@_register_kernel_internal(solarize, tv_tensors.Image)
-def solarize_image(image: torch.Tensor, threshold: float) -> torch.Tensor:
-    """solarize_image (_color.py): torch.where(image >= threshold, invert(image), image).  The comparison is torch's: a
-    float threshold is rounded to float32 (a uint8 image is promoted to float32 against it); an integer threshold against a
-    uint8 image is first wrapped to uint8."""
-    _check_color_dtype(image, "solarize")
-    if threshold > _max_value(image.dtype):
-        raise TypeError(f"Threshold should be less or equal the maximum value of the dtype, but got {threshold}")
-    if image.numel() == 0:
-        return torch.empty_like(image)
-    if image.dtype == torch.uint8 and isinstance(threshold, int) and not isinstance(threshold, bool):
-        threshold = threshold % 256
-    return _pointwise(image, "solarize", float(threshold))
-
-
-@_register_kernel_internal(solarize, tv_tensors.Video)
-def solarize_video(video: torch.Tensor, threshold: float) -> torch.Tensor:
-    return solarize_image(video, threshold=threshold)
-
-
-def autocontrast(inpt: torch.Tensor) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `autocontrast`."""
-    kernel = _get_kernel(autocontrast, type(inpt))
-    return kernel(inpt)
-
-
-@_register_kernel_internal(autocontrast, torch.Tensor)
-@_register_kernel_internal(autocontrast, tv_tensors.Image)
-def autocontrast_image(image: torch.Tensor) -> torch.Tensor:
-    """autocontrast_image (_color.py): per (image, channel) plane, (x - min) / ((max - min) * (1 / bound)) clamped to
-    [0, bound] (uint8 truncated), min = 0 and scale 1 on flat planes; a NaN makes its float plane NaN.  Empty images are
-    returned as they are."""
-    _check_color_channels(image)
-    _check_color_dtype(image, "autocontrast")
-    if image.numel() == 0:
-        return image
-    return _plane_op(image, "autocontrast")
-
-
-@_register_kernel_internal(autocontrast, tv_tensors.Video)
-def autocontrast_video(video: torch.Tensor) -> torch.Tensor:
-    return autocontrast_image(video)
-
-
-def equalize(inpt: torch.Tensor) -> torch.Tensor:
-    """Dispatcher, as transforms/v2/functional/_color.py `equalize`."""
-    kernel = _get_kernel(equalize, type(inpt))
-    return kernel(inpt)
-
-
-@_register_kernel_internal(equalize, torch.Tensor)
-@_register_kernel_internal(equalize, tv_tensors.Image)
-def equalize_image(image: torch.Tensor) -> torch.Tensor:
-    """equalize_image (_color.py): per (H, W) plane, the 256-bin histogram of the uint8 image (float32: of
-    to_dtype(scale=True)), PIL's LUT, planes with step == 0 unequalised; float32 comes back as the uint8 result / 255, so it
-    is always quantised to 256 levels.  Float values outside [0, 1] (and NaN), where the reference's float -> uint8 cast is
-    undefined, are saturated: below 0 and NaN bin as 0, above 1 as 255.  Empty images are returned as they are."""
-    _check_color_dtype(image, "equalize")
-    if image.numel() == 0:
-        return image
-    return _plane_op(image, "equalize")
-
-
-@_register_kernel_internal(equalize, tv_tensors.Video)
-def equalize_video(video: torch.Tensor) -> torch.Tensor:
-    return equalize_image(video)
-
-
-for _f in (invert, posterize, solarize, autocontrast, equalize):
-    if _pil.PIL is not None:
-        _register_kernel_internal(_f, _pil.PIL.Image.Image)(_autoaug_pil_unsupported(_f.__name__))
-del _f
 
 
 def to_dtype(inpt: torch.Tensor, dtype: torch.dtype = torch.float, scale: bool = False) -> torch.Tensor:
