@@ -100,6 +100,12 @@ SYMBOLS = {
     "mv_equalize_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
     "mv_equalize_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
     "mv_equalize_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "mv_resized_crop_u8": (_i, [_vp, _vp, _i64] + [_i] * 10 + [_vp, _i64, _vp]),
+    "mv_resized_crop_f32": (_i, [_vp, _vp, _i64] + [_i] * 10 + [_vp, _i64, _vp]),
+    "mv_resized_crop_preset_u8": (_i, [_vp, _vp, _i64] + [_i] * 12 + [_fp, _fp, _vp, _i64, _vp]),
+    "mv_resized_crop_preset_f32": (_i, [_vp, _vp, _i64] + [_i] * 12 + [_fp, _fp, _vp, _i64, _vp]),
+    "mv_pad_crop_flip": (_i, [_vp, _vp, _i64] + [_i] * 11 + [_vp, _vp]),
+    "mv_erase": (_i, [_vp, _vp, _i64] + [_i] * 8 + [_vp, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

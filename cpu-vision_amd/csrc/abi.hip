@@ -851,6 +851,119 @@ int mv_preset_classification_f32(const float* x, float* y, int64_t n, int c, int
                 workspace_bytes, stream);
 }
 
+// F.resized_crop: the window's size takes the place of the input size; the window itself and the flips ride in ResizeWindow
+static int resized_crop(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int wdt, int top, int left, int wh,
+                        int ww, int oh, int ow, int flip_h, int flip_v, int preset, const float* mean, const float* stdv,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+  if (h <= 0 || wdt <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "resized_crop: bad image size (%d, %d)", h, wdt);
+  if (int rc = check_resize(x, y, planes, wh, ww, oh, ow, oh, ow)) return rc;
+  // the window's corner plus its size must stay an int
+  if (top < -0x3fffffff || top > 0x3fffffff || left < -0x3fffffff || left > 0x3fffffff || wh > 0x3fffffff || ww > 0x3fffffff)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "resized_crop: window (%d, %d, %d, %d) out of range", top, left, wh, ww);
+  if (planes == 0) return MV_OK;
+  if (preset) {
+    if (!mean || !stdv) return set_error(MV_ERR_INVALID_ARGUMENT, "preset: null mean / std");
+    for (int i = 0; i < channels; ++i)
+      if (stdv[i] == 0.f) return set_error(MV_ERR_INVALID_ARGUMENT, "std evaluated to zero, leading to division by zero.");
+  }
+  const ResizeWindow win = {top, left, h, wdt, flip_h ? 1 : 0, flip_v ? 1 : 0};
+  return launch_resize(x, y, u8, planes, channels, wh, ww, oh, ow, 0, 0, oh, ow, preset, mean, stdv, workspace, workspace_bytes,
+                       (hipStream_t)stream, &win);
+}
+
+int mv_resized_crop_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int wdt, int top, int left, int wh, int ww, int oh,
+                       int ow, int flip_h, int flip_v, void* workspace, int64_t workspace_bytes, void* stream) {
+  return resized_crop(x, y, true, planes, 1, h, wdt, top, left, wh, ww, oh, ow, flip_h, flip_v, 0, nullptr, nullptr, workspace,
+                      workspace_bytes, stream);
+}
+
+int mv_resized_crop_f32(const float* x, float* y, int64_t planes, int h, int wdt, int top, int left, int wh, int ww, int oh,
+                        int ow, int flip_h, int flip_v, void* workspace, int64_t workspace_bytes, void* stream) {
+  return resized_crop(x, y, false, planes, 1, h, wdt, top, left, wh, ww, oh, ow, flip_h, flip_v, 0, nullptr, nullptr, workspace,
+                      workspace_bytes, stream);
+}
+
+int mv_resized_crop_preset_u8(const uint8_t* x, float* y, int64_t n, int c, int h, int wdt, int top, int left, int wh, int ww,
+                              int oh, int ow, int flip_h, int flip_v, int v2_scale, const float* mean, const float* stdv,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n < 0 || c <= 0 || c > 4) return set_error(MV_ERR_INVALID_ARGUMENT, "preset: n=%lld, c=%d (1..4 channels)", (long long)n, c);
+  return resized_crop(x, y, true, n * c, c, h, wdt, top, left, wh, ww, oh, ow, flip_h, flip_v, v2_scale ? 2 : 1, mean, stdv, workspace,
+                      workspace_bytes, stream);
+}
+
+int mv_resized_crop_preset_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int top, int left, int wh, int ww,
+                               int oh, int ow, int flip_h, int flip_v, int v2_scale, const float* mean, const float* stdv,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n < 0 || c <= 0 || c > 4) return set_error(MV_ERR_INVALID_ARGUMENT, "preset: n=%lld, c=%d (1..4 channels)", (long long)n, c);
+  return resized_crop(x, y, false, n * c, c, h, wdt, top, left, wh, ww, oh, ow, flip_h, flip_v, 1, mean, stdv, workspace,
+                      workspace_bytes, stream);
+}
+
+// ---- pad / crop / flip / erase: the gather kernel of crop.hip -------------------------------------------------------------------
+static int check_elem_bytes(const char* what, int elem_bytes) {
+  if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: elem_bytes must be 1, 2, 4 or 8, got %d", what, elem_bytes);
+  return MV_OK;
+}
+
+int mv_pad_crop_flip(const void* x, void* y, int64_t planes, int channels, int elem_bytes, int ih, int iw, int oh, int ow, int top,
+                     int left, int mode, int flip_h, int flip_v, const void* fill, void* stream) {
+  if (int rc = check_elem_bytes("pad_crop_flip", elem_bytes)) return rc;
+  if (planes < 0 || ih < 0 || iw < 0 || oh < 0 || ow < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: bad shape planes=%lld (%d, %d) -> (%d, %d)", (long long)planes, ih, iw,
+                     oh, ow);
+  if (mode < MV_PAD_CONSTANT || mode > MV_PAD_SYMMETRIC)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: unknown padding mode %d (0 constant, 1 edge, 2 reflect, 3 symmetric)", mode);
+  if (channels < 1 || channels > 4)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: a fill has 1 to 4 channels, got %d", channels);
+  if (planes % channels != 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: planes (%lld) must be a multiple of channels (%d)", (long long)planes, channels);
+  if (top < -0x3fffffff || top > 0x3fffffff || left < -0x3fffffff || left > 0x3fffffff || ih > 0x3fffffff || iw > 0x3fffffff ||
+      oh > 0x3fffffff || ow > 0x3fffffff)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: offsets (%d, %d) out of range", top, left);
+  if (planes == 0 || oh == 0 || ow == 0) return MV_OK;
+  if (mode != MV_PAD_CONSTANT && (ih == 0 || iw == 0))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: an empty image has no border to repeat");
+  if (ih > 0 && iw > 0 && (!gather_axis_ok(ih, oh, top, mode) || !gather_axis_ok(iw, ow, left, mode))) {
+    if (mode == MV_PAD_REFLECT)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: reflect padding (%d, %d, %d, %d) must be smaller than the image side (%d, %d)",
+                       -left, ow - iw + left, -top, oh - ih + top, ih, iw);
+    return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: symmetric padding (%d, %d, %d, %d) exceeds the image side (%d, %d)",
+                     -left, ow - iw + left, -top, oh - ih + top, ih, iw);
+  }
+  if (!y || (!x && ih > 0 && iw > 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "pad_crop_flip: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (!gather_grid_fits(planes, oh, ow, elem_bytes))
+    return set_error(MV_ERR_UNSUPPORTED, "pad_crop_flip: %lld planes of %d x %d exceed the launch grid", (long long)planes, oh, ow);
+  unsigned long long bits[4] = {0, 0, 0, 0};
+  if (fill)
+    for (int c = 0; c < channels; ++c) __builtin_memcpy(&bits[c], static_cast<const char*>(fill) + (size_t)c * elem_bytes, elem_bytes);
+  if (ih == 0 || iw == 0) ih = iw = 1, top = left = 0x3fffffff;  // constant mode on an empty image: every pixel is fill
+  return launch_gather(x, y, planes, channels, elem_bytes, ih, iw, oh, ow, top, left, mode, flip_h ? 1 : 0, flip_v ? 1 : 0, bits,
+                       nullptr, 0, 0, 0, 0, 0, (hipStream_t)stream);
+}
+
+int mv_erase(const void* x, void* y, int64_t planes, int channels, int elem_bytes, int h, int w, int i, int j, int eh, int ew,
+             const void* v, int v_is_per_pixel, void* stream) {
+  if (int rc = check_elem_bytes("erase", elem_bytes)) return rc;
+  if (planes < 0 || h < 0 || w < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "erase: bad shape planes=%lld (%d, %d)", (long long)planes, h, w);
+  if (channels < 1 || planes % channels != 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "erase: planes (%lld) must be a multiple of channels (%d)", (long long)planes, channels);
+  if (eh < 0 || ew < 0 || i < 0 || j < 0 || i > h - eh || j > w - ew)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "erase: the box (%d, %d, %d, %d) must lie inside the (%d, %d) image", i, j, eh, ew, h, w);
+  if (planes == 0 || h == 0 || w == 0) return MV_OK;
+  if (!x || !y || (!v && eh > 0 && ew > 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "erase: null pointer");
+  if (eh == 0 || ew == 0) eh = ew = 0;
+  if (x == y) {
+    if (planes * (long long)eh * ew > 256LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "erase: box too large for one launch");
+    return launch_erase_box(y, planes, channels, elem_bytes, h, w, i, j, eh, ew, v, v_is_per_pixel ? 1 : 0, (hipStream_t)stream);
+  }
+  if (!gather_grid_fits(planes, h, w, elem_bytes))
+    return set_error(MV_ERR_UNSUPPORTED, "erase: %lld planes of %d x %d exceed the launch grid", (long long)planes, h, w);
+  return launch_gather(x, y, planes, channels, elem_bytes, h, w, h, w, 0, 0, MV_PAD_CONSTANT, 0, 0, nullptr, v, i, j, eh, ew,
+                       v_is_per_pixel ? 1 : 0, (hipStream_t)stream);
+}
+
 static int elastic(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int wdt, const float* base_x,
                    const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
                    const float* fill, void* stream) {

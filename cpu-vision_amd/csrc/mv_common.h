@@ -281,9 +281,26 @@ int launch_maxpool2d(const float* x, float* y, int64_t planes, int h, int w, int
 
 // F.resize(bilinear, antialias) [+ center_crop] [+ preset tail] (resize.hip)
 int64_t resize_workspace_bytes(int64_t planes, int h, int w, int oh, int ow, int ct, int cl, int ch, int cw);
+// win: nullptr (the whole image), or the source window of F.resized_crop and the flips of the output; (h, w) is then the
+// window's size, which is what the interpolation axes and the workspace are made from
+struct ResizeWindow {
+  int top, left;        // the window's corner in the (ih, iw) image; the window may reach outside it (zeros)
+  int ih, iw;           // the image's own size
+  int flip_h, flip_v;   // mirror the output
+};
 int launch_resize(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int w, int oh, int ow, int ct,
                   int cl, int ch, int cw, int preset, const float* mean, const float* stdv, void* workspace,
-                  int64_t workspace_bytes, hipStream_t s);
+                  int64_t workspace_bytes, hipStream_t s, const ResizeWindow* win = nullptr);
+
+// F.pad / F.crop / F.*_flip / F.erase (crop.hip; the index maps in mi355vision.h mv_pad_crop_flip).  The entry points have
+// checked the arguments (gather_axis_ok per axis) and the grid (gather_grid_fits).
+bool gather_axis_ok(int in, int out, int off, int mode);
+bool gather_grid_fits(int64_t planes, int oh, int ow, int elem_bytes);
+int launch_gather(const void* x, void* y, int64_t planes, int channels, int elem_bytes, int ih, int iw, int oh, int ow, int top,
+                  int left, int mode, int flip_h, int flip_v, const unsigned long long* fill, const void* v, int bi, int bj,
+                  int bh, int bw, int v_per_pixel, hipStream_t s);
+int launch_erase_box(void* y, int64_t planes, int channels, int elem_bytes, int h, int w, int bi, int bj, int bh, int bw,
+                     const void* v, int v_per_pixel, hipStream_t s);
 
 // F.elastic: grid_sample of every plane at identity grid + displacement (elastic.hip).  base_x / base_y: the reference's
 // linspace vectors (W and H floats, device); disp (1, H, W, 2) fp32 by strides; mode 0 bilinear, 1 nearest; fill: NULL or

@@ -16,6 +16,10 @@
 // Every thread recomputes the weights of its own window (2*scale+1 taps; a few dozen flops) instead of reading a
 // table: no setup launch, no host->device copy, nothing to capture besides two kernel nodes.  The path is
 // launch- and latency-bound per image (a 500x375 photo is 0.5 MB); batches of equal-sized images amortise it.
+//
+// F.resized_crop is the same kernels reading a WINDOW of the input (ResizeArgs::wt ...; in_row / in_at below) and, optionally,
+// mirroring the output in the final store: the WIN = true instantiations.  Whole images run WIN = false, whose address
+// arithmetic is what it was before the window existed.
 #include "mv_common.h"
 
 namespace mv {
@@ -67,11 +71,51 @@ struct ResizeArgs {
   int c0, nc;             // resized columns the width pass computes: [c0, c0 + nc)
   long long planes;
   int channels;
-  int preset;             // 0: same dtype out; 1: float out = ((v [/ 255]) - mean) / std
+  int preset;             // 0: same dtype out; 1: float out = ((v [/ 255]) - mean) / std; 2 (WIN only): v2's to_dtype, v * (1 / 255)
   float mean[4], stdv[4];
+  // F.resized_crop (the WIN instantiations only): ax.in / ay.in are the size of a source WINDOW whose corner is (wt, wl) in the
+  // (ih, iw) image; the output (ch, cw) is mirrored by the final store.  Whole images run the instantiations without it.
+  int wt, wl, ih, iw;
+  int flip_h, flip_v;
 };
 
-template <typename T>
+// The one way the kernels read the input.  in_row(): the pointer to window column 0 of window row r (WIN: it may point outside the
+// image and is then never dereferenced); in_at(): column c of that row, 0 outside the image -- the reference's crop_image
+// zero-pads a box that reaches outside.  Without a window both are the plain address arithmetic.
+template <typename T, bool WIN>
+__device__ inline const T* in_row(const ResizeArgs& A, long long plane, int r) {
+  if constexpr (WIN)
+    return static_cast<const T*>(A.x) + ((long long)plane * A.ih + (r + A.wt)) * (long long)A.iw + A.wl;
+  else
+    return static_cast<const T*>(A.x) + ((size_t)plane * A.ay.in + r) * A.ax.in;
+}
+template <bool WIN>
+__device__ inline bool in_row_ok(const ResizeArgs& A, int r) {
+  if constexpr (WIN) return (unsigned)(r + A.wt) < (unsigned)A.ih;
+  else return true;
+}
+// `row` points at window column c0 of its row; the element j columns further
+template <typename T, bool WIN>
+__device__ inline T in_at(const ResizeArgs& A, const T* row, bool row_ok, int c0, int j) {
+  if constexpr (WIN) return (row_ok && (unsigned)(c0 + j + A.wl) < (unsigned)A.iw) ? row[j] : (T)0;
+  else return row[j];
+}
+template <bool WIN>
+__device__ inline int in_pitch(const ResizeArgs& A) {
+  if constexpr (WIN) return A.iw;
+  else return A.ax.in;
+}
+// where output pixel (oy, ox) of plane `plane` is stored: mirrored when the window instantiation flips
+template <bool WIN>
+__device__ inline size_t out_index(const ResizeArgs& A, long long plane, int oy, int ox) {
+  if constexpr (WIN) {
+    if (A.flip_v) oy = A.ch - 1 - oy;
+    if (A.flip_h) ox = A.cw - 1 - ox;
+  }
+  return ((size_t)plane * A.ch + oy) * A.cw + ox;
+}
+
+template <typename T, bool WIN>
 __global__ __launch_bounds__(256) void k_resize_w(const ResizeArgs A) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long per_plane = (long long)A.nr * A.nc;
@@ -79,10 +123,11 @@ __global__ __launch_bounds__(256) void k_resize_w(const ResizeArgs A) {
   const long long plane = idx / per_plane;
   const int rem = (int)(idx - plane * per_plane);
   const int r = rem / A.nc, i = rem - r * A.nc;
-  const T* src = static_cast<const T*>(A.x) + ((size_t)plane * A.ay.in + (A.r0 + r)) * A.ax.in;
+  const T* src = in_row<T, WIN>(A, plane, A.r0 + r);
+  const bool row_ok = in_row_ok<WIN>(A, A.r0 + r);
   float t;
   if (A.ax.identity) {
-    t = (float)src[A.c0 + i];
+    t = (float)in_at<T, WIN>(A, src, row_ok, 0, A.c0 + i);
   } else {
     int xmin, xsize;
     float center;
@@ -94,7 +139,7 @@ __global__ __launch_bounds__(256) void k_resize_w(const ResizeArgs A) {
     for (int j = 0; j < xsize; ++j) {
       float wj = aa_weight(A.ax, j, xmin, center);
       if (norm) wj /= total;
-      const float s = (float)src[xmin + j];
+      const float s = (float)in_at<T, WIN>(A, src, row_ok, 0, xmin + j);
       t = (j == 0) ? s * wj : fmaf(s, wj, t);
     }
   }
@@ -108,7 +153,7 @@ __global__ __launch_bounds__(256) void k_resize_w(const ResizeArgs A) {
 constexpr int kWRows = 64;
 constexpr int kWMaxTaps = 96;
 
-template <typename T>
+template <typename T, bool WIN>
 __global__ __launch_bounds__(256) void k_resize_w_tiled(const ResizeArgs A) {
   __shared__ float wts[kWMaxTaps * 64];
   __shared__ int xmins[64], xsizes[64];
@@ -139,10 +184,11 @@ __global__ __launch_bounds__(256) void k_resize_w_tiled(const ResizeArgs A) {
   const int xmin = xmins[lane], xsize = xsizes[lane];
   const int r_end = min((rt + 1) * kWRows, A.nr);
   for (int r = rt * kWRows + wave; r < r_end; r += 4) {
-    const T* src = static_cast<const T*>(A.x) + ((size_t)plane * A.ay.in + (A.r0 + r)) * A.ax.in + xmin;
+    const T* src = in_row<T, WIN>(A, plane, A.r0 + r) + xmin;
+    const bool row_ok = in_row_ok<WIN>(A, A.r0 + r);
     float t = 0.f;
     for (int j = 0; j < xsize; ++j) {
-      const float s = (float)src[j];
+      const float s = (float)in_at<T, WIN>(A, src, row_ok, xmin, j);
       const float wj = wts[j * 64 + lane];
       t = (j == 0) ? s * wj : fmaf(s, wj, t);
     }
@@ -150,14 +196,15 @@ __global__ __launch_bounds__(256) void k_resize_w_tiled(const ResizeArgs A) {
   }
 }
 
-template <typename T>
+template <typename T, bool WIN>
 __global__ __launch_bounds__(256) void k_resize_h(const ResizeArgs A) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long lin = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long per_plane = (long long)A.ch * A.cw;
-  if (idx >= A.planes * per_plane) return;
-  const long long plane = idx / per_plane;
-  const int rem = (int)(idx - plane * per_plane);
+  if (lin >= A.planes * per_plane) return;
+  const long long plane = lin / per_plane;
+  const int rem = (int)(lin - plane * per_plane);
   const int oy = rem / A.cw, ox = rem - oy * A.cw;
+  const size_t idx = WIN ? out_index<WIN>(A, plane, oy, ox) : (size_t)lin;
   const int ry = oy + A.ct, rx = ox + A.cl;  // position in the resized image
   float t = 0.f;                             // center_crop pads with 0 (transforms/functional.py:587)
   const bool inside = ry >= 0 && ry < A.ay.out && rx >= 0 && rx < A.ax.out;
@@ -188,7 +235,7 @@ __global__ __launch_bounds__(256) void k_resize_h(const ResizeArgs A) {
   if (A.preset) {
     // convert_image_dtype(float): uint8 -> `.to(float32) / 255.0` (v1, _functional_tensor.py:93-99); float stays.
     // normalize: tensor.sub_(mean).div_(std) (:928)
-    if (u8) t = t / 255.0f;
+    if (u8) t = (WIN && A.preset == 2) ? t * (float)(1.0 / 255.0) : t / 255.0f;
     const int c = (int)(plane % A.channels);
     static_cast<float*>(A.y)[idx] = (t - A.mean[c]) / A.stdv[c];
   } else {
@@ -216,7 +263,7 @@ struct ResizeFusedArgs {
 // RB x MAXT loads of RB rows back to back (tap index clamped into the window, bytes kept raw) and only then runs the chains; the
 // run-time loop `for j < xsize: t = fma((float)src[j], w[j], t)` waits a memory round trip per tap (taps past xsize are skipped, so
 // the chain is the same).  Which form runs: launch_resize.
-template <typename T, int MAXT>
+template <typename T, int MAXT, bool WIN>
 __global__ __launch_bounds__(256) void k_resize_fused(const ResizeFusedArgs F) {
   const ResizeArgs& A = F.r;
   extern __shared__ __attribute__((aligned(16))) float rl[];
@@ -292,15 +339,17 @@ __global__ __launch_bounds__(256) void k_resize_fused(const ResizeFusedArgs F) {
       float wj[MAXT];
 #pragma unroll
       for (int j = 0; j < MAXT; ++j) wj[j] = (j < xsize) ? wx[j * 64 + lane] : 0.f;
-      const T* const col = static_cast<const T*>(A.x) + ((size_t)plane * A.ay.in + r_lo) * A.ax.in + xmin;
+      const T* const col = in_row<T, WIN>(A, plane, r_lo) + xmin;
       for (int r = wave; r < nr; r += 4 * RB) {
         T raw[RB][MAXT];
         if (xsize > 0) {
 #pragma unroll
           for (int k = 0; k < RB; ++k) {
-            const T* src = col + (size_t)min(r + 4 * k, nr - 1) * A.ax.in;  // a row past the tile: a valid row, loaded and dropped
+            const int rk = min(r + 4 * k, nr - 1);  // a row past the tile: a valid row, loaded and dropped
+            const T* src = col + (size_t)rk * in_pitch<WIN>(A);
+            const bool row_ok = in_row_ok<WIN>(A, r_lo + rk);
 #pragma unroll
-            for (int j = 0; j < MAXT; ++j) raw[k][j] = src[min(j, xsize - 1)];
+            for (int j = 0; j < MAXT; ++j) raw[k][j] = in_at<T, WIN>(A, src, row_ok, xmin, min(j, xsize - 1));
           }
         }
 #pragma unroll
@@ -320,12 +369,13 @@ __global__ __launch_bounds__(256) void k_resize_fused(const ResizeFusedArgs F) {
       for (int r = wave; r < nr; r += 4) {
         float t = 0.f;
         if (xsize > 0) {
-          const T* src = static_cast<const T*>(A.x) + ((size_t)plane * A.ay.in + (r_lo + r)) * A.ax.in + xmin;
+          const T* src = in_row<T, WIN>(A, plane, r_lo + r) + xmin;
+          const bool row_ok = in_row_ok<WIN>(A, r_lo + r);
           if (A.ax.identity) {
-            t = (float)src[0];
+            t = (float)in_at<T, WIN>(A, src, row_ok, xmin, 0);
           } else {
             for (int j = 0; j < xsize; ++j) {
-              const float sv = (float)src[j];
+              const float sv = (float)in_at<T, WIN>(A, src, row_ok, xmin, j);
               const float wj = wx[j * 64 + lane];
               t = (j == 0) ? sv * wj : fmaf(sv, wj, t);
             }
@@ -359,9 +409,9 @@ __global__ __launch_bounds__(256) void k_resize_fused(const ResizeFusedArgs F) {
       t = __builtin_rintf(t);
       t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
     }
-    const size_t idx = ((size_t)plane * A.ch + oy) * A.cw + ox;
+    const size_t idx = out_index<WIN>(A, plane, oy, ox);
     if (A.preset) {
-      if (u8) t = t / 255.0f;
+      if (u8) t = (WIN && A.preset == 2) ? t * (float)(1.0 / 255.0) : t / 255.0f;
       const int c = (int)(plane % A.channels);
       static_cast<float*>(A.y)[idx] = (t - A.mean[c]) / A.stdv[c];
     } else {
@@ -432,9 +482,14 @@ int64_t resize_workspace_bytes(int64_t planes, int h, int w, int oh, int ow, int
 
 int launch_resize(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int w, int oh, int ow, int ct,
                   int cl, int ch, int cw, int preset, const float* mean, const float* stdv, void* workspace,
-                  int64_t workspace_bytes, hipStream_t s) {
+                  int64_t workspace_bytes, hipStream_t s, const ResizeWindow* win) {
   ResizeArgs a = {};
-  fill_geometry(a, planes, h, w, oh, ow, ct, cl, ch, cw);
+  fill_geometry(a, planes, h, w, oh, ow, ct, cl, ch, cw);  // (h, w): the window's size when there is one
+  a.ih = h, a.iw = w;
+  // a window that is the whole image, unflipped, is a plain resize: it runs the instantiations that never look at the window
+  const bool windowed = win && !(win->top == 0 && win->left == 0 && win->ih == h && win->iw == w && !win->flip_h && !win->flip_v &&
+                                 preset != 2);
+  if (windowed) a.wt = win->top, a.wl = win->left, a.ih = win->ih, a.iw = win->iw, a.flip_h = win->flip_h, a.flip_v = win->flip_v;
   a.x = x, a.y = y, a.tmp = static_cast<float*>(workspace);
   a.channels = channels > 0 ? channels : 1;
   a.preset = preset;
@@ -455,12 +510,22 @@ int launch_resize(const void* x, void* y, bool u8, int64_t planes, int channels,
         if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, f);
       };
+      if (windowed) {
+        if (u8) {
+          if (batched) launch(k_resize_fused<uint8_t, 16, true>);
+          else launch(k_resize_fused<uint8_t, 0, true>);
+        } else {
+          if (batched) launch(k_resize_fused<float, 16, true>);
+          else launch(k_resize_fused<float, 0, true>);
+        }
+        return check_launchf("k_resize_fused<%s,th%d,window>", u8 ? "u8" : "f32", f.th);
+      }
       if (u8) {
-        if (batched) launch(k_resize_fused<uint8_t, 16>);
-        else launch(k_resize_fused<uint8_t, 0>);
+        if (batched) launch(k_resize_fused<uint8_t, 16, false>);
+        else launch(k_resize_fused<uint8_t, 0, false>);
       } else {
-        if (batched) launch(k_resize_fused<float, 16>);
-        else launch(k_resize_fused<float, 0>);
+        if (batched) launch(k_resize_fused<float, 16, false>);
+        else launch(k_resize_fused<float, 0, false>);
       }
       return check_launchf("k_resize_fused<%s,th%d>", u8 ? "u8" : "f32", f.th);
     }
@@ -475,25 +540,34 @@ int launch_resize(const void* x, void* y, bool u8, int64_t planes, int channels,
   if (n1 > 0) {
     const long long tiles = planes * ((a.nc + 63) / 64) * ((a.nr + kWRows - 1) / kWRows);
     if (!a.ax.identity && a.ax.max_interp <= kWMaxTaps && tiles <= 0x7fffffffLL) {
-      if (u8)
-        hipLaunchKernelGGL((k_resize_w_tiled<uint8_t>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+      if (windowed) {
+        if (u8) hipLaunchKernelGGL((k_resize_w_tiled<uint8_t, true>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_resize_w_tiled<float, true>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+      } else if (u8)
+        hipLaunchKernelGGL((k_resize_w_tiled<uint8_t, false>), dim3((unsigned)tiles), dim3(256), 0, s, a);
       else
-        hipLaunchKernelGGL((k_resize_w_tiled<float>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_resize_w_tiled<float, false>), dim3((unsigned)tiles), dim3(256), 0, s, a);
     } else {
       const unsigned nb = (unsigned)((n1 + 255) / 256);
-      if (u8)
-        hipLaunchKernelGGL((k_resize_w<uint8_t>), dim3(nb), dim3(256), 0, s, a);
+      if (windowed) {
+        if (u8) hipLaunchKernelGGL((k_resize_w<uint8_t, true>), dim3(nb), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_resize_w<float, true>), dim3(nb), dim3(256), 0, s, a);
+      } else if (u8)
+        hipLaunchKernelGGL((k_resize_w<uint8_t, false>), dim3(nb), dim3(256), 0, s, a);
       else
-        hipLaunchKernelGGL((k_resize_w<float>), dim3(nb), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_resize_w<float, false>), dim3(nb), dim3(256), 0, s, a);
     }
     if (int rc = check_launch("k_resize_w")) return rc;
   }
   if (n2 > 0) {
     const unsigned nb = (unsigned)((n2 + 255) / 256);
-    if (u8)
-      hipLaunchKernelGGL((k_resize_h<uint8_t>), dim3(nb), dim3(256), 0, s, a);
+    if (windowed) {
+      if (u8) hipLaunchKernelGGL((k_resize_h<uint8_t, true>), dim3(nb), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_resize_h<float, true>), dim3(nb), dim3(256), 0, s, a);
+    } else if (u8)
+      hipLaunchKernelGGL((k_resize_h<uint8_t, false>), dim3(nb), dim3(256), 0, s, a);
     else
-      hipLaunchKernelGGL((k_resize_h<float>), dim3(nb), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_resize_h<float, false>), dim3(nb), dim3(256), 0, s, a);
     return check_launch("k_resize_h");
   }
   return MV_OK;

@@ -30,7 +30,7 @@ import ctypes as C
 import torch
 
 from . import _lib, _pil, tv_tensors
-# moved code, same objects: everything _color and _geometry define is reached through this module
+# same objects: everything _color, _crop and _geometry define is reached through this module
 from ._color import (_add_alpha_fuses, adjust_brightness, adjust_brightness_image, adjust_brightness_video,  # noqa: F401
                      adjust_contrast, adjust_contrast_image, adjust_contrast_video, adjust_hue, adjust_hue_image,
                      adjust_hue_video, adjust_saturation, adjust_saturation_image, adjust_saturation_video,
@@ -39,6 +39,11 @@ from ._color import (_add_alpha_fuses, adjust_brightness, adjust_brightness_imag
                      equalize_video, invert, invert_image, invert_video, _plane_op, _POINT_OPS, _pointwise,
                      posterize, posterize_image, posterize_video, rgb_to_grayscale, rgb_to_grayscale_image,
                      solarize, solarize_image, solarize_video)
+from ._crop import (axis_index_map, crop, crop_image, crop_mask, crop_video, erase, erase_image, erase_video, hflip,  # noqa: F401
+                    horizontal_flip, horizontal_flip_image, horizontal_flip_mask, horizontal_flip_video, pad, pad_crop,
+                    pad_crop_image, pad_image, pad_mask, PAD_MODES, pad_video, _parse_pad_padding, resized_crop,
+                    resized_crop_flip_normalize, resized_crop_image, resized_crop_video, vertical_flip,
+                    vertical_flip_image, vertical_flip_mask, vertical_flip_video, vflip)
 from ._geometry import (affine, _affine_coeffs, affine_image, affine_mask, _affine_parse_args, affine_video,  # noqa: F401
                         _assert_grid_transform_inputs, _blocked_bmm_fuses, _BMM_NAIVE_LIMIT,
                         _compute_affine_output_size, elastic, _elastic_bounding_boxes_dispatch, _elastic_fill,

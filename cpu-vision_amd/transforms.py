@@ -12,6 +12,8 @@
   AutoAugment / RandAugment / TrivialAugmentWide      transforms/v2/_auto_augment.py (-> F.affine / rotate / adjust_* /
                                                       posterize / solarize / autocontrast / equalize / invert)
   Resize / CenterCrop / ToDtype / Normalize / Compose   v2/_geometry.py:76-193, v2/_misc.py:134-304, v2/_container.py:10-64
+  RandomHorizontalFlip / RandomVerticalFlip / Pad / RandomCrop / RandomResizedCrop   transforms/v2/_geometry.py
+  RandomErasing                           transforms/v2/_augment.py (-> F.erase)
 
 Parameter sampling stays on the host RNG exactly like the reference (torch.empty(1).uniform_ / torch.rand(1)).
 """
@@ -1104,6 +1106,232 @@ class TrivialAugmentWide(_AutoAugmentBase):
             magnitude = 0.0
         image_or_video = self._apply(image_or_video, transform_id, magnitude)
         return self._unflatten_and_insert_image_or_video(flat_inputs_with_spec, image_or_video)
+
+
+# ---- the training recipes' geometry: flips, Pad, RandomCrop, RandomResizedCrop, RandomErasing (v2/_geometry.py, v2/_augment.py).
+#      The host RNG calls are the reference's, in its order.
+def _check_padding_arg(padding) -> None:
+    """transforms/v2/_utils.py `_check_padding_arg`."""
+    if not isinstance(padding, (numbers.Number, tuple, list)):
+        raise TypeError("Got inappropriate padding arg")
+    if isinstance(padding, (tuple, list)) and len(padding) not in [1, 2, 4]:
+        raise ValueError(f"Padding must be an int or a 1, 2, or 4 element tuple, not a {len(padding)} element tuple")
+
+
+def _check_padding_mode_arg(padding_mode) -> None:
+    """transforms/v2/_utils.py `_check_padding_mode_arg`."""
+    if padding_mode not in ["constant", "edge", "reflect", "symmetric"]:
+        raise ValueError("Padding mode should be either constant, edge, reflect or symmetric")
+
+
+class RandomHorizontalFlip(_RandomApplyTransform):
+    """v2.RandomHorizontalFlip(p=0.5) -- transforms/v2/_geometry.py."""
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.horizontal_flip, inpt)
+
+
+class RandomVerticalFlip(_RandomApplyTransform):
+    """v2.RandomVerticalFlip(p=0.5) -- transforms/v2/_geometry.py."""
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.vertical_flip, inpt)
+
+
+class Pad(Transform):
+    """v2.Pad(padding, fill=0, padding_mode="constant") -- transforms/v2/_geometry.py."""
+
+    def __init__(self, padding, fill=0, padding_mode: str = "constant") -> None:
+        super().__init__()
+        _check_padding_arg(padding)
+        _check_padding_mode_arg(padding_mode)
+        if not isinstance(padding, int):
+            padding = list(padding)
+        self.padding = padding
+        self.fill = fill
+        self._fill = _setup_fill_arg(fill)
+        self.padding_mode = padding_mode
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        fill = _get_fill(self._fill, type(inpt))
+        return self._call_kernel(F.pad, inpt, padding=self.padding, fill=fill, padding_mode=self.padding_mode)
+
+
+class RandomCrop(Transform):
+    """v2.RandomCrop(size, padding=None, pad_if_needed=False, fill=0, padding_mode="constant") -- transforms/v2/_geometry.py.
+    When a sample is both padded and cropped the two steps run as ONE gather launch (F.pad_crop)."""
+
+    def __init__(self, size, padding=None, pad_if_needed: bool = False, fill=0, padding_mode: str = "constant") -> None:
+        super().__init__()
+        self.size = _setup_size(size, "Please provide only two dimensions (h, w) for size.")
+        if pad_if_needed or padding is not None:
+            if padding is not None:
+                _check_padding_arg(padding)
+            _check_padding_mode_arg(padding_mode)
+        self.padding = F._parse_pad_padding(padding) if padding else None
+        self.pad_if_needed = pad_if_needed
+        self.fill = fill
+        self._fill = _setup_fill_arg(fill)
+        self.padding_mode = padding_mode
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        padded_height, padded_width = query_size(flat_inputs)
+        if self.padding is not None:
+            pad_left, pad_right, pad_top, pad_bottom = self.padding
+            padded_height += pad_top + pad_bottom
+            padded_width += pad_left + pad_right
+        else:
+            pad_left = pad_right = pad_top = pad_bottom = 0
+        cropped_height, cropped_width = self.size
+        if self.pad_if_needed:
+            if padded_height < cropped_height:
+                diff = cropped_height - padded_height
+                pad_top += diff
+                pad_bottom += diff
+                padded_height += 2 * diff
+            if padded_width < cropped_width:
+                diff = cropped_width - padded_width
+                pad_left += diff
+                pad_right += diff
+                padded_width += 2 * diff
+        if padded_height < cropped_height or padded_width < cropped_width:
+            raise ValueError(f"Required crop size {(cropped_height, cropped_width)} is larger than "
+                             f"{'padded ' if self.padding is not None else ''}input image size {(padded_height, padded_width)}.")
+        padding = [pad_left, pad_top, pad_right, pad_bottom]  # F.pad's order
+        needs_pad = any(padding)
+        needs_vert_crop, top = ((True, int(torch.randint(0, padded_height - cropped_height + 1, size=())))
+                                if padded_height > cropped_height else (False, 0))
+        needs_horz_crop, left = ((True, int(torch.randint(0, padded_width - cropped_width + 1, size=())))
+                                 if padded_width > cropped_width else (False, 0))
+        return dict(needs_crop=needs_vert_crop or needs_horz_crop, top=top, left=left, height=cropped_height,
+                    width=cropped_width, needs_pad=needs_pad, padding=padding)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        box = dict(top=params["top"], left=params["left"], height=params["height"], width=params["width"])
+        if params["needs_pad"]:
+            fill = _get_fill(self._fill, type(inpt))
+            if params["needs_crop"]:
+                return self._call_kernel(F.pad_crop, inpt, padding=params["padding"], fill=fill, padding_mode=self.padding_mode,
+                                         **box)
+            return self._call_kernel(F.pad, inpt, padding=params["padding"], fill=fill, padding_mode=self.padding_mode)
+        if params["needs_crop"]:
+            return self._call_kernel(F.crop, inpt, **box)
+        return inpt
+
+
+def _check_scale_ratio(scale, ratio) -> None:
+    import warnings
+    if not isinstance(scale, Sequence):
+        raise TypeError("Scale should be a sequence")
+    if not isinstance(ratio, Sequence):
+        raise TypeError("Ratio should be a sequence")
+    if (scale[0] > scale[1]) or (ratio[0] > ratio[1]):
+        warnings.warn("Scale and ratio should be of kind (min, max)")
+
+
+class RandomResizedCrop(Transform):
+    """v2.RandomResizedCrop(size, scale=(0.08, 1.0), ratio=(3/4, 4/3), interpolation=BILINEAR, antialias=True) --
+    transforms/v2/_geometry.py; the crop and the resize are one launch (F.resized_crop)."""
+
+    def __init__(self, size, scale: Tuple[float, float] = (0.08, 1.0), ratio: Tuple[float, float] = (3.0 / 4.0, 4.0 / 3.0),
+                 interpolation=InterpolationMode.BILINEAR, antialias: Optional[bool] = True) -> None:
+        super().__init__()
+        self.size = _setup_size(size, "Please provide only two dimensions (h, w) for size.")
+        _check_scale_ratio(scale, ratio)
+        self.scale = scale
+        self.ratio = ratio
+        self.interpolation = interpolation
+        self.antialias = antialias
+        self._log_ratio = torch.log(torch.tensor(self.ratio))
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        height, width = query_size(flat_inputs)
+        area = height * width
+        log_ratio = self._log_ratio
+        for _ in range(10):
+            target_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1]).item()
+            aspect_ratio = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1])).item()
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            if 0 < w <= width and 0 < h <= height:
+                i = torch.randint(0, height - h + 1, size=(1,)).item()
+                j = torch.randint(0, width - w + 1, size=(1,)).item()
+                break
+        else:  # the central crop
+            in_ratio = float(width) / float(height)
+            if in_ratio < min(self.ratio):
+                w = width
+                h = int(round(w / min(self.ratio)))
+            elif in_ratio > max(self.ratio):
+                h = height
+                w = int(round(h * max(self.ratio)))
+            else:
+                w = width
+                h = height
+            i = (height - h) // 2
+            j = (width - w) // 2
+        return dict(top=i, left=j, height=h, width=w)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        return self._call_kernel(F.resized_crop, inpt, **params, size=list(self.size), interpolation=self.interpolation,
+                                 antialias=self.antialias)
+
+
+class RandomErasing(_RandomApplyTransform):
+    """v2.RandomErasing(p=0.5, scale=(0.02, 0.33), ratio=(0.3, 3.3), value=0.0, inplace=False) -- transforms/v2/_augment.py.
+    The "random" values are drawn on the host, as the reference draws them, and copied to the device."""
+
+    def __init__(self, p: float = 0.5, scale: Tuple[float, float] = (0.02, 0.33), ratio: Tuple[float, float] = (0.3, 3.3),
+                 value=0.0, inplace: bool = False) -> None:
+        super().__init__(p=p)
+        if not isinstance(value, (numbers.Number, str, tuple, list)):
+            raise TypeError("Argument value should be either a number or str or a sequence")
+        if isinstance(value, str) and value != "random":
+            raise ValueError("If value is str, it should be 'random'")
+        _check_scale_ratio(scale, ratio)
+        if scale[0] < 0 or scale[1] > 1:
+            raise ValueError("Scale should be between 0 and 1")
+        self.scale = scale
+        self.ratio = ratio
+        if isinstance(value, (int, float)):
+            self.value = [float(value)]
+        elif isinstance(value, str):
+            self.value = None
+        elif isinstance(value, (list, tuple)):
+            self.value = [float(v) for v in value]
+        else:
+            self.value = value
+        self.inplace = inplace
+        self._log_ratio = torch.log(torch.tensor(self.ratio))
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        img_c, img_h, img_w = query_chw(flat_inputs)
+        if self.value is not None and not (len(self.value) in (1, img_c)):
+            raise ValueError(f"If value is a sequence, it should have either a single value or {img_c} (number of inpt channels)")
+        area = img_h * img_w
+        log_ratio = self._log_ratio
+        for _ in range(10):
+            erase_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1]).item()
+            aspect_ratio = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1])).item()
+            h = int(round(math.sqrt(erase_area * aspect_ratio)))
+            w = int(round(math.sqrt(erase_area / aspect_ratio)))
+            if not (h < img_h and w < img_w):
+                continue
+            if self.value is None:
+                v = torch.empty([img_c, h, w], dtype=torch.float32).normal_()
+            else:
+                v = torch.tensor(self.value)[:, None, None]
+            i = torch.randint(0, img_h - h + 1, size=(1,)).item()
+            j = torch.randint(0, img_w - w + 1, size=(1,)).item()
+            break
+        else:
+            i, j, h, w, v = 0, 0, img_h, img_w, None
+        return dict(i=i, j=j, h=h, w=w, v=v)
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        if params["v"] is not None:
+            inpt = self._call_kernel(F.erase, inpt, **params, inplace=self.inplace)
+        return inpt
 
 
 class GaussianBlurV1(nn.Module):

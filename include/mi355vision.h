@@ -466,6 +466,45 @@ int mv_equalize_f32(const float* x, float* y, int64_t planes, int h, int w, void
 int mv_equalize_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, void* workspace, int64_t workspace_bytes,
                    void* stream);
 
+/* ---- RandomResizedCrop's hot path: F.resized_crop = resize_image(crop_image(x, top, left, wh, ww), (oh, ow)) without a copy of
+ * the crop.  x is (planes, h, w); the source window [top, top + wh) x [left, left + ww) is in input coordinates and may reach
+ * outside the image (crop_image's zero padding: such pixels read as 0); the interpolation axes are those of a (wh, ww) image.
+ * flip_h / flip_v mirror the OUTPUT (the reference flips after the resize; flipping the input first runs the fma chains in the
+ * other order and is not bit-identical).  Workspace: mv_resize_workspace_bytes(planes, wh, ww, oh, ow, 0, 0, oh, ow).  The
+ * *_preset_* forms add the tail of mv_preset_classification_*: uint8 `/ 255` (v2_scale = 0, v1's convert_image_dtype) or
+ * uint8 `* (1 / 255)` (v2_scale = 1, v2's to_dtype(scale=True)), then `(v - mean[c]) / std[c]` into fp32; float32 input is
+ * not rescaled. */
+int mv_resized_crop_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int wdt, int top, int left, int wh, int ww, int oh,
+                       int ow, int flip_h, int flip_v, void* workspace, int64_t workspace_bytes, void* stream);
+int mv_resized_crop_f32(const float* x, float* y, int64_t planes, int h, int wdt, int top, int left, int wh, int ww, int oh,
+                        int ow, int flip_h, int flip_v, void* workspace, int64_t workspace_bytes, void* stream);
+int mv_resized_crop_preset_u8(const uint8_t* x, float* y, int64_t n, int c, int h, int wdt, int top, int left, int wh, int ww,
+                              int oh, int ow, int flip_h, int flip_v, int v2_scale, const float* mean, const float* stdv,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int mv_resized_crop_preset_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int top, int left, int wh, int ww,
+                               int oh, int ow, int flip_h, int flip_v, int v2_scale, const float* mean, const float* stdv,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- F.pad / F.crop / F.horizontal_flip / F.vertical_flip / F.erase: one gather kernel that moves elements of elem_bytes
+ * (1, 2, 4 or 8) bytes, whatever their dtype.  x is (planes, ih, iw), y is (planes, oh, ow).  Output pixel (oy, ox) takes source
+ * pixel (map(oy), map(ox)), per axis: p = (flip ? out - 1 - o : o) + offset with offset = `top` / `left` (negative: padding,
+ * positive: cropping); 0 <= p < in is p itself, otherwise the border mode decides: MV_PAD_CONSTANT the fill, MV_PAD_EDGE
+ * clamp(p), MV_PAD_REFLECT -p or 2 (in - 1) - p (each padding must be smaller than the side, as ATen requires),
+ * MV_PAD_SYMMETRIC -1 - p or 2 in - 1 - p (each padding at most the side).  `fill` is NULL (zeros)
+ * or a HOST array of `channels` (1..4) elements of elem_bytes each, already in the image's dtype; plane p takes
+ * fill[p % channels].  One launch, no workspace. */
+#define MV_PAD_CONSTANT 0
+#define MV_PAD_EDGE 1
+#define MV_PAD_REFLECT 2
+#define MV_PAD_SYMMETRIC 3
+int mv_pad_crop_flip(const void* x, void* y, int64_t planes, int channels, int elem_bytes, int ih, int iw, int oh, int ow, int top,
+                     int left, int mode, int flip_h, int flip_v, const void* fill, void* stream);
+/* erase: y = x with the box [i, i + eh) x [j, j + ew) (inside the image) replaced by v, a DEVICE array in the image's dtype of
+ * `channels` elements (v_is_per_pixel = 0) or channels x eh x ew elements (1); plane p takes channel p % channels.  Out of
+ * place it is one launch of the gather kernel and the source pixels under the box are not read; with y == x only the box is
+ * written. */
+int mv_erase(const void* x, void* y, int64_t planes, int channels, int elem_bytes, int h, int w, int i, int j, int eh, int ew,
+             const void* v, int v_is_per_pixel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
