@@ -106,6 +106,11 @@ SYMBOLS = {
     "mv_resized_crop_preset_f32": (_i, [_vp, _vp, _i64] + [_i] * 12 + [_fp, _fp, _vp, _i64, _vp]),
     "mv_pad_crop_flip": (_i, [_vp, _vp, _i64] + [_i] * 11 + [_vp, _vp]),
     "mv_erase": (_i, [_vp, _vp, _i64] + [_i] * 8 + [_vp, _i, _vp]),
+    "mv_mixup_f32": (_i, [_vp, _vp, _i64, _i64, _d, _vp]),
+    "mv_mixup_f16": (_i, [_vp, _vp, _i64, _i64, _d, _vp]),
+    "mv_mixup_f64": (_i, [_vp, _vp, _i64, _i64, _d, _vp]),
+    "mv_cutmix": (_i, [_vp, _vp, _i64, _i64] + [_i] * 7 + [_vp]),
+    "mv_mixup_labels_i64": (_i, [_vp, _vp, _i64, _i, _d, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -964,6 +964,68 @@ int mv_erase(const void* x, void* y, int64_t planes, int channels, int elem_byte
                        v_is_per_pixel ? 1 : 0, (hipStream_t)stream);
 }
 
+// ---- MixUp / CutMix: batchmix.hip ------------------------------------------------------------------------------------------------
+static int mixup(const void* x, void* y, int elem_bytes, int64_t batch, int64_t sample_elems, double lam, void* stream) {
+  if (batch < 0 || sample_elems < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "mixup: bad shape batch=%lld, sample_elems=%lld", (long long)batch, (long long)sample_elems);
+  if (lam != lam) return set_error(MV_ERR_INVALID_ARGUMENT, "mixup: lam is NaN");
+  if (batch == 0 || sample_elems == 0) return MV_OK;
+  if (sample_elems > 0x7fffffffffffLL / batch)
+    return set_error(MV_ERR_UNSUPPORTED, "mixup: %lld samples of %lld elements are too many", (long long)batch, (long long)sample_elems);
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "mixup: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (!mix_grid_fits(batch, sample_elems, elem_bytes))
+    return set_error(MV_ERR_UNSUPPORTED, "mixup: %lld samples of %lld elements exceed the launch grid", (long long)batch,
+                     (long long)sample_elems);
+  return launch_mixup(x, y, elem_bytes, batch, sample_elems, lam, (hipStream_t)stream);
+}
+
+int mv_mixup_f32(const float* x, float* y, int64_t batch, int64_t sample_elems, double lam, void* stream) {
+  return mixup(x, y, 4, batch, sample_elems, lam, stream);
+}
+
+int mv_mixup_f16(const void* x, void* y, int64_t batch, int64_t sample_elems, double lam, void* stream) {
+  return mixup(x, y, 2, batch, sample_elems, lam, stream);
+}
+
+int mv_mixup_f64(const double* x, double* y, int64_t batch, int64_t sample_elems, double lam, void* stream) {
+  return mixup(x, y, 8, batch, sample_elems, lam, stream);
+}
+
+int mv_cutmix(const void* x, void* y, int64_t batch, int64_t planes_per_sample, int elem_bytes, int h, int w, int x1, int y1, int x2,
+              int y2, void* stream) {
+  if (int rc = check_elem_bytes("cutmix", elem_bytes)) return rc;
+  if (batch < 0 || planes_per_sample < 0 || h < 0 || w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "cutmix: bad shape batch=%lld, planes_per_sample=%lld (%d, %d)", (long long)batch,
+                     (long long)planes_per_sample, h, w);
+  if (x1 < 0 || y1 < 0 || x2 < x1 || y2 < y1 || x2 > w || y2 > h)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "cutmix: the box x [%d, %d) y [%d, %d) must lie inside the (%d, %d) image", x1, x2, y1, y2,
+                     h, w);
+  if (batch == 0 || planes_per_sample == 0 || h == 0 || w == 0) return MV_OK;
+  if (planes_per_sample > 0x7fffffffffffLL / batch / h / w)
+    return set_error(MV_ERR_UNSUPPORTED, "cutmix: %lld samples of %lld planes of %d x %d are too many", (long long)batch,
+                     (long long)planes_per_sample, h, w);
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "cutmix: null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  const int64_t elems = planes_per_sample * h * w;
+  if (!mix_grid_fits(batch, elems, elem_bytes))
+    return set_error(MV_ERR_UNSUPPORTED, "cutmix: %lld samples of %lld elements exceed the launch grid", (long long)batch,
+                     (long long)elems);
+  return launch_cutmix(x, y, batch, elems, elem_bytes, h, w, x1, y1, x2, y2, (hipStream_t)stream);
+}
+
+int mv_mixup_labels_i64(const int64_t* labels, float* y, int64_t batch, int num_classes, double lam, void* stream) {
+  if (batch < 0 || num_classes <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "mixup_labels: bad shape batch=%lld, num_classes=%d", (long long)batch, num_classes);
+  if (lam != lam) return set_error(MV_ERR_INVALID_ARGUMENT, "mixup_labels: lam is NaN");
+  if (batch == 0) return MV_OK;
+  if (batch > (0x7fffffffLL * 1024) / num_classes)
+    return set_error(MV_ERR_UNSUPPORTED, "mixup_labels: %lld x %d outputs exceed the launch grid", (long long)batch, num_classes);
+  if (!labels || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "mixup_labels: null pointer");
+  if ((const void*)labels == (const void*)y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  return launch_mixup_labels(labels, y, batch, num_classes, lam, (hipStream_t)stream);
+}
+
 static int elastic(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int wdt, const float* base_x,
                    const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
                    const float* fill, void* stream) {

@@ -302,6 +302,14 @@ int launch_gather(const void* x, void* y, int64_t planes, int channels, int elem
 int launch_erase_box(void* y, int64_t planes, int channels, int elem_bytes, int h, int w, int bi, int bj, int bh, int bw,
                      const void* v, int v_per_pixel, hipStream_t s);
 
+// MixUp / CutMix over a contiguous (batch, elems) batch (batchmix.hip; arithmetic in mi355vision.h mv_mixup_f32).  The entry
+// points have checked the arguments and the grid (mix_grid_fits); elem_bytes of launch_mixup: 4 float32, 2 float16, 8 float64.
+bool mix_grid_fits(int64_t batch, int64_t elems, int elem_bytes);
+int launch_mixup(const void* x, void* y, int elem_bytes, int64_t batch, int64_t elems, double lam, hipStream_t s);
+int launch_cutmix(const void* x, void* y, int64_t batch, int64_t elems, int elem_bytes, int h, int w, int x1, int y1, int x2, int y2,
+                  hipStream_t s);
+int launch_mixup_labels(const int64_t* labels, float* y, int64_t batch, int classes, double lam, hipStream_t s);
+
 // F.elastic: grid_sample of every plane at identity grid + displacement (elastic.hip).  base_x / base_y: the reference's
 // linspace vectors (W and H floats, device); disp (1, H, W, 2) fp32 by strides; mode 0 bilinear, 1 nearest; fill: NULL or
 // `channels` host floats (plane p takes fill[p % channels]).

@@ -30,7 +30,7 @@ import ctypes as C
 import torch
 
 from . import _lib, _pil, tv_tensors
-# same objects: everything _color, _crop and _geometry define is reached through this module
+# same objects: everything _color, _crop, _geometry and _mix define is reached through this module
 from ._color import (_add_alpha_fuses, adjust_brightness, adjust_brightness_image, adjust_brightness_video,  # noqa: F401
                      adjust_contrast, adjust_contrast_image, adjust_contrast_video, adjust_hue, adjust_hue_image,
                      adjust_hue_video, adjust_saturation, adjust_saturation_image, adjust_saturation_video,
@@ -44,6 +44,7 @@ from ._crop import (axis_index_map, crop, crop_image, crop_mask, crop_video, era
                     pad_crop_image, pad_image, pad_mask, PAD_MODES, pad_video, _parse_pad_padding, resized_crop,
                     resized_crop_flip_normalize, resized_crop_image, resized_crop_video, vertical_flip,
                     vertical_flip_image, vertical_flip_mask, vertical_flip_video, vflip)
+from ._mix import cutmix_image, mixup_image, mixup_labels  # noqa: F401
 from ._geometry import (affine, _affine_coeffs, affine_image, affine_mask, _affine_parse_args, affine_video,  # noqa: F401
                         _assert_grid_transform_inputs, _blocked_bmm_fuses, _BMM_NAIVE_LIMIT,
                         _compute_affine_output_size, elastic, _elastic_bounding_boxes_dispatch, _elastic_fill,

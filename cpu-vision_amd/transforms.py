@@ -14,6 +14,8 @@
   Resize / CenterCrop / ToDtype / Normalize / Compose   v2/_geometry.py:76-193, v2/_misc.py:134-304, v2/_container.py:10-64
   RandomHorizontalFlip / RandomVerticalFlip / Pad / RandomCrop / RandomResizedCrop   transforms/v2/_geometry.py
   RandomErasing                           transforms/v2/_augment.py (-> F.erase)
+  MixUp / CutMix                          transforms/v2/_augment.py (-> F.mixup_image / F.cutmix_image / F.mixup_labels)
+  RandomApply / RandomChoice / RandomOrder   transforms/v2/_container.py
 
 Parameter sampling stays on the host RNG exactly like the reference (torch.empty(1).uniform_ / torch.rand(1)).
 """
@@ -1332,6 +1334,198 @@ class RandomErasing(_RandomApplyTransform):
         if params["v"] is not None:
             inpt = self._call_kernel(F.erase, inpt, **params, inplace=self.inplace)
         return inpt
+
+
+def _find_labels_default_heuristic(inputs: Any) -> torch.Tensor:
+    """transforms/v2/_utils.py `_find_labels_default_heuristic`: the second item of a tuple or list sample, itself the labels
+    or a dict that holds them under "label" / "labels" (any letter case)."""
+    if isinstance(inputs, (tuple, list)):
+        inputs = inputs[1]
+    if is_pure_tensor(inputs):
+        return inputs
+    if not isinstance(inputs, collections.abc.Mapping):
+        raise ValueError("When using the default labels_getter, the input passed to forward must be a dictionary or a two-tuple "
+                         f"whose second item is a dictionary or a tensor, but got {inputs} instead.")
+    candidate_key = next((key for key in inputs.keys() if key.lower() in ("label", "labels")), None)
+    if candidate_key is None:
+        raise ValueError("Could not infer where the labels are in the sample. Try passing a callable as the labels_getter "
+                         "parameter? If there are no labels in the sample by design, pass labels_getter=None.")
+    return inputs[candidate_key]
+
+
+def _parse_labels_getter(labels_getter: Union[str, Callable[[Any], Any], None]) -> Callable[[Any], Any]:
+    """transforms/v2/_utils.py `_parse_labels_getter`."""
+    if labels_getter == "default":
+        return _find_labels_default_heuristic
+    if callable(labels_getter):
+        return labels_getter
+    if labels_getter is None:
+        return lambda _: None
+    raise ValueError(f"labels_getter should either be 'default', a callable, or None, but got {labels_getter}.")
+
+
+class _BaseMixUpCutMix(Transform):
+    """transforms/v2/_augment.py `_BaseMixUpCutMix`: a batch-level transform of (images, labels) after collation.  Sample b is
+    mixed with sample b - 1; the labels become (B, num_classes) float probabilities."""
+
+    def __init__(self, *, alpha: float = 1.0, num_classes: Optional[int] = None, labels_getter="default") -> None:
+        super().__init__()
+        self.alpha = float(alpha)
+        self._dist = torch.distributions.Beta(torch.tensor([alpha]), torch.tensor([alpha]))
+        self.num_classes = num_classes
+        self._labels_getter = _parse_labels_getter(labels_getter)
+
+    def forward(self, *inputs: Any) -> Any:
+        inputs = inputs if len(inputs) > 1 else inputs[0]
+        flat_inputs, spec = tree_flatten(inputs)
+        needs = self._needs_transform_list(flat_inputs)
+        if any(isinstance(i, _PIL_TYPES + (tv_tensors.BoundingBoxes, tv_tensors.Mask)) for i in flat_inputs):
+            raise ValueError(f"{type(self).__name__}() does not support PIL images, bounding boxes and masks.")
+        labels = self._labels_getter(inputs)
+        if not isinstance(labels, torch.Tensor):
+            raise ValueError(f"The labels must be a tensor, but got {type(labels)} instead.")
+        if labels.ndim not in (1, 2):
+            raise ValueError("labels should be index based with shape (batch_size,) or probability based with shape (batch_size, "
+                             f"num_classes), but got a tensor of shape {labels.shape} instead.")
+        if labels.ndim == 2 and self.num_classes is not None and labels.shape[-1] != self.num_classes:
+            raise ValueError("When passing 2D labels, the number of elements in last dimension must match num_classes: "
+                             f"{labels.shape[-1]} != {self.num_classes}. You can Leave num_classes to None.")
+        if labels.ndim == 1 and self.num_classes is None:
+            raise ValueError("num_classes must be passed if the labels are index-based (1D)")
+        params = {"labels": labels, "batch_size": labels.shape[0],
+                  **self._get_params([i for i, n in zip(flat_inputs, needs) if n])}
+        # the labels are transformed by identity, not by the pure-tensor heuristic; _get_params above does not see them
+        needs[next(k for k, i in enumerate(flat_inputs) if i is labels)] = True
+        flat_outputs = [self._transform(i, params) if n else i for i, n in zip(flat_inputs, needs)]
+        return tree_unflatten(flat_outputs, spec)
+
+    def _check_image_or_video(self, inpt: torch.Tensor, *, batch_size: int) -> None:
+        expected_num_dims = 5 if isinstance(inpt, tv_tensors.Video) else 4
+        if inpt.ndim != expected_num_dims:
+            raise ValueError(f"Expected a batched input with {expected_num_dims} dims, but got {inpt.ndim} dimensions instead.")
+        if inpt.shape[0] != batch_size:
+            raise ValueError("The batch size of the image or video does not match the batch size of the labels: "
+                             f"{inpt.shape[0]} != {batch_size}.")
+
+    def _mixup_label(self, label: torch.Tensor, *, lam: float) -> torch.Tensor:
+        return F.mixup_labels(label.as_subclass(torch.Tensor), lam, num_classes=self.num_classes)
+
+    def _mix(self, image: torch.Tensor, params: Dict[str, Any]) -> torch.Tensor:
+        raise NotImplementedError
+
+    def _transform(self, inpt: Any, params: Dict[str, Any]) -> Any:
+        if inpt is params["labels"]:
+            return self._mixup_label(inpt, lam=params["lam"])
+        if isinstance(inpt, (tv_tensors.Image, tv_tensors.Video)) or is_pure_tensor(inpt):
+            self._check_image_or_video(inpt, batch_size=params["batch_size"])
+            output = self._mix(inpt.as_subclass(torch.Tensor), params)
+            if isinstance(inpt, (tv_tensors.Image, tv_tensors.Video)):
+                output = tv_tensors.wrap(output, like=inpt)
+            return output
+        return inpt
+
+
+class MixUp(_BaseMixUpCutMix):
+    """v2.MixUp(*, alpha=1.0, num_classes=None, labels_getter="default") -- transforms/v2/_augment.py: images and labels become
+    lam * x[b] + (1 - lam) * x[b - 1] with lam ~ Beta(alpha, alpha) drawn on the host; one launch for the images that reads the
+    batch once, one for the labels.  Integer images raise TypeError (the reference's mul_ raises): convert with ToDtype first."""
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        return dict(lam=float(self._dist.sample(())))
+
+    def _mix(self, image: torch.Tensor, params: Dict[str, Any]) -> torch.Tensor:
+        return F.mixup_image(image, params["lam"])
+
+
+class CutMix(_BaseMixUpCutMix):
+    """v2.CutMix(*, alpha=1.0, num_classes=None, labels_getter="default") -- transforms/v2/_augment.py: a box of every image is
+    replaced by the same box of the previous image of the batch, and the labels are mixed by the share of the area that is left.
+    The box is drawn on the host with the reference's calls in the reference's order."""
+
+    def _get_params(self, flat_inputs: List[Any]) -> Dict[str, Any]:
+        lam = float(self._dist.sample(()))
+        H, W = query_size(flat_inputs)
+        r_x = torch.randint(W, size=(1,))
+        r_y = torch.randint(H, size=(1,))
+        r = 0.5 * math.sqrt(1.0 - lam)
+        r_w_half = int(r * W)
+        r_h_half = int(r * H)
+        x1 = int(torch.clamp(r_x - r_w_half, min=0))
+        y1 = int(torch.clamp(r_y - r_h_half, min=0))
+        x2 = int(torch.clamp(r_x + r_w_half, max=W))
+        y2 = int(torch.clamp(r_y + r_h_half, max=H))
+        box = (x1, y1, x2, y2)
+        lam_adjusted = float(1.0 - (x2 - x1) * (y2 - y1) / (W * H))
+        return dict(box=box, lam=lam_adjusted)
+
+    def _mix(self, image: torch.Tensor, params: Dict[str, Any]) -> torch.Tensor:
+        return F.cutmix_image(image, params["box"])
+
+
+def _thread_through(transforms, order, inputs: Tuple[Any, ...]) -> Any:
+    """Compose.forward's loop over transforms[k] for k in `order`: multi-argument outputs are fed back as *inputs.  An empty
+    `order` hands the inputs back, where the reference's loop leaves `outputs` unbound and raises UnboundLocalError."""
+    needs_unpacking = len(inputs) > 1
+    outputs = inputs if needs_unpacking else inputs[0]
+    for k in order:
+        outputs = transforms[k](*inputs)
+        inputs = outputs if needs_unpacking else (outputs,)
+    return outputs
+
+
+class RandomApply(Transform):
+    """v2.RandomApply(transforms, p=0.5) -- transforms/v2/_container.py: all of `transforms` in turn, or none of them."""
+
+    def __init__(self, transforms: Union[Sequence[Callable], nn.ModuleList], p: float = 0.5) -> None:
+        super().__init__()
+        if not isinstance(transforms, (Sequence, nn.ModuleList)):
+            raise TypeError("Argument transforms should be a sequence of callables or a `nn.ModuleList`")
+        self.transforms = transforms
+        if not (0.0 <= p <= 1.0):
+            raise ValueError("`p` should be a floating point value in the interval [0.0, 1.0].")
+        self.p = p
+
+    def forward(self, *inputs: Any) -> Any:
+        if torch.rand(1) >= self.p:
+            return inputs if len(inputs) > 1 else inputs[0]
+        return _thread_through(self.transforms, range(len(self.transforms)), inputs)
+
+    def extra_repr(self) -> str:
+        return "\n".join(f"    {t}" for t in self.transforms)
+
+
+class RandomChoice(Transform):
+    """v2.RandomChoice(transforms, p=None) -- transforms/v2/_container.py: one of `transforms`, drawn with torch.multinomial
+    from the weights `p` (default: equal), which are stored normalised."""
+
+    def __init__(self, transforms: Sequence[Callable], p: Optional[List[float]] = None) -> None:
+        if not isinstance(transforms, Sequence):
+            raise TypeError("Argument transforms should be a sequence of callables")
+        if p is None:
+            p = [1] * len(transforms)
+        elif len(p) != len(transforms):
+            raise ValueError(f"Length of p doesn't match the number of transforms: {len(p)} != {len(transforms)}")
+        super().__init__()
+        self.transforms = transforms
+        total = sum(p)
+        self.p = [prob / total for prob in p]
+
+    def forward(self, *inputs: Any) -> Any:
+        idx = int(torch.multinomial(torch.tensor(self.p), 1))
+        return self.transforms[idx](*inputs)
+
+
+class RandomOrder(Transform):
+    """v2.RandomOrder(transforms) -- transforms/v2/_container.py: all of `transforms`, in the order of one torch.randperm."""
+
+    def __init__(self, transforms: Sequence[Callable]) -> None:
+        if not isinstance(transforms, Sequence):
+            raise TypeError("Argument transforms should be a sequence of callables")
+        super().__init__()
+        self.transforms = transforms
+
+    def forward(self, *inputs: Any) -> Any:
+        return _thread_through(self.transforms, [int(k) for k in torch.randperm(len(self.transforms))], inputs)
 
 
 class GaussianBlurV1(nn.Module):

@@ -504,6 +504,24 @@ int mv_pad_crop_flip(const void* x, void* y, int64_t planes, int channels, int e
  * written. */
 int mv_erase(const void* x, void* y, int64_t planes, int channels, int elem_bytes, int h, int w, int i, int j, int eh, int ew,
              const void* v, int v_is_per_pixel, void* stream);
+/* ---- MixUp / CutMix (transforms/v2/_augment.py) over a contiguous batch x of `batch` samples: sample b is paired with sample
+ * (b - 1 + batch) % batch, the reference's roll(1, 0).  x and y must not alias; batch == 0 or empty samples are a no-op.
+ * mixup: y[b] = fl(fl(x[b - 1] * wp) + fl(x[b] * ws)) with wp = 1 - lam and ws = lam narrowed from double to the compute type
+ * (float for _f32 and _f16, double for _f64): two separately rounded products and one rounded sum, never an fma; _f16 rounds
+ * each of the three results to float16.  Probability labels (batch, num_classes) go through the same entries. */
+int mv_mixup_f32(const float* x, float* y, int64_t batch, int64_t sample_elems, double lam, void* stream);
+int mv_mixup_f16(const void* x, void* y, int64_t batch, int64_t sample_elems, double lam, void* stream);
+int mv_mixup_f64(const double* x, double* y, int64_t batch, int64_t sample_elems, double lam, void* stream);
+/* cutmix: a sample is planes_per_sample planes of (h, w) elements of elem_bytes (1, 2, 4 or 8) bytes, whatever their dtype; inside
+ * the box [y1, y2) x [x1, x2) (0 <= x1 <= x2 <= w, 0 <= y1 <= y2 <= h) y[b] takes x[b - 1], outside it x[b].  An empty box is a
+ * copy, the whole image a roll. */
+int mv_cutmix(const void* x, void* y, int64_t batch, int64_t planes_per_sample, int elem_bytes, int h, int w, int x1, int y1, int x2,
+              int y2, void* stream);
+/* index labels: y (batch, num_classes) float32 = the mixup of one_hot(labels, num_classes).float(), in one launch and with the
+ * same three roundings (a row whose neighbour has the same label holds fl(fl(1 - lam) + fl(lam)) there, not a literal 1).  A label
+ * outside [0, num_classes) is not reported (that would need a read-back): it matches no column, its row's own share is zeros and
+ * nothing is written outside y. */
+int mv_mixup_labels_i64(const int64_t* labels, float* y, int64_t batch, int num_classes, double lam, void* stream);
 
 #ifdef __cplusplus
 }
