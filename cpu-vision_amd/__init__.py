@@ -1,11 +1,11 @@
 """mi355vision -- the MI355X (gfx950) implementation of CPU-Vision's image-filtering hot path.
 
 Python host layer (the reference is Python) over the C ABI in include/mi355vision.h:
-  functional      gaussian_blur / adjust_sharpness (+ _image/_video kernels), box / separable / Sobel, conv+ReLU; the one
-                  namespace of the v2 functional surface (re-exports _geometry and _color)
-  _geometry       elastic / affine / rotate / perspective (+ _image/_mask/_video kernels)
-  _color          adjust_brightness / contrast / saturation / hue, rgb_to_grayscale, invert / posterize / solarize /
-                  autocontrast / equalize (+ _image/_video kernels)
+  functional      the one namespace of the functional surface: the module-level switches, and re-exports of
+  _filters        gaussian_blur / adjust_sharpness (+ _image/_video kernels, *_frames), box / separable / Sobel
+  _layers         conv+ReLU, pools, linear, conv_norm_act, inverted_residual (what nn and mobilenet run on)
+  _misc           resize / center_crop / to_dtype / normalize (+ kernels), to_float_normalize
+  _crop, _mix     pad / crop / flip / erase / resized_crop; MixUp / CutMix on a batch
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
   ops             deform_conv2d / DeformConv2d (+ registration behind torch.ops.torchvision.deform_conv2d)

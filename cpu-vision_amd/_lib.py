@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 from pathlib import Path
 from typing import Optional, Sequence
 
@@ -259,6 +260,70 @@ def stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def launch(fn, on: torch.Tensor, *args) -> None:
+    """fn(*args, stream) on `on`'s device and its current stream; a non-zero status raises."""
+    with on_device_of(on):
+        check(fn(*args, stream_ptr(on)))
+
+
+def ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def workspace(nbytes: int, device):
+    """(buffer, pointer, nbytes) of a uint8 device buffer for a *_ws entry point, (None, None, 0) when it needs none.  The
+    caller holds `buffer` until the launch is queued."""
+    if not nbytes:
+        return None, None, 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr(), nbytes
+
+
+def f32_on(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
+    """An optional tensor as a detached contiguous float32 tensor on `device` (a layer's bias, folded norm, residual ...).
+    A tensor that already is one comes back itself: a new tensor object per call is measurable at batch 1."""
+    if t is None or (t.device == device and t.dtype == torch.float32 and t.is_contiguous()):
+        return t
+    return t.detach().to(device, torch.float32).contiguous()
+
+
+def require_f32_layer(name: str, x: torch.Tensor, weight: torch.Tensor) -> None:
+    """The CNN layers compute in float32 only."""
+    if x.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise TypeError(f"{name} computes in float32. Got input {x.dtype}, weight {weight.dtype}")
+
+
+def launch_xy(fn, image: torch.Tensor, args, *, out_shape=None, out_dtype=None, pair: bool = False):
+    """ONE call of fn(x, y, *args, stream) -- the filters, the pools and the preset steps: x the contiguous image, y a fresh
+    output of x's shape and dtype unless `out_shape` / `out_dtype` say otherwise.  pair: fn(x, y0, y1, *args, stream) with two
+    such outputs, returned as a tuple.  The caller has checked its arguments; a device tensor whose pointer is in `args` lives
+    on the image's device, and the caller keeps it alive over this call."""
+    require_device(image)
+    x = image.contiguous()
+    # each case's cheapest binding of the same allocation, as in launch_image_op
+    if out_shape is None and out_dtype is None:
+        y = torch.empty_like(x)
+    else:
+        y = torch.empty(out_shape or x.shape, dtype=out_dtype or x.dtype, device=x.device)
+    if pair:
+        y1 = torch.empty(y.shape, dtype=y.dtype, device=y.device)
+        launch(fn, x, x.data_ptr(), y.data_ptr(), y1.data_ptr(), *args)
+        return y, y1
+    launch(fn, x, x.data_ptr(), y.data_ptr(), *args)
+    return y
+
+
+def launch_frames(fn, frames, args):
+    """ONE call of a mv_*_v entry point, fn(xs, ys, n, *args, stream), over separately allocated, equally shaped frames on one
+    device (host tables of their pointers); returns views of one output batch."""
+    f0 = frames[0]
+    xs = [f.contiguous() for f in frames]
+    out = torch.empty((len(xs),) + tuple(f0.shape), dtype=f0.dtype, device=f0.device)
+    ys = [out[i] for i in range(len(xs))]
+    launch(fn, f0, pointer_table(xs), pointer_table(ys), len(xs), *args)
+    return ys
+
+
 def launch_image_op(name: str, image: torch.Tensor, args, *, out_shape=None, workspace=None, allow_bool: bool = False,
                     what: Optional[str] = None, deps=()) -> torch.Tensor:
     """ONE call of mv_<name>_u8 / mv_<name>_f32 (chosen by the storage type) on a non-empty float32 / uint8 image:
@@ -272,7 +337,9 @@ def launch_image_op(name: str, image: torch.Tensor, args, *, out_shape=None, wor
       what, deps  float32 results are forward-only (forward_only) under the name `what` (default: `name`), computed from
                   the image and `deps`
 
-    The filters and the CNN layers do not come through here: they widen dtypes, return pairs or take pointer tables."""
+    The filters, the pools and the preset steps, which widen other dtypes or return pairs, go through launch_xy, lists of frames
+    through launch_frames; the CNN layers, with several input tensors each, prepare those with f32_on / ptr / workspace and
+    call launch."""
     require_device(image)
     lib = load()
     u8 = image.dtype is torch.uint8
@@ -293,6 +360,13 @@ def launch_image_op(name: str, image: torch.Tensor, args, *, out_shape=None, wor
     if u8:
         return y
     return forward_only(y, what or name, image, *deps)
+
+
+def switch(name: str):
+    """The value, now, of one of the module-level switches of `functional` (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION,
+    CONV2D_*): the one place where they are defined and set.  The modules behind `functional` read them through here at call
+    time -- a `from .functional import X` would freeze the default, and `functional` imports those modules."""
+    return getattr(sys.modules[__package__ + ".functional"], name)
 
 
 def taps(values: Sequence[float]):

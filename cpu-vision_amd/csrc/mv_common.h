@@ -17,15 +17,6 @@
 #else
 namespace mv {
 constexpr const char* tune_env(const char*) { return nullptr; }
-// The v2 colour ops (color.hip; layout and arithmetic in mi355vision.h mv_color_chain_f32).  The entry points have checked
-// the arguments, the workspace size (color_workspace_bytes) and the grid (color_grid_fits).
-int64_t color_workspace_bytes(int64_t images, int h, int w, bool u8);
-bool color_grid_fits(int64_t images, int h, int w, bool u8);
-int launch_color_chain(const void* x, void* y, bool u8, int64_t images, int channels, int h, int w, const int* ops,
-                       const double* factors, int n_ops, int form, void* ws, hipStream_t s);
-int launch_rgb_to_grayscale(const void* x, void* y, bool u8, int64_t images, int h, int w, int out_channels, int form,
-                            hipStream_t s);
-
 }  // namespace mv
 #endif
 

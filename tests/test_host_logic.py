@@ -397,3 +397,61 @@ def test_slice_plans_depend_on_the_batch_and_the_switch_is_exposed():
         assert blk._fused_plan(x1) is None and blk._fused_plan(x256) == (1, 384)
     finally:
         F.BATCH_INVARIANT_SUMMATION = False
+
+
+# every name `functional` had before the filters, the layers and the preset steps moved into _filters / _layers / _misc
+# (imported modules and typing names aside)
+_FUNCTIONAL_NAMES = """
+    BATCH_INVARIANT_SUMMATION CONV2D_COLUMNS_WORKSPACE CONV2D_SMALL_LAUNCH_WORKSPACE INTEGER_BLUR_EXACT_2D
+    INTEGER_BLUR_EXACT_FAST PAD_MODES _ACT_CODES _AFFINE_CODES _BMM_NAIVE_LIMIT _COLOR_OPS _CONV_WORKSPACE_BYTES
+    _DIRECT_2D_MAX_TAPS _ELASTIC_MODES _PIL_INTERPOLATION _POINT_OPS _WARP_KINDS _add_alpha_fuses
+    _adjust_sharpness_image_pil _affine_coeffs _affine_parse_args _assert_grid_transform_inputs _blend_form
+    _blocked_bmm_fuses _blur_with_taps _border _check_color_channels _check_color_factor _check_gaussian_args _color_chain
+    _compute_affine_output_size _compute_dtype _elastic_bounding_boxes_dispatch _elastic_fill _elastic_image_pil
+    _filter_f32_u8 _frames_call _gaussian_blur_image_pil _get_gaussian_kernel1d _get_gaussian_kernel2d
+    _get_inverse_affine_matrix _get_kernel _get_perspective_coeffs _grid_order _host_taps _identity_grid_vectors
+    _interpolation_name _inverted_residual_workspace_bytes _max_value _mean_std _nearest_on_mask _pair_f32
+    _parse_pad_padding _perspective_coefficients _perspective_grid_coeffs _plane_op _planes _pointwise
+    _register_kernel_internal _same_frames _sharpness _taps_dtype _to_dtype_tensor_dispatch _use_separable _warp
+    adaptive_avg_pool2d adjust_brightness adjust_brightness_image adjust_brightness_video adjust_contrast
+    adjust_contrast_image adjust_contrast_video adjust_hue adjust_hue_image adjust_hue_video adjust_saturation
+    adjust_saturation_image adjust_saturation_video adjust_sharpness adjust_sharpness_frames adjust_sharpness_image
+    adjust_sharpness_video affine affine_image affine_mask affine_video annotations autocontrast autocontrast_image
+    autocontrast_video axis_index_map box_filter center_crop center_crop_image color_jitter_image conv1x1_k_slices
+    conv2d_bias_act conv2d_bias_relu conv3x3_k_slices conv_norm_act crop crop_image crop_mask crop_video cutmix_image
+    depthwise_conv2d elastic elastic_image elastic_mask elastic_transform elastic_video equalize equalize_image
+    equalize_video erase erase_image erase_video fold_batchnorm gaussian_blur gaussian_blur_frames gaussian_blur_image
+    gaussian_blur_video gaussian_sobel hflip horizontal_flip horizontal_flip_image horizontal_flip_mask
+    horizontal_flip_video invert invert_image invert_video inverted_residual inverted_residual_k_slices linear_bias_relu
+    linear_k_slices max_pool2d max_pool2d_2x2 mixup_image mixup_labels normalize normalize_image
+    normalized_conv2d_bias_relu pad pad_crop pad_crop_image pad_image pad_mask pad_video perspective perspective_image
+    perspective_mask perspective_video posterize posterize_image posterize_video resize resize_image resize_video
+    resized_crop resized_crop_flip_normalize resized_crop_image resized_crop_video rgb_to_grayscale rgb_to_grayscale_image
+    rotate rotate_image rotate_mask rotate_video separable_gaussian_blur sobel solarize solarize_image solarize_video
+    to_dtype to_dtype_image to_float_normalize vertical_flip vertical_flip_image vertical_flip_mask vertical_flip_video
+    vflip
+""".split()
+
+
+def test_functional_stays_the_one_namespace():
+    """Every recorded name is still reached through `functional`, and a function reached there IS the object its defining module
+    holds (the kernel registry is keyed on function objects); `functional` itself defines switches only."""
+    import sys
+    assert len(_FUNCTIONAL_NAMES) == 180
+    missing = [n for n in _FUNCTIONAL_NAMES if not hasattr(F, n)]
+    assert not missing, missing
+    for n in _FUNCTIONAL_NAMES:
+        obj = getattr(F, n)
+        if not callable(obj):
+            continue
+        assert obj.__module__.startswith(mv.__name__ + ".") and obj.__module__ != F.__name__, (n, obj.__module__)
+        assert getattr(sys.modules[obj.__module__], obj.__name__) is obj, n
+    assert F.gaussian_blur in _registry._KERNEL_REGISTRY and F.normalize in _registry._KERNEL_REGISTRY
+
+
+def test_moved_code_reads_the_switches_from_functional(monkeypatch):
+    """_use_separable lives in _filters and reads INTEGER_BLUR_EXACT_2D where tests and tools set it: on `functional`."""
+    image = torch.zeros((3, 8, 32), dtype=torch.uint8)
+    assert F._use_separable(5, 5, image) is False
+    monkeypatch.setattr(F, "INTEGER_BLUR_EXACT_2D", False)
+    assert F._use_separable(5, 5, image) is True
