@@ -437,7 +437,14 @@ int mv_rgb_to_grayscale_u8(const uint8_t* x, uint8_t* y, int64_t images, int h, 
  * MV_POINT_POSTERIZE, param = bits in [0, 8]: float floor(x * 2^bits) clamped to [0, 2^bits - 1], times 2^-bits (NaN stays
  * NaN); uint8 x & (((1 << bits) - 1) << (8 - bits)).  MV_POINT_SOLARIZE, param = threshold: (float)x >= (float)threshold ?
  * invert(x) : x -- the comparison of a uint8 image against a float threshold, which torch promotes to float32 (a host with an
- * integer threshold passes the uint8 value it wraps to). */
+ * integer threshold passes the uint8 value it wraps to).
+ *
+ * Alignment, for every entry point from the colour ops down to mv_mixup_labels_i64: x and y need the alignment of their
+ * element type only (a contiguous view at any element offset of an allocation is fine); a workspace must be 16-byte
+ * aligned, which the entry points check.  mv_pointwise_* moves 16 bytes per lane when both x and y are 16-byte aligned
+ * (whatever n is: the last partial group goes element by element) and element by element otherwise -- "vec16" / "px" in
+ * mv_last_kernel(); the colour and plane ops additionally need a plane length that is a multiple of 16 / elem_bytes for their
+ * 16-byte path.  Nothing outside x, y and the stated workspace size is read or written. */
 #define MV_POINT_INVERT 0
 #define MV_POINT_POSTERIZE 1
 #define MV_POINT_SOLARIZE 2
@@ -520,7 +527,8 @@ int mv_cutmix(const void* x, void* y, int64_t batch, int64_t planes_per_sample, 
 /* index labels: y (batch, num_classes) float32 = the mixup of one_hot(labels, num_classes).float(), in one launch and with the
  * same three roundings (a row whose neighbour has the same label holds fl(fl(1 - lam) + fl(lam)) there, not a literal 1).  A label
  * outside [0, num_classes) is not reported (that would need a read-back): it matches no column, its row's own share is zeros and
- * nothing is written outside y. */
+ * nothing is written outside y.  labels needs 8-byte and y 4-byte alignment; a 16-byte aligned y is written with 16-byte stores
+ * (k_mixup_labels<vec>), any other element by element (k_mixup_labels<scalar>): the same values. */
 int mv_mixup_labels_i64(const int64_t* labels, float* y, int64_t batch, int num_classes, double lam, void* stream);
 
 #ifdef __cplusplus
