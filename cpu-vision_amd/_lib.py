@@ -112,6 +112,9 @@ SYMBOLS = {
     "mv_mixup_f64": (_i, [_vp, _vp, _i64, _i64, _d, _vp]),
     "mv_cutmix": (_i, [_vp, _vp, _i64, _i64] + [_i] * 7 + [_vp]),
     "mv_mixup_labels_i64": (_i, [_vp, _vp, _i64, _i, _d, _vp]),
+    "mv_nms_workspace_bytes": (_i64, [_i64]),
+    "mv_nms_f32": (_i, [_vp, _vp, _i64, _d, _vp, _vp, _vp, _i64, _vp]),
+    "mv_roi_align_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1026,6 +1026,46 @@ int mv_mixup_labels_i64(const int64_t* labels, float* y, int64_t batch, int num_
   return launch_mixup_labels(labels, y, batch, num_classes, lam, (hipStream_t)stream);
 }
 
+// ---- nms / roi_align: detect.hip -----------------------------------------------------------------------------------------------
+int64_t mv_nms_workspace_bytes(int64_t n) {
+  if (n <= 0 || n > kNmsMaxBoxes) return 0;
+  return nms_workspace_bytes(n);
+}
+
+int mv_nms_f32(const float* boxes, const float* scores, int64_t n, double iou_threshold, int64_t* keep_out, int64_t* keep_count_out,
+               void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "nms: bad box count %lld", (long long)n);
+  if (n == 0) return MV_OK;
+  if (n > kNmsMaxBoxes) return set_error(MV_ERR_UNSUPPORTED, "nms: up to %d boxes per call, got %lld", kNmsMaxBoxes, (long long)n);
+  if (!boxes || !scores || !keep_out || !keep_count_out) return set_error(MV_ERR_INVALID_ARGUMENT, "nms: null pointer");
+  if ((uintptr_t)keep_out % 8 || (uintptr_t)keep_count_out % 8)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "nms: keep_out and keep_count_out must be 8-byte aligned");
+  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "nms: needs a workspace");
+  if (workspace_bytes < nms_workspace_bytes(n))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "nms: workspace of %lld bytes, need %lld (mv_nms_workspace_bytes)", (long long)workspace_bytes,
+                     (long long)nms_workspace_bytes(n));
+  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "nms: the workspace must be 16-byte aligned");
+  return launch_nms(boxes, scores, (int)n, iou_threshold, keep_out, keep_count_out, workspace, (hipStream_t)stream);
+}
+
+int mv_roi_align_f32(const float* x, const float* rois, float* y, int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
+                     double spatial_scale, int sampling_ratio, int aligned, void* stream) {
+  if (n < 0 || c < 0 || h < 0 || w < 0 || k < 0 || pooled_h < 0 || pooled_w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_align: bad shape n=%lld c=%d (%d, %d), k=%lld, output (%d, %d)", (long long)n, c, h, w,
+                     (long long)k, pooled_h, pooled_w);
+  if (k == 0 || c == 0 || pooled_h == 0 || pooled_w == 0) return MV_OK;
+  if (n > 0 && (h == 0 || w == 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_align: empty (%d, %d) feature map", h, w);
+  if (n > 0x7fffffffLL || (int64_t)h * w > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "roi_align: %lld images of %d x %d exceed the 32-bit plane index", (long long)n, h, w);
+  if (k > ((0x7fffffffLL * 256) / c) / pooled_h / pooled_w)
+    return set_error(MV_ERR_UNSUPPORTED, "roi_align: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid", (long long)k, c,
+                     pooled_h, pooled_w);
+  if (!rois || !y || (n > 0 && !x)) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_align: null pointer");
+  if (x == y || rois == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  return launch_roi_align(x, rois, y, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, sampling_ratio, aligned ? 1 : 0,
+                          (hipStream_t)stream);
+}
+
 static int elastic(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int wdt, const float* base_x,
                    const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
                    const float* fill, void* stream) {

@@ -301,6 +301,15 @@ int launch_cutmix(const void* x, void* y, int64_t batch, int64_t elems, int elem
                   hipStream_t s);
 int launch_mixup_labels(const int64_t* labels, float* y, int64_t batch, int classes, double lam, hipStream_t s);
 
+// ops.nms / ops.roi_align (detect.hip; semantics in mi355vision.h mv_nms_f32, mv_roi_align_f32).  The entry points have checked
+// the arguments, the workspace (nms_workspace_bytes, 16-byte aligned) and the grids; n and k are positive here.
+constexpr int kNmsMaxBoxes = 64 * 4096;  // the reduce phase keeps one bit per box in LDS (32 KiB at this size)
+int64_t nms_workspace_bytes(int64_t n);
+int launch_nms(const float* boxes, const float* scores, int n, double iou_threshold, int64_t* keep, int64_t* keep_count, void* workspace,
+               hipStream_t s);
+int launch_roi_align(const float* x, const float* rois, float* y, int n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
+                     float spatial_scale, int sampling_ratio, int aligned, hipStream_t s);
+
 // F.elastic: grid_sample of every plane at identity grid + displacement (elastic.hip).  base_x / base_y: the reference's
 // linspace vectors (W and H floats, device); disp (1, H, W, 2) fp32 by strides; mode 0 bilinear, 1 nearest; fill: NULL or
 // `channels` host floats (plane p takes fill[p % channels]).

@@ -531,6 +531,34 @@ int mv_cutmix(const void* x, void* y, int64_t batch, int64_t planes_per_sample, 
  * (k_mixup_labels<vec>), any other element by element (k_mixup_labels<scalar>): the same values. */
 int mv_mixup_labels_i64(const int64_t* labels, float* y, int64_t batch, int num_classes, double lam, void* stream);
 
+/* ---- torchvision.ops.nms (forward), the arithmetic of the reference's CPU kernel.  boxes (n, 4) float32 as x1, y1, x2, y2 and
+ * scores (n) float32, both DEVICE arrays that need 4-byte alignment only; n <= 262144.  The boxes are taken in descending score
+ * order, equal scores in index order (the stable sort of the reference; -0 == +0, a NaN score ranks first as in torch.sort), and a
+ * box j is dropped when a box i kept before it has  inter / ((area_i + area_j) - inter) > iou_threshold  with
+ * area = (x2 - x1) * (y2 - y1), inter = max(0, min(x2) - max(x1)) * max(0, min(y2) - max(y1)): every operation rounded once to
+ * float32, the division correctly rounded, the quotient compared with the threshold as a double.  keep_out (n int64, DEVICE)
+ * receives the kept indices in that order -- only its first *keep_count_out (one int64, DEVICE) elements are written.  Three
+ * launches (order, 64 x 64 suppression-mask tiles on and above the diagonal, one workgroup that walks the mask rows with the
+ * "removed" bitset in LDS); nothing is read back and nothing is allocated: the sorted boxes, the order and the mask words live in
+ * `workspace`, a 16-byte aligned DEVICE buffer of mv_nms_workspace_bytes(n) bytes (16 n + 8 n ceil(n / 64) + 4 n, rounded up to
+ * 16; 0 for n <= 0 or an unsupported n) with any content.  n == 0 is a no-op: nothing is launched and not even the count is
+ * written. */
+int64_t mv_nms_workspace_bytes(int64_t n);
+int mv_nms_f32(const float* boxes, const float* scores, int64_t n, double iou_threshold, int64_t* keep_out, int64_t* keep_count_out,
+               void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- torchvision.ops.roi_align (forward), the arithmetic of the reference's CPU kernel.  x (n, c, h, w) float32, rois (k, 5)
+ * float32 rows [batch_idx, x1, y1, x2, y2], y (k, c, pooled_h, pooled_w) float32; h * w < 2^31.  Per roi: the corners times
+ * (float)spatial_scale minus 0.5 when `aligned`; without `aligned` the roi's width and height are clamped to at least 1; bin =
+ * size / pooled; grid = sampling_ratio when positive, else ceil(size / pooled) per axis.  Output (ph, pw) is the sum over the
+ * grid_h x grid_w samples at  start + p * bin + (i + 0.5) * bin / grid  (ascending iy, then ix) of the bilinear value
+ * ((w1 v1 + w2 v2) + w3 v3) + w4 v4, divided by max(grid_h * grid_w, 1).  A sample outside [-1, h] x [-1, w] adds zero; inside,
+ * coordinates below 0 clamp to 0 and the last row / column has no upper neighbour (bilinear_interpolate of the reference).
+ * Every product, sum and quotient is rounded once to float32 -- nothing is fused.  One lane per output element, one launch, no
+ * workspace.  rois stay on the device and are not read back, so a batch index that does not truncate into [0, n) cannot be
+ * reported: that roi's outputs are zeros and x is not read for it.  k == 0 (or an empty output) is a no-op. */
+int mv_roi_align_f32(const float* x, const float* rois, float* y, int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
+                     double spatial_scale, int sampling_ratio, int aligned, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""ops.nms and ops.roi_align on one MI355X: time per call (HIP events, median of 7 rounds of `--iters` back-to-back calls after a
+warm-up, the two sides of a comparison alternating round by round) against the same op on the same GPU -- torchvision's own
+when that package is importable, otherwise a restatement in torch ops:
+
+  nms        sort + the (n, n) IoU matrix + the greedy walk over its rows as a host loop that reads each decision back -- what a
+             user without a native kernel writes.  The walk costs a host round trip per kept box, so its time is mostly that.
+  roi_align  the reference's own pure-torch formulation (ops/roi_align.py _roi_align: masked gathers over a (K, C, PH, PW, IY, IX)
+             index space) for a fixed sampling_ratio.
+
+  python tools/perf_detect.py [--iters 5]
+
+Cases: nms at 1 000 / 4 000 / 20 000 clustered boxes (threshold 0.5); roi_align at 1 000 rois x 256
+channels x 7 x 7 on a 2 x 256 x 200 x 304 map (spatial_scale 0.25, sampling_ratio 2, aligned), with the bytes it must move
+(the output once; the map's touched part at most once) against the 8 TB/s HBM peak."""
+import argparse
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import torch  # noqa: E402
+
+from cpu_vision_amd import _lib, ops  # noqa: E402
+
+try:
+    import torchvision.ops as tv_ops
+except Exception:
+    tv_ops = None
+
+PEAK_TBS = 8.0
+
+
+def alternate(fns, iters, rounds=7):
+    """Median ms per call of each fn, the fns taking turns round by round."""
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[k].append(e0.elapsed_time(e1) / iters)
+    return [sorted(t)[len(t) // 2] for t in ts]
+
+
+def boxes(n, seed=0):
+    """Clusters of jittered boxes, 8 per centre on average, as a detector's raw output has them."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    centres = torch.rand((n // 8 + 1, 2), device="cuda", generator=g) * 1000
+    c = centres[torch.randint(0, n // 8 + 1, (n,), device="cuda", generator=g)] + torch.randn((n, 2), device="cuda", generator=g) * 4
+    wh = 20 + torch.rand((n, 2), device="cuda", generator=g) * 30
+    return torch.cat([c - wh / 2, c + wh / 2], 1).contiguous(), torch.rand(n, device="cuda", generator=g)
+
+
+def torch_nms(b, s, thr):
+    order = torch.sort(s, stable=True, descending=True).indices
+    b = b[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    lt, rb = torch.max(b[:, None, :2], b[None, :, :2]), torch.min(b[:, None, 2:], b[None, :, 2:])
+    wh = (rb - lt).clamp(min=0)
+    inter = wh[..., 0] * wh[..., 1]
+    over = (inter / (area[:, None] + area[None, :] - inter) > thr).triu(1)
+    removed = torch.zeros(len(b), dtype=torch.bool, device=b.device)
+    keep = []
+    for i in range(len(b)):
+        if not removed[i]:  # one read-back per box
+            keep.append(i)
+            removed |= over[i]
+    return order[torch.tensor(keep, device=b.device)]
+
+
+def torch_roi_align(x, rois, scale, ph_n, pw_n, ratio, aligned):
+    """ops/roi_align.py _roi_align for ratio > 0, in torch ops on the device."""
+    _, c, h, w = x.shape
+    off = 0.5 if aligned else 0.0
+    idx = rois[:, 0].long()
+    sw, sh, ew, eh = (rois[:, i] * scale - off for i in (1, 2, 3, 4))
+    rw, rh = ew - sw, eh - sh
+    if not aligned:
+        rw, rh = rw.clamp(min=1.0), rh.clamp(min=1.0)
+    bh, bw = rh / ph_n, rw / pw_n
+    ar = lambda n: torch.arange(n, device=x.device, dtype=x.dtype)  # noqa: E731
+    y = sh[:, None, None] + ar(ph_n)[None, :, None] * bh[:, None, None] + (ar(ratio)[None, None, :] + 0.5) * (bh[:, None, None] / ratio)
+    xs = sw[:, None, None] + ar(pw_n)[None, :, None] * bw[:, None, None] + (ar(ratio)[None, None, :] + 0.5) * (bw[:, None, None] / ratio)
+
+    def axis(v, size):
+        outside = (v < -1.0) | (v > size)
+        v = v.clamp(min=0)
+        lo = v.long().clamp(max=size - 1)
+        hi = (lo + 1).clamp(max=size - 1)
+        v = torch.where(lo >= size - 1, lo.to(v.dtype), v)
+        frac = v - lo
+        return lo, hi, frac, 1 - frac, outside
+
+    yl, yh, ly, hy, yo = axis(y, h)  # (K, PH, IY)
+    xl, xh, lx, hx, xo = axis(xs, w)  # (K, PW, IX)
+
+    def tap(yi, xi):  # (K, C, PH, PW, IY, IX)
+        return x[idx[:, None, None, None, None, None], ar(c).long()[None, :, None, None, None, None], yi[:, None, :, None, :, None],
+                 xi[:, None, None, :, None, :]]
+
+    def wgt(a, b):
+        return a[:, None, :, None, :, None] * b[:, None, None, :, None, :]
+
+    val = wgt(hy, hx) * tap(yl, xl) + wgt(hy, lx) * tap(yl, xh) + wgt(ly, hx) * tap(yh, xl) + wgt(ly, lx) * tap(yh, xh)
+    val = val.masked_fill(yo[:, None, :, None, :, None] | xo[:, None, None, :, None, :], 0)
+    return val.sum((-1, -2)) / (ratio * ratio)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    args = ap.parse_args()
+    it = args.iters
+    print(f"baseline: {'torchvision.ops on the GPU' if tv_ops is not None else 'torch-op restatements (no torchvision on this machine)'}")
+    for n in (1000, 4000, 20000):
+        b, s = boxes(n)
+        ours = lambda: ops.nms(b, s, 0.5)  # noqa: E731
+        if tv_ops is not None:
+            ref, ref_name = (lambda: tv_ops.nms(b, s, 0.5)), "torchvision.ops.nms"
+        else:
+            ref, ref_name = (lambda: torch_nms(b, s, 0.5)), "torch: sort + IoU matrix + host walk"
+        kept = ours()
+        same = kept.tolist() == ref().tolist()
+        if n > 4000 and tv_ops is None:  # the host walk takes seconds at this size: one call, not a series
+            ms = alternate([ours], it)[0]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ref()
+            e1.record()
+            torch.cuda.synchronize()
+            ms_ref = e0.elapsed_time(e1)
+        else:
+            ms, ms_ref = alternate([ours, ref], it)
+        print(f"nms n={n:6d} thr=0.5 kept={len(kept):6d}  {ms:9.4f} ms   {ref_name}: {ms_ref:10.4f} ms -> {ms_ref / ms:.1f}x   "
+              f"same indices: {same}   {_lib.last_kernel()}", flush=True)
+
+    x = torch.rand((2, 256, 200, 304), device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(1)
+    p = torch.rand((1000, 2), device="cuda", generator=g) * torch.tensor([1216.0 - 64, 800.0 - 64], device="cuda")
+    wh = 32 + torch.rand((1000, 2), device="cuda", generator=g) * 300
+    rois = torch.cat([torch.randint(0, 2, (1000, 1), device="cuda", generator=g).float(), p, p + wh], 1)
+    ours = lambda: ops.roi_align(x, rois, 7, 0.25, 2, True)  # noqa: E731
+    if tv_ops is not None:
+        ref, ref_name = (lambda: tv_ops.roi_align(x, rois, 7, 0.25, 2, True)), "torchvision.ops.roi_align"
+    else:
+        ref, ref_name = (lambda: torch_roi_align(x, rois, 0.25, 7, 7, 2, True)), "torch: the reference's _roi_align in torch ops"
+    err = (ours() - ref()).abs().max().item()
+    ms, ms_ref = alternate([ours, ref], it)
+    out_bytes = 1000 * 256 * 49 * 4
+    taps = 1000 * 256 * 49 * 4 * 4 * 4  # every tap as its own 4-byte read: what the lanes request (mostly from L2)
+    print(f"roi_align 1000 rois x 256 ch x 7x7 on 2x256x200x304  {ms:9.4f} ms   output {out_bytes / 1e6:.1f} MB = "
+          f"{out_bytes / (ms * 1e-3) / 1e12:.3f} TB/s ({out_bytes / (ms * 1e-3) / 1e12 / PEAK_TBS * 100:.1f} % of 8 TB/s), tap requests "
+          f"{taps / 1e9:.2f} GB = {taps / (ms * 1e-3) / 1e12:.2f} TB/s   {_lib.last_kernel()}")
+    print(f"  {ref_name}: {ms_ref:9.4f} ms -> {ms_ref / ms:.1f}x   max |difference| {err:.2e}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
