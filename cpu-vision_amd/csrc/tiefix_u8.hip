@@ -244,9 +244,9 @@ int launch_gaussian_blur_u8_hybrid(const uint8_t* x, uint8_t* y, int64_t planes,
                                    const float* k1d_y, int ky, void* workspace, int64_t workspace_bytes, hipStream_t s) {
   const int npx = hybrid_npx(kx, ky);
   int64_t cap = (workspace_bytes - (int64_t)offsetof(TieList, idx)) / 8;
-  if (workspace == nullptr || cap < 1 || (uintptr_t)workspace % 8)
+  if (workspace == nullptr || cap < 1 || (uintptr_t)workspace % 16)
     return set_error(MV_ERR_INVALID_ARGUMENT, "gaussian_blur_u8 (exact, separable cost): workspace of mv_gaussian_blur_u8_workspace_bytes() "
-                     "bytes, 8-byte aligned, needed (got %lld bytes)", (long long)workspace_bytes);
+                     "bytes, 16-byte aligned, needed (got %lld bytes)", (long long)workspace_bytes);
   const int64_t want = tie_capacity(planes, h, w, npx);
   if (const char* e = tune_env("MV_U8_TIE_CAP")) cap = atoll(e) > 0 ? atoll(e) : cap;  // tests: force the overflow path
   else if (cap > want) cap = want;

@@ -26,6 +26,13 @@
  *     for the calling thread.  Nothing throws or aborts across this boundary.
  *   - re-entrant; no global mutable state besides the thread-local error / last-kernel strings, and no
  *     environment lookups: kernel selection depends on the arguments alone.
+ *   - alignment, filter entry points (everything from mv_depthwise_conv2d_f32 down to the *_v entries): x, y / gx / gy, every
+ *     frame of a *_v list and a device tap array need the alignment of their element type only (a contiguous view at any
+ *     element offset of an allocation is fine); the workspace of mv_gaussian_blur_u8_ws must be 16-byte aligned
+ *     (MV_ERR_INVALID_ARGUMENT otherwise), its content on entry does not matter.  Every output is written whole; nothing outside the outputs and the stated workspace size is
+ *     written, and no value from outside an input reaches a result.  Alignment buys speed only: with W % 4 == 0 and x and y
+ *     aligned to 4 pixels (16 bytes float32, 8 half types, 4 uint8) the 4-pixel kernels take their vector instantiation
+ *     ("vec16" in mv_last_kernel()), and mv_separable_blur_f32 / mv_gaussian_sobel_f32 take k_sepfast only on 16-byte pointers.
  *   - numerics: fp32 taps and accumulation, one fused multiply-add chain per output in
  *     row-major tap order starting from +0 (bit-identical to oracle/oracle.c); uint8 paths
  *     convert to fp32, accumulate, round half-to-even (torch.round_) and narrow.
