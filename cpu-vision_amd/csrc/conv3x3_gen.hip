@@ -184,7 +184,8 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
   // ---- chunk staging, split in two halves so that the NEXT chunk's global loads are in flight while the current
   //      chunk's MFMAs run: gload(ch) -> registers, lstore(buf) -> LDS (fragment order / zero-padded rows).
   //      Every per-thread index (source offset, LDS destination, validity) is chunk-invariant and computed once here:
-  //      the loop itself contains no integer division.  LDS is double-buffered: one barrier per chunk.
+  //      the loop itself contains no integer division -- except on the element-wise weight path (cin % 4 != 0 or a w that is
+  //      not 16-byte aligned), which recomputes an item's 4 q by a division by a constant.  LDS is double-buffered: one barrier per chunk.
   constexpr int XP = kXP;   // float4 of input per thread held in registers (maps up to ~120 wide; wider: direct staging)
   constexpr int WQ = kCK * 9 / 4;                 // float4 per channel row of a weight chunk (9)
   constexpr int WU = (kBM * WQ + 255) / 256;      // float4 of weights per thread (5 for 128 channels)
@@ -301,7 +302,11 @@ __global__ __launch_bounds__(SPEC ? 512 : 256, (SPEC && MT * PT >= 8) ? 1 : 2) v
       } else if (wsrc[u] >= 0) {
         const float* src = A.w + wsrc[u] + kbase;
         {
-          const int kq = (int)(wsrc[u] % Kreal) + kbase;  // tap index of element 0 (slow path: cin % 4 != 0)
+          // tap index of element 0 (slow path: cin % 4 != 0 or an unaligned w): 4 * q of the item, recomputed here -- not
+          // wsrc % Kreal, which wraps for cin < 4 (Kreal < 36: items 4q >= Kreal looked valid and read the next row's taps,
+          // past the end of w for the last row)
+          const int idx = tid + 256 * u;
+          const int kq = 4 * (A.colfast ? idx / kBM : idx % WQ) + kbase;
           if (kq + 0 < Kreal) v.x = src[0];
           if (kq + 1 < Kreal) v.y = src[1];
           if (kq + 2 < Kreal) v.z = src[2];

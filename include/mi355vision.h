@@ -33,6 +33,26 @@
  *     written, and no value from outside an input reaches a result.  Alignment buys speed only: with W % 4 == 0 and x and y
  *     aligned to 4 pixels (16 bytes float32, 8 half types, 4 uint8) the 4-pixel kernels take their vector instantiation
  *     ("vec16" in mv_last_kernel()), and mv_separable_blur_f32 / mv_gaussian_sobel_f32 take k_sepfast only on 16-byte pointers.
+ *   - alignment, CNN layer entry points (mv_conv3x3_bias_relu_*, mv_linear_bias_relu_*, the pools, mv_conv_norm_act_f32,
+ *     mv_conv2d_bias_act_f32, mv_deform_conv2d_f32): every tensor -- x, weights, bias, alpha, beta, residual, offset, mask, y --
+ *     needs the alignment of its element type only, and a workspace 4 bytes (mv_linear_bias_relu_ws_f32 checks it:
+ *     MV_ERR_INVALID_ARGUMENT otherwise); a workspace's content on entry does not matter.  Every output is written whole, nothing
+ *     outside y and the stated workspace size is written, and no value from outside an input reaches a result.  Alignment buys
+ *     speed only -- each launcher tests its pointers once per launch and takes 16-byte loads / stores where the pointer is
+ *     16-byte aligned and the shape keeps every row so (k % 4, cin % 4, h * w % 4, w % 4 or w % 8 == 0), the same kernel element
+ *     by element otherwise, with the same bits -- except where another KERNEL is chosen:
+ *       mv_conv3x3_bias_relu_f32 / _ws_f32, cin == 3: the first-layer kernel (k_conv3x3_c3) needs w % 4 == 0 and a 16-byte y;
+ *         otherwise the general kernel runs (same bits);
+ *       mv_conv3x3_bias_relu_u8norm_f32: has no other kernel -- w % 4 != 0 or a y that is not 16-byte aligned returns
+ *         MV_ERR_UNSUPPORTED and writes nothing (x, uint8, may start at any byte);
+ *       mv_linear_bias_relu_*: the batch <= 4 kernel (k_linear_gemv) needs k % 4 == 0 and 16-byte x and w, else k_linear runs;
+ *       mv_conv_norm_act_f32, MV_CONV_DW3X3 on 7 / 14 / 28-pixel-wide maps: k_dwpc3x3_small needs a 16-byte x, else k_dwpc3x3 runs.
+ *     mv_inverted_residual_f32 is the one layer with a 16-byte requirement: x, y, w_expand, w_project and the workspace
+ *     (MV_ERR_INVALID_ARGUMENT, "inverted_residual: x, y, the 1x1 weights and the workspace must be 16-byte aligned", nothing
+ *     written); w_dw and the six norm vectors need 4 bytes.  The columns workspace of mv_conv2d_bias_act_f32 and
+ *     mv_deform_conv2d_f32 needs 4 bytes and may hold one image's columns or more (one pass per as many images as fit); a
+ *     mv_deform_conv2d_f32 geometry without a fused kernel called with no or too small a workspace returns
+ *     MV_ERR_INVALID_ARGUMENT ("... workspace of at least N bytes ...") and writes nothing.
  *   - numerics: fp32 taps and accumulation, one fused multiply-add chain per output in
  *     row-major tap order starting from +0 (bit-identical to oracle/oracle.c); uint8 paths
  *     convert to fp32, accumulate, round half-to-even (torch.round_) and narrow.

@@ -8,7 +8,8 @@ A helper module, not a conftest and without fixtures; it works on any device (te
   assert_guards_intact(buf, view, sentinel, what)                     nothing outside the view changed
   assert_unchanged(buf, before, what)                                  an input buffer still holds the bits of `before`
   assert_same(got, want, what)                                         the NaN-aware equality of test_gpu_autoaug._same
-  guarded_workspace(nbytes, device, fill)                              exactly nbytes bytes, 256-byte aligned, guarded
+  guarded_workspace(nbytes, device, fill, offset_bytes=0)              exactly nbytes bytes, offset_bytes past a 256-byte
+                                                                       boundary, guarded
 
 A sentinel is a scalar or a 1-D pattern that is repeated over the guard (index 0 of the pattern at element 0 of the buffer).
 Output views are pre-filled with the sentinel too: equality with the reference then proves that every element was written.
@@ -118,13 +119,13 @@ def assert_same(got, want, what=""):
                              f"{got.reshape(-1)[first].item()!r}, want {want.reshape(-1)[first].item()!r}")
 
 
-def guarded_workspace(nbytes, device, fill=0xFF, guard_bytes=GUARD_ELEMS):
-    """-> (buf, ws): a workspace of exactly `nbytes` bytes holding `fill`, at a 256-byte aligned position of a byte buffer
-    whose guards hold the 1-byte sentinel; (None, None) when nbytes == 0."""
+def guarded_workspace(nbytes, device, fill=0xFF, guard_bytes=GUARD_ELEMS, offset_bytes=0):
+    """-> (buf, ws): a workspace of exactly `nbytes` bytes holding `fill`, `offset_bytes` (< 256; 0: 256-byte aligned) past a
+    256-byte aligned position of a byte buffer whose guards hold the 1-byte sentinel; (None, None) when nbytes == 0."""
     if not nbytes:
         return None, None
-    assert guard_bytes % 256 == 0
-    buf, ws = guarded((int(nbytes),), torch.uint8, device, 0, guard_elems=guard_bytes)
-    assert buf.device.type == "cpu" or ws.data_ptr() % 256 == 0
+    assert guard_bytes % 256 == 0 and 0 <= offset_bytes < 256
+    buf, ws = guarded((int(nbytes),), torch.uint8, device, offset_bytes, guard_elems=guard_bytes)
+    assert buf.device.type == "cpu" or ws.data_ptr() % 256 == offset_bytes
     ws.fill_(fill)
     return buf, ws

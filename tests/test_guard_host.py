@@ -142,3 +142,17 @@ def test_guarded_workspace():
     buf[G.GUARD_ELEMS + 48] = 0
     with pytest.raises(AssertionError, match="workspace: 1 guard element"):
         G.assert_guards_intact(buf, ws, what="workspace")
+
+
+def test_guarded_workspace_at_a_byte_offset():
+    """offset_bytes moves the workspace off its 256-byte boundary: still exactly nbytes bytes of `fill`, and the bytes between
+    the boundary and the workspace are guard bytes like the rest."""
+    buf, ws = G.guarded_workspace(40, "cpu", fill=0x00, offset_bytes=4)
+    assert ws.numel() == 40 and bool((ws == 0).all())
+    assert ws.storage_offset() - buf.storage_offset() == G.GUARD_ELEMS + 4 and buf.numel() == 2 * G.GUARD_ELEMS + 4 + 40
+    G.assert_guards_intact(buf, ws, what="workspace")
+    buf[G.GUARD_ELEMS + 3] = 0
+    with pytest.raises(AssertionError, match=r"workspace: 1 guard element\(s\) changed, the first at index -1 "):
+        G.assert_guards_intact(buf, ws, what="workspace")
+    with pytest.raises(AssertionError):
+        G.guarded_workspace(8, "cpu", offset_bytes=256)
