@@ -8,7 +8,8 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   _crop, _mix     pad / crop / flip / erase / resized_crop; MixUp / CutMix on a batch
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
-  ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign (+ registration behind torch.ops.torchvision.*)
+  ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
+                  ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*)
   graphs          HIP-graph capture of a whole forward (batch-1 latency)
   presets         ImageClassification (resize -> center_crop -> float -> normalize in one call)
   transforms      GaussianBlur, RandomAdjustSharpness, GaussianBlurV1, the geometric and colour v2 transforms

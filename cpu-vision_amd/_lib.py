@@ -115,6 +115,9 @@ SYMBOLS = {
     "mv_nms_workspace_bytes": (_i64, [_i64]),
     "mv_nms_f32": (_i, [_vp, _vp, _i64, _d, _vp, _vp, _vp, _i64, _vp]),
     "mv_roi_align_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _i, _i, _vp]),
+    "mv_roi_pool_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _vp]),
+    "mv_ps_roi_pool_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _vp]),
+    "mv_ps_roi_align_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

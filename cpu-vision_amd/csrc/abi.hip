@@ -1066,6 +1066,52 @@ int mv_roi_align_f32(const float* x, const float* rois, float* y, int64_t n, int
                           (hipStream_t)stream);
 }
 
+// ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------
+// The checks the three entry points share, in the order of mv_roi_align_f32: 0 launch, 1 nothing to do, < 0 the error.
+static int roi_pool_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, const int* second,
+                          int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w) {
+  if (n < 0 || c < 0 || h < 0 || w < 0 || k < 0 || pooled_h < 0 || pooled_w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld c=%d (%d, %d), k=%lld, output (%d, %d)", op, (long long)n, c, h, w,
+                     (long long)k, pooled_h, pooled_w);
+  if (k == 0 || c == 0 || pooled_h == 0 || pooled_w == 0) return 1;
+  if (position_sensitive && c % ((int64_t)pooled_h * pooled_w))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: input channels must be a multiple of pooling height * pooling width, got %d for (%d, %d)",
+                     op, c, pooled_h, pooled_w);
+  if (n > 0 && (h == 0 || w == 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: empty (%d, %d) feature map", op, h, w);
+  if (n > 0x7fffffffLL || (int64_t)h * w > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images of %d x %d exceed the 32-bit plane index", op, (long long)n, h, w);
+  const int c_out = position_sensitive ? c / (pooled_h * pooled_w) : c;
+  if (k > ((0x7fffffffLL * 256) / c_out) / pooled_h / pooled_w)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid", op, (long long)k, c_out,
+                     pooled_h, pooled_w);
+  if (!rois || !y || !second || (n > 0 && !x)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  if (x == y || rois == y || (const void*)x == (const void*)second || (const void*)rois == (const void*)second ||
+      (const void*)y == (const void*)second)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input or the other output");
+  return 0;
+}
+
+int mv_roi_pool_f32(const float* x, const float* rois, float* y, int* argmax, int64_t n, int c, int h, int w, int64_t k, int pooled_h,
+                    int pooled_w, double spatial_scale, void* stream) {
+  if (int rc = roi_pool_check("roi_pool", false, x, rois, y, argmax, n, c, h, w, k, pooled_h, pooled_w)) return rc < 0 ? rc : MV_OK;
+  return launch_roi_pool(x, rois, y, argmax, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, (hipStream_t)stream);
+}
+
+int mv_ps_roi_pool_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
+                       int pooled_h, int pooled_w, double spatial_scale, void* stream) {
+  if (int rc = roi_pool_check("ps_roi_pool", true, x, rois, y, channel_mapping, n, c, h, w, k, pooled_h, pooled_w))
+    return rc < 0 ? rc : MV_OK;
+  return launch_ps_roi_pool(x, rois, y, channel_mapping, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, (hipStream_t)stream);
+}
+
+int mv_ps_roi_align_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
+                        int pooled_h, int pooled_w, double spatial_scale, int sampling_ratio, void* stream) {
+  if (int rc = roi_pool_check("ps_roi_align", true, x, rois, y, channel_mapping, n, c, h, w, k, pooled_h, pooled_w))
+    return rc < 0 ? rc : MV_OK;
+  return launch_ps_roi_align(x, rois, y, channel_mapping, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, sampling_ratio,
+                             (hipStream_t)stream);
+}
+
 static int elastic(const void* x, void* y, bool u8, int64_t planes, int channels, int h, int wdt, const float* base_x,
                    const float* base_y, const float* disp, int64_t disp_sh, int64_t disp_sw, int64_t disp_sc, int mode,
                    const float* fill, void* stream) {

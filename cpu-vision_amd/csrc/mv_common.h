@@ -309,6 +309,14 @@ int launch_nms(const float* boxes, const float* scores, int n, double iou_thresh
                hipStream_t s);
 int launch_roi_align(const float* x, const float* rois, float* y, int n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
                      float spatial_scale, int sampling_ratio, int aligned, hipStream_t s);
+// ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
+// launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
+int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,
+                    int pooled_w, float spatial_scale, hipStream_t s);
+int launch_ps_roi_pool(const float* x, const float* rois, float* y, int* channel_mapping, int n, int c, int h, int w, int64_t k,
+                       int pooled_h, int pooled_w, float spatial_scale, hipStream_t s);
+int launch_ps_roi_align(const float* x, const float* rois, float* y, int* channel_mapping, int n, int c, int h, int w, int64_t k,
+                        int pooled_h, int pooled_w, float spatial_scale, int sampling_ratio, hipStream_t s);
 
 // F.elastic: grid_sample of every plane at identity grid + displacement (elastic.hip).  base_x / base_y: the reference's
 // linspace vectors (W and H floats, device); disp (1, H, W, 2) fp32 by strides; mode 0 bilinear, 1 nearest; fill: NULL or

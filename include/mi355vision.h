@@ -585,6 +585,48 @@ int mv_nms_f32(const float* boxes, const float* scores, int64_t n, double iou_th
  * reported: that roi's outputs are zeros and x is not read for it.  k == 0 (or an empty output) is a no-op. */
 int mv_roi_align_f32(const float* x, const float* rois, float* y, int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
                      double spatial_scale, int sampling_ratio, int aligned, void* stream);
+/* ---- torchvision.ops.roi_pool, ps_roi_pool and ps_roi_align (forward), the arithmetic of the reference's CPU kernels.  x (n, c, h,
+ * w) float32, rois (k, 5) float32 rows [batch_idx, x1, y1, x2, y2], h * w < 2^31, as for mv_roi_align_f32.  Each op writes two
+ * outputs of one shape, y float32 and a second one of 32-bit ints (`int` is 32 bits on every supported target), which must not be
+ * NULL and must not overlap y or an input.  Every float product, sum, difference and quotient is rounded once to float32 --
+ * nothing is fused.  One lane per output element, one launch, no workspace.  A roi whose batch index does not truncate into
+ * [0, n) (or is NaN) cannot be reported without a read-back: its elements of y are 0, those of the second output -1 (roi_pool) or
+ * the input channel (the position-sensitive ops, where it does not depend on data), and x is not read for it.  k == 0, c == 0 or
+ * a zero output side is a no-op.
+ *
+ * Rounded corners (roi_pool, ps_roi_pool): start_w = (int)roundf(x1 * (float)spatial_scale), roundf half away from zero, and
+ * likewise start_h (y1), end_w (x2), end_h (y2).  The rounded float is clamped to +-2^29 and a NaN becomes 0 before the
+ * conversion: inside that range this is the reference; outside it the reference's conversion is undefined.
+ *
+ * mv_roi_pool_f32: y and argmax are (k, c, pooled_h, pooled_w).  roi_w = max(end_w - start_w + 1, 1), roi_h likewise; bin =
+ * (float)roi / (float)pooled; bin (ph, pw) covers rows [floor(ph * bin_h) + start_h, ceil((ph + 1) * bin_h) + start_h) and the
+ * columns likewise, each bound clamped to [0, h] resp. [0, w].  y is the window's maximum, found with a strict `>` from -FLT_MAX in
+ * row-major order (the first of equal values wins, a NaN is never taken), argmax its index hh * w + ww in the plane; an empty
+ * window gives 0 and -1, a window of NaNs -FLT_MAX and -1.
+ *
+ * mv_ps_roi_pool_f32: c must be a multiple of pooled_h * pooled_w (MV_ERR_INVALID_ARGUMENT otherwise); y and channel_mapping are
+ * (k, c / (pooled_h * pooled_w), pooled_h, pooled_w).  roi_w = max(end_w - start_w, 1) (no + 1), roi_h likewise; rows
+ * [floor(ph * bin_h + (float)start_h), ceil((ph + 1) * bin_h + (float)start_h)), columns likewise, clamped as above.  Output
+ * (c_out, ph, pw) reads input channel c_in = (c_out * pooled_h + ph) * pooled_w + pw: y is the sum of the window (rows ascending,
+ * columns ascending, from 0) divided by its element count, 0 for an empty window; channel_mapping is c_in.
+ *
+ * mv_ps_roi_align_f32: shapes and channel mapping of mv_ps_roi_pool_f32.  The corners are x * (float)spatial_scale - 0.5 (the
+ * half-pixel shift is always applied; there is no `aligned` flag) and the roi's size is NOT clamped to 1.  bin = size / pooled;
+ * grid = sampling_ratio when positive, else (int)ceil(size / pooled) per axis.  y is the sum over the grid_h x grid_w samples at
+ * (p * bin + start) + ((i + 0.5) * bin) / grid (ascending iy, then ix) of the bilinear value of mv_roi_align_f32, divided by
+ * (float)(grid_h * grid_w) -- NOT by max(.., 1).  This differs from mv_roi_align_f32: a roi of zero size (and one of negative
+ * size whenever ceil(size / pooled) is 0 on an axis) has an adaptive grid whose product is 0, and its outputs are 0 / 0 = NaN, as
+ * the reference's loop computes; a roi with a negative grid whose product is not 0 adds no sample and gives 0 / product, a
+ * signed zero.  With sampling_ratio > 0 the outputs of such rois are finite.
+ *
+ * Loops a roi can size: a pooling window is at most h x w elements.  The adaptive grid of ps_roi_align grows with the roi's size
+ * exactly as that of mv_roi_align_f32 does and has no cap that roi_align does not have. */
+int mv_roi_pool_f32(const float* x, const float* rois, float* y, int* argmax, int64_t n, int c, int h, int w, int64_t k, int pooled_h,
+                    int pooled_w, double spatial_scale, void* stream);
+int mv_ps_roi_pool_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
+                       int pooled_h, int pooled_w, double spatial_scale, void* stream);
+int mv_ps_roi_align_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
+                        int pooled_h, int pooled_w, double spatial_scale, int sampling_ratio, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ops.nms and ops.roi_align on one MI355X: time per call (HIP events, median of 7 rounds of `--iters` back-to-back calls after a
+"""ops.nms, ops.roi_align, ops.roi_pool, ops.ps_roi_pool and ops.ps_roi_align on one MI355X: time per call (HIP events, median of 7 rounds of `--iters` back-to-back calls after a
 warm-up, the two sides of a comparison alternating round by round) against the same op on the same GPU -- torchvision's own
 when that package is importable, otherwise a restatement in torch ops:
 
@@ -8,11 +8,14 @@ when that package is importable, otherwise a restatement in torch ops:
   roi_align  the reference's own pure-torch formulation (ops/roi_align.py _roi_align: masked gathers over a (K, C, PH, PW, IY, IX)
              index space) for a fixed sampling_ratio.
 
-  python tools/perf_detect.py [--iters 5]
+  python tools/perf_detect.py [--iters 5] [--pooling-only]
 
 Cases: nms at 1 000 / 4 000 / 20 000 clustered boxes (threshold 0.5); roi_align at 1 000 rois x 256
 channels x 7 x 7 on a 2 x 256 x 200 x 304 map (spatial_scale 0.25, sampling_ratio 2, aligned), with the bytes it must move
-(the output once; the map's touched part at most once) against the 8 TB/s HBM peak."""
+(the output once; the map's touched part at most once) against the 8 TB/s HBM peak; roi_pool / ps_roi_pool / ps_roi_align at
+1 000 rois x 7 x 7 on a 2 x 256 x 50 x 68 map (spatial_scale 0.25; 245 = 5 x 49 channels for the position-sensitive ops;
+ps_roi_align with sampling_ratio 2) against torchvision's op on the GPU where that package is importable -- otherwise the op's
+own time and the bytes it moves are printed, without a baseline."""
 import argparse
 import sys
 from pathlib import Path
@@ -115,8 +118,11 @@ def torch_roi_align(x, rois, scale, ph_n, pw_n, ratio, aligned):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--pooling-only", action="store_true", help="only the roi_pool / ps_roi_pool / ps_roi_align rows")
     args = ap.parse_args()
     it = args.iters
+    if args.pooling_only:
+        return pooling_rows(it)
     print(f"baseline: {'torchvision.ops on the GPU' if tv_ops is not None else 'torch-op restatements (no torchvision on this machine)'}")
     for n in (1000, 4000, 20000):
         b, s = boxes(n)
@@ -158,6 +164,34 @@ def main():
           f"{out_bytes / (ms * 1e-3) / 1e12:.3f} TB/s ({out_bytes / (ms * 1e-3) / 1e12 / PEAK_TBS * 100:.1f} % of 8 TB/s), tap requests "
           f"{taps / 1e9:.2f} GB = {taps / (ms * 1e-3) / 1e12:.2f} TB/s   {_lib.last_kernel()}")
     print(f"  {ref_name}: {ms_ref:9.4f} ms -> {ms_ref / ms:.1f}x   max |difference| {err:.2e}", flush=True)
+
+    pooling_rows(it)
+
+
+def pooling_rows(it):
+    """roi_pool / ps_roi_pool / ps_roi_align: 1 000 rois, 7 x 7 outputs, a 256-channel 50 x 68 map (the channel count rounded to a
+    multiple of 49 for the position-sensitive ops)."""
+    g = torch.Generator(device="cuda").manual_seed(2)
+    p = torch.rand((1000, 2), device="cuda", generator=g) * torch.tensor([272.0 - 32, 200.0 - 32], device="cuda")
+    wh = 16 + torch.rand((1000, 2), device="cuda", generator=g) * 120
+    rois = torch.cat([torch.randint(0, 2, (1000, 1), device="cuda", generator=g).float(), p, p + wh], 1)
+    for name, c, tail in (("roi_pool", 256, ()), ("ps_roi_pool", 245, ()), ("ps_roi_align", 245, (2,))):
+        x = torch.rand((2, c, 50, 68), device="cuda")
+        ours = lambda: getattr(ops, name)(x, rois, 7, 0.25, *tail)  # noqa: E731
+        c_out = c if name == "roi_pool" else c // 49
+        out_bytes = 1000 * c_out * 49 * (4 + 4)  # both outputs
+        in_bytes = x.numel() * 4  # the map at most once from HBM (it fits the L2s)
+        if tv_ops is not None:
+            ref = lambda: getattr(tv_ops, name)(x, rois, 7, 0.25, *tail)  # noqa: E731
+            same = torch.equal(ours().nan_to_num(), ref().nan_to_num())
+            ms, ms_ref = alternate([ours, ref], it)
+            against = f"torchvision.ops.{name}: {ms_ref:9.4f} ms -> {ms_ref / ms:.1f}x   same values: {same}"
+        else:
+            ms = alternate([ours], it)[0]
+            against = "no baseline (torchvision cannot be imported)"
+        print(f"{name} 1000 rois x {c_out} ch x 7x7 on 2x{c}x50x68  {ms:9.4f} ms   outputs {out_bytes / 1e6:.2f} MB + map "
+              f"{in_bytes / 1e6:.2f} MB = {(out_bytes + in_bytes) / (ms * 1e-3) / 1e12:.4f} TB/s   {against}   {_lib.last_kernel()}",
+              flush=True)
 
 
 if __name__ == "__main__":
