@@ -9,7 +9,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
   ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
-                  ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*)
+                  ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*); box_iou / generalized_box_iou /
+                  distance_box_iou, masks_to_boxes, MultiScaleRoIAlign, box_area / box_convert / clip_boxes_to_image /
+                  remove_small_boxes
   graphs          HIP-graph capture of a whole forward (batch-1 latency)
   presets         ImageClassification (resize -> center_crop -> float -> normalize in one call)
   transforms      GaussianBlur, RandomAdjustSharpness, GaussianBlurV1, the geometric and colour v2 transforms
@@ -22,6 +24,8 @@ The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias pa
 from . import functional, functional_v1, graphs, mobilenet, nn, ops, presets, sharding, transforms, tv_tensors  # noqa: F401
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
+from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
+                  generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401
                          depthwise_conv2d, gaussian_blur, gaussian_blur_image, gaussian_sobel,
                          separable_gaussian_blur, sobel)

@@ -118,6 +118,12 @@ SYMBOLS = {
     "mv_roi_pool_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _vp]),
     "mv_ps_roi_pool_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _vp]),
     "mv_ps_roi_align_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i, _i, _d, _i, _vp]),
+    "mv_multiscale_roi_align_f32": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), _i, _vp, _vp, _vp, _i64, _i,
+                                         _i64, _i, _i, _i, _i, _vp]),
+    "mv_box_iou_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp]),
+    "mv_masks_to_boxes_workspace_bytes": (_i64, [_i64]),
+    "mv_masks_to_boxes_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "mv_masks_to_boxes_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1066,6 +1066,86 @@ int mv_roi_align_f32(const float* x, const float* rois, float* y, int64_t n, int
                           (hipStream_t)stream);
 }
 
+int mv_multiscale_roi_align_f32(const float* const* xs, const int* hs, const int* ws, const double* scales, int levels, const float* rois,
+                                const int64_t* roi_levels, float* y, int64_t n, int c, int64_t k, int pooled_h, int pooled_w,
+                                int sampling_ratio, int aligned, void* stream) {
+  if (levels < 0 || n < 0 || c < 0 || k < 0 || pooled_h < 0 || pooled_w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: bad shape levels=%d n=%lld c=%d, k=%lld, output (%d, %d)", levels,
+                     (long long)n, c, (long long)k, pooled_h, pooled_w);
+  if (levels > kMaxRoiLevels)
+    return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: up to %d feature maps per call, got %d", kMaxRoiLevels, levels);
+  if (k == 0 || c == 0 || pooled_h == 0 || pooled_w == 0) return MV_OK;
+  if (levels > 0 && (!xs || !hs || !ws || !scales)) return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: null level table");
+  for (int l = 0; l < levels; ++l) {
+    if (hs[l] < 0 || ws[l] < 0)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: bad shape (%d, %d) of feature map %d", hs[l], ws[l], l);
+    if (n > 0 && (hs[l] == 0 || ws[l] == 0))
+      return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: empty (%d, %d) feature map %d", hs[l], ws[l], l);
+    if ((int64_t)hs[l] * ws[l] > 0x7fffffffLL)
+      return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: feature map %d of %d x %d exceeds the 32-bit plane index", l, hs[l], ws[l]);
+  }
+  if (n > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: %lld images exceed the 32-bit plane index", (long long)n);
+  if (k > ((0x7fffffffLL * 256) / c) / pooled_h / pooled_w)
+    return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid",
+                     (long long)k, c, pooled_h, pooled_w);
+  if (!rois || !roi_levels || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: null pointer");
+  if (rois == y || (const void*)roi_levels == (const void*)y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if ((uintptr_t)roi_levels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: roi_levels must be 8-byte aligned");
+  for (int l = 0; l < levels; ++l) {
+    if (n > 0 && !xs[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: null pointer (feature map %d)", l);
+    if (xs[l] == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  }
+  return launch_multiscale_roi_align(xs, hs, ws, scales, levels, rois, roi_levels, y, (int)n, c, k, pooled_h, pooled_w, sampling_ratio,
+                                     aligned ? 1 : 0, (hipStream_t)stream);
+}
+
+// ---- box_iou family / masks_to_boxes: boxes.hip -------------------------------------------------------------------------------------
+int mv_box_iou_f32(const float* boxes1, const float* boxes2, float* out, int64_t n, int64_t m, int mode, void* stream) {
+  if (n < 0 || m < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "box_iou: bad shape n=%lld, m=%lld", (long long)n, (long long)m);
+  if (mode < 0 || mode > 2)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "box_iou: unknown mode %d (0 iou, 1 generalized, 2 distance)", mode);
+  if (n == 0 || m == 0) return MV_OK;
+  if (!boxes1 || !boxes2 || !out) return set_error(MV_ERR_INVALID_ARGUMENT, "box_iou: null pointer");
+  if (boxes1 == out || boxes2 == out) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (n > 0x7fffffffffffLL / m || !box_iou_grid_fits(n, m))
+    return set_error(MV_ERR_UNSUPPORTED, "box_iou: %lld x %lld pairs exceed the launch grid", (long long)n, (long long)m);
+  return launch_box_iou(boxes1, boxes2, out, n, m, mode, (hipStream_t)stream);
+}
+
+int64_t mv_masks_to_boxes_workspace_bytes(int64_t n) {
+  if (n <= 0 || n > 0x7fffffffLL) return 0;
+  return 16 * n;
+}
+
+static int masks_to_boxes(const void* masks, bool f32, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  if (n < 0 || h < 0 || w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "masks_to_boxes: bad shape n=%lld (%d, %d)", (long long)n, h, w);
+  if (n == 0) return MV_OK;
+  if (n > 0x7fffffffLL || !masks_to_boxes_grid_fits(n, h))
+    return set_error(MV_ERR_UNSUPPORTED, "masks_to_boxes: %lld masks of %d rows exceed the launch grid", (long long)n, h);
+  if (!boxes || !empty_flag || (h > 0 && w > 0 && !masks)) return set_error(MV_ERR_INVALID_ARGUMENT, "masks_to_boxes: null pointer");
+  if (masks == (const void*)boxes || masks == (const void*)empty_flag || (const void*)boxes == (const void*)empty_flag)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input or the other output");
+  if ((uintptr_t)empty_flag % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "masks_to_boxes: empty_flag must be 4-byte aligned");
+  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "masks_to_boxes: needs a workspace");
+  if (workspace_bytes < 16 * n)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "masks_to_boxes: workspace of %lld bytes, need %lld (mv_masks_to_boxes_workspace_bytes)",
+                     (long long)workspace_bytes, (long long)(16 * n));
+  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "masks_to_boxes: the workspace must be 16-byte aligned");
+  return launch_masks_to_boxes(masks, f32, boxes, empty_flag, n, h, w, workspace, (hipStream_t)stream);
+}
+
+int mv_masks_to_boxes_u8(const unsigned char* masks, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+  return masks_to_boxes(masks, false, boxes, empty_flag, n, h, w, workspace, workspace_bytes, stream);
+}
+
+int mv_masks_to_boxes_f32(const float* masks, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  return masks_to_boxes(masks, true, boxes, empty_flag, n, h, w, workspace, workspace_bytes, stream);
+}
+
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------
 // The checks the three entry points share, in the order of mv_roi_align_f32: 0 launch, 1 nothing to do, < 0 the error.
 static int roi_pool_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, const int* second,

@@ -16,7 +16,8 @@
 //                words of the bitset -- those loads do not depend on each other, unlike a walk box by box.
 //
 // roi_align: one lane per output element (k, c, ph, pw), pw fastest; the lane recomputes its roi's geometry (a few dozen flops)
-// and walks its samples in ascending (iy, ix) order.
+// and walks its samples in ascending (iy, ix) order (roi_align_element).  k_multiscale_roi_align (ops/poolers.py MultiScaleRoIAlign)
+// is the same element function on the feature map of the roi's level: one launch over all levels, no read-back.
 #include "mv_common.h"
 
 namespace mv {
@@ -156,9 +157,9 @@ struct RoiAlignArgs {
   float spatial_scale;
 };
 
-__global__ __launch_bounds__(256) void k_roi_align(const RoiAlignArgs A) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= A.total) return;
+// Output element idx of roi_align on the map A.x (A.h x A.w, A.spatial_scale): k_roi_align hands over its arguments as they are,
+// k_multiscale_roi_align the map of the roi's level.
+__device__ inline void roi_align_element(const RoiAlignArgs& A, long long idx) {
   const int pw = (int)(idx % A.pooled_w);
   const int ph = (int)((idx / A.pooled_w) % A.pooled_h);
   const long long kc = idx / ((long long)A.pooled_w * A.pooled_h);
@@ -223,6 +224,40 @@ __global__ __launch_bounds__(256) void k_roi_align(const RoiAlignArgs A) {
   A.y[idx] = __fdiv_rn(out, count);
 }
 
+__global__ __launch_bounds__(256) void k_roi_align(const RoiAlignArgs A) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= A.total) return;
+  roi_align_element(A, idx);
+}
+
+// MultiScaleRoIAlign in one launch: the per-level maps travel by value (host tables copied into the arguments); a lane reads its
+// roi's level, picks that level's map with a chain of selects (no indexed access to the argument arrays, which would move them to
+// scratch) and computes roi_align_element on it.  A level outside [0, levels): zeros, nothing is read.
+struct MultiScaleArgs {
+  const float* xs[kMaxRoiLevels];
+  int hs[kMaxRoiLevels], ws[kMaxRoiLevels];
+  float scales[kMaxRoiLevels];
+  const long long* roi_levels;
+  int levels;
+  RoiAlignArgs roi;  // x, h, w and spatial_scale are set per lane
+};
+
+__global__ __launch_bounds__(256) void k_multiscale_roi_align(const MultiScaleArgs M) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M.roi.total) return;
+  const long long k = idx / ((long long)M.roi.pooled_w * M.roi.pooled_h * M.roi.c);
+  const long long level = M.roi_levels[k];
+  if (level < 0 || level >= M.levels) {
+    M.roi.y[idx] = 0.f;
+    return;
+  }
+  RoiAlignArgs A = M.roi;
+#pragma unroll
+  for (int l = 0; l < kMaxRoiLevels; ++l)
+    if (l == (int)level) A.x = M.xs[l], A.h = M.hs[l], A.w = M.ws[l], A.spatial_scale = M.scales[l];
+  roi_align_element(A, idx);
+}
+
 }  // namespace
 
 // ---- nms workspace: [sorted boxes: n x 4 float][mask: n x tiles uint64][order: n int32], rounded up to 16 bytes ----------------
@@ -265,6 +300,19 @@ int launch_roi_align(const float* x, const float* rois, float* y, int n, int c, 
   RoiAlignArgs a = {x, rois, y, (long long)k * c * pooled_h * pooled_w, n, c, h, w, pooled_h, pooled_w, sampling_ratio, aligned, spatial_scale};
   hipLaunchKernelGGL(k_roi_align, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, a);
   return check_launchf("k_roi_align<%s,%s>", aligned ? "aligned" : "legacy", sampling_ratio > 0 ? "fixed" : "adaptive");
+}
+
+int launch_multiscale_roi_align(const float* const* xs, const int* hs, const int* ws, const double* scales, int levels, const float* rois,
+                                const int64_t* roi_levels, float* y, int n, int c, int64_t k, int pooled_h, int pooled_w, int sampling_ratio,
+                                int aligned, hipStream_t s) {
+  MultiScaleArgs m = {};
+  for (int l = 0; l < levels; ++l) m.xs[l] = xs[l], m.hs[l] = hs[l], m.ws[l] = ws[l], m.scales[l] = (float)scales[l];
+  m.roi_levels = reinterpret_cast<const long long*>(roi_levels);
+  m.levels = levels;
+  m.roi = {nullptr, rois, y, (long long)k * c * pooled_h * pooled_w, n, c, 0, 0, pooled_h, pooled_w, sampling_ratio, aligned, 0.f};
+  hipLaunchKernelGGL(k_multiscale_roi_align, dim3((unsigned)((m.roi.total + 255) / 256)), dim3(256), 0, s, m);
+  return check_launchf("k_multiscale_roi_align<levels%d,%s,%s>", levels, aligned ? "aligned" : "legacy",
+                       sampling_ratio > 0 ? "fixed" : "adaptive");
 }
 
 }  // namespace mv

@@ -309,6 +309,19 @@ int launch_nms(const float* boxes, const float* scores, int n, double iou_thresh
                hipStream_t s);
 int launch_roi_align(const float* x, const float* rois, float* y, int n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
                      float spatial_scale, int sampling_ratio, int aligned, hipStream_t s);
+// ops.MultiScaleRoIAlign (detect.hip; mv_multiscale_roi_align_f32): xs / hs / ws / scales are HOST tables of `levels` <= kMaxRoiLevels
+// entries, copied into the kernel arguments; checked per level as for launch_roi_align.
+constexpr int kMaxRoiLevels = 8;
+int launch_multiscale_roi_align(const float* const* xs, const int* hs, const int* ws, const double* scales, int levels, const float* rois,
+                                const int64_t* roi_levels, float* y, int n, int c, int64_t k, int pooled_h, int pooled_w, int sampling_ratio,
+                                int aligned, hipStream_t s);
+// ops.box_iou / generalized_box_iou / distance_box_iou and ops.masks_to_boxes (boxes.hip; semantics in mi355vision.h).  The entry
+// points have checked the arguments, the workspace and the grids (*_grid_fits); n, m (and for the masks h, w >= 0) are positive.
+bool box_iou_grid_fits(int64_t n, int64_t m);
+int launch_box_iou(const float* boxes1, const float* boxes2, float* out, int64_t n, int64_t m, int mode, hipStream_t s);
+bool masks_to_boxes_grid_fits(int64_t n, int h);
+int launch_masks_to_boxes(const void* masks, bool f32, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
+                          hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

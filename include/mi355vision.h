@@ -628,6 +628,48 @@ int mv_ps_roi_pool_f32(const float* x, const float* rois, float* y, int* channel
 int mv_ps_roi_align_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
                         int pooled_h, int pooled_w, double spatial_scale, int sampling_ratio, void* stream);
 
+/* ---- torchvision.ops.MultiScaleRoIAlign (ops/poolers.py, forward): mv_roi_align_f32 over up to 8 feature maps in ONE launch.
+ * xs, hs, ws and scales are HOST tables of `levels` entries (as the pointer tables of the mv_*_v entry points; they are copied
+ * into the kernel arguments): xs[l] a DEVICE map (n, c, hs[l], ws[l]) float32 with spatial scale (float)scales[l].  rois (k, 5)
+ * float32 and roi_levels (k) int64 (8-byte aligned) are DEVICE arrays; y (k, c, pooled_h, pooled_w) float32.  Roi i is pooled from
+ * the map xs[roi_levels[i]] with exactly the arithmetic of mv_roi_align_f32 (one device function serves both kernels), so the
+ * result equals, bit for bit, a roi_align per level scattered into y.  A level outside [0, levels) cannot be reported without a
+ * read-back: that roi's outputs are zeros and nothing is read for it, as for a batch index outside [0, n).  The checks are those
+ * of mv_roi_align_f32 for every level; levels > 8 is MV_ERR_UNSUPPORTED; k == 0 (or an empty output) is a no-op that touches no
+ * pointer. */
+int mv_multiscale_roi_align_f32(const float* const* xs, const int* hs, const int* ws, const double* scales, int levels, const float* rois,
+                                const int64_t* roi_levels, float* y, int64_t n, int c, int64_t k, int pooled_h, int pooled_w,
+                                int sampling_ratio, int aligned, void* stream);
+
+/* ---- torchvision.ops.box_iou / generalized_box_iou / distance_box_iou (ops/boxes.py, forward).  boxes1 (n, 4) and boxes2 (m, 4)
+ * float32 rows x1, y1, x2, y2 that need 4-byte alignment only; out (n, m) float32 row-major.  mode 0 iou, 1 generalized, 2
+ * distance; any other mode is MV_ERR_INVALID_ARGUMENT.  The values are the reference's chain of broadcast torch ops evaluated in
+ * float32, every operation rounded once and nothing fused:
+ *   area = (x2 - x1) * (y2 - y1);  wh = clamp(min(x2, y2 corners) - max(x1, y1 corners), min = 0);  inter = w * h;
+ *   union = (area1 + area2) - inter;  iou = inter / union                     (0 / 0 = NaN, as the reference);
+ *   enclosing box: whi = clamp(max(x2, y2 corners) - min(x1, y1 corners), min = 0);
+ *   generalized: iou - (wi * hi - union) / (wi * hi);
+ *   distance:    iou - (dx * dx + dy * dy) / ((wi * wi + hi * hi) + (float)1e-7), dx, dy the differences of the centres (a + b) / 2.
+ * min, max and clamp give NaN for a NaN operand, as torch.min / torch.max / torch.clamp do.  One launch, no workspace: a wave
+ * keeps 4 columns per lane in registers over a strip of rows and writes a row with one 16-byte store per lane when m % 4 == 0 and
+ * out is 16-byte aligned (k_box_iou<.., vec16>), with 4-byte stores otherwise (k_box_iou<.., scalar>): the same values.  n == 0 or
+ * m == 0 is a no-op that touches no pointer; a grid that n * m exceeds is MV_ERR_UNSUPPORTED. */
+int mv_box_iou_f32(const float* boxes1, const float* boxes2, float* out, int64_t n, int64_t m, int mode, void* stream);
+
+/* ---- torchvision.ops.masks_to_boxes.  masks (n, h, w) of bytes (_u8: uint8 or bool storage) or float32 (_f32); boxes (n, 4)
+ * float32 = [min x, min y, max x, max y] over the elements `!= 0` of each mask (the C operator: a NaN is set, -0.0 is clear).
+ * Masks are split into chunks of rows over several workgroups, which combine with integer atomicMin / atomicMax in `workspace`: a
+ * 16-byte aligned DEVICE buffer of mv_masks_to_boxes_workspace_bytes(n) = 16 n bytes (0 for n <= 0) with any content; the result
+ * is exact and does not depend on the order.  Rows are read with 16-byte loads between the 16-byte boundaries and element by
+ * element outside them, at any w and any alignment of masks.  A mask without a set element (h * w == 0 included) cannot be
+ * reported without a read-back: its box is zeros and 1 is ORed into *empty_flag (one int, DEVICE, 4-byte aligned), which the caller
+ * clears beforehand and reads afterwards; the flag is not written otherwise.  n == 0 is a no-op that touches no pointer. */
+int64_t mv_masks_to_boxes_workspace_bytes(int64_t n);
+int mv_masks_to_boxes_u8(const unsigned char* masks, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int mv_masks_to_boxes_f32(const float* masks, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,12 @@ when that package is importable, otherwise a restatement in torch ops:
   roi_align  the reference's own pure-torch formulation (ops/roi_align.py _roi_align: masked gathers over a (K, C, PH, PW, IY, IX)
              index space) for a fixed sampling_ratio.
 
-  python tools/perf_detect.py [--iters 5] [--pooling-only]
+  box_iou / generalized_box_iou / distance_box_iou   the reference's chain of broadcast torch ops (ops/boxes.py) on the same GPU.
+  masks_to_boxes      the reference's loop, a torch.where per mask (one host round trip each).
+  MultiScaleRoIAlign  the reference's per-level loop (torch.where, gather, roi_align, scatter) built from ops.roi_align: the same
+                      kernel arithmetic, so the difference is the syncs, gathers and scatters.
+
+  python tools/perf_detect.py [--iters 5] [--pooling-only] [--boxes-only]
 
 Cases: nms at 1 000 / 4 000 / 20 000 clustered boxes (threshold 0.5); roi_align at 1 000 rois x 256
 channels x 7 x 7 on a 2 x 256 x 200 x 304 map (spatial_scale 0.25, sampling_ratio 2, aligned), with the bytes it must move
@@ -119,10 +124,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--pooling-only", action="store_true", help="only the roi_pool / ps_roi_pool / ps_roi_align rows")
+    ap.add_argument("--boxes-only", action="store_true", help="only the box_iou family / masks_to_boxes / MultiScaleRoIAlign rows")
     args = ap.parse_args()
     it = args.iters
     if args.pooling_only:
         return pooling_rows(it)
+    if args.boxes_only:
+        return boxes_rows(it)
     print(f"baseline: {'torchvision.ops on the GPU' if tv_ops is not None else 'torch-op restatements (no torchvision on this machine)'}")
     for n in (1000, 4000, 20000):
         b, s = boxes(n)
@@ -166,6 +174,98 @@ def main():
     print(f"  {ref_name}: {ms_ref:9.4f} ms -> {ms_ref / ms:.1f}x   max |difference| {err:.2e}", flush=True)
 
     pooling_rows(it)
+    boxes_rows(it)
+
+
+def _torch_inter_union(b1, b2):
+    area1, area2 = (b1[:, 2] - b1[:, 0]) * (b1[:, 3] - b1[:, 1]), (b2[:, 2] - b2[:, 0]) * (b2[:, 3] - b2[:, 1])
+    lt, rb = torch.max(b1[:, None, :2], b2[:, :2]), torch.min(b1[:, None, 2:], b2[:, 2:])
+    wh = (rb - lt).clamp(min=0)
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    return inter, area1[:, None] + area2 - inter
+
+
+def torch_box_iou(b1, b2):
+    inter, union = _torch_inter_union(b1, b2)
+    return inter / union
+
+
+def torch_generalized_box_iou(b1, b2):
+    inter, union = _torch_inter_union(b1, b2)
+    iou = inter / union
+    lti, rbi = torch.min(b1[:, None, :2], b2[:, :2]), torch.max(b1[:, None, 2:], b2[:, 2:])
+    whi = (rbi - lti).clamp(min=0)
+    areai = whi[:, :, 0] * whi[:, :, 1]
+    return iou - (areai - union) / areai
+
+
+def torch_distance_box_iou(b1, b2, eps=1e-7):
+    iou = torch_box_iou(b1, b2)
+    lti, rbi = torch.min(b1[:, None, :2], b2[:, :2]), torch.max(b1[:, None, 2:], b2[:, 2:])
+    whi = (rbi - lti).clamp(min=0)
+    diag = (whi[:, :, 0] ** 2) + (whi[:, :, 1] ** 2) + eps
+    xp, yp = (b1[:, 0] + b1[:, 2]) / 2, (b1[:, 1] + b1[:, 3]) / 2
+    xg, yg = (b2[:, 0] + b2[:, 2]) / 2, (b2[:, 1] + b2[:, 3]) / 2
+    return iou - (((xp[:, None] - xg[None, :]) ** 2) + ((yp[:, None] - yg[None, :]) ** 2)) / diag
+
+
+def torch_masks_to_boxes(masks):
+    out = torch.zeros((masks.shape[0], 4), device=masks.device, dtype=torch.float)
+    for index, mask in enumerate(masks):
+        y, x = torch.where(mask != 0)
+        out[index, 0], out[index, 1], out[index, 2], out[index, 3] = torch.min(x), torch.min(y), torch.max(x), torch.max(y)
+    return out
+
+
+def per_level_roi_align(feats, rois, levels, scales, size, ratio):
+    result = torch.zeros((len(rois), feats[0].shape[1]) + size, dtype=feats[0].dtype, device=feats[0].device)
+    for level, (f, scale) in enumerate(zip(feats, scales)):
+        idx = torch.where(levels == level)[0]
+        result[idx] = ops.roi_align(f, rois[idx], size, scale, ratio)
+    return result
+
+
+def boxes_rows(it):
+    """The pairwise IoU family at 100 000 x 128 (anchors against ground truth) and 4 096 x 4 096, masks_to_boxes on 100 bool masks
+    of 800 x 1216, MultiScaleRoIAlign with 1 000 rois x 256 channels x 7 x 7 on the strides 4 .. 32 of a 2 x 800 x 1216 batch."""
+    for n, m in ((100000, 128), (4096, 4096)):
+        b1, b2 = boxes(n, seed=3)[0], boxes(m, seed=4)[0]
+        for name, ref in (("box_iou", torch_box_iou), ("generalized_box_iou", torch_generalized_box_iou),
+                          ("distance_box_iou", torch_distance_box_iou)):
+            fn = getattr(ops, name)
+            same = torch.equal(fn(b1, b2).nan_to_num(), ref(b1, b2).nan_to_num())
+            ms, ms_ref = alternate([lambda: fn(b1, b2), lambda: ref(b1, b2)], it)
+            out_bytes = n * m * 4
+            print(f"{name} {n} x {m}  {ms:9.4f} ms   output {out_bytes / 1e6:.1f} MB = {out_bytes / (ms * 1e-3) / 1e12:.3f} TB/s "
+                  f"({out_bytes / (ms * 1e-3) / 1e12 / PEAK_TBS * 100:.1f} % of 8 TB/s)   torch ops on the GPU: {ms_ref:9.4f} ms -> "
+                  f"{ms_ref / ms:.1f}x   same values: {same}   {_lib.last_kernel()}", flush=True)
+
+    g = torch.Generator(device="cuda").manual_seed(5)
+    masks = torch.zeros((100, 800, 1216), dtype=torch.bool, device="cuda")
+    corners = torch.randint(0, 400, (100, 2), device="cuda", generator=g).tolist()
+    for i, (y0, x0) in enumerate(corners):
+        masks[i, y0:y0 + 300, x0:x0 + 500] = torch.rand((300, 500), device="cuda", generator=g) < 0.5
+    same = torch.equal(ops.masks_to_boxes(masks), torch_masks_to_boxes(masks))
+    ms, ms_ref = alternate([lambda: ops.masks_to_boxes(masks), lambda: torch_masks_to_boxes(masks)], it)
+    print(f"masks_to_boxes 100 x 800 x 1216 bool  {ms:9.4f} ms   masks {masks.numel() / 1e6:.1f} MB = "
+          f"{masks.numel() / (ms * 1e-3) / 1e12:.3f} TB/s   the reference's loop on the GPU: {ms_ref:9.4f} ms -> {ms_ref / ms:.1f}x   "
+          f"same values: {same}   {_lib.last_kernel()}", flush=True)
+
+    feats = [torch.rand((2, 256, 800 // s, 1216 // s), device="cuda") for s in (4, 8, 16, 32)]
+    scales = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
+    p = torch.rand((1000, 2), device="cuda", generator=g) * torch.tensor([1216.0 - 64, 800.0 - 64], device="cuda")
+    wh = 16 * 2 ** (torch.rand((1000, 2), device="cuda", generator=g) * 5)  # sides 16 .. 512: every level takes its share
+    rois = torch.cat([torch.randint(0, 2, (1000, 1), device="cuda", generator=g).float(), p, p + wh], 1)
+    levels = ops.LevelMapper(2, 5)([rois[:, 1:]])
+    counts = torch.bincount(levels, minlength=4).tolist()
+    ours = lambda: ops._multiscale_roi_align_impl(feats, rois, levels, scales, 7, 7, 2)  # noqa: E731
+    ref = lambda: per_level_roi_align(feats, rois, levels, scales, (7, 7), 2)  # noqa: E731
+    fused = ours()
+    kernel = _lib.last_kernel()
+    same = torch.equal(fused, ref())
+    ms, ms_ref = alternate([ours, ref], it)
+    print(f"MultiScaleRoIAlign 1000 rois {counts} x 256 ch x 7x7 on 4 maps of 2x800x1216  {ms:9.4f} ms   per-level loop of "
+          f"ops.roi_align: {ms_ref:9.4f} ms -> {ms_ref / ms:.1f}x   same bits: {same}   {kernel}", flush=True)
 
 
 def pooling_rows(it):
