@@ -1,6 +1,6 @@
 """The CNN layers behind nn.py, mobilenet.py and presets.py -- none of them a transforms.v2.functional function: conv2d_bias_relu
-(models/vgg.py:81-85, ops/misc.py:97-119), max_pool2d*, conv2d_bias_act, adaptive_avg_pool2d, linear_bias_relu, conv_norm_act /
-inverted_residual / fold_batchnorm (ops/misc.py:68-128, models/mobilenetv2.py:39-63), normalized_conv2d_bias_relu and the
+(models/vgg.py:81-85, ops/misc.py:97-119), max_pool2d*, conv2d_bias_act, conv2d_affine_act (models/resnet.py), adaptive_avg_pool2d,
+linear_bias_relu, conv_norm_act / inverted_residual / fold_batchnorm (ops/misc.py:68-128, models/mobilenetv2.py:39-63), normalized_conv2d_bias_relu and the
 *_k_slices queries.  All compute in float32 and are forward-only.  The pools launch through _lib.launch_xy; the layers with
 several input tensors prepare them with _lib.f32_on / ptr / workspace and call _lib.launch.
 
@@ -80,9 +80,13 @@ def max_pool2d_2x2(x: torch.Tensor) -> torch.Tensor:
                           out_dtype=torch.float32)
 
 
-def max_pool2d(x: torch.Tensor, kernel_size: int, stride: Optional[int] = None) -> torch.Tensor:
-    """nn.MaxPool2d(kernel_size, stride) without padding, floor mode (AlexNet: 3, 2; models/alexnet.py:24) on (..., H, W)."""
+def max_pool2d(x: torch.Tensor, kernel_size: int, stride: Optional[int] = None, padding: int = 0) -> torch.Tensor:
+    """nn.MaxPool2d(kernel_size, stride, padding), floor mode, dilation 1 on (..., H, W): without padding AlexNet's 3, 2
+    (models/alexnet.py:24); with padding (0 < padding <= kernel_size // 2: ResNet's stem, 3, 2, 1; models/resnet.py:201) the padded
+    positions never win and NaN propagates as in torch's CPU kernel (mv_maxpool2d_pad_f32)."""
     stride = kernel_size if stride is None else stride
+    if padding != 0:
+        return _max_pool2d_padded(x, int(kernel_size), int(stride), int(padding))
     if (kernel_size, stride) == (2, 2):
         return max_pool2d_2x2(x)
     _lib.require_device(x)
@@ -93,6 +97,20 @@ def max_pool2d(x: torch.Tensor, kernel_size: int, stride: Optional[int] = None) 
         raise RuntimeError(f"max_pool2d: kernel {kernel_size} exceeds the {h}x{w} input")
     out_shape = tuple(x.shape[:-2]) + ((h - kernel_size) // stride + 1, (w - kernel_size) // stride + 1)
     return _lib.launch_xy(_lib.load().mv_maxpool2d_f32, x, (planes, h, w, kernel_size, stride), out_shape=out_shape,
+                          out_dtype=torch.float32)
+
+
+def _max_pool2d_padded(x: torch.Tensor, kernel_size: int, stride: int, padding: int) -> torch.Tensor:
+    _lib.require_device(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"max_pool2d computes in float32. Got {x.dtype}")
+    if padding < 0 or padding > kernel_size // 2:
+        raise RuntimeError(f"pad should be at most half of effective kernel size, but got pad={padding}, kernel_size={kernel_size}")
+    planes, h, w = _planes(x)
+    if h + 2 * padding < kernel_size or w + 2 * padding < kernel_size:
+        raise RuntimeError(f"max_pool2d: kernel {kernel_size} exceeds the {h}x{w} input padded by {padding}")
+    out_shape = tuple(x.shape[:-2]) + ((h + 2 * padding - kernel_size) // stride + 1, (w + 2 * padding - kernel_size) // stride + 1)
+    return _lib.launch_xy(_lib.load().mv_maxpool2d_pad_f32, x, (planes, h, w, kernel_size, stride, padding), out_shape=out_shape,
                           out_dtype=torch.float32)
 
 
@@ -257,6 +275,55 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     _lib.launch(lib.mv_conv_norm_act_f32, xc, kind, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
                 n, cin, h, w, cout, stride, _AFFINE_CODES[affine], _ACT_CODES[activation])
     return _lib.forward_only(y, "conv_norm_act", x, weight, bias, alpha, beta, residual)
+
+
+def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                      alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                      residual: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, groups: int = 1,
+                      affine: Optional[str] = None, activation: Optional[str] = None) -> torch.Tensor:
+    """Any nn.Conv2d -> + bias -> folded norm (`affine`: "mul_add" = FrozenBatchNorm2d, "fma" = BatchNorm2d eval) -> + residual ->
+    activation as ONE launch (mv_conv2d_affine_act_f32): conv2d_bias_act's implicit GEMM -- any kernel size, stride, padding,
+    dilation, groups; one ascending (c, ky, kx) chain per output -- with conv_norm_act's epilogue.  ResNet's 7x7 stride-2 stem,
+    its 3x3 convs and its 1x1 stride-2 downsample (models/resnet.py); 1x1 convs at stride 1 are conv_norm_act's."""
+    if x.ndim != 4 or weight.ndim != 4:
+        raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
+    _lib.require_device(x)
+    _lib.require_device(weight, "weight")
+    _lib.require_f32_layer("conv2d_affine_act", x, weight)
+    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))  # noqa: E731
+    (sh, sw), (ph, pw), (dh, dw) = pair(stride), pair(padding), pair(dilation)
+    n, cin, h, w = (int(d) for d in x.shape)
+    cout, cg, kh, kw = (int(d) for d in weight.shape)
+    if groups <= 0 or cg * groups != cin or cout % groups:
+        raise RuntimeError(f"weight {tuple(weight.shape)} does not fit {cin} input channels in {groups} groups")
+    if activation not in _ACT_CODES or affine not in _AFFINE_CODES:
+        raise ValueError(f"unknown activation {activation!r} / affine {affine!r}")
+    if _AFFINE_CODES[affine] != 0 and (alpha is None or beta is None):
+        raise ValueError(f"affine={affine!r} needs alpha and beta")
+    oh, ow = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+    if oh <= 0 or ow <= 0:
+        raise RuntimeError(f"Calculated output size too small - out_h: {oh} out_w: {ow}")
+    lib = _lib.load()
+    xc, wc = x.contiguous(), weight.detach().contiguous()
+    bc, ac, btc, rc = (_lib.f32_on(t, x.device) for t in (bias, alpha, beta, residual))
+    if rc is not None and tuple(rc.shape) != (n, cout, oh, ow):
+        raise RuntimeError(f"residual of shape {tuple(rc.shape)} does not match the output {(n, cout, oh, ow)}")
+    for t, name in ((bc, "bias"), (ac, "alpha"), (btc, "beta")):
+        if t is not None and t.numel() != cout:
+            raise RuntimeError(f"{name} has {t.numel()} elements for {cout} output channels")
+    y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
+    if n == 0:
+        return y
+    nbytes = 0
+    need = int(lib.mv_conv2d_needs_workspace(n, cin, cout, h, w, kh, kw, sh, sw, ph, pw, dh, dw, groups))
+    if need == 1 or (need == 2 and _lib.switch("CONV2D_SMALL_LAUNCH_WORKSPACE")) or _lib.switch("CONV2D_COLUMNS_WORKSPACE"):
+        per_image = int(lib.mv_deform_conv2d_workspace_bytes(1, cin, h, w, kh, kw, sh, sw, ph, pw, dh, dw))
+        nbytes = max(1, min(n, _CONV_WORKSPACE_BYTES // max(per_image, 1))) * per_image
+    ws, ws_ptr, nbytes = _lib.workspace(nbytes, x.device)
+    p = _lib.ptr
+    _lib.launch(lib.mv_conv2d_affine_act_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(), n, cin, h, w,
+                cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, _AFFINE_CODES[affine], _ACT_CODES[activation], ws_ptr, nbytes)
+    return _lib.forward_only(y, "conv2d_affine_act", x, weight, bias, alpha, beta, residual)
 
 
 def inverted_residual_k_slices(n: int, cin: int, hidden: int, cout: int, h: int, w: int, stride: int) -> Tuple[int, int]:

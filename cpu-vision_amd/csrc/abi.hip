@@ -785,6 +785,47 @@ int mv_conv2d_bias_act_f32(const float* x, const float* weight, const float* bia
                               dilation_h, dilation_w, groups, 1, 0, workspace, workspace_bytes, (hipStream_t)stream, act);
 }
 
+// [a, a + an) and [b, b + bn) floats share an element
+static bool overlaps(const float* a, long long an, const float* b, long long bn) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)bn * sizeof(float) && b0 < a0 + (uintptr_t)an * sizeof(float);
+}
+
+int mv_conv2d_affine_act_f32(const float* x, const float* weight, const float* bias, const float* alpha, const float* beta,
+                             const float* residual, float* y, int64_t n, int cin, int h, int wdt, int cout, int kh, int kw,
+                             int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w, int groups,
+                             int affine, int act, void* workspace, int64_t workspace_bytes, void* stream) {
+  int oh = 0, ow = 0;
+  if (n < 0 || cin <= 0 || cout <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv2d shape n=%lld cin=%d cout=%d", (long long)n, cin, cout);
+  if (int rc = deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow)) return rc;
+  if (groups <= 0 || cin % groups || cout % groups)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "channels (%d -> %d) must divide into %d groups", cin, cout, groups);
+  if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
+  if (n == 0) return MV_OK;
+  if (!x || !weight || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
+  const long long ny = (long long)n * cout * oh * ow;
+  if (overlaps(y, ny, x, (long long)n * cin * h * wdt) || overlaps(y, ny, weight, (long long)cout * (cin / groups) * kh * kw) ||
+      (residual && overlaps(y, ny, residual, ny)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, weight or residual");
+  const Epilogue e = {bias, affine ? alpha : nullptr, affine ? beta : nullptr, residual, affine, act};
+  return launch_deform_conv2d(x, weight, nullptr, nullptr, bias, y, n, cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w,
+                              dilation_h, dilation_w, groups, 1, 0, workspace, workspace_bytes, (hipStream_t)stream, act, &e);
+}
+
+int mv_maxpool2d_pad_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, int pad, void* stream) {
+  if (planes < 0 || h <= 0 || wdt <= 0 || k <= 0 || stride <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad pooling shape planes=%lld (%d, %d) k=%d stride=%d", (long long)planes, h, wdt, k, stride);
+  if (pad < 0 || pad > k / 2) return set_error(MV_ERR_INVALID_ARGUMENT, "pad should be at most half of effective kernel size, but got pad=%d, kernel_size=%d", pad, k);
+  if ((long long)h + 2 * pad < k || (long long)wdt + 2 * pad < k)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "Output size is too small: (%d, %d) with k=%d pad=%d", h, wdt, k, pad);
+  if (planes == 0) return MV_OK;
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  return launch_maxpool2d_pad(x, y, planes, h, wdt, k, stride, pad, (hipStream_t)stream);
+}
+
 int mv_maxpool2d_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, void* stream) {
   if (planes < 0 || h <= 0 || wdt <= 0 || k <= 0 || stride <= 0 || k > h || k > wdt)
     return set_error(MV_ERR_INVALID_ARGUMENT, "bad pooling shape planes=%lld (%d, %d) k=%d stride=%d", (long long)planes, h, wdt, k, stride);

@@ -216,4 +216,37 @@ int launch_maxpool2d(const float* x, float* y, int64_t planes, int h, int w, int
   return check_launch("k_maxpool2d");
 }
 
+// nn.MaxPool2d(kernel_size=k, stride=s, padding=pad), floor mode, dilation 1 (ResNet's stem: 3, 2, 1; models/resnet.py:201): lane per
+// output, consecutive lanes = consecutive ox (coalesced stores; the loads of a wave cover one contiguous span of each input row).
+// The window is clipped to the image -- a padded position never wins, as with ATen's -inf padding -- and pad <= k / 2 keeps
+// every window non-empty.  ATen's CPU kernel (MaxPoolKernel.cpp): m = -inf; `if ((v > m) || isnan(v)) m = v` in (iy, ix) order.
+__global__ __launch_bounds__(256) void k_maxpool2d_pad(const float* x, float* y, long long total, int h, int w, int oh, int ow, int k,
+                                                        int stride, int pad) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ox = (int)(idx % ow);
+  const long long t = idx / ow;
+  const int oy = (int)(t % oh);
+  const long long plane = t / oh;
+  const int y0 = oy * stride - pad, x0 = ox * stride - pad;
+  const int ya = max(y0, 0), yb = min(y0 + k, h), xa = max(x0, 0), xb = min(x0 + k, w);
+  const float* xp = x + (size_t)plane * h * w;
+  float m = -__builtin_inff();
+  for (int iy = ya; iy < yb; ++iy)
+    for (int ix = xa; ix < xb; ++ix) {
+      const float a = xp[(size_t)iy * w + ix];
+      if (a > m || a != a) m = a;
+    }
+  y[idx] = m;
+}
+
+int launch_maxpool2d_pad(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s) {
+  const int oh = (h + 2 * pad - k) / stride + 1, ow = (w + 2 * pad - k) / stride + 1;
+  const long long total = (long long)planes * oh * ow;
+  if (total > 256LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "maxpool2d: batch too large for one launch");
+  if (total == 0) return MV_OK;
+  hipLaunchKernelGGL(k_maxpool2d_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, total, h, w, oh, ow, k, stride, pad);
+  return check_launch("k_maxpool2d_pad");
+}
+
 }  // namespace mv

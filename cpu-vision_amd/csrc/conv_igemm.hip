@@ -20,6 +20,14 @@
 //   epilogue    each 32 x 32 tile is transposed through a wave-private LDS buffer so that a store instruction writes 8 full
 //               128-byte lines of 8 channel planes.
 // Zero padding of the image = zeros in the X chunk; k past K = zeros in both operands (an exact no-op of the chain).
+//
+// mv_conv2d_affine_act_f32 (ResNet: the 7x7 stride-2 stem, the 3x3 convs, the 1x1 stride-2 downsample; models/resnet.py) runs the
+// same kernel with the FULL epilogue, k_conv_igemm<CT, PT, true> ("k_conv_igemm_full" in mv_last_kernel()): + bias -> folded norm
+// (alpha / beta loaded once per channel next to the bias) -> residual + v -> activation, mv_epilogue.h's functions in
+// mv_epilogue.h's order.  The residual is read with the addressing of the store: one 16-byte load where the store is one and the
+// residual pointer allows it, else four guarded scalars -- nothing past HW or past channel mg.  FULL is a compile-time switch; the
+// bias + activation instances (FULL = false, kernel argument IgArgs) compile to the instructions and the registers they had
+// before it existed.
 #include <cstdlib>
 
 #include "mv_common.h"
@@ -34,6 +42,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr int kIgK = 32;   // k per chunk
+constexpr int kIgTile = 64;  // the workgroup tile is kIgTile * CT channels x kIgTile * PT pixels (CT in 1..3, PT in 1, 2, 4)
 constexpr int kIgP = 36;   // floats per operand row: [parity][16] + 4 (pitch / 4 odd: conflict-free 16-byte reads of 16 lanes)
 
 struct IgArgs {
@@ -48,11 +57,33 @@ struct IgArgs {
   int mblocks, chunks, act, vec_w, vec_y;
 };
 
+// the rest of mv_epilogue.h's chain for mv_conv2d_affine_act_f32 (the FULL instances): folded norm, residual
+struct IgEpi {
+  const float* alpha;  // [mg] (affine != 0)
+  const float* beta;
+  const float* res;    // at the group's first channel, shaped and strided like y; or null
+  int affine, vec_r;   // vec_r: the residual can be read with the store's 16-byte addressing
+};
+struct IgFullArgs : IgArgs {
+  IgEpi e;
+};
+template <bool FULL>
+struct IgArgsOf {
+  typedef IgArgs type;
+};
+template <>
+struct IgArgsOf<true> {
+  typedef IgFullArgs type;
+};
+
 __device__ __forceinline__ unsigned ig_div(unsigned n, unsigned d, unsigned m) { return d == 1 ? n : __umulhi(n, m); }
 
-template <int CT, int PT>
-__global__ __launch_bounds__(256, 2) void k_conv_igemm(const IgArgs A) {
-  constexpr int MB = 64 * CT, PB = 64 * PT;    // workgroup tile: channels x pixels
+// FULL = false: + bias, activation (mv_conv2d_bias_act_f32; the kernel argument is IgArgs and every `if constexpr (FULL)` below is
+// discarded: the function the compiler sees is the one it saw before FULL existed).  FULL = true: + bias -> folded norm ->
+// + residual -> activation, in mv_epilogue.h's order (epi_norm, `res + v`, epi_act) -- orc_conv2d_affine_act_f32's.
+template <int CT, int PT, bool FULL = false>
+__global__ __launch_bounds__(256, 2) void k_conv_igemm(const typename IgArgsOf<FULL>::type A) {
+  constexpr int MB = kIgTile * CT, PB = kIgTile * PT;    // workgroup tile: channels x pixels
   constexpr int WU = MB / 32;                  // float4 of W per thread and chunk (MB rows x 8 float4)
   constexpr int XU = PB / 8;                   // gathered X elements per thread and chunk (32 k x PB pixels / 256)
   constexpr int XROWS = 256 / PB > 0 ? 256 / PB : 1;  // k rows covered by the 256 threads at once (PB <= 256)
@@ -172,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const IgArgs A) {
     }
   }
 
-  // ---- epilogue: + bias, activation; every tile through a wave-private [channel][pixel] buffer, then 128-byte lines per channel
+  // ---- epilogue: + bias [FULL: -> norm -> + residual] -> activation; every tile through a wave-private [channel][pixel] buffer, then 128-byte lines per channel
   __syncthreads();
   float* const tb = xs + wave * (32 * kIgP);
   const int r0 = lane >> 3, q4 = (lane & 7) * 4;
@@ -188,6 +219,19 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const IgArgs A) {
       const int co = co0 + (wc * CT + i) * 32 + r0 + 8 * jj;
       biasv[i][jj] = A.bias ? A.bias[min(co, A.mg - 1)] : 0.f;
     }
+  float alphav[FULL ? CT : 1][4], betav[FULL ? CT : 1][4];  // the norm's per-channel terms, in the same batch
+  const float* R = nullptr;                                  // the residual's image (strided like y)
+  if constexpr (FULL) {
+    if (A.e.res) R = A.e.res + (size_t)img * A.y_img_stride;
+#pragma unroll
+    for (int i = 0; i < CT; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int co = min(co0 + (wc * CT + i) * 32 + r0 + 8 * jj, A.mg - 1);
+        alphav[i][jj] = A.e.affine ? A.e.alpha[co] : 1.f;
+        betav[i][jj] = A.e.affine ? A.e.beta[co] : 0.f;
+      }
+  }
 #pragma unroll
   for (int i = 0; i < CT; ++i) {
     const int cbase = co0 + (wc * CT + i) * 32;
@@ -208,10 +252,31 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const IgArgs A) {
         if (co >= A.mg || pq >= HW) continue;
         const float bv = biasv[i][jj];
         float v[4] = {t4.x, t4.y, t4.z, t4.w};
+        if constexpr (FULL) {
+          const ChannelTerms ct = {bv, alphav[i][jj], betav[i][jj]};
+          const Epilogue ep = {A.bias, nullptr, nullptr, nullptr, A.e.affine, A.act};  // epi_norm reads bias (as a flag) and affine
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (A.bias) v[r] = v[r] + bv;
-          v[r] = (A.act == 3) ? epi_act<1>(v[r], cl) : ((A.act == 4) ? epi_act<2>(v[r], cl) : epi_act<0>(v[r], cl));
+          for (int r = 0; r < 4; ++r) v[r] = epi_norm(v[r], ct, ep);
+          if (R) {  // the residual with the addressing of the store: 16 bytes where the store is, else guarded scalars
+            const float* src = R + (size_t)co * HW + pq;
+            if (A.e.vec_r && pq + 3 < HW) {
+              const f32x4 r4 = *reinterpret_cast<const f32x4*>(src);
+              v[0] = r4.x + v[0], v[1] = r4.y + v[1], v[2] = r4.z + v[2], v[3] = r4.w + v[3];
+            } else {
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (pq + r < HW) v[r] = src[r] + v[r];
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            v[r] = (A.act == 3) ? epi_act<1>(v[r], cl) : ((A.act == 4) ? epi_act<2>(v[r], cl) : epi_act<0>(v[r], cl));
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if (A.bias) v[r] = v[r] + bv;
+            v[r] = (A.act == 3) ? epi_act<1>(v[r], cl) : ((A.act == 4) ? epi_act<2>(v[r], cl) : epi_act<0>(v[r], cl));
+          }
         }
         float* dst = Y + (size_t)co * HW + pq;
         if (A.vec_y && pq + 3 < HW) {
@@ -226,12 +291,20 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const IgArgs A) {
   }
 }
 
+// e == nullptr: the bias + activation instances; else the instances with the full epilogue
 template <int CT, int PT>
-static int ig_launch(IgArgs& a, int64_t n, hipStream_t s) {
+static int ig_launch(IgArgs& a, const IgEpi* e, int64_t n, hipStream_t s) {
   a.mblocks = (a.mg + 64 * CT - 1) / (64 * CT);
   const long long pblocks = (a.HW + 64 * PT - 1) / (64 * PT);
   const long long nb = a.mblocks * pblocks;
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv2d (implicit GEMM): problem too large for one launch");
+  if (e != nullptr) {
+    IgFullArgs f;
+    static_cast<IgArgs&>(f) = a;
+    f.e = *e;
+    hipLaunchKernelGGL((k_conv_igemm<CT, PT, true>), dim3((unsigned)nb, (unsigned)n), dim3(256), 0, s, f);
+    return check_launchf("k_conv_igemm_full<%dch,%dpx,implicit %dx%d>", 64 * CT, 64 * PT, a.taps / a.kw, a.kw);
+  }
   hipLaunchKernelGGL((k_conv_igemm<CT, PT>), dim3((unsigned)nb, (unsigned)n), dim3(256), 0, s, a);
   return check_launchf("k_conv_igemm<%dch,%dpx,implicit %dx%d>", 64 * CT, 64 * PT, a.taps / a.kw, a.kw);
 }
@@ -252,7 +325,8 @@ int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, 
                            int sw, int ph, int pw_, int dh, int dw, int oh, int ow, const Epilogue& e, hipStream_t s,
                            int64_t x_img_stride, int64_t y_img_stride) {
   if ((long long)cg * h * wd >= (1LL << 30)) return set_error(MV_ERR_UNSUPPORTED, "conv2d (implicit GEMM): one image of a group has 2^30 elements or more");
-  if (e.affine != 0 || e.res != nullptr) return set_error(MV_ERR_UNSUPPORTED, "conv2d (implicit GEMM): bias + activation only");
+  // bias + activation alone keeps the instances of mv_conv2d_bias_act_f32; a norm or a residual takes the ones with the full epilogue
+  const bool full = e.affine != 0 || e.res != nullptr;
   IgArgs a = {};
   a.x = x, a.w = w, a.bias = e.bias, a.y = y;
   a.x_img_stride = x_img_stride, a.y_img_stride = y_img_stride;
@@ -264,6 +338,8 @@ int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, 
   a.act = e.act;
   a.vec_w = (a.K % 4 == 0) && ((uintptr_t)w % 16 == 0);
   a.vec_y = (a.HW % 4 == 0) && ((uintptr_t)y % 16 == 0) && (y_img_stride % 4 == 0);
+  IgEpi epi = {e.alpha, e.beta, e.res, e.affine, a.vec_y && ((uintptr_t)e.res % 16 == 0)};  // the residual's image stride is y's
+  const IgEpi* ep = full ? &epi : nullptr;
   if (n == 0 || a.HW == 0) return MV_OK;
   // channel tile: 64, 128 or 192 channels per workgroup, whichever pads the least (ties: the larger -- every gathered element
   // then feeds more channels); pixel tile: 256 pixels with one channel tile per wave, else 128; small problems take 64-pixel
@@ -276,16 +352,16 @@ int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, 
   if (const char* ev = tune_env("MV_IG_CT")) ct = atoi(ev) >= 1 && atoi(ev) <= 3 ? atoi(ev) : ct;
   const long long wgs256 = padded(mg, 64 * ct) / (64 * ct) * ((a.HW + 255) / 256) * n;
   if (ct == 1) {
-    if (wgs256 >= 512 || a.HW > 4096) return ig_launch<1, 4>(a, n, s);
-    if (padded(mg, 64) / 64 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<1, 2>(a, n, s);
-    return ig_launch<1, 1>(a, n, s);
+    if (wgs256 >= 512 || a.HW > 4096) return ig_launch<1, 4>(a, ep, n, s);
+    if (padded(mg, 64) / 64 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<1, 2>(a, ep, n, s);
+    return ig_launch<1, 1>(a, ep, n, s);
   }
   if (ct == 2) {
-    if (padded(mg, 128) / 128 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<2, 2>(a, n, s);
-    return ig_launch<2, 1>(a, n, s);
+    if (padded(mg, 128) / 128 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<2, 2>(a, ep, n, s);
+    return ig_launch<2, 1>(a, ep, n, s);
   }
-  if (padded(mg, 192) / 192 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<3, 2>(a, n, s);
-  return ig_launch<3, 1>(a, n, s);
+  if (padded(mg, 192) / 192 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<3, 2>(a, ep, n, s);
+  return ig_launch<3, 1>(a, ep, n, s);
 }
 
 }  // namespace mv

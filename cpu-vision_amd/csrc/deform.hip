@@ -229,10 +229,24 @@ int64_t deform_workspace_bytes_per_image(int cin, int kh, int kw, int oh, int ow
   return (int64_t)sizeof(float) * cin * kh * kw * oh * ow;
 }
 
-// offset == nullptr: ordinary convolution (plain im2col); act: MV_ACT_* applied after the bias
+// offset == nullptr: ordinary convolution (plain im2col); act: MV_ACT_* applied after the bias.  epi (ordinary convolution only:
+// mv_conv2d_affine_act_f32): the whole-tensor epilogue -- bias, alpha, beta, residual, affine, act; replaces `bias` and `act` --
+// which every group's launch receives at the group's first channel, in the implicit and in the columns form alike.
 int launch_deform_conv2d(const float* x, const float* weight, const float* offset, const float* mask, const float* bias, float* y,
                          int64_t n, int cin, int h, int wd, int cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                         int groups, int offset_groups, int use_mask, void* workspace, int64_t workspace_bytes, hipStream_t s, int act) {
+                         int groups, int offset_groups, int use_mask, void* workspace, int64_t workspace_bytes, hipStream_t s, int act,
+                         const Epilogue* epi) {
+  Epilogue whole = {bias, nullptr, nullptr, nullptr, 0, act};
+  if (epi != nullptr && offset == nullptr) whole = *epi;
+  // group g's terms; the residual of images from b0 on (shaped like y)
+  auto group_epilogue = [&](int g, int mg, int64_t b0, int64_t ohw) {
+    Epilogue e = whole;
+    if (e.bias) e.bias += (size_t)g * mg;
+    if (e.alpha) e.alpha += (size_t)g * mg;
+    if (e.beta) e.beta += (size_t)g * mg;
+    if (e.res) e.res += ((size_t)b0 * cout + (size_t)g * mg) * ohw;
+    return e;
+  };
   const int oh = (h + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
   const int ow = (wd + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
   // deformable sampling: the fused kernel (deform_fused.hip) whenever its tiles fit -- every usual DCN layer; no workspace.
@@ -252,7 +266,7 @@ int launch_deform_conv2d(const float* x, const float* weight, const float* offse
   if (offset == nullptr && conv2d_implicit_supported(cin / groups, kh, kw, oh, ow) && !small_launch_with_workspace) {
     const int cg = cin / groups, mg = cout / groups;
     for (int g = 0; g < groups; ++g) {
-      Epilogue e = {bias ? bias + (size_t)g * mg : nullptr, nullptr, nullptr, nullptr, 0, act};
+      const Epilogue e = group_epilogue(g, mg, 0, (int64_t)oh * ow);
       const int rc = launch_conv2d_implicit(x + (size_t)g * cg * h * wd, weight + (size_t)g * mg * cg * kh * kw, y + (size_t)g * mg * oh * ow, n,
                                             cg, h, wd, mg, kh, kw, sh, sw, ph, pw, dh, dw, oh, ow, e, s, (int64_t)cin * h * wd,
                                             (int64_t)cout * oh * ow);
@@ -269,7 +283,6 @@ int launch_deform_conv2d(const float* x, const float* weight, const float* offse
   if (pass > 65535) pass = 65535;
   const int taps = kh * kw, cg = cin / groups, mg = cout / groups;
   const int64_t ohw = (int64_t)oh * ow;
-  const Epilogue none = {nullptr, nullptr, nullptr, nullptr, 0, 0};
   for (int64_t b0 = 0; b0 < n; b0 += pass) {
     const int64_t nb = (n - b0 < pass) ? n - b0 : pass;
     DeformArgs a = {};
@@ -320,9 +333,7 @@ int launch_deform_conv2d(const float* x, const float* weight, const float* offse
       if (int rc = check_launch("k_deform_im2col")) return rc;
     }
     for (int g = 0; g < groups; ++g) {
-      Epilogue e = none;
-      e.bias = bias ? bias + (size_t)g * mg : nullptr;
-      e.act = act;
+      const Epilogue e = group_epilogue(g, mg, b0, ohw);
       const int rc = launch_conv1x1(a.col + (size_t)g * cg * taps * ohw, weight + (size_t)g * mg * cg * taps,
                                     y + ((size_t)b0 * cout + (size_t)g * mg) * ohw, nb, cg * taps, ohw, mg, e, s,
                                     (int64_t)cin * taps * ohw, (int64_t)cout * ohw, /*allow_k_slices=*/false);

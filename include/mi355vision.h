@@ -34,7 +34,7 @@
  *     aligned to 4 pixels (16 bytes float32, 8 half types, 4 uint8) the 4-pixel kernels take their vector instantiation
  *     ("vec16" in mv_last_kernel()), and mv_separable_blur_f32 / mv_gaussian_sobel_f32 take k_sepfast only on 16-byte pointers.
  *   - alignment, CNN layer entry points (mv_conv3x3_bias_relu_*, mv_linear_bias_relu_*, the pools, mv_conv_norm_act_f32,
- *     mv_conv2d_bias_act_f32, mv_deform_conv2d_f32): every tensor -- x, weights, bias, alpha, beta, residual, offset, mask, y --
+ *     mv_conv2d_bias_act_f32, mv_conv2d_affine_act_f32, mv_deform_conv2d_f32): every tensor -- x, weights, bias, alpha, beta, residual, offset, mask, y --
  *     needs the alignment of its element type only, and a workspace 4 bytes (mv_linear_bias_relu_ws_f32 checks it:
  *     MV_ERR_INVALID_ARGUMENT otherwise); a workspace's content on entry does not matter.  Every output is written whole, nothing
  *     outside y and the stated workspace size is written, and no value from outside an input reaches a result.  Alignment buys
@@ -329,6 +329,28 @@ int mv_conv2d_bias_act_f32(const float* x, const float* weight, const float* bia
 /* nn.MaxPool2d(kernel_size=k, stride=stride) without padding, floor mode (AlexNet's 3x3 stride 2): y is planes x
  * ((h-k)/stride+1) x ((w-k)/stride+1). */
 int mv_maxpool2d_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, void* stream);
+/* ---- nn.Conv2d + folded norm + residual + activation in one launch (ResNet: models/resnet.py:58-163) ----------------
+ * mv_conv2d_bias_act_f32's convolution -- same geometry, groups (one launch per group), summation (one accumulator per output
+ * in ascending (channel, ky, kx) order from +0), workspace rules and mv_conv2d_needs_workspace() answers -- followed by the whole
+ * epilogue of mv_conv_norm_act_f32 in the same order: `+ bias` (may be NULL) -> folded norm (`affine`: MV_AFFINE_MUL_ADD rounds
+ * v * alpha, then + beta; MV_AFFINE_FMA is one fmaf(v, alpha, beta); alpha / beta (cout) are required iff affine != 0) ->
+ * `residual + v` (NULL, or shaped like y) -> activation (MV_ACT_*).  oracle/oracle.c::orc_conv2d_affine_act_f32 is the same
+ * chain, bit for bit, in the implicit form (k_conv_igemm_full; with neither norm nor residual the instances of
+ * mv_conv2d_bias_act_f32 run) and in the columns form (plain im2col into `workspace` + the pointwise GEMM) alike.
+ * ResNet's 7x7 stride-2 stem, its 3x3 convs at any stride / dilation and its 1x1 stride-2 downsample run here; 1x1 convs at
+ * stride 1 are mv_conv_norm_act_f32's (MV_CONV_PW1X1).  y must not overlap x, weight or residual (MV_ERR_INVALID_ARGUMENT);
+ * alignment: as for mv_conv2d_bias_act_f32 -- the residual is read with 16-byte loads where y is stored so and the residual
+ * pointer is 16-byte aligned, else element by element, never past h * w of a plane or the last channel; same bits.
+ * Bad arguments return a negative status before any launch; n == 0 is a successful no-op. */
+int mv_conv2d_affine_act_f32(const float* x, const float* weight, const float* bias, const float* alpha, const float* beta,
+                             const float* residual, float* y, int64_t n, int cin, int h, int wdt, int cout, int kh, int kw,
+                             int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w, int groups,
+                             int affine, int act, void* workspace, int64_t workspace_bytes, void* stream);
+/* nn.MaxPool2d(kernel_size=k, stride=stride, padding=pad), floor mode, dilation 1 (ResNet's stem: 3, 2, 1): y is planes x
+ * ((h+2*pad-k)/stride+1) x ((w+2*pad-k)/stride+1).  Padded positions never win (the window is clipped to the image);
+ * 0 <= pad <= k / 2, else MV_ERR_INVALID_ARGUMENT (torch's own rule), as is a non-positive output size.  NaN: torch's CPU kernel's
+ * rule -- m = -inf, then `if (v > m || isnan(v)) m = v` over the window in row-major order. */
+int mv_maxpool2d_pad_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, int pad, void* stream);
 
 /* ---- the step BEFORE the path: ImageClassification's tail, transforms/_presets.py:58-60 -------
  * convert_image_dtype(float) = image.to(float32).mul_(1/255) (_misc.py:286-288), then normalize =
