@@ -122,36 +122,7 @@ def conv2d_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     """Any nn.Conv2d [+ ReLU ...] of the small CNNs that the specialised kernels do not cover (AlexNet's 11x11 stride 4 and
     5x5: models/alexnet.py:22-33): implicit GEMM on the fp32 MFMA (mv_conv2d_bias_act_f32) -- the im2col columns are gathered
     from the input chunk by chunk into LDS and never reach HBM; no workspace unless mv_conv2d_needs_workspace() asks for one."""
-    if x.ndim != 4 or weight.ndim != 4:
-        raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
-    _lib.require_device(x)
-    _lib.require_device(weight, "weight")
-    _lib.require_f32_layer("conv2d_bias_act", x, weight)
-    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))  # noqa: E731
-    (sh, sw), (ph, pw), (dh, dw) = pair(stride), pair(padding), pair(dilation)
-    n, cin, h, w = (int(d) for d in x.shape)
-    cout, cg, kh, kw = (int(d) for d in weight.shape)
-    if cg * groups != cin or cout % groups:
-        raise RuntimeError(f"weight {tuple(weight.shape)} does not fit {cin} input channels in {groups} groups")
-    if activation not in _ACT_CODES:
-        raise ValueError(f"unknown activation {activation!r}")
-    oh, ow = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
-    if oh <= 0 or ow <= 0:
-        raise RuntimeError(f"Calculated output size too small - out_h: {oh} out_w: {ow}")
-    lib = _lib.load()
-    xc, wc, bc = x.contiguous(), weight.detach().contiguous(), _lib.f32_on(bias, x.device)
-    y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
-    if n == 0:
-        return y
-    nbytes = 0
-    need = int(lib.mv_conv2d_needs_workspace(n, cin, cout, h, w, kh, kw, sh, sw, ph, pw, dh, dw, groups))
-    if need == 1 or (need == 2 and _lib.switch("CONV2D_SMALL_LAUNCH_WORKSPACE")) or _lib.switch("CONV2D_COLUMNS_WORKSPACE"):
-        per_image = int(lib.mv_deform_conv2d_workspace_bytes(1, cin, h, w, kh, kw, sh, sw, ph, pw, dh, dw))
-        nbytes = max(1, min(n, _CONV_WORKSPACE_BYTES // max(per_image, 1))) * per_image
-    ws, ws_ptr, nbytes = _lib.workspace(nbytes, x.device)
-    _lib.launch(lib.mv_conv2d_bias_act_f32, xc, xc.data_ptr(), wc.data_ptr(), _lib.ptr(bc), y.data_ptr(), n, cin, h, w, cout, kh, kw,
-                sh, sw, ph, pw, dh, dw, groups, _ACT_CODES[activation], ws_ptr, nbytes)
-    return _lib.forward_only(y, "conv2d_bias_act", x, weight, bias)
+    return _conv2d("conv2d_bias_act", x, weight, bias, None, None, None, stride, padding, dilation, groups, None, activation)
 
 
 def adaptive_avg_pool2d(x: torch.Tensor, output_size: Sequence[int]) -> torch.Tensor:
@@ -232,6 +203,16 @@ def fold_batchnorm(weight, bias, running_mean, running_var, eps: float = 1e-5):
     return alpha, beta
 
 
+def _check_epilogue_terms(out_shape, bias, alpha, beta, residual) -> None:
+    """conv_norm_act's and conv2d_affine_act's epilogue tensors: a residual shaped like the output, per-channel terms of cout
+    elements."""
+    if residual is not None and tuple(residual.shape) != out_shape:
+        raise RuntimeError(f"residual of shape {tuple(residual.shape)} does not match the output {out_shape}")
+    for t, name in ((bias, "bias"), (alpha, "alpha"), (beta, "beta")):
+        if t is not None and t.numel() != out_shape[1]:
+            raise RuntimeError(f"{name} has {t.numel()} elements for {out_shape[1]} output channels")
+
+
 def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                   alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                   residual: Optional[torch.Tensor] = None, stride: int = 1, groups: int = 1, affine: Optional[str] = None,
@@ -265,11 +246,7 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     lib = _lib.load()
     xc, wc = x.contiguous(), weight.detach().contiguous()
     bc, ac, btc, rc = (_lib.f32_on(t, x.device) for t in (bias, alpha, beta, residual))
-    if rc is not None and tuple(rc.shape) != (n, cout, oh, ow):
-        raise RuntimeError(f"residual of shape {tuple(rc.shape)} does not match the output {(n, cout, oh, ow)}")
-    for t, name in ((bc, "bias"), (ac, "alpha"), (btc, "beta")):
-        if t is not None and t.numel() != cout:
-            raise RuntimeError(f"{name} has {t.numel()} elements for {cout} output channels")
+    _check_epilogue_terms((n, cout, oh, ow), bc, ac, btc, rc)
     y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
     p = _lib.ptr
     _lib.launch(lib.mv_conv_norm_act_f32, xc, kind, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
@@ -285,11 +262,19 @@ def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     activation as ONE launch (mv_conv2d_affine_act_f32): conv2d_bias_act's implicit GEMM -- any kernel size, stride, padding,
     dilation, groups; one ascending (c, ky, kx) chain per output -- with conv_norm_act's epilogue.  ResNet's 7x7 stride-2 stem,
     its 3x3 convs and its 1x1 stride-2 downsample (models/resnet.py); 1x1 convs at stride 1 are conv_norm_act's."""
+    return _conv2d("conv2d_affine_act", x, weight, bias, alpha, beta, residual, stride, padding, dilation, groups, affine, activation)
+
+
+def _conv2d(name: str, x, weight, bias, alpha, beta, residual, stride, padding, dilation, groups, affine, activation) -> torch.Tensor:
+    """The body of conv2d_bias_act and conv2d_affine_act (`name`): checks, the columns workspace when mv_conv2d_needs_workspace() or
+    a switch asks for one, ONE launch of mv_<name>_f32.  mv_conv2d_bias_act_f32 takes no alpha, beta, residual or affine code:
+    conv2d_bias_act passes None for them, and its bias's length is not checked (a known gap)."""
+    full = name == "conv2d_affine_act"
     if x.ndim != 4 or weight.ndim != 4:
         raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
     _lib.require_device(x)
     _lib.require_device(weight, "weight")
-    _lib.require_f32_layer("conv2d_affine_act", x, weight)
+    _lib.require_f32_layer(name, x, weight)
     pair = lambda v: (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))  # noqa: E731
     (sh, sw), (ph, pw), (dh, dw) = pair(stride), pair(padding), pair(dilation)
     n, cin, h, w = (int(d) for d in x.shape)
@@ -297,7 +282,7 @@ def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     if groups <= 0 or cg * groups != cin or cout % groups:
         raise RuntimeError(f"weight {tuple(weight.shape)} does not fit {cin} input channels in {groups} groups")
     if activation not in _ACT_CODES or affine not in _AFFINE_CODES:
-        raise ValueError(f"unknown activation {activation!r} / affine {affine!r}")
+        raise ValueError(f"unknown activation {activation!r} / affine {affine!r}" if full else f"unknown activation {activation!r}")
     if _AFFINE_CODES[affine] != 0 and (alpha is None or beta is None):
         raise ValueError(f"affine={affine!r} needs alpha and beta")
     oh, ow = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
@@ -306,11 +291,8 @@ def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     lib = _lib.load()
     xc, wc = x.contiguous(), weight.detach().contiguous()
     bc, ac, btc, rc = (_lib.f32_on(t, x.device) for t in (bias, alpha, beta, residual))
-    if rc is not None and tuple(rc.shape) != (n, cout, oh, ow):
-        raise RuntimeError(f"residual of shape {tuple(rc.shape)} does not match the output {(n, cout, oh, ow)}")
-    for t, name in ((bc, "bias"), (ac, "alpha"), (btc, "beta")):
-        if t is not None and t.numel() != cout:
-            raise RuntimeError(f"{name} has {t.numel()} elements for {cout} output channels")
+    if full:
+        _check_epilogue_terms((n, cout, oh, ow), bc, ac, btc, rc)
     y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
     if n == 0:
         return y
@@ -318,12 +300,13 @@ def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     need = int(lib.mv_conv2d_needs_workspace(n, cin, cout, h, w, kh, kw, sh, sw, ph, pw, dh, dw, groups))
     if need == 1 or (need == 2 and _lib.switch("CONV2D_SMALL_LAUNCH_WORKSPACE")) or _lib.switch("CONV2D_COLUMNS_WORKSPACE"):
         per_image = int(lib.mv_deform_conv2d_workspace_bytes(1, cin, h, w, kh, kw, sh, sw, ph, pw, dh, dw))
-        nbytes = max(1, min(n, _CONV_WORKSPACE_BYTES // max(per_image, 1))) * per_image
+        nbytes = _lib.columns_workspace_bytes(n, per_image, _CONV_WORKSPACE_BYTES)
     ws, ws_ptr, nbytes = _lib.workspace(nbytes, x.device)
     p = _lib.ptr
-    _lib.launch(lib.mv_conv2d_affine_act_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(), n, cin, h, w,
-                cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, _AFFINE_CODES[affine], _ACT_CODES[activation], ws_ptr, nbytes)
-    return _lib.forward_only(y, "conv2d_affine_act", x, weight, bias, alpha, beta, residual)
+    terms, codes = ((p(bc), p(ac), p(btc), p(rc)), (_AFFINE_CODES[affine], _ACT_CODES[activation])) if full else ((p(bc),), (_ACT_CODES[activation],))
+    _lib.launch(getattr(lib, "mv_" + name + "_f32"), xc, xc.data_ptr(), wc.data_ptr(), *terms, y.data_ptr(), n, cin, h, w, cout, kh, kw,
+                sh, sw, ph, pw, dh, dw, groups, *codes, ws_ptr, nbytes)
+    return _lib.forward_only(y, name, x, weight, bias, alpha, beta, residual)
 
 
 def inverted_residual_k_slices(n: int, cin: int, hidden: int, cout: int, h: int, w: int, stride: int) -> Tuple[int, int]:

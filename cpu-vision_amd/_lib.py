@@ -293,6 +293,12 @@ def workspace(nbytes: int, device):
     return ws, ws.data_ptr(), nbytes
 
 
+def columns_workspace_bytes(n: int, per_image: int, cap: int) -> int:
+    """Bytes of the im2col columns workspace for a batch of n: whole images, as many as stay below `cap`, one at the least (the
+    library then runs the batch in passes of as many images as the workspace holds)."""
+    return max(1, min(n, cap // max(per_image, 1))) * per_image
+
+
 def f32_on(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     """An optional tensor as a detached contiguous float32 tensor on `device` (a layer's bias, folded norm, residual ...).
     A tensor that already is one comes back itself: a new tensor object per call is measurable at batch 1."""

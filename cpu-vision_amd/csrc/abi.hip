@@ -714,75 +714,68 @@ void mv_fold_batchnorm(const float* weight, const float* bias, const float* mean
   }
 }
 
-static int deform_out(int h, int wdt, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int* oh, int* ow) {
-  if (h <= 0 || wdt <= 0 || kh <= 0 || kw <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad deform_conv2d shape (%d, %d) kernel (%d, %d)", h, wdt, kh, kw);
-  if (sh <= 0 || sw <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "stride_h: %d stride_w: %d", sh, sw);  // deform_conv2d_kernel.cpp:1004-1006
-  if (ph < 0 || pw < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "pad_h: %d pad_w: %d", ph, pw);
-  if (dh <= 0 || dw <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "dil_h: %d dil_w: %d", dh, dw);
-  *oh = (h + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
-  *ow = (wdt + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
-  if (*oh <= 0 || *ow <= 0)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "Calculated output size too small - out_h: %d out_w: %d", *oh, *ow);  // :1040-1045
+// Validates a convolution's kernel, stride, padding and dilation on its image (the reference's checks and messages,
+// deform_conv2d_kernel.cpp:1004-1045, for the ordinary convolutions as well) and sets g->oh / g->ow
+static int conv2d_geometry(Conv2dGeom* g) {
+  if (g->h <= 0 || g->w <= 0 || g->kh <= 0 || g->kw <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad deform_conv2d shape (%d, %d) kernel (%d, %d)", g->h, g->w, g->kh, g->kw);
+  if (g->sh <= 0 || g->sw <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "stride_h: %d stride_w: %d", g->sh, g->sw);  // :1004-1006
+  if (g->ph < 0 || g->pw < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "pad_h: %d pad_w: %d", g->ph, g->pw);
+  if (g->dh <= 0 || g->dw <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "dil_h: %d dil_w: %d", g->dh, g->dw);
+  g->oh = (g->h + 2 * g->ph - (g->dh * (g->kh - 1) + 1)) / g->sh + 1;
+  g->ow = (g->w + 2 * g->pw - (g->dw * (g->kw - 1) + 1)) / g->sw + 1;
+  if (g->oh <= 0 || g->ow <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "Calculated output size too small - out_h: %d out_w: %d", g->oh, g->ow);  // :1040-1045
   return MV_OK;
+}
+
+static bool channels_divide(const Conv2dGeom& g, int offset_groups) {
+  return g.cin > 0 && g.cout > 0 && g.groups > 0 && offset_groups > 0 && g.cin % g.groups == 0 && g.cout % g.groups == 0 && g.cin % offset_groups == 0;
+}
+
+// What the three convolution entries check first, in the order they report it: batch and channel counts, geometry, groups.
+// offset_groups == nullptr: an ordinary convolution
+static int check_conv2d(int64_t n, Conv2dGeom* g, const int* offset_groups) {
+  if (n < 0 || g->cin <= 0 || g->cout <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad %s shape n=%lld cin=%d cout=%d", offset_groups ? "deform_conv2d" : "conv2d", (long long)n, g->cin, g->cout);
+  if (int rc = conv2d_geometry(g)) return rc;
+  if (channels_divide(*g, offset_groups ? *offset_groups : 1)) return MV_OK;
+  if (offset_groups)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "channels (%d -> %d) must divide into %d weight groups and %d offset groups", g->cin, g->cout,
+                     g->groups, *offset_groups);
+  return set_error(MV_ERR_INVALID_ARGUMENT, "channels (%d -> %d) must divide into %d groups", g->cin, g->cout, g->groups);
 }
 
 int64_t mv_deform_conv2d_workspace_bytes(int64_t images, int cin, int h, int wdt, int kh, int kw, int stride_h, int stride_w,
                                          int pad_h, int pad_w, int dilation_h, int dilation_w) {
-  int oh = 0, ow = 0;
-  if (images <= 0 || cin <= 0 || deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow)) return 0;
-  return images * deform_workspace_bytes_per_image(cin, kh, kw, oh, ow);
+  Conv2dGeom g = {cin, h, wdt, /*cout=*/0, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, /*groups=*/1};
+  if (images <= 0 || cin <= 0 || conv2d_geometry(&g)) return 0;
+  return images * columns_bytes_per_image(g);
 }
 
 int mv_deform_conv2d_needs_workspace(int64_t images, int cin, int cout, int h, int wdt, int kh, int kw, int stride_h, int stride_w,
                                      int pad_h, int pad_w, int dilation_h, int dilation_w, int groups, int offset_groups) {
-  int oh = 0, ow = 0;
-  if (images <= 0 || cin <= 0 || cout <= 0 || groups <= 0 || offset_groups <= 0 || cin % groups || cout % groups || cin % offset_groups ||
-      deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow))
-    return 1;
-  if (tune_env("MV_DEFORM_UNFUSED")) return 1;
-  const int64_t wgs = deform_fused_workgroups(images, cin, cout, h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
-                                              groups, offset_groups);
-  return wgs == 0 ? 1 : (wgs >= kDeformFusedMinWorkgroups ? 0 : 2);
+  Conv2dGeom g = {cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups};
+  if (images <= 0 || !channels_divide(g, offset_groups) || conv2d_geometry(&g)) return kFormColumns;
+  return deform_conv2d_form(images, g, offset_groups);
 }
 
 int mv_deform_conv2d_f32(const float* x, const float* weight, const float* offset, const float* mask, const float* bias, float* y,
                          int64_t n, int cin, int h, int wdt, int cout, int kh, int kw, int stride_h, int stride_w, int pad_h,
                          int pad_w, int dilation_h, int dilation_w, int groups, int offset_groups, int use_mask, void* workspace,
                          int64_t workspace_bytes, void* stream) {
-  int oh = 0, ow = 0;
-  if (n < 0 || cin <= 0 || cout <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad deform_conv2d shape n=%lld cin=%d cout=%d", (long long)n, cin, cout);
-  if (int rc = deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow)) return rc;
-  if (groups <= 0 || offset_groups <= 0 || cin % groups || cout % groups || cin % offset_groups)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "channels (%d -> %d) must divide into %d weight groups and %d offset groups", cin, cout,
-                     groups, offset_groups);
+  Conv2dGeom g = {cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups};
+  if (int rc = check_conv2d(n, &g, &offset_groups)) return rc;
   if (n == 0) return MV_OK;
   if (!x || !weight || !offset || !y || (use_mask && !mask)) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
-  return launch_deform_conv2d(x, weight, offset, mask, bias, y, n, cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w,
-                              dilation_h, dilation_w, groups, offset_groups, use_mask, workspace, workspace_bytes, (hipStream_t)stream);
+  return launch_deform_conv2d(x, weight, offset, use_mask ? mask : nullptr, bias, y, n, g, offset_groups, workspace, workspace_bytes,
+                              (hipStream_t)stream);
 }
 
 int mv_conv2d_needs_workspace(int64_t n, int cin, int cout, int h, int wdt, int kh, int kw, int stride_h, int stride_w, int pad_h,
                               int pad_w, int dilation_h, int dilation_w, int groups) {
-  int oh = 0, ow = 0;
-  if (groups <= 0 || cin <= 0 || cin % groups || cout <= 0 || cout % groups) return 1;
-  if (deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow)) return 1;
-  if (!conv2d_implicit_supported(cin / groups, kh, kw, oh, ow)) return 1;
-  return conv2d_implicit_min_workgroups(n, cout / groups, oh, ow) * groups < 128 ? 2 : 0;  // 2: optional -- a handful of workgroups
-}
-
-int mv_conv2d_bias_act_f32(const float* x, const float* weight, const float* bias, float* y, int64_t n, int cin, int h, int wdt,
-                           int cout, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h,
-                           int dilation_w, int groups, int act, void* workspace, int64_t workspace_bytes, void* stream) {
-  int oh = 0, ow = 0;
-  if (n < 0 || cin <= 0 || cout <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv2d shape n=%lld cin=%d cout=%d", (long long)n, cin, cout);
-  if (int rc = deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow)) return rc;
-  if (groups <= 0 || cin % groups || cout % groups)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "channels (%d -> %d) must divide into %d groups", cin, cout, groups);
-  if (act < MV_ACT_NONE || act > MV_ACT_SILU) return set_error(MV_ERR_INVALID_ARGUMENT, "bad activation code %d", act);
-  if (n == 0) return MV_OK;
-  if (!x || !weight || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
-  return launch_deform_conv2d(x, weight, nullptr, nullptr, bias, y, n, cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w,
-                              dilation_h, dilation_w, groups, 1, 0, workspace, workspace_bytes, (hipStream_t)stream, act);
+  Conv2dGeom g = {cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups};
+  if (!channels_divide(g, 1) || conv2d_geometry(&g)) return kFormColumns;
+  return conv2d_form(n, g);
 }
 
 // [a, a + an) and [b, b + bn) floats share an element
@@ -791,27 +784,39 @@ static bool overlaps(const float* a, long long an, const float* b, long long bn)
   return a0 < b0 + (uintptr_t)bn * sizeof(float) && b0 < a0 + (uintptr_t)an * sizeof(float);
 }
 
+// the rest of the two ordinary entries' checks; check_overlap: mv_conv2d_affine_act_f32 only (host dispatch: a known gap)
+static int launch_checked_conv2d(const float* x, const float* weight, float* y, int64_t n, const Conv2dGeom& g, const Epilogue& e,
+                                 bool check_overlap, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n == 0) return MV_OK;
+  if (!x || !weight || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (e.affine != MV_AFFINE_NONE && (!e.alpha || !e.beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
+  const long long ny = (long long)n * g.cout * g.oh * g.ow;
+  if (check_overlap && (overlaps(y, ny, x, (long long)n * g.cin * g.h * g.w) ||
+                        overlaps(y, ny, weight, (long long)g.cout * (g.cin / g.groups) * g.kh * g.kw) || (e.res && overlaps(y, ny, e.res, ny))))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, weight or residual");
+  return launch_conv2d(x, weight, y, n, g, e, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int mv_conv2d_bias_act_f32(const float* x, const float* weight, const float* bias, float* y, int64_t n, int cin, int h, int wdt,
+                           int cout, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h,
+                           int dilation_w, int groups, int act, void* workspace, int64_t workspace_bytes, void* stream) {
+  Conv2dGeom g = {cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups};
+  if (int rc = check_conv2d(n, &g, nullptr)) return rc;
+  if (act < MV_ACT_NONE || act > MV_ACT_SILU) return set_error(MV_ERR_INVALID_ARGUMENT, "bad activation code %d", act);
+  return launch_checked_conv2d(x, weight, y, n, g, {bias, nullptr, nullptr, nullptr, MV_AFFINE_NONE, act}, false, workspace,
+                               workspace_bytes, stream);
+}
+
 int mv_conv2d_affine_act_f32(const float* x, const float* weight, const float* bias, const float* alpha, const float* beta,
                              const float* residual, float* y, int64_t n, int cin, int h, int wdt, int cout, int kh, int kw,
                              int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w, int groups,
                              int affine, int act, void* workspace, int64_t workspace_bytes, void* stream) {
-  int oh = 0, ow = 0;
-  if (n < 0 || cin <= 0 || cout <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv2d shape n=%lld cin=%d cout=%d", (long long)n, cin, cout);
-  if (int rc = deform_out(h, wdt, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, &oh, &ow)) return rc;
-  if (groups <= 0 || cin % groups || cout % groups)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "channels (%d -> %d) must divide into %d groups", cin, cout, groups);
+  Conv2dGeom g = {cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups};
+  if (int rc = check_conv2d(n, &g, nullptr)) return rc;
   if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
     return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
-  if (n == 0) return MV_OK;
-  if (!x || !weight || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
-  if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
-  const long long ny = (long long)n * cout * oh * ow;
-  if (overlaps(y, ny, x, (long long)n * cin * h * wdt) || overlaps(y, ny, weight, (long long)cout * (cin / groups) * kh * kw) ||
-      (residual && overlaps(y, ny, residual, ny)))
-    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, weight or residual");
-  const Epilogue e = {bias, affine ? alpha : nullptr, affine ? beta : nullptr, residual, affine, act};
-  return launch_deform_conv2d(x, weight, nullptr, nullptr, bias, y, n, cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w,
-                              dilation_h, dilation_w, groups, 1, 0, workspace, workspace_bytes, (hipStream_t)stream, act, &e);
+  return launch_checked_conv2d(x, weight, y, n, g, {bias, affine ? alpha : nullptr, affine ? beta : nullptr, residual, affine, act}, true,
+                               workspace, workspace_bytes, stream);
 }
 
 int mv_maxpool2d_pad_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, int pad, void* stream) {

@@ -20,6 +20,7 @@
 //   epilogue    each 32 x 32 tile is transposed through a wave-private LDS buffer so that a store instruction writes 8 full
 //               128-byte lines of 8 channel planes.
 // Zero padding of the image = zeros in the X chunk; k past K = zeros in both operands (an exact no-op of the chain).
+// Host side: launch_conv2d runs what conv2d_form says -- this kernel per weight group, or deform.hip's launch_conv2d_columns.
 //
 // mv_conv2d_affine_act_f32 (ResNet: the 7x7 stride-2 stem, the 3x3 convs, the 1x1 stride-2 downsample; models/resnet.py) runs the
 // same kernel with the FULL epilogue, k_conv_igemm<CT, PT, true> ("k_conv_igemm_full" in mv_last_kernel()): + bias -> folded norm
@@ -309,31 +310,43 @@ static int ig_launch(IgArgs& a, const IgEpi* e, int64_t n, hipStream_t s) {
   return check_launchf("k_conv_igemm<%dch,%dpx,implicit %dx%d>", 64 * CT, 64 * PT, a.taps / a.kw, a.kw);
 }
 
-// Workgroups the implicit kernel would launch with its smallest tiles (64 channels x 64 pixels): a launch of fewer than 128 is a
-// few workgroups walking all of K in sequence (AlexNet's conv2 at batch 1: 36 workgroups x 50 chunks) -- the columns form cuts
-// smaller tiles and is faster there, so mv_conv2d_needs_workspace() answers 2 (optional) and the caller may bring the workspace.
-long long conv2d_implicit_min_workgroups(int64_t n, int mg, int oh, int ow) {
-  return (long long)n * ((mg + 63) / 64) * (((long long)oh * ow + 63) / 64);
+// kFormColumns: sizes the implicit kernel's index arithmetic does not cover (and A/B in the tuning build: MV_CONV_COLUMNS).
+// kFormEither: the smallest tiles (64 channels x 64 pixels) would make fewer than 128 workgroups, a few of them walking all of K in
+// sequence (AlexNet's conv2 at batch 1: 36 workgroups x 50 chunks) -- the columns form cuts smaller tiles and is faster there.
+ConvForm conv2d_form(int64_t n, const Conv2dGeom& g) {
+  const long long K = (long long)(g.cin / g.groups) * g.kh * g.kw, HW = (long long)g.oh * g.ow;
+  if (!(K < 65536 && HW < (1 << 20) && g.ow < 4096 && g.kh * g.kw < 4096) || tune_env("MV_CONV_COLUMNS")) return kFormColumns;
+  const long long min_workgroups = (long long)n * ((g.cout / g.groups + 63) / 64) * ((HW + 63) / 64) * g.groups;
+  return min_workgroups < 128 ? kFormEither : kFormDirect;
 }
 
-bool conv2d_implicit_supported(int cg, int kh, int kw, int oh, int ow) {
-  const long long K = (long long)cg * kh * kw, HW = (long long)oh * ow;
-  return K < 65536 && HW < (1 << 20) && ow < 4096 && kh * kw < 4096 && !tune_env("MV_CONV_COLUMNS");
+int launch_conv2d(const float* x, const float* weight, float* y, int64_t n, const Conv2dGeom& g, const Epilogue& whole, void* workspace,
+                  int64_t workspace_bytes, hipStream_t s) {
+  if (takes_columns(conv2d_form(n, g), g, workspace, workspace_bytes))
+    return launch_conv2d_columns(x, weight, nullptr, nullptr, y, n, g, 1, whole, workspace, workspace_bytes, s);
+  // implicit GEMM: the K chunk's columns are gathered from the input while the GEMM stages them, so they never exist in HBM
+  const int cg = g.cin / g.groups, mg = g.cout / g.groups;
+  for (int i = 0; i < g.groups; ++i) {
+    const int rc = launch_conv2d_implicit(x + (size_t)i * cg * g.h * g.w, weight + (size_t)i * mg * cg * g.kh * g.kw,
+                                          y + (size_t)i * mg * g.oh * g.ow, n, g, group_epilogue(whole, g, i, 0), s);
+    if (rc) return rc;
+  }
+  return MV_OK;
 }
 
-int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, int cg, int h, int wd, int mg, int kh, int kw, int sh,
-                           int sw, int ph, int pw_, int dh, int dw, int oh, int ow, const Epilogue& e, hipStream_t s,
-                           int64_t x_img_stride, int64_t y_img_stride) {
-  if ((long long)cg * h * wd >= (1LL << 30)) return set_error(MV_ERR_UNSUPPORTED, "conv2d (implicit GEMM): one image of a group has 2^30 elements or more");
+int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, const Conv2dGeom& g, const Epilogue& e, hipStream_t s) {
+  const int cg = g.cin / g.groups, mg = g.cout / g.groups, kw = g.kw;
+  const int64_t y_img_stride = (int64_t)g.cout * g.oh * g.ow;
+  if ((long long)cg * g.h * g.w >= (1LL << 30)) return set_error(MV_ERR_UNSUPPORTED, "conv2d (implicit GEMM): one image of a group has 2^30 elements or more");
   // bias + activation alone keeps the instances of mv_conv2d_bias_act_f32; a norm or a residual takes the ones with the full epilogue
   const bool full = e.affine != 0 || e.res != nullptr;
   IgArgs a = {};
   a.x = x, a.w = w, a.bias = e.bias, a.y = y;
-  a.x_img_stride = x_img_stride, a.y_img_stride = y_img_stride;
-  a.mg = mg, a.K = cg * kh * kw, a.HW = oh * ow;
-  a.ih = h, a.iw = wd, a.ow = ow, a.kw = kw, a.taps = kh * kw, a.sh = sh, a.sw = sw, a.ph = ph, a.pw = pw_, a.dh = dh, a.dw = dw;
+  a.x_img_stride = (int64_t)g.cin * g.h * g.w, a.y_img_stride = y_img_stride;
+  a.mg = mg, a.K = cg * g.kh * kw, a.HW = g.oh * g.ow;
+  a.ih = g.h, a.iw = g.w, a.ow = g.ow, a.kw = kw, a.taps = g.kh * kw, a.sh = g.sh, a.sw = g.sw, a.ph = g.ph, a.pw = g.pw, a.dh = g.dh, a.dw = g.dw;
   auto magic = [](unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; };
-  a.m_taps = magic((unsigned)a.taps), a.m_kw = magic((unsigned)kw), a.m_ow = magic((unsigned)ow);
+  a.m_taps = magic((unsigned)a.taps), a.m_kw = magic((unsigned)kw), a.m_ow = magic((unsigned)g.ow);
   a.chunks = (a.K + kIgK - 1) / kIgK;
   a.act = e.act;
   a.vec_w = (a.K % 4 == 0) && ((uintptr_t)w % 16 == 0);

@@ -9,8 +9,9 @@
 //      accumulator per output in ascending k, bias in the epilogue), reading the group's channel slice of `columns`.
 // `columns` lives in caller-provided workspace ([images][cin*kh*kw][oh*ow] floats); the batch is processed in passes of
 // as many images as the workspace holds (the reference does the same with up to 32 "parallel images").
-// This two-kernel form serves the plain im2col convolutions (mv_conv2d_bias_act_f32) and the deformable geometries whose
-// tiles do not fit the fused kernel of deform_fused.hip (more than 40 taps, huge stride x dilation windows).
+// This two-kernel form (launch_conv2d_columns) serves the plain im2col convolutions (conv_igemm.hip's launch_conv2d, with a null
+// offset) and the deformable geometries whose tiles do not fit the fused kernel of deform_fused.hip (more than 40 taps, huge
+// stride x dilation windows); launch_deform_conv2d chooses between the two deformable forms (deform_conv2d_form).
 #include "mv_common.h"
 #include "mv_conv.h"
 #include "mv_deform.h"
@@ -225,76 +226,29 @@ __global__ __launch_bounds__(256) void k_deform_im2col_lds(const DeformLdsArgs A
   }
 }
 
-int64_t deform_workspace_bytes_per_image(int cin, int kh, int kw, int oh, int ow) {
-  return (int64_t)sizeof(float) * cin * kh * kw * oh * ow;
-}
-
-// offset == nullptr: ordinary convolution (plain im2col); act: MV_ACT_* applied after the bias.  epi (ordinary convolution only:
-// mv_conv2d_affine_act_f32): the whole-tensor epilogue -- bias, alpha, beta, residual, affine, act; replaces `bias` and `act` --
-// which every group's launch receives at the group's first channel, in the implicit and in the columns form alike.
-int launch_deform_conv2d(const float* x, const float* weight, const float* offset, const float* mask, const float* bias, float* y,
-                         int64_t n, int cin, int h, int wd, int cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                         int groups, int offset_groups, int use_mask, void* workspace, int64_t workspace_bytes, hipStream_t s, int act,
-                         const Epilogue* epi) {
-  Epilogue whole = {bias, nullptr, nullptr, nullptr, 0, act};
-  if (epi != nullptr && offset == nullptr) whole = *epi;
-  // group g's terms; the residual of images from b0 on (shaped like y)
-  auto group_epilogue = [&](int g, int mg, int64_t b0, int64_t ohw) {
-    Epilogue e = whole;
-    if (e.bias) e.bias += (size_t)g * mg;
-    if (e.alpha) e.alpha += (size_t)g * mg;
-    if (e.beta) e.beta += (size_t)g * mg;
-    if (e.res) e.res += ((size_t)b0 * cout + (size_t)g * mg) * ohw;
-    return e;
-  };
-  const int oh = (h + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
-  const int ow = (wd + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
-  // deformable sampling: the fused kernel (deform_fused.hip) whenever its tiles fit -- every usual DCN layer; no workspace.
-  // Launches too small to fill the chip with it use the two kernels below if the caller brought a workspace
-  if (offset != nullptr && !tune_env("MV_DEFORM_UNFUSED")) {
-    const int64_t wgs = deform_fused_workgroups(n, cin, cout, h, wd, kh, kw, sh, sw, ph, pw, dh, dw, groups, offset_groups);
-    const bool have_ws = workspace != nullptr && workspace_bytes >= deform_workspace_bytes_per_image(cin, kh, kw, oh, ow);
-    if (wgs > 0 && (wgs >= kDeformFusedMinWorkgroups || !have_ws))
-      return launch_deform_fused(x, weight, offset, mask, bias, y, n, cin, h, wd, cout, kh, kw, sh, sw, ph, pw, dh, dw, groups,
-                                 offset_groups, use_mask, s, act);
-  }
-  // ordinary convolution (mv_conv2d_bias_act_f32): implicit GEMM -- the K chunk's columns are gathered from the input while the
-  // GEMM stages them, so they never exist in HBM and the workspace is not used (the columns form below remains for sizes the
-  // implicit kernel's index arithmetic does not cover, and for A/B in the tuning build: MV_CONV_COLUMNS)
-  const bool small_launch_with_workspace = offset == nullptr && conv2d_implicit_min_workgroups(n, cout / groups, oh, ow) * groups < 128 &&
-                                           workspace != nullptr && workspace_bytes >= deform_workspace_bytes_per_image(cin, kh, kw, oh, ow);
-  if (offset == nullptr && conv2d_implicit_supported(cin / groups, kh, kw, oh, ow) && !small_launch_with_workspace) {
-    const int cg = cin / groups, mg = cout / groups;
-    for (int g = 0; g < groups; ++g) {
-      const Epilogue e = group_epilogue(g, mg, 0, (int64_t)oh * ow);
-      const int rc = launch_conv2d_implicit(x + (size_t)g * cg * h * wd, weight + (size_t)g * mg * cg * kh * kw, y + (size_t)g * mg * oh * ow, n,
-                                            cg, h, wd, mg, kh, kw, sh, sw, ph, pw, dh, dw, oh, ow, e, s, (int64_t)cin * h * wd,
-                                            (int64_t)cout * oh * ow);
-      if (rc) return rc;
-    }
-    return MV_OK;
-  }
-  const int64_t per_image = deform_workspace_bytes_per_image(cin, kh, kw, oh, ow);
+int launch_conv2d_columns(const float* x, const float* weight, const float* offset, const float* mask, float* y, int64_t n,
+                          const Conv2dGeom& g, int offset_groups, const Epilogue& whole, void* workspace, int64_t workspace_bytes,
+                          hipStream_t s) {
+  const int64_t per_image = columns_bytes_per_image(g);
   if (workspace == nullptr || workspace_bytes < per_image)
     return set_error(MV_ERR_INVALID_ARGUMENT, "deform_conv2d: workspace of at least %lld bytes (one image's columns) needed, got %lld",
                      (long long)per_image, (long long)workspace_bytes);
   int64_t pass = workspace_bytes / per_image;
   if (pass > n) pass = n;
   if (pass > 65535) pass = 65535;
-  const int taps = kh * kw, cg = cin / groups, mg = cout / groups;
-  const int64_t ohw = (int64_t)oh * ow;
+  const int taps = g.kh * g.kw, cg = g.cin / g.groups, mg = g.cout / g.groups;
+  const int64_t ohw = (int64_t)g.oh * g.ow;
   for (int64_t b0 = 0; b0 < n; b0 += pass) {
     const int64_t nb = (n - b0 < pass) ? n - b0 : pass;
     DeformArgs a = {};
-    a.x = x + (size_t)b0 * cin * h * wd;
+    a.x = x + (size_t)b0 * g.cin * g.h * g.w;
     a.offset = offset ? offset + (size_t)b0 * offset_groups * 2 * taps * ohw : nullptr;
-    a.mask = use_mask ? mask + (size_t)b0 * offset_groups * taps * ohw : nullptr;
+    a.mask = mask ? mask + (size_t)b0 * offset_groups * taps * ohw : nullptr;
     a.col = static_cast<float*>(workspace);
-    a.cin = cin, a.h = h, a.wd = wd, a.kh = kh, a.kw = kw, a.sh = sh, a.sw = sw, a.ph = ph, a.pw = pw, a.dh = dh, a.dw = dw;
-    a.oh = oh, a.ow = ow, a.offset_groups = offset_groups, a.use_mask = use_mask;
-    if (!offset) a.offset_groups = 1;
+    a.cin = g.cin, a.h = g.h, a.wd = g.w, a.kh = g.kh, a.kw = g.kw, a.sh = g.sh, a.sw = g.sw, a.ph = g.ph, a.pw = g.pw, a.dh = g.dh, a.dw = g.dw;
+    a.oh = g.oh, a.ow = g.ow, a.offset_groups = offset ? offset_groups : 1, a.use_mask = mask != nullptr;
     // channels per thread: as many as keeps >= ~500k threads in flight (the per-tap work is amortised over them)
-    const int cog = cin / a.offset_groups;
+    const int cog = g.cin / a.offset_groups;
     a.cchunks = 1;
     while (a.cchunks < cog && nb * a.offset_groups * a.cchunks * taps * ohw < 500000) a.cchunks *= 2;
     if (a.cchunks > cog) a.cchunks = cog;
@@ -305,23 +259,22 @@ int launch_deform_conv2d(const float* x, const float* weight, const float* offse
     // deformable sampling: the LDS-window kernel when its window fits (every usual DCN layer); plain im2col and exotic
     // geometries (huge stride x dilation) keep the direct gather
     DeformLdsArgs l = {};
-    l.win_h = (kDefTH - 1) * sh + (kh - 1) * dh + 2 + 2 * kDefMargin;
-    l.win_w = (kDefTW - 1) * sw + (kw - 1) * dw + 2 + 2 * kDefMargin;
+    l.win_h = (kDefTH - 1) * g.sh + (g.kh - 1) * g.dh + 2 + 2 * kDefMargin;
+    l.win_w = (kDefTW - 1) * g.sw + (g.kw - 1) * g.dw + 2 + 2 * kDefMargin;
     l.win_pitch = l.win_w | 1;
     const size_t lds = sizeof(float) * (size_t)kDefCB * l.win_h * l.win_pitch;
     const bool use_lds = offset != nullptr && lds <= 64 * 1024 && !tune_env("MV_DEFORM_DIRECT");
     if (use_lds) {
       l.x = a.x, l.offset = a.offset, l.mask = a.mask, l.col = a.col;
-      l.cin = cin, l.h = h, l.wd = wd, l.kh = kh, l.kw = kw, l.sh = sh, l.sw = sw, l.ph = ph, l.pw = pw, l.dh = dh, l.dw = dw;
-      l.oh = oh, l.ow = ow, l.offset_groups = offset_groups, l.use_mask = use_mask;
-      l.tiles_x = (ow + kDefTW - 1) / kDefTW, l.tiles_y = (oh + kDefTH - 1) / kDefTH;
+      l.cin = a.cin, l.h = a.h, l.wd = a.wd, l.kh = a.kh, l.kw = a.kw, l.sh = a.sh, l.sw = a.sw, l.ph = a.ph, l.pw = a.pw, l.dh = a.dh, l.dw = a.dw;
+      l.oh = a.oh, l.ow = a.ow, l.offset_groups = offset_groups, l.use_mask = a.use_mask;
+      l.tiles_x = (g.ow + kDefTW - 1) / kDefTW, l.tiles_y = (g.oh + kDefTH - 1) / kDefTH;
       // channel ranges: enough workgroups to fill the chip several times over (each re-reads the tile's offsets once per chunk)
-      const int cog_l = cin / offset_groups;
       const long long tiles_all = (long long)nb * offset_groups * l.tiles_x * l.tiles_y;
-      int chunks = (cog_l + kDefCB - 1) / kDefCB, per = chunks;  // chunks of kDefCB channels per workgroup
+      int chunks = (cog + kDefCB - 1) / kDefCB, per = chunks;  // chunks of kDefCB channels per workgroup
       while (per > 1 && tiles_all * ((chunks + per - 1) / per) < 4096) per = (per + 1) / 2;
       l.cper = per * kDefCB;
-      l.csplit = (cog_l + l.cper - 1) / l.cper;
+      l.csplit = (cog + l.cper - 1) / l.cper;
       const long long blocks = tiles_all * l.csplit;
       if (blocks > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "deform_conv2d: pass too large for one launch");
       if (lds > 48 * 1024)
@@ -332,15 +285,31 @@ int launch_deform_conv2d(const float* x, const float* weight, const float* offse
       hipLaunchKernelGGL(k_deform_im2col, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, a);
       if (int rc = check_launch("k_deform_im2col")) return rc;
     }
-    for (int g = 0; g < groups; ++g) {
-      const Epilogue e = group_epilogue(g, mg, b0, ohw);
-      const int rc = launch_conv1x1(a.col + (size_t)g * cg * taps * ohw, weight + (size_t)g * mg * cg * taps,
-                                    y + ((size_t)b0 * cout + (size_t)g * mg) * ohw, nb, cg * taps, ohw, mg, e, s,
-                                    (int64_t)cin * taps * ohw, (int64_t)cout * ohw, /*allow_k_slices=*/false);
+    for (int i = 0; i < g.groups; ++i) {
+      const int rc = launch_conv1x1(a.col + (size_t)i * cg * taps * ohw, weight + (size_t)i * mg * cg * taps,
+                                    y + ((size_t)b0 * g.cout + (size_t)i * mg) * ohw, nb, cg * taps, ohw, mg, group_epilogue(whole, g, i, b0), s,
+                                    (int64_t)g.cin * taps * ohw, (int64_t)g.cout * ohw, /*allow_k_slices=*/false);
       if (rc) return rc;
     }
   }
   return MV_OK;
+}
+
+// Which form a deformable convolution runs in: the fused kernel (deform_fused.hip) whenever its tiles fit -- every usual DCN layer.
+// One workgroup per CU: a launch of fewer than 256 fills the chip better in the columns form, which cuts the GEMM into smaller
+// tiles (4 x 512 x 32 x 32 -> 512: 128 workgroups, 0.44 ms fused, 0.30 ms with the workspace), if the caller brought a workspace.
+ConvForm deform_conv2d_form(int64_t n, const Conv2dGeom& g, int offset_groups) {
+  if (tune_env("MV_DEFORM_UNFUSED")) return kFormColumns;
+  const int64_t wgs = deform_fused_workgroups(n, g, offset_groups);
+  return wgs == 0 ? kFormColumns : (wgs >= 256 ? kFormDirect : kFormEither);
+}
+
+int launch_deform_conv2d(const float* x, const float* weight, const float* offset, const float* mask, const float* bias, float* y,
+                         int64_t n, const Conv2dGeom& g, int offset_groups, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+  if (takes_columns(deform_conv2d_form(n, g, offset_groups), g, workspace, workspace_bytes))
+    return launch_conv2d_columns(x, weight, offset, mask, y, n, g, offset_groups, {bias, nullptr, nullptr, nullptr, 0, MV_ACT_NONE},
+                                 workspace, workspace_bytes, s);
+  return launch_deform_fused(x, weight, offset, mask, bias, y, n, g, offset_groups, s);
 }
 
 }  // namespace mv

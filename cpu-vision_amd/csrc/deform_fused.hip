@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "mv_common.h"
+#include "mv_deform.h"
 #include "mv_epilogue.h"
 
 namespace mv {
@@ -546,7 +547,7 @@ __global__ __launch_bounds__(512, 2) void k_deform_fused(const DeformFusedArgs A
   }
 }
 
-// ---- geometry -> tiles: one place for the launcher and for deform_fused_supported()
+// ---- geometry -> tiles: one place for the launcher and for deform_fused_workgroups()
 struct FusedPlan {
   bool ok;
   int mw, cb, kc, kcp, kq, wp, win_h, win_w, win_pitch, xs_off, win_off, par_off;
@@ -561,22 +562,21 @@ static int gcd_int(int a, int b) {
   return a;
 }
 
-static FusedPlan fused_plan(int cin, int cout, int h, int wd, int kh, int kw, int sh, int sw, int dh, int dw, int groups,
-                            int offset_groups) {
+static FusedPlan fused_plan(const Conv2dGeom& g, int offset_groups) {
   FusedPlan p = {};
-  const int taps = kh * kw, cg = cin / groups, mg = cout / groups, cog = cin / offset_groups;
+  const int taps = g.kh * g.kw, cg = g.cin / g.groups, mg = g.cout / g.groups, cog = g.cin / offset_groups;
   p.mw = mg <= 32 ? 1 : (mg <= 64 ? 2 : (mg <= 128 ? 4 : 8));
   if (const char* e = tune_env("MV_DF_MW")) p.mw = (atoi(e) == 4 && p.mw == 8) ? 4 : p.mw;
   const int px = fused_px(p.mw), th = px / kFTW;
-  p.win_h = (th - 1) * sh + (kh - 1) * dh + 2 + 2 * kFMargin;
-  p.win_w = (kFTW - 1) * sw + (kw - 1) * dw + 2 + 2 * kFMargin;
+  p.win_h = (th - 1) * g.sh + (g.kh - 1) * g.dh + 2 + 2 * kFMargin;
+  p.win_w = (kFTW - 1) * g.sw + (g.kw - 1) * g.dw + 2 + 2 * kFMargin;
   p.win_pitch = p.win_w | 1;
   if (taps > kFKMax || (long long)p.win_h * p.win_w > kFWinU * 256) return p;
   const int common = gcd_int(cg, cog);  // a chunk stays inside one weight group and one offset group
   int cb = 8;
   const int positions = (p.win_h * p.win_w + 255) / 256;  // window positions per producer thread, x cb channels each
   while (cb > 1 && (common % cb || cb * taps > kFKMax || cb * positions > kFWinU)) cb /= 2;
-  if ((long long)cg * h * wd >= 0x1fffffffLL || (long long)p.mw * 32 * cg * taps >= 0x1fffffffLL) return p;  // byte offsets stay below 2^31
+  if ((long long)cg * g.h * g.w >= 0x1fffffffLL || (long long)p.mw * 32 * cg * taps >= 0x1fffffffLL) return p;  // byte offsets stay below 2^31
   p.cb = cb;
   p.kc = cb * taps, p.kcp = (p.kc + 1) & ~1, p.kq = (p.kc + 3) / 4, p.wp = fused_w_pitch(p.kcp);
   const int wl = ((p.mw * 32 * p.wp + 3) & ~3) + 4;                                              // x 2 buffers, + a spare slot
@@ -590,20 +590,12 @@ static FusedPlan fused_plan(int cin, int cout, int h, int wd, int kh, int kw, in
   return p;
 }
 
-bool deform_fused_supported(int cin, int cout, int h, int wd, int kh, int kw, int sh, int sw, int dh, int dw, int groups,
-                            int offset_groups) {
-  return fused_plan(cin, cout, h, wd, kh, kw, sh, sw, dh, dw, groups, offset_groups).ok;
-}
-
-// workgroups of the fused launch (0: unsupported).  One workgroup per CU: below 256 the two-kernel form, which cuts the GEMM into
-// smaller tiles, fills the chip better (4 x 512 x 32 x 32 -> 512: 128 workgroups, 0.44 ms fused, 0.30 ms with the workspace)
-int64_t deform_fused_workgroups(int64_t n, int cin, int cout, int h, int wd, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                                int dw, int groups, int offset_groups) {
-  const FusedPlan p = fused_plan(cin, cout, h, wd, kh, kw, sh, sw, dh, dw, groups, offset_groups);
+// workgroups of the fused launch (0: unsupported)
+int64_t deform_fused_workgroups(int64_t n, const Conv2dGeom& g, int offset_groups) {
+  const FusedPlan p = fused_plan(g, offset_groups);
   if (!p.ok) return 0;
-  const int oh = (h + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, ow = (wd + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
   const int th = fused_px(p.mw) / kFTW;
-  return n * ((oh + th - 1) / th) * ((ow + kFTW - 1) / kFTW) * groups * ((cout / groups + p.mw * 32 - 1) / (p.mw * 32));
+  return n * ((g.oh + th - 1) / th) * ((g.ow + kFTW - 1) / kFTW) * g.groups * ((g.cout / g.groups + p.mw * 32 - 1) / (p.mw * 32));
 }
 
 template <int MW>
@@ -622,24 +614,22 @@ static int fused_launch(const DeformFusedArgs& a, const FusedPlan& p, long long 
 }
 
 int launch_deform_fused(const float* x, const float* weight, const float* offset, const float* mask, const float* bias, float* y,
-                        int64_t n, int cin, int h, int wd, int cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                        int groups, int offset_groups, int use_mask, hipStream_t s, int act) {
-  const FusedPlan p = fused_plan(cin, cout, h, wd, kh, kw, sh, sw, dh, dw, groups, offset_groups);
+                        int64_t n, const Conv2dGeom& g, int offset_groups, hipStream_t s) {
+  const FusedPlan p = fused_plan(g, offset_groups);
   if (!p.ok) return set_error(MV_ERR_UNSUPPORTED, "deform_conv2d: geometry outside the fused kernel's tiles");
   DeformFusedArgs a = {};
-  a.x = x, a.w = weight, a.offset = offset, a.mask = use_mask ? mask : nullptr, a.bias = bias, a.y = y;
-  a.cin = cin, a.cout = cout, a.h = h, a.wd = wd, a.kh = kh, a.kw = kw, a.sh = sh, a.sw = sw, a.ph = ph, a.pw = pw, a.dh = dh, a.dw = dw;
-  a.oh = (h + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
-  a.ow = (wd + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
-  a.groups = groups, a.offset_groups = offset_groups, a.act = act;
+  a.x = x, a.w = weight, a.offset = offset, a.mask = mask, a.bias = bias, a.y = y;
+  a.cin = g.cin, a.cout = g.cout, a.h = g.h, a.wd = g.w, a.kh = g.kh, a.kw = g.kw, a.sh = g.sh, a.sw = g.sw, a.ph = g.ph, a.pw = g.pw, a.dh = g.dh, a.dw = g.dw;
+  a.oh = g.oh, a.ow = g.ow;
+  a.groups = g.groups, a.offset_groups = offset_groups, a.act = MV_ACT_NONE;
   const int th = fused_px(p.mw) / kFTW;
   a.tiles_x = (a.ow + kFTW - 1) / kFTW, a.tiles_y = (a.oh + th - 1) / th;
-  a.mblocks = (cout / groups + p.mw * 32 - 1) / (p.mw * 32);
+  a.mblocks = (g.cout / g.groups + p.mw * 32 - 1) / (p.mw * 32);
   a.cb = p.cb, a.kc = p.kc, a.kcp = p.kcp, a.kq = p.kq, a.wp = p.wp;
   a.win_h = p.win_h, a.win_w = p.win_w, a.win_pitch = p.win_pitch;
   a.xs_off = p.xs_off, a.win_off = p.win_off, a.par_off = p.par_off;
   a.vec_y = (a.ow % 4 == 0) && ((uintptr_t)y % 16 == 0);
-  const long long blocks = (long long)n * a.tiles_y * a.tiles_x * groups * a.mblocks;
+  const long long blocks = (long long)n * a.tiles_y * a.tiles_x * g.groups * a.mblocks;
   if (blocks > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "deform_conv2d: batch too large for one launch");
   if (blocks == 0) return MV_OK;
   if (p.mw == 1) return fused_launch<1>(a, p, blocks, s);

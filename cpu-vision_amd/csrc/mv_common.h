@@ -252,24 +252,13 @@ int launch_dwpc3x3(const float* x, const float* w, float* y, int64_t n, int c, i
 int launch_conv3x3_smallcin(const float* x, const float* w, float* y, int64_t n, int cin, int h, int wd, int cout, int stride,
                             const Epilogue& e, hipStream_t s);
 // x_img_stride / y_img_stride: floats between consecutive images (0 = dense: cin*hw / cout*hw); a channel slice of a
-// wider tensor passes the full tensor's strides (deform_conv2d's weight groups)
+// wider tensor passes the full tensor's strides (the weight groups of the columns form, launch_conv2d_columns)
 int launch_conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e,
                    hipStream_t s, int64_t x_img_stride = 0, int64_t y_img_stride = 0, bool allow_k_slices = true);
-// any nn.Conv2d geometry as an implicit GEMM (no columns in HBM, no workspace); one weight group per call.  e: bias + activation
-// (k_conv_igemm), or with a norm / residual the full epilogue (k_conv_igemm_full); e.res is strided like y
-bool conv2d_implicit_supported(int cg, int kh, int kw, int oh, int ow);
-int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, int cg, int h, int wd, int mg, int kh, int kw, int sh,
-                           int sw, int ph, int pw, int dh, int dw, int oh, int ow, const Epilogue& e, hipStream_t s,
-                           int64_t x_img_stride, int64_t y_img_stride);
 // the K slicing launch_conv1x1 applies to this shape: slices == 1 -> one ascending-k chain per output; otherwise `slices`
 // chains over `slice_len` channels each (the last may be shorter), added in ascending slice order
 void conv1x1_plan(int64_t n, int cin, int64_t hw, int cout, int* slices, int* slice_len);
-// deform_conv2d forward (deform.hip)
-int64_t deform_workspace_bytes_per_image(int cin, int kh, int kw, int oh, int ow);
-int launch_deform_conv2d(const float* x, const float* weight, const float* offset, const float* mask, const float* bias, float* y,
-                         int64_t n, int cin, int h, int wd, int cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                         int groups, int offset_groups, int use_mask, void* workspace, int64_t workspace_bytes, hipStream_t s, int act = 0,
-                         const Epilogue* epi = nullptr);
+// nn.Conv2d of any geometry and deform_conv2d: mv_conv.h, mv_deform.h
 int launch_maxpool2d(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, hipStream_t s);
 int launch_maxpool2d_pad(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s);
 

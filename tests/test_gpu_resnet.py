@@ -8,7 +8,7 @@ from torch import nn
 
 pytestmark = pytest.mark.gpu
 
-from cpu_vision_amd import _lib, resnet  # noqa: E402
+from cpu_vision_amd import _layers, _lib, resnet  # noqa: E402
 from cpu_vision_amd import functional as F  # noqa: E402
 from cpu_vision_amd.mobilenet import FrozenBatchNorm2d  # noqa: E402
 from oracle import ref  # noqa: E402
@@ -160,21 +160,34 @@ def test_nan_and_inf_come_out_where_the_oracle_puts_them(small_launch_workspace,
             np.testing.assert_array_equal(got, want, err_msg=f"{affine} {act}")
 
 
-def test_with_and_without_the_optional_workspace_same_bits(monkeypatch):
-    n, cin, h, w, cout = 1, 64, 14, 14, 64
-    assert _lib.load().mv_conv2d_needs_workspace(n, cin, cout, h, w, 3, 3, 1, 1, 1, 1, 1, 1, 1) == 2
-    x, wt, a, b, _ = _data(3600, n, cin, h, w, cout, 3, 3)
+def _with_and_without_the_optional_workspace(monkeypatch, n, cin, h, w, cout, groups, affines):
+    assert _lib.load().mv_conv2d_needs_workspace(n, cin, cout, h, w, 3, 3, 1, 1, 1, 1, 1, 1, groups) == 2
+    x, wt, a, b, _ = _data(3600, n, cin, h, w, cout, 3, 3, groups)
     res = philox_f32(3606, (n, cout, h, w)) - 0.5
     out = {}
     for flag, kernel in ((False, "k_conv_igemm_full"), (True, "k_conv1x1")):
         monkeypatch.setattr(F, "CONV2D_SMALL_LAUNCH_WORKSPACE", flag)
-        for affine in AFFINES:
-            got, want = _both(x, wt, None, a, b, res, 1, 1, 1, 1, affine, "relu")
+        for affine in affines:
+            got, want = _both(x, wt, None, a, b, res, 1, 1, 1, groups, affine, "relu")
             assert _lib.last_kernel().startswith(kernel), _lib.last_kernel()
             np.testing.assert_array_equal(got, want, err_msg=f"{affine} workspace={flag}")
             out[flag, affine] = got
-    for affine in AFFINES:
+    for affine in affines:
         np.testing.assert_array_equal(out[False, affine], out[True, affine])
+
+
+def test_with_and_without_the_optional_workspace_same_bits(monkeypatch):
+    _with_and_without_the_optional_workspace(monkeypatch, 1, 64, 14, 14, 64, 1, AFFINES)
+
+
+def test_grouped_columns_form_in_several_passes_with_a_residual(monkeypatch):
+    """Two weight groups, and a workspace of exactly one image's columns: three passes, in which the residual (like y) advances
+    per pass and per group at once."""
+    n, cin, h, w, cout = 3, 4, 5, 5, 6
+    per_image = _lib.load().mv_deform_conv2d_workspace_bytes(1, cin, h, w, 3, 3, 1, 1, 1, 1, 1, 1)
+    assert per_image == cin * 9 * h * w * 4
+    monkeypatch.setattr(_layers, "_CONV_WORKSPACE_BYTES", per_image)
+    _with_and_without_the_optional_workspace(monkeypatch, n, cin, h, w, cout, 2, ("fma",))
 
 
 def test_python_checks():
