@@ -254,6 +254,45 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return _lib.forward_only(y, "conv_norm_act", x, weight, bias, alpha, beta, residual)
 
 
+def conv1x1_upsample_add(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                         alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                         top: Optional[torch.Tensor] = None, affine: Optional[str] = None,
+                         activation: Optional[str] = None) -> torch.Tensor:
+    """FeaturePyramidNetwork's top-down merge (ops/feature_pyramid_network.py:  inner_block(x) + F.interpolate(last_inner,
+    size=feat_shape, mode="nearest")) as ONE launch (mv_conv1x1_upsample_add_f32): conv_norm_act's pointwise kernel, whose
+    epilogue reads `top` (N, Cout, any H', W') at torch's nearest source index of each output pixel where conv_norm_act reads a
+    residual -- no upsampled map and no separate sum in memory.  Same bits as conv_norm_act(..., residual=interpolate(top,
+    size=x.shape[-2:], mode="nearest")); summation order: conv1x1_k_slices.  `top` is required (conv_norm_act is the call
+    without one)."""
+    if x.ndim != 4 or weight.ndim != 4:
+        raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if top is None:
+        raise ValueError("conv1x1_upsample_add needs `top`; conv_norm_act is the pointwise conv without a top-down map")
+    n, cin, h, w = (int(d) for d in x.shape)
+    cout, cg, kh, kw = (int(d) for d in weight.shape)
+    if (kh, kw) != (1, 1) or cg != cin:
+        raise NotImplementedError(f"conv1x1_upsample_add covers pointwise 1x1 convs; got weight {tuple(weight.shape)} on {cin} input channels")
+    if activation not in _ACT_CODES or affine not in _AFFINE_CODES:
+        raise ValueError(f"unknown activation {activation!r} / affine {affine!r}")
+    if _AFFINE_CODES[affine] != 0 and (alpha is None or beta is None):
+        raise ValueError(f"affine={affine!r} needs alpha and beta")
+    if top.ndim != 4 or int(top.shape[0]) != n or int(top.shape[1]) != cout or top.shape[2] < 1 or top.shape[3] < 1:
+        raise RuntimeError(f"top of shape {tuple(top.shape)} does not match the output's batch and channels ({n}, {cout})")
+    _check_epilogue_terms((n, cout, h, w), bias, alpha, beta, None)
+    _lib.require_device(x)
+    _lib.require_device(weight, "weight")
+    _lib.require_device(top, "top")
+    _lib.require_f32_layer("conv1x1_upsample_add", x, weight)
+    lib = _lib.load()
+    xc, wc = x.contiguous(), weight.detach().contiguous()
+    bc, ac, btc, tc = (_lib.f32_on(t, x.device) for t in (bias, alpha, beta, top))
+    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
+    p = _lib.ptr
+    _lib.launch(lib.mv_conv1x1_upsample_add_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), tc.data_ptr(), y.data_ptr(),
+                n, cin, h, w, cout, int(tc.shape[2]), int(tc.shape[3]), _AFFINE_CODES[affine], _ACT_CODES[activation])
+    return _lib.forward_only(y, "conv1x1_upsample_add", x, weight, bias, alpha, beta, top)
+
+
 def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                       alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                       residual: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, groups: int = 1,

@@ -669,6 +669,30 @@ int mv_conv_norm_act_f32(int kind, const float* x, const float* w, const float* 
   return set_error(MV_ERR_INVALID_ARGUMENT, "unknown conv kind %d", kind);
 }
 
+// [a, a + an) and [b, b + bn) floats share an element
+static bool overlaps(const float* a, long long an, const float* b, long long bn) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)bn * sizeof(float) && b0 < a0 + (uintptr_t)an * sizeof(float);
+}
+
+int mv_conv1x1_upsample_add_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta,
+                                const float* top, float* y, int64_t n, int cin, int h, int wdt, int cout, int top_h, int top_w,
+                                int affine, int act, void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, cin, cout, h, wdt);
+  if (top_h < 1 || top_w < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "bad top size (%d, %d)", top_h, top_w);
+  if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
+  if (n == 0) return MV_OK;
+  if (!x || !w || !y || !top) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
+  const long long hw = (long long)h * wdt, ny = n * cout * hw;
+  if (overlaps(y, ny, x, n * cin * hw) || overlaps(y, ny, w, (long long)cout * cin) || overlaps(y, ny, top, n * cout * (long long)top_h * top_w))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, weight or top");
+  const Epilogue e = {bias, affine ? alpha : nullptr, affine ? beta : nullptr, nullptr, affine, act};
+  return launch_conv1x1_upsample_add(x, w, top, y, n, cin, h, wdt, cout, top_h, top_w, e, (hipStream_t)stream);
+}
+
 int mv_conv1x1_k_slices(int64_t n, int cin, int h, int wdt, int cout, int* slice_len) {
   int slices = 1, len = cin;
   if (n > 0 && cin > 0 && cout > 0 && h > 0 && wdt > 0) conv1x1_plan(n, cin, (int64_t)h * wdt, cout, &slices, &len);
@@ -776,12 +800,6 @@ int mv_conv2d_needs_workspace(int64_t n, int cin, int cout, int h, int wdt, int 
   Conv2dGeom g = {cin, h, wdt, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups};
   if (!channels_divide(g, 1) || conv2d_geometry(&g)) return kFormColumns;
   return conv2d_form(n, g);
-}
-
-// [a, a + an) and [b, b + bn) floats share an element
-static bool overlaps(const float* a, long long an, const float* b, long long bn) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)bn * sizeof(float) && b0 < a0 + (uintptr_t)an * sizeof(float);
 }
 
 // the rest of the two ordinary entries' checks; check_overlap: mv_conv2d_affine_act_f32 only (host dispatch: a known gap)

@@ -504,6 +504,12 @@ struct PwArgs {
   int cps;  // K chunks per K slice (== chunks without slicing)
   int vec_x, vec_w, vec_y;
   long long x_img_stride, y_img_stride;  // floats between consecutive images (cin*hw / cout*hw unless a channel slice)
+  // UP instances only (FPN's top-down merge, launch_conv1x1_upsample_add): the residual is `top` (n, cout, top_h, top_w), read at
+  // ATen's nearest source index of each output pixel.  Kept behind the fields above: the other instances' arguments stay where they were
+  const float* top;
+  long long top_img_stride;  // cout * top_h * top_w
+  int top_h, top_w, wdt;     // wdt: the output's row length (hw = h * wdt)
+  float top_sy, top_sx;      // (float)top_h / (float)h and (float)top_w / (float)wdt: one float division each, on the host
 };
 
 
@@ -518,7 +524,13 @@ constexpr int kTP = 36;  // transpose buffer pitch (floats): rows stay 16-byte a
 // and comes back with 8 consecutive lanes covering one channel's 32 pixels: every store instruction writes 8 full 128-byte
 // lines (16 B per lane), and the residual is read the same way.
 // FAST: BatchNorm2d(eval) fold, no conv bias, none / ReLU / ReLU6 -- every block of the MobileNet / ResNet family
-template <int NT, int ACTK, bool RES, bool FAST>
+// UP: the residual is A.top[img][m][iy(oy)][ix(ox)] with ATen's upsample_nearest source index per axis (UpSampleKernel.cpp
+// nearest_idx): min((int)floorf((float)o * scale), in - 1), scale = (float)in / (float)out.  The reference's two shortcuts are
+// this formula's values: out == in has scale 1 and floorf(o * 1) == o, out == 2 * in has scale 0.5 and floorf(o * 0.5) == o >> 1,
+// both products exact for o < 2^24 -- so no case distinction per element.  A lane's four pixels p .. p + 3 are consecutive in the
+// flattened plane and may cross a row end: (oy, ox) comes from p once per tile and is stepped; the four source offsets are shared
+// by the lane's four channels.  `top` is read element by element (a quarter of the output in FPN: it stays in L2).
+template <int NT, int ACTK, bool RES, bool FAST, bool UP = false>
 __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& T, const PwArgs& A, float* tb, int lane) {
   const int M = A.cout, HW = A.hw;
   const Clamp cl = make_clamp(A.e.act);
@@ -535,17 +547,33 @@ __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& 
         *reinterpret_cast<f32x4*>(tb + l31 * kTP + 8 * g + 4 * hf) =
             (f32x4){acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
       const int p = T.p_base + 32 * t + q;
+      int uo[4] = {0, 0, 0, 0};  // UP: iy * top_w + ix of pixels p .. p + 3 (pixels past the plane clamp into `top` and are not read)
+      if constexpr (UP) {
+        int oy = p / A.wdt, ox = p - oy * A.wdt;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int iy = min((int)floorf((float)oy * A.top_sy), A.top_h - 1);
+          const int ix = min((int)floorf((float)ox * A.top_sx), A.top_w - 1);
+          uo[i] = iy * A.top_w + ix;
+          if (++ox == A.wdt) ox = 0, ++oy;
+        }
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int m = T.m + r0 + 8 * j;
         const f32x4 a = *reinterpret_cast<const f32x4*>(tb + (r0 + 8 * j) * kTP + q);
         if (m < M && p < HW) {
           const size_t row = (size_t)T.img * A.y_img_stride + (size_t)m * HW;
+          const float* tp = nullptr;
+          if constexpr (UP) tp = A.top + (size_t)T.img * A.top_img_stride + (size_t)m * A.top_h * A.top_w;
           float v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = FAST ? fmaf(v[i], c[j].alpha, c[j].beta) : epi_norm(v[i], c[j], A.e);
           if (A.vec_y && p + 3 < HW) {
-            if (RES) {
+            if constexpr (UP) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) v[i] = tp[uo[i]] + v[i];
+            } else if (RES) {
               const f32x4 r = *reinterpret_cast<const f32x4*>(A.e.res + row + p);
               v[0] = r.x + v[0], v[1] = r.y + v[1], v[2] = r.z + v[2], v[3] = r.w + v[3];
             }
@@ -555,7 +583,8 @@ __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& 
 #pragma unroll
             for (int i = 0; i < 4; ++i)
               if (p + i < HW) {
-                if (RES) v[i] = A.e.res[row + p + i] + v[i];
+                if constexpr (UP) v[i] = tp[uo[i]] + v[i];
+                else if (RES) v[i] = A.e.res[row + p + i] + v[i];
                 A.y[row + p + i] = epi_act<ACTK>(v[i], cl);
               }
           }
@@ -573,7 +602,7 @@ __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& 
 // second launch; the summation order -- one ascending-k chain per slice from +0, slices added in order -- is stated by
 // mv_conv1x1_k_slices() and restated by the oracle (orc_pointwise_sliced_affine_act_f32): bit-exact against that, within
 // 1e-6 relative of the single chain.
-template <int NT, int MW, int KS>
+template <int NT, int MW, int KS, bool UP = false>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwArgs A) {
   constexpr int PG = 4 / MW;              // pixel groups (waves along pixels)
   constexpr int PXB = PG * NT * 32;       // pixels per workgroup
@@ -750,15 +779,15 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
   if (!live) return;
   float* tb = xs + wave * (32 * kTP);
   const PwTile tile = {j0 + mt * 32, pw0, ntiles, img};
-  const bool res = A.e.res != nullptr;
+  const bool res = UP || A.e.res != nullptr;  // UP instances always add `top`: their other halves fold away
   if (A.e.act <= 2 && A.e.affine == 2 && A.e.bias == nullptr) {
-    res ? pw_store<NT, 0, true, true>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, true>(acc, tile, A, tb, lane);
+    res ? pw_store<NT, 0, true, true, UP>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, true, UP>(acc, tile, A, tb, lane);
   } else if (A.e.act == 3) {
-    res ? pw_store<NT, 1, true, false>(acc, tile, A, tb, lane) : pw_store<NT, 1, false, false>(acc, tile, A, tb, lane);
+    res ? pw_store<NT, 1, true, false, UP>(acc, tile, A, tb, lane) : pw_store<NT, 1, false, false, UP>(acc, tile, A, tb, lane);
   } else if (A.e.act == 4) {
-    res ? pw_store<NT, 2, true, false>(acc, tile, A, tb, lane) : pw_store<NT, 2, false, false>(acc, tile, A, tb, lane);
+    res ? pw_store<NT, 2, true, false, UP>(acc, tile, A, tb, lane) : pw_store<NT, 2, false, false, UP>(acc, tile, A, tb, lane);
   } else {
-    res ? pw_store<NT, 0, true, false>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, false>(acc, tile, A, tb, lane);
+    res ? pw_store<NT, 0, true, false, UP>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, false, UP>(acc, tile, A, tb, lane);
   }
 }
 
@@ -817,15 +846,23 @@ static int pw_launch(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   a.cps = p.cps;
   const long long nb = (long long)a.mblocks * a.ptiles;
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: problem too large for one launch");
+  const dim3 grid((unsigned)nb, (unsigned)n);
+  const bool up = a.top != nullptr;  // the same plan, the instances that gather their residual from `top`
   if constexpr (NT == 1) {
     if (p.ks > 1) {
-      if (p.ks == 2) hipLaunchKernelGGL((k_conv1x1<1, MW, 2>), dim3((unsigned)nb, (unsigned)n), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((k_conv1x1<1, MW, 4>), dim3((unsigned)nb, (unsigned)n), dim3(1024), 0, s, a);
-      return check_launchf("k_conv1x1<1,%d,ks%d>", MW, p.ks);
+      if (p.ks == 2) {
+        if (up) hipLaunchKernelGGL((k_conv1x1<1, MW, 2, true>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((k_conv1x1<1, MW, 2>), grid, dim3(512), 0, s, a);
+      } else {
+        if (up) hipLaunchKernelGGL((k_conv1x1<1, MW, 4, true>), grid, dim3(1024), 0, s, a);
+        else hipLaunchKernelGGL((k_conv1x1<1, MW, 4>), grid, dim3(1024), 0, s, a);
+      }
+      return check_launchf(up ? "k_conv1x1_up<1,%d,ks%d>" : "k_conv1x1<1,%d,ks%d>", MW, p.ks);
     }
   }
-  hipLaunchKernelGGL((k_conv1x1<NT, MW, 1>), dim3((unsigned)nb, (unsigned)n), dim3(256), 0, s, a);
-  return check_launchf("k_conv1x1<%d,%d>", NT, MW);
+  if (up) hipLaunchKernelGGL((k_conv1x1<NT, MW, 1, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_conv1x1<NT, MW, 1>), grid, dim3(256), 0, s, a);
+  return check_launchf(up ? "k_conv1x1_up<%d,%d>" : "k_conv1x1<%d,%d>", NT, MW);
 }
 
 template <int MW>
@@ -835,10 +872,12 @@ static int pw_pick_nt(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   return pw_launch<(MW == 1 ? 2 : 4), MW>(a, n, p, s);
 }
 
-int launch_conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e,
-                   hipStream_t s, int64_t x_img_stride, int64_t y_img_stride, bool allow_k_slices) {
+// up: null, or the coarser map of launch_conv1x1_upsample_add (e.res is null then)
+static int conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e, hipStream_t s,
+                   int64_t x_img_stride, int64_t y_img_stride, bool allow_k_slices, const PwArgs* up) {
   if (hw > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: plane too large");
   PwArgs a = {};
+  if (up) a = *up;
   a.x = x, a.w = w, a.y = y, a.e = e;
   a.cin = cin, a.cout = cout, a.hw = (int)hw;
   a.x_img_stride = x_img_stride > 0 ? x_img_stride : (long long)cin * hw;
@@ -853,6 +892,21 @@ int launch_conv1x1(const float* x, const float* w, float* y, int64_t n, int cin,
   if (p.mw == 1) return pw_pick_nt<1>(a, n, p, s);
   if (p.mw == 2) return pw_pick_nt<2>(a, n, p, s);
   return pw_pick_nt<4>(a, n, p, s);
+}
+
+int launch_conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e,
+                   hipStream_t s, int64_t x_img_stride, int64_t y_img_stride, bool allow_k_slices) {
+  return conv1x1(x, w, y, n, cin, hw, cout, e, s, x_img_stride, y_img_stride, allow_k_slices, nullptr);
+}
+
+int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top, float* y, int64_t n, int cin, int h, int wd, int cout,
+                                int top_h, int top_w, const Epilogue& e, hipStream_t s) {
+  if ((long long)top_h * top_w > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: top plane too large");
+  PwArgs up = {};
+  up.top = top, up.top_h = top_h, up.top_w = top_w, up.wdt = wd;
+  up.top_img_stride = (long long)cout * top_h * top_w;
+  up.top_sy = (float)top_h / (float)h, up.top_sx = (float)top_w / (float)wd;
+  return conv1x1(x, w, y, n, cin, (int64_t)h * wd, cout, e, s, 0, 0, true, &up);
 }
 
 }  // namespace mv

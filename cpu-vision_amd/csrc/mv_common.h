@@ -258,6 +258,10 @@ int launch_conv1x1(const float* x, const float* w, float* y, int64_t n, int cin,
 // the K slicing launch_conv1x1 applies to this shape: slices == 1 -> one ascending-k chain per output; otherwise `slices`
 // chains over `slice_len` channels each (the last may be shorter), added in ascending slice order
 void conv1x1_plan(int64_t n, int cin, int64_t hw, int cout, int* slices, int* slice_len);
+// FPN's top-down merge: launch_conv1x1 on (n, cin, h, wd) whose residual is top (n, cout, top_h, top_w) read at ATen's nearest
+// source index of each output pixel (k_conv1x1_up: the same plan, tiles and summation order; e.res must be null)
+int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top, float* y, int64_t n, int cin, int h, int wd, int cout,
+                                int top_h, int top_w, const Epilogue& e, hipStream_t s);
 // nn.Conv2d of any geometry and deform_conv2d: mv_conv.h, mv_deform.h
 int launch_maxpool2d(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, hipStream_t s);
 int launch_maxpool2d_pad(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s);

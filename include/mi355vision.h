@@ -258,6 +258,25 @@ int mv_conv_norm_act_f32(int kind, const float* x, const float* w, const float* 
  * added in ascending order, then bias / norm / residual / activation.  Deterministic (no atomics, no workspace); within
  * 1e-6 relative of the single chain; oracle/oracle.c restates it (orc_pointwise_sliced_affine_act_f32). */
 int mv_conv1x1_k_slices(int64_t n, int cin, int h, int wdt, int cout, int* slice_len);
+/* ---- FeaturePyramidNetwork's top-down merge (ops/feature_pyramid_network.py:  inner_lateral = inner_block(x);
+ * inner_top_down = F.interpolate(last_inner, size=feat_shape, mode="nearest"); last_inner = inner_lateral + inner_top_down) in ONE
+ * launch:  y[i, co, oy, ox] = act(top[i, co, iy(oy), ix(ox)] + norm(conv1x1(x)[i, co, oy, ox] + bias[co])).
+ *   x (n, cin, h, w), w (cout, cin), top (n, cout, top_h, top_w), y (n, cout, h, w); bias / alpha / beta / affine / act as for
+ *   mv_conv_norm_act_f32 (bias may be NULL; alpha and beta are required iff affine != 0).  All DEVICE pointers.
+ * The pointwise kernel of MV_CONV_PW1X1 with a second residual addressing: same tiles, same plan and the summation order
+ * mv_conv1x1_k_slices(n, cin, h, w, cout) states; epilogue order `+ bias` -> folded norm -> `top + v` -> activation.  Bit for bit
+ * mv_conv_norm_act_f32(MV_CONV_PW1X1, ..., residual = R) with R = interpolate(top, size=(h, w), mode="nearest"), without R in memory.
+ * Source index per axis = ATen's CPU nearest_idx: min((int)floorf((float)o * scale), in - 1) with scale = (float)in / (float)out,
+ * one float division on the host and a plain rounded product on the device; for out == in and out == 2 * in this is ATen's `o` and
+ * `o >> 1`.  Any top_h, top_w >= 1: equal size, 1 x 1 and a coarser OUTPUT give torch's values too (the integer o * in / out does not:
+ * 65 -> 110 differs).  Kernels: k_conv1x1_up<NT,MW[,ksN]> (mv_last_kernel).
+ * Refused before any launch, with a negative status and the text in mv_last_error(): a bad shape, top_h or top_w < 1, unknown affine /
+ * act codes, NULL x / w / y / top, affine without alpha / beta, y overlapping x, w or top, sizes beyond one launch (n > 65535, a plane
+ * of 2^31 elements).  n == 0 is a successful no-op.  Alignment: 4 bytes for every tensor; y is stored with 16-byte stores where
+ * h * w % 4 == 0 and y is 16-byte aligned, else element by element; top is read element by element, never past its last element. */
+int mv_conv1x1_upsample_add_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta,
+                                const float* top, float* y, int64_t n, int cin, int h, int wdt, int cout, int top_h, int top_w,
+                                int affine, int act, void* stream);
 /* ---- InvertedResidual (models/mobilenetv2.py:39-63) as ONE kernel -------------------------------------------------------
  * [1x1 expand cin -> hidden + norm + ReLU6] -> 3x3 depthwise (stride 1 | 2, zero padding 1) + norm + ReLU6 -> 1x1 project
  * hidden -> cout + norm [-> + x when `residual` (stride 1, cin == cout)].  The hidden tensor never reaches HBM: a workgroup
