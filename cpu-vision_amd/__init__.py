@@ -5,12 +5,16 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   _filters        gaussian_blur / adjust_sharpness (+ _image/_video kernels, *_frames), box / separable / Sobel
   _layers         conv+ReLU, pools, linear, conv_norm_act, inverted_residual (what nn and mobilenet run on)
   _misc           resize / center_crop / to_dtype / normalize (+ kernels), to_float_normalize
+  _detection      rpn_topk / rpn_decode / box_decode (what rpn runs on)
   _crop, _mix     pad / crop / flip / erase / resized_crop; MixUp / CutMix on a batch
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
   resnet          BasicBlock / Bottleneck / ResNet, resnet18 ... resnet152, wide_resnet50_2 / 101_2: one launch per conv + norm (+ add) + ReLU
   fpn             FeaturePyramidNetwork, LastLevelMaxPool, LastLevelP6P7: lateral 1x1 conv + nearest upsample + add in one launch
   backbone_utils  IntermediateLayerGetter, BackboneWithFPN, resnet_fpn_backbone
+  anchor_utils    AnchorGenerator; image_list: ImageList
+  rpn             BoxCoder (decode), RPNHead (cls_logits + bbox_pred as one pointwise launch), RegionProposalNetwork: top-k on the
+                  head's NCHW maps, then anchors + decode + clip + sigmoid of the selected candidates only, then batched_nms
   ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
                   ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*); box_iou / generalized_box_iou /
                   distance_box_iou, masks_to_boxes, MultiScaleRoIAlign, box_area / box_convert / clip_boxes_to_image /
@@ -24,12 +28,15 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
 
 The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias package at the repo root).
 """
-from . import (backbone_utils, fpn, functional, functional_v1, graphs, mobilenet, nn, ops, presets, resnet, sharding,  # noqa: F401
-               transforms, tv_tensors)
+from . import (anchor_utils, backbone_utils, fpn, functional, functional_v1, graphs, image_list, mobilenet, nn, ops, presets,  # noqa: F401
+               resnet, rpn, sharding, transforms, tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
 from .backbone_utils import BackboneWithFPN, IntermediateLayerGetter, resnet_fpn_backbone  # noqa: F401
 from .fpn import ExtraFPNBlock, FeaturePyramidNetwork, LastLevelMaxPool, LastLevelP6P7  # noqa: F401
+from .anchor_utils import AnchorGenerator  # noqa: F401
+from .image_list import ImageList  # noqa: F401
+from .rpn import BoxCoder, RegionProposalNetwork, RPNHead  # noqa: F401
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
                   generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401

@@ -1,0 +1,167 @@
+"""The functional entries of the detection heads (models/detection/rpn.py, _utils.py BoxCoder): rpn_topk, rpn_decode and
+box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip).  float32, forward-only; the argument
+checks fire before a device is needed.  Every name here is re-exported by `functional`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+
+MAX_RPN_LEVELS = 8   # kMaxRpnLevels
+MAX_RPN_TOPK = 4096  # kRpnMaxK
+BBOX_XFORM_CLIP = math.log(1000.0 / 16)
+
+
+def _level_maps(name: str, maps: Sequence[torch.Tensor], what: str, per_anchor: int, anchors: Optional[List[int]] = None):
+    """The checks of a list of per-level NCHW maps ((n, per_anchor * A_l, H_l, W_l) float32) -> [(n, A_l, H_l, W_l)]."""
+    if not isinstance(maps, (list, tuple)) or not maps:
+        raise TypeError(f"{name}: {what} should be a non-empty list of tensors, one per level")
+    if len(maps) > MAX_RPN_LEVELS:
+        raise _lib.Mi355VisionError(f"{name}: up to {MAX_RPN_LEVELS} levels per call, got {len(maps)}")
+    shapes = []
+    for l, m in enumerate(maps):
+        if not isinstance(m, torch.Tensor) or m.dim() != 4:
+            raise RuntimeError(f"{name}: {what}[{l}] should be a 4-D tensor (N, C, H, W)")
+        if m.dtype != torch.float32:
+            raise TypeError(f"{name} computes in float32. Got {what}[{l}] {m.dtype}")
+        n, c, h, w = (int(d) for d in m.shape)
+        if n != int(maps[0].shape[0]):
+            raise RuntimeError(f"{name}: {what}[{l}] holds {n} images, {what}[0] holds {int(maps[0].shape[0])}")
+        if c < 1 or h < 1 or w < 1 or c % per_anchor:
+            raise RuntimeError(f"{name}: bad shape {tuple(m.shape)} of {what}[{l}]")
+        if anchors is not None and c != per_anchor * anchors[l]:
+            raise RuntimeError(f"{name}: {what}[{l}] has {c} channels for {anchors[l]} anchors per location")
+        shapes.append((n, c // per_anchor, h, w))
+    if sum(a * h * w for _, a, h, w in shapes) >= 2 ** 31:
+        raise _lib.Mi355VisionError(f"{name}: the anchors of all levels exceed the 32-bit index")
+    return shapes
+
+
+def _dense_images(m: torch.Tensor) -> torch.Tensor:
+    """The map itself when each of its images is dense (a channel slice of a wider contiguous tensor is), else a contiguous copy."""
+    m = m.detach()
+    _, c, h, w = m.shape
+    if m.stride(3) == 1 and m.stride(2) == w and m.stride(1) == h * w and (m.shape[0] == 1 or m.stride(0) >= c * h * w):
+        return m
+    return m.contiguous()
+
+
+def _tables(shapes):
+    num = len(shapes)
+    return ((C.c_int * num)(*[s[2] for s in shapes]), (C.c_int * num)(*[s[3] for s in shapes]), (C.c_int * num)(*[s[1] for s in shapes]))
+
+
+def _img_strides(maps):
+    return (C.c_int64 * len(maps))(*[int(m.stride(0)) if m.shape[0] > 1 else int(m[0].numel()) for m in maps])
+
+
+def rpn_topk(logits: List[torch.Tensor], k: int) -> torch.Tensor:
+    """filter_proposals' per-level top-k (rpn.py) on the head's own NCHW logits, ONE launch: logits[l] (N, A_l, H_l, W_l) -> idx
+    (N, K) int32, K = sum_l min(k, A_l H_l W_l): per image, level after level, the indices into the reference's concatenated
+    (y, x, a) layout of the level's greatest logits in stable descending order (equal logits by ascending index, NaN greatest)."""
+    shapes = _level_maps("rpn_topk", logits, "logits", 1)
+    if not isinstance(k, int) or k < 1:
+        raise ValueError(f"rpn_topk: k must be a positive int, got {k!r}")
+    if k > MAX_RPN_TOPK:
+        raise _lib.Mi355VisionError(f"rpn_topk: k up to {MAX_RPN_TOPK}, got {k}")
+    for m in logits:
+        _lib.require_device(m, "logits")
+    lib = _lib.load()
+    l0 = logits[0]
+    n = shapes[0][0]
+    total = sum(min(k, a * h * w) for _, a, h, w in shapes)
+    with _lib.on_device_of(l0):
+        maps = [_dense_images(m) for m in logits]
+        idx = torch.empty((n, total), dtype=torch.int32, device=l0.device)
+        if n:
+            hs, ws, as_ = _tables(shapes)
+            nbytes = int(lib.mv_rpn_topk_workspace_bytes(n, hs, ws, as_, len(maps), k))
+            if not nbytes:
+                raise _lib.Mi355VisionError(f"rpn_topk: {n} images are more than one call takes")
+            buf, ws_ptr, nbytes = _lib.workspace(nbytes, l0.device)
+            _lib.launch(lib.mv_rpn_topk_f32, l0, _lib.pointer_table(maps), hs, ws, as_, _img_strides(maps), len(maps), n, k, idx.data_ptr(),
+                        ws_ptr, nbytes)
+    return idx
+
+
+def rpn_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx: torch.Tensor, cell_anchors: List[torch.Tensor],
+               strides: Sequence[Tuple[int, int]], image_sizes, weights: Tuple[float, float, float, float] = (1.0, 1.0, 1.0, 1.0),
+               bbox_xform_clip: float = BBOX_XFORM_CLIP, min_size: float = 1e-3,
+               score_thresh: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The rest of filter_proposals before the nms for the candidates idx (N, K) of rpn_topk, ONE launch, one lane per candidate:
+    its anchor from cell_anchors[l] (A_l, 4) and strides[l] = (stride_h, stride_w), BoxCoder.decode_single with `weights`,
+    clip_boxes_to_image with image_sizes (N rows (h, w): a list, or an (N, 2) tensor), sigmoid -> boxes (N, K, 4), scores (N, K),
+    levels (N, K) int64, valid (N, K) bool = both sides >= min_size and score >= score_thresh."""
+    shapes = _level_maps("rpn_decode", logits, "logits", 1)
+    anchors = [a for _, a, _, _ in shapes]
+    dshapes = _level_maps("rpn_decode", deltas, "deltas", 4, anchors) if isinstance(deltas, (list, tuple)) and len(deltas) == len(logits) else None
+    if dshapes is None or any(d[2:] != s[2:] or d[0] != s[0] for d, s in zip(dshapes, shapes)):
+        raise RuntimeError("rpn_decode: deltas should hold one map per level of logits, of the same batch and size with 4 channels per anchor")
+    num, n = len(shapes), shapes[0][0]
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
+        raise RuntimeError(f"rpn_decode: idx should be an int32 tensor of shape ({n}, K)")
+    if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or \
+            any(tuple(c.shape) != (a, 4) for c, a in zip(cell_anchors, anchors)):
+        raise RuntimeError(f"rpn_decode: cell_anchors should hold one (A, 4) tensor per level, A = {anchors}")
+    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
+        raise RuntimeError(f"rpn_decode: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
+    if len(weights) != 4:
+        raise ValueError(f"rpn_decode: four weights (wx, wy, ww, wh), got {weights!r}")
+    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
+                                                                                 dtype=torch.float32).reshape(-1, 2)
+    if tuple(sizes.shape) != (n, 2):
+        raise RuntimeError(f"rpn_decode: image_sizes should hold {n} rows (height, width), got {tuple(sizes.shape)}")
+    for m in (*logits, *deltas, idx):
+        _lib.require_device(m, "rpn_decode input")
+    lib = _lib.load()
+    l0 = logits[0]
+    k = int(idx.shape[1])
+    with _lib.on_device_of(l0):
+        lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
+        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
+        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
+        ix = idx.contiguous()
+        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
+        levels = torch.empty((n, k), dtype=torch.int64, device=l0.device)
+        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
+        if n and k:
+            hs, ws, as_ = _tables(shapes)
+            sh = (C.c_int * num)(*[int(s[0]) for s in strides])
+            sw = (C.c_int * num)(*[int(s[1]) for s in strides])
+            _lib.launch(lib.mv_rpn_decode_f32, l0, _lib.pointer_table(lmaps), _lib.pointer_table(dmaps), hs, ws, as_, _img_strides(lmaps),
+                        _img_strides(dmaps), sh, sw, num, base.data_ptr(), sizes.data_ptr(), ix.data_ptr(), n, k,
+                        *[float(w) for w in weights], float(bbox_xform_clip), float(min_size), float(score_thresh), boxes.data_ptr(),
+                        scores.data_ptr(), levels.data_ptr(), valid.data_ptr())
+    deps = (*logits, *deltas)
+    return (_lib.forward_only(boxes, "rpn_decode", *deps), _lib.forward_only(scores, "rpn_decode", *deps), levels, valid.view(torch.bool))
+
+
+def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[float, float, float, float],
+               bbox_xform_clip: float = BBOX_XFORM_CLIP) -> torch.Tensor:
+    """BoxCoder.decode_single (_utils.py): boxes (M, 4) and rel_codes (M, 4 C) -> (M, 4 C), one lane per (box, class)."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.size(1) != 4:
+        raise RuntimeError("box_decode: boxes should have shape (M, 4)")
+    if not isinstance(rel_codes, torch.Tensor) or rel_codes.dim() != 2 or rel_codes.size(0) != boxes.size(0) or rel_codes.size(1) % 4 or \
+            (rel_codes.size(1) == 0 and rel_codes.size(0) > 0):
+        raise RuntimeError(f"box_decode: rel_codes should have shape ({boxes.size(0)}, 4 C), got {tuple(rel_codes.shape)}")
+    if boxes.dtype != torch.float32 or rel_codes.dtype != torch.float32:
+        raise TypeError(f"box_decode computes in float32. Got boxes {boxes.dtype}, rel_codes {rel_codes.dtype}")
+    if len(weights) != 4:
+        raise ValueError(f"box_decode: four weights (wx, wy, ww, wh), got {weights!r}")
+    _lib.require_device(rel_codes, "rel_codes")
+    _lib.require_device(boxes, "boxes")
+    lib = _lib.load()
+    m, c4 = int(rel_codes.size(0)), int(rel_codes.size(1))
+    with _lib.on_device_of(rel_codes):
+        b, r = boxes.detach().to(rel_codes.device).contiguous(), rel_codes.detach().contiguous()
+        out = torch.empty((m, c4), dtype=torch.float32, device=rel_codes.device)
+        if m:
+            _lib.launch(lib.mv_box_decode_f32, r, b.data_ptr(), r.data_ptr(), out.data_ptr(), m, c4 // 4, *[float(w) for w in weights],
+                        float(bbox_xform_clip))
+    return _lib.forward_only(out, "box_decode", boxes, rel_codes)

@@ -25,6 +25,7 @@ MAX_TAPS_1D = 63
 # every symbol include/mi355vision.h declares: (name, restype, argtypes)
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _fp = C.POINTER(C.c_float)
+_ip = C.POINTER(C.c_int)
 SYMBOLS = {
     "mv_abi_version": (_i, []),
     "mv_last_error": (C.c_char_p, []),
@@ -127,6 +128,11 @@ SYMBOLS = {
     "mv_masks_to_boxes_workspace_bytes": (_i64, [_i64]),
     "mv_masks_to_boxes_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
     "mv_masks_to_boxes_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "mv_rpn_topk_workspace_bytes": (_i64, [_i64, _ip, _ip, _ip, _i, _i]),
+    "mv_rpn_topk_f32": (_i, [_vp, _ip, _ip, _ip, C.POINTER(C.c_int64), _i, _i64, _i, _vp, _vp, _i64, _vp]),
+    "mv_rpn_decode_f32": (_i, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip, _ip, _i, _vp, _vp, _vp, _i64, _i64]
+                          + [_d] * 7 + [_vp] * 5),
+    "mv_box_decode_f32": (_i, [_vp, _vp, _vp, _i64, _i] + [_d] * 5 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

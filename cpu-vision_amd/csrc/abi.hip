@@ -1210,6 +1210,136 @@ int mv_masks_to_boxes_f32(const float* masks, float* boxes, int* empty_flag, int
   return masks_to_boxes(masks, true, boxes, empty_flag, n, h, w, workspace, workspace_bytes, stream);
 }
 
+// ---- RPN top-k / decode, BoxCoder.decode: rpn.hip -------------------------------------------------------------------------------------
+struct ByteRange {
+  const void* p;
+  long long bytes;
+};
+static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a0 < b0 + (uintptr_t)b.bytes && b0 < a0 + (uintptr_t)a.bytes;
+}
+// no output shares a byte with an input or with another output
+static bool outputs_clear(const ByteRange* outs, int n_out, const ByteRange* ins, int n_in) {
+  for (int i = 0; i < n_out; ++i) {
+    for (int j = 0; j < n_in; ++j)
+      if (ranges_overlap(outs[i], ins[j])) return false;
+    for (int j = i + 1; j < n_out; ++j)
+      if (ranges_overlap(outs[i], outs[j])) return false;
+  }
+  return true;
+}
+
+// The level tables of the three rpn entries: 0 and the totals, or the error.  anchors: sum of a * h * w (< 2^31); taken: sum of
+// min(k, a * h * w) (k < 1: not computed).
+static int rpn_levels_check(const char* op, const int* hs, const int* ws, const int* as, int levels, int k, int64_t* anchors, int64_t* taken) {
+  if (levels < 1 || levels > kMaxRpnLevels)
+    return set_error(levels > kMaxRpnLevels ? MV_ERR_UNSUPPORTED : MV_ERR_INVALID_ARGUMENT, "%s: 1 to %d levels per call, got %d", op,
+                     kMaxRpnLevels, levels);
+  if (!hs || !ws || !as) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null level table", op);
+  int64_t total = 0, take = 0;
+  for (int l = 0; l < levels; ++l) {
+    if (hs[l] < 1 || ws[l] < 1 || as[l] < 1)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape (%d anchors, %d, %d) of level %d", op, as[l], hs[l], ws[l], l);
+    const int64_t hw = (int64_t)hs[l] * ws[l];
+    if (hw > 0x7fffffffLL || hw * as[l] > 0x7fffffffLL || (total += hw * as[l]) > 0x7fffffffLL)
+      return set_error(MV_ERR_UNSUPPORTED, "%s: the anchors of all levels exceed the 32-bit index", op);
+    take += hw * as[l] < k ? hw * as[l] : k;
+  }
+  *anchors = total, *taken = take;
+  return MV_OK;
+}
+
+int64_t mv_rpn_topk_workspace_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int k) {
+  int64_t anchors, taken;
+  if (n <= 0 || n > 65535 || k < 1 || k > kRpnMaxK || rpn_levels_check("rpn_topk", hs, ws, as, levels, k, &anchors, &taken)) return 0;
+  return (n * taken * 8 + 15) / 16 * 16;
+}
+
+int mv_rpn_topk_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                    int64_t n, int k, int* idx, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: bad image count %lld", (long long)n);
+  if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: k must be positive, got %d", k);
+  int64_t anchors, taken;
+  if (int rc = rpn_levels_check("rpn_topk", hs, ws, as, levels, k, &anchors, &taken)) return rc;
+  if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "rpn_topk: k up to %d, got %d", kRpnMaxK, k);
+  if (n == 0) return MV_OK;
+  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "rpn_topk: %lld images exceed the launch grid", (long long)n);
+  if (!logits || !img_strides || !idx) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: null pointer");
+  const int64_t need = (n * taken * 8 + 15) / 16 * 16;
+  ByteRange ins[kMaxRpnLevels];
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l];
+    if (!logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: null pointer (level %d)", l);
+    if (img_strides[l] < nl || img_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: image stride %lld of level %d, its map has %lld elements", (long long)img_strides[l],
+                       l, (long long)nl);
+    ins[l] = {logits[l], ((n - 1) * img_strides[l] + nl) * 4};
+  }
+  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: needs a workspace");
+  if (workspace_bytes < need)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: workspace of %lld bytes, need %lld (mv_rpn_topk_workspace_bytes)",
+                     (long long)workspace_bytes, (long long)need);
+  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: the workspace must be 16-byte aligned");
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: idx must be 4-byte aligned");
+  const ByteRange outs[2] = {{idx, n * taken * 4}, {workspace, need}};
+  if (!outputs_clear(outs, 2, ins, levels)) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: idx and the workspace must not overlap an input or each other");
+  return launch_rpn_topk(logits, hs, ws, as, img_strides, levels, (int)n, k, idx, workspace, (hipStream_t)stream);
+}
+
+int mv_rpn_decode_f32(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                      const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w, int levels,
+                      const float* base_anchors, const float* image_sizes, const int* idx, int64_t n, int64_t k, double wx, double wy,
+                      double ww, double wh, double clip, double min_size, double score_thresh, float* boxes, float* scores,
+                      int64_t* levels_out, unsigned char* valid, void* stream) {
+  if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: bad shape n=%lld, k=%lld", (long long)n, (long long)k);
+  int64_t anchors, taken;
+  if (int rc = rpn_levels_check("rpn_decode", hs, ws, as, levels, 1, &anchors, &taken)) return rc;
+  if (!strides_h || !strides_w) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: null level table");
+  for (int l = 0; l < levels; ++l)
+    if (strides_h[l] < 0 || strides_w[l] < 0 || (int64_t)strides_h[l] * hs[l] > 0x7fffffffLL || (int64_t)strides_w[l] * ws[l] > 0x7fffffffLL)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: bad strides (%d, %d) of level %d", strides_h[l], strides_w[l], l);
+  if (n == 0 || k == 0) return MV_OK;
+  if (n > 0x7fffffffLL || k > (0x7fffffffLL * 256) / n)
+    return set_error(MV_ERR_UNSUPPORTED, "rpn_decode: %lld x %lld candidates exceed the launch grid", (long long)n, (long long)k);
+  if (!logits || !deltas || !logit_strides || !delta_strides || !base_anchors || !image_sizes || !idx || !boxes || !scores || !levels_out || !valid)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: null pointer");
+  if ((uintptr_t)levels_out % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: levels must be 8-byte aligned");
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: idx must be 4-byte aligned");
+  ByteRange ins[2 * kMaxRpnLevels + 3];
+  int64_t base_rows = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l];
+    if (!logits[l] || !deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: null pointer (level %d)", l);
+    if (logit_strides[l] < nl || delta_strides[l] < 4 * nl || logit_strides[l] > 0x7fffffffffffLL / n || delta_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: image strides (%lld, %lld) of level %d, its maps have %lld and %lld elements",
+                       (long long)logit_strides[l], (long long)delta_strides[l], l, (long long)nl, (long long)(4 * nl));
+    ins[2 * l] = {logits[l], ((n - 1) * logit_strides[l] + nl) * 4};
+    ins[2 * l + 1] = {deltas[l], ((n - 1) * delta_strides[l] + 4 * nl) * 4};
+    base_rows += as[l];
+  }
+  ins[2 * levels] = {base_anchors, base_rows * 16}, ins[2 * levels + 1] = {image_sizes, n * 8}, ins[2 * levels + 2] = {idx, n * k * 4};
+  const ByteRange outs[4] = {{boxes, n * k * 16}, {scores, n * k * 4}, {levels_out, n * k * 8}, {valid, n * k}};
+  if (!outputs_clear(outs, 4, ins, 2 * levels + 3))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: the outputs must not overlap an input or each other");
+  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
+  return launch_rpn_decode(logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, base_anchors, image_sizes,
+                           idx, n, k, coef, (float)min_size, (float)score_thresh, boxes, scores, levels_out, valid, (hipStream_t)stream);
+}
+
+int mv_box_decode_f32(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, double wx, double wy, double ww,
+                      double wh, double clip, void* stream) {
+  if (m < 0 || classes < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "box_decode: bad shape m=%lld, classes=%d", (long long)m, classes);
+  if (m == 0) return MV_OK;
+  if (m > (0x7fffffffLL * 256) / classes)
+    return set_error(MV_ERR_UNSUPPORTED, "box_decode: %lld boxes x %d classes exceed the launch grid", (long long)m, classes);
+  if (!boxes || !rel_codes || !out) return set_error(MV_ERR_INVALID_ARGUMENT, "box_decode: null pointer");
+  const ByteRange ins[2] = {{boxes, m * 16}, {rel_codes, m * classes * 16}}, outs[1] = {{out, m * classes * 16}};
+  if (!outputs_clear(outs, 1, ins, 2)) return set_error(MV_ERR_INVALID_ARGUMENT, "box_decode: the output must not overlap an input");
+  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
+  return launch_box_decode(boxes, rel_codes, out, m, classes, coef, (hipStream_t)stream);
+}
+
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------
 // The checks the three entry points share, in the order of mv_roi_align_f32: 0 launch, 1 nothing to do, < 0 the error.
 static int roi_pool_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, const int* second,

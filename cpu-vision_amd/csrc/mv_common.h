@@ -318,6 +318,19 @@ int launch_box_iou(const float* boxes1, const float* boxes2, float* out, int64_t
 bool masks_to_boxes_grid_fits(int64_t n, int h);
 int launch_masks_to_boxes(const void* masks, bool f32, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
                           hipStream_t s);
+// RegionProposalNetwork's top-k and decode, BoxCoder.decode (rpn.hip; semantics in mi355vision.h mv_rpn_topk_f32 and below).  The
+// entry points have checked the arguments, the extents, the workspace and the grids; the tables are HOST arrays of `levels` <=
+// kMaxRpnLevels entries, copied into the kernel arguments; coef5 = {wx, wy, ww, wh, clip} as floats.
+constexpr int kMaxRpnLevels = 8;
+constexpr int kRpnMaxK = 4096;  // the candidates of a level are ranked pairwise: k^2 comparisons per (image, level)
+int launch_rpn_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels, int n,
+                    int k, int* idx, void* workspace, hipStream_t s);
+int launch_rpn_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                      const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w, int levels,
+                      const float* base_anchors, const float* image_sizes, const int* idx, int64_t n, int64_t k, const float* coef5,
+                      float min_size, float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid,
+                      hipStream_t s);
+int launch_box_decode(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, const float* coef5, hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

@@ -711,6 +711,59 @@ int mv_masks_to_boxes_u8(const unsigned char* masks, float* boxes, int* empty_fl
 int mv_masks_to_boxes_f32(const float* masks, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* ---- RegionProposalNetwork inference (models/detection/rpn.py filter_proposals up to the nms, anchor_utils.py, _utils.py
+ * BoxCoder.decode_single): select first, on the head's own NCHW maps, then decode only what was selected.
+ *
+ * The level tables (logits, deltas, hs, ws, as, the strides) are HOST arrays of 1 <= levels <= 8 entries, copied into the kernel
+ * arguments as those of mv_multiscale_roi_align_f32; logits[l] is a DEVICE map (n, as[l], hs[l], ws[l]) float32 and deltas[l] one of
+ * (n, 4 as[l], hs[l], ws[l]), image i of a map starting img_strides[l] * i ELEMENTS after image 0 (>= the map's own size: a channel
+ * slice of a wider tensor can be passed).  Anchor (y, x, a) of level l has the flat index  start_l + (y ws[l] + x) as[l] + a,
+ * start_l the anchors of the levels before it -- the reference's permute(0, 3, 4, 1, 2) and concatenation; its logit is channel
+ * a and its delta q channel 4 a + q.  The anchors of all levels number less than 2^31 (MV_ERR_UNSUPPORTED otherwise).
+ *
+ * mv_rpn_topk_f32: idx (n, K) int32, K = sum_l min(k, as[l] hs[l] ws[l]), receives for every image, level after level, the flat
+ * indices of the level's min(k, n_l) greatest logits in STABLE DESCENDING order: greater logit first, equal logits by ascending flat
+ * index, -0 equal to +0, every NaN the one greatest value (the keys of mv_nms_f32; the first k of torch.sort(stable=True,
+ * descending=True) and one of torch.topk's valid answers).  One workgroup per (level, image): a four-pass radix select of the k-th
+ * key with the histograms in LDS, a compaction that takes the ties in ascending flat index, a pairwise rank of the <= k candidates.
+ * k <= 4096 (MV_ERR_UNSUPPORTED above), n <= 65535.  The candidates pass through `workspace`: a 16-byte aligned DEVICE buffer of
+ * mv_rpn_topk_workspace_bytes(n, hs, ws, as, levels, k) = 8 n K bytes rounded up to 16 (0 for arguments the entry refuses), any
+ * content.  Nothing is allocated or read back.
+ *
+ * mv_rpn_decode_f32: one lane per candidate idx[i, j] (idx (n, k) int32; k is any count per image, for the pair of calls the K
+ * above).  The lane finds the level from the index, reads the logit and the four deltas, builds the anchor
+ *   (x sw + b[a][0], y sh + b[a][1], x sw + b[a][2], y sh + b[a][3]),  sh = strides_h[l], sw = strides_w[l],
+ * from base_anchors (a DEVICE (sum_l as[l], 4) float32 array, level after level: AnchorGenerator.cell_anchors concatenated),
+ * applies decode_single (below) with the weights and clip given, clamps x to [0, width] and y to [0, height] of its image
+ * (image_sizes: DEVICE (n, 2) float32 rows (height, width); a NaN stays) and writes
+ *   boxes (n, k, 4) float32;  scores (n, k) = 1 / (1 + E(-logit));  levels (n, k) int64 (8-byte aligned);
+ *   valid (n, k) uint8 = (x2 - x1 >= (float)min_size) & (y2 - y1 >= (float)min_size) & (score >= (float)score_thresh).
+ * An index outside [0, anchors) cannot be reported without a read-back: zeros, level -1, valid 0, and nothing is read for it.
+ *
+ * mv_box_decode_f32 (BoxCoder.decode): boxes (m, 4), rel_codes (m, 4 classes) -> out (m, 4 classes), decode_single per (box, class).
+ *
+ * decode_single, every operation rounded once to float32, nothing fused, the divisions correctly rounded:
+ *   w = x2 - x1; h = y2 - y1; cx = x1 + 0.5 w; cy = y1 + 0.5 h;  dx = c0 / wx; dy = c1 / wy; dw = min(c2 / ww, clip); dh likewise
+ *   (a NaN stays); pcx = dx w + cx; pcy = dy h + cy; pw = E(dw) w; ph = E(dh) h;  box = (pcx - 0.5 pw, pcy - 0.5 ph, pcx + 0.5 pw,
+ *   pcy + 0.5 ph); the weights and clip are taken as (float).
+ * E is the CORRECTLY ROUNDED float32 exponential, (float)exp((double)v) -- not torch's CPU exp, a 1-ulp vector routine that
+ * differs from it in about 1 % of arguments and that no other implementation reproduces bit for bit.
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a null pointer or table, levels outside 1 .. 8 (above 8:
+ * MV_ERR_UNSUPPORTED), a non-positive h, w or a, k < 1 (topk), an image stride below the map's size, a negative stride_h / stride_w,
+ * an output that overlaps an input or another output, a workspace that is missing, too small or misaligned.  n == 0 (k == 0 for
+ * decode, m == 0 for box_decode) is a no-op. */
+int64_t mv_rpn_topk_workspace_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int k);
+int mv_rpn_topk_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                    int64_t n, int k, int* idx, void* workspace, int64_t workspace_bytes, void* stream);
+int mv_rpn_decode_f32(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                      const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w, int levels,
+                      const float* base_anchors, const float* image_sizes, const int* idx, int64_t n, int64_t k, double wx, double wy,
+                      double ww, double wh, double clip, double min_size, double score_thresh, float* boxes, float* scores,
+                      int64_t* levels_out, unsigned char* valid, void* stream);
+int mv_box_decode_f32(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, double wx, double wy, double ww,
+                      double wh, double clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
