@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kMtbBlock) void k_mtb_reduce(const T* __restrict__ 
   constexpr int E = 16 / (int)sizeof(T);  // elements of one 16-byte load
   const long long mask = blockIdx.x / chunks;
   const int chunk = blockIdx.x % chunks;
-  const int y_end = min(h, (chunk + 1) * kMtbChunkRows);
+  const int y_end = (int)min((long long)h, ((long long)chunk + 1) * kMtbChunkRows);  // the product passes 2^31 for h within 32 of it
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   int min_x = INT_MAX, min_y = INT_MAX, max_x = -1, max_y = -1;
   for (int y = chunk * kMtbChunkRows + wave; y < y_end; y += kMtbBlock / kWave) {
@@ -210,7 +210,9 @@ int launch_box_iou(const float* boxes1, const float* boxes2, float* out, int64_t
 
 bool masks_to_boxes_grid_fits(int64_t n, int h) {
   const int64_t chunks = ((int64_t)h + kMtbChunkRows - 1) / kMtbChunkRows;
-  return n <= 0x7fffffffLL / (chunks > 0 ? chunks : 1);
+  // one workgroup of kMtbBlock threads per (mask, chunk); the runtime takes a grid of fewer than 2^32 threads in all (a launch of
+  // 2^26 workgroups of 256 -- one mask of nearly 2^31 rows -- fails with "invalid configuration argument")
+  return n <= ((1LL << 32) / kMtbBlock - 1) / (chunks > 0 ? chunks : 1);
 }
 
 int launch_masks_to_boxes(const void* masks, bool f32, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,

@@ -66,12 +66,13 @@ __global__ __launch_bounds__(256) void k_adaptive_avgpool(const float* __restric
     const long long t = i / ow;
     const int oy = (int)(t % oh);
     const long long p = t / oh;
-    const int y0 = (oy * h) / oh, y1 = ((oy + 1) * h + oh - 1) / oh;
-    const int x0 = (ox * w) / ow, x1 = ((ox + 1) * w + ow - 1) / ow;
+    // 64-bit products: oy * h passes 2^31 from oh * h >= 2^31 on (a 70000 x 1 plane pooled to 40000 x 1)
+    const int y0 = (int)(((long long)oy * h) / oh), y1 = (int)((((long long)oy + 1) * h + oh - 1) / oh);
+    const int x0 = (int)(((long long)ox * w) / ow), x1 = (int)((((long long)ox + 1) * w + ow - 1) / ow);
     float acc = 0.f;
     for (int yy = y0; yy < y1; ++yy)
       for (int xx = x0; xx < x1; ++xx) acc += x[((size_t)p * h + yy) * w + xx];
-    y[i] = acc / (float)((y1 - y0) * (x1 - x0));
+    y[i] = acc / (float)((long long)(y1 - y0) * (x1 - x0));
   }
 }
 
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void k_global_avgpool_small(const float* __res
 int launch_adaptive_avgpool(const float* x, float* y, int64_t planes, int h, int w, int oh, int ow, hipStream_t s) {
   const long long total = (long long)planes * oh * ow;
   if (total == 0) return MV_OK;
-  if (oh == 1 && ow == 1 && h * w <= 64 && (planes + 255) / 256 <= 0x7fffffffLL) {
+  if (oh == 1 && ow == 1 && (long long)h * w <= 64 && (planes + 255) / 256 <= 0x7fffffffLL) {
     hipLaunchKernelGGL(k_global_avgpool_small, dim3((unsigned)((planes + 255) / 256)), dim3(256), 0, s, x, y, (long long)planes, h * w);
     return check_launch("k_global_avgpool_small");
   }

@@ -59,7 +59,8 @@ __device__ inline float act(float v) {
 // KS > 0: static k-step count, weights register-resident (requires mtiles <= MT).
 // KS == 0: runtime k-steps, weights re-read from LDS per step, any number of 32-channel tiles.
 // FULLM: cout is a multiple of 32 (no per-channel store predicate).
-// FULLW: w is a multiple of 32 (no per-lane store predicate: the pipelined loop is one basic block).
+// FULLW: w is a multiple of the workgroup's wc columns, so every 32-pixel tile lies inside the row (no per-lane store
+//        predicate: the pipelined loop is one basic block).
 template <int KS, int MT, bool FULLM, bool RELU, bool FULLW>
 __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -217,7 +218,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs A) {
       return xin + ly * pitch + nx * 32 + l31;
     };
     // output address = uniform base (SGPR pair) + 32-bit per-lane byte offset -> global_store ... saddr form,
-    // the per-channel stride is added on the scalar unit
+    // the per-channel stride is added on the scalar unit.  launch_conv3x3 sends planes with 20*h*w >= 2^32 bytes of lane
+    // offset to the KS == 0 instantiation, so the offset below never wraps.
     char* const simg = reinterpret_cast<char*>(A.y + (size_t)img * cout * plane);
     auto tile_voff = [&](int j, bool& ok) -> unsigned {
       const int t = wave + 4 * j, ly = t / A.ntx, nx = t - ly * A.ntx;
@@ -317,12 +319,16 @@ static int launch_kw(const ConvArgs& a, size_t lds_bytes, hipStream_t s) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_bytes);
   hipLaunchKernelGGL(k, dim3(a.nblocks), dim3(256), lds_bytes, s, a);
-  return check_launch("k_conv3x3");
+  // ks0: the run-time k-step epilogue (64-bit pointers); ks5 / ks14: the pipelined one, ",fullw" without its per-lane store predicate
+  return check_launchf("k_conv3x3<ks%d%s>", KS, FULLW ? ",fullw" : "");
 }
 
 template <int KS, int MT, bool FULLM>
 static int launch_k(const ConvArgs& a, size_t lds_bytes, hipStream_t s) {
-  const bool fullw = KS > 0 && (a.wdt % 32 == 0);  // only the pipelined path distinguishes it
+  // Only the pipelined path distinguishes it.  Every 32-pixel tile of every workgroup must lie inside the row: a width that is
+  // a multiple of 32 but not of the workgroup's wc columns (wc = 256 for w > 256) leaves tiles past the right edge in the last
+  // workgroup of a row, and their unpredicated stores would land at the start of the next row (past the tensor after the last).
+  const bool fullw = KS > 0 && (a.wdt % a.wc == 0);
   if (fullw)
     return a.relu ? launch_kw<KS, MT, FULLM, true, true>(a, lds_bytes, s) : launch_kw<KS, MT, FULLM, false, true>(a, lds_bytes, s);
   return a.relu ? launch_kw<KS, MT, FULLM, true, false>(a, lds_bytes, s) : launch_kw<KS, MT, FULLM, false, false>(a, lds_bytes, s);
@@ -358,9 +364,13 @@ int launch_conv3x3(const float* x, const float* w, const float* b, float* y, int
   a.nblocks = (unsigned)nb;
   const size_t lds_bytes = bytes(th);
   const bool fullm = (cout % 32 == 0);
-  if (cin == 3 && cout == 64) return launch_k<14, 2, true>(a, lds_bytes, s);
-  if (cin == 3 && cout <= 64) return launch_k<14, 2, false>(a, lds_bytes, s);
-  if (cin == 1 && cout <= 64) return launch_k<5, 2, false>(a, lds_bytes, s);
+  // The pipelined epilogue's per-lane byte offset (tile_voff) spans the 4*hf planes of the lane half plus one plane:
+  // up to 20*h*w - 4 bytes, held in 32 bits.  Larger planes take the KS == 0 epilogue (64-bit pointers), the same
+  // k-ordered chain with the same bias slot and so the same bits.
+  const bool voff32 = 20ull * (size_t)h * wdt < (1ull << 32);
+  if (voff32 && cin == 3 && cout == 64) return launch_k<14, 2, true>(a, lds_bytes, s);
+  if (voff32 && cin == 3 && cout <= 64) return launch_k<14, 2, false>(a, lds_bytes, s);
+  if (voff32 && cin == 1 && cout <= 64) return launch_k<5, 2, false>(a, lds_bytes, s);
   return fullm ? launch_k<0, 2, true>(a, lds_bytes, s) : launch_k<0, 2, false>(a, lds_bytes, s);
 }
 

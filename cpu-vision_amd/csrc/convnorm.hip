@@ -875,7 +875,8 @@ static int pw_pick_nt(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
 // up: null, or the coarser map of launch_conv1x1_upsample_add (e.res is null then)
 static int conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e, hipStream_t s,
                    int64_t x_img_stride, int64_t y_img_stride, bool allow_k_slices, const PwArgs* up) {
-  if (hw > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: plane too large");
+  // pixel indices are ints, and a workgroup's last tile (p0 + PXB, the epilogue's p + 3) may reach up to 1024 pixels past the plane
+  if (hw > 0x7fffffffLL - 1024) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: plane too large");
   PwArgs a = {};
   if (up) a = *up;
   a.x = x, a.w = w, a.y = y, a.e = e;

@@ -112,6 +112,10 @@ def test_abi_validates_on_the_host():
         assert fn(16, 32, 64, 2, 8, 8, 256, 31, None) == -1 and b"mv_masks_to_boxes_workspace_bytes" in err()
         assert fn(16, 32, 64, 2, 8, 8, 264, 32, None) == -1 and b"16-byte aligned" in err()
         assert fn(16, 32, 64, 1 << 30, 1 << 20, 8, 256, 1 << 40, None) == -2 and b"launch grid" in err()
+        # one workgroup of 256 threads per (mask, 32-row chunk), fewer than 2^32 threads in all: at most 2^24 - 1 workgroups
+        assert fn(16, 32, 64, 1, 2 ** 31 - 16, 1, 256, 1 << 20, None) == -2 and b"launch grid" in err()
+        assert fn(16, 32, 64, 1, 32 * (2 ** 24 - 1) + 1, 1, 256, 1 << 20, None) == -2 and b"launch grid" in err()
+        assert fn(16, 32, 64, 1 << 24, 32, 8, 256, 1 << 40, None) == -2 and b"launch grid" in err()
 
     I, D = _lib.C.c_int, _lib.C.c_double
     xs = (_lib.C.c_void_p * 2)(1024, 2048)

@@ -15,6 +15,7 @@ BASE = dict(PTR, n=2, cin=4, h=8, w=8, cout=6, kh=3, kw=3, sh=1, sw=1, ph=1, pw=
             use_mask=0, affine=0, act=1, workspace=None, workspace_bytes=0)
 NULLS = dict.fromkeys(PTR)
 DEFORM_7X7 = dict(n=64, cin=8, cout=8, h=20, w=20, kh=7, kw=7, ph=3, pw=3)     # 49 taps: no fused kernel
+FAR = dict(x=1 << 40, weight=2 << 40, residual=3 << 40, y=4 << 40)             # tensors of GBs that do not overlap
 LONG_K = dict(n=1, cin=65536, cout=1, h=1, w=1, kh=1, kw=1, ph=0, pw=0)        # K = 65536: outside the implicit kernel
 
 
@@ -96,6 +97,12 @@ REJECTED = [
     ((B, A), dict(LONG_K), -1, "deform_conv2d: workspace of at least 262144 bytes (one image's columns) needed, got 0"),
     ((B, A), dict(LONG_K, workspace=1 << 30, workspace_bytes=65536 * 4 - 4), -1, "deform_conv2d: workspace of at least 262144 bytes (one image's columns) needed, got 262140"),
     ((A,), dict(LONG_K, affine=2, residual=None), -1, "deform_conv2d: workspace of at least 262144 bytes (one image's columns) needed, got 0"),
+    # one group image of exactly 2^30 elements (K, the output plane and its width all inside the implicit kernel's ranges): the kernel's
+    # 32-bit byte offsets into an image end there; 357 x 1000000 x 3 = 2^30 - 2741824 elements is taken (tests/test_gpu_large_offsets.py)
+    ((B, A), dict(FAR, n=1, cin=1024, cout=8, h=1024, w=1024, kh=3, kw=3, sh=2, sw=2, ph=1, pw=1), -2,
+     "conv2d (implicit GEMM): one image of a group has 2^30 elements or more"),
+    ((B, A), dict(FAR, n=1, cin=2048, cout=8, groups=2, h=1024, w=1024, kh=3, kw=3, sh=2, sw=2, ph=1, pw=1), -2,
+     "conv2d (implicit GEMM): one image of a group has 2^30 elements or more"),
 ]
 
 

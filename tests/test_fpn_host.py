@@ -69,6 +69,8 @@ def test_abi_refusals_without_a_device():
     refused(_call(lib, **far, n=65536, cin=1, cout=1, h=1, wd=1, top_h=1, top_w=1), "too large for one launch", UNSUPPORTED)
     refused(_call(lib, **far, n=1, cin=1, cout=1, h=65536, wd=32768, top_h=1, top_w=1), "plane too large", UNSUPPORTED)
     refused(_call(lib, **far, n=1, cin=1, cout=1, h=2, wd=2, top_h=65536, top_w=32768), "top plane too large", UNSUPPORTED)
+    # a plane within 1024 pixels of 2^31: the last workgroup's int pixel indices would pass 2^31
+    refused(_call(lib, **far, n=1, cin=1, cout=1, h=1, wd=2 ** 31 - 1024, top_h=1, top_w=1), "plane too large", UNSUPPORTED)
     assert np.all(y == -7.25)
 
     # n == 0: a successful no-op that looks at no pointer -- but after the shape and code checks

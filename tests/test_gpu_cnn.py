@@ -73,8 +73,29 @@ def test_wide_maps_take_the_first_generation_kernel():
         wt = (philox_f32(7401 + cout, (cout, cin, 3, 3)) - 0.5) * 0.5
         b = philox_f32(7402, (cout,)) - 0.5
         got = host(F.conv2d_bias_relu(dev(x), dev(wt), dev(b)))
-        assert _lib.last_kernel() == "k_conv3x3", _lib.last_kernel()
+        assert _lib.last_kernel() == ("k_conv3x3<ks14>" if cin == 3 else "k_conv3x3<ks0>"), _lib.last_kernel()
         np.testing.assert_array_equal(got, oracle_conv3x3(ref, x, wt, b))
+
+
+@pytest.mark.parametrize("n,cin,cout,h,w", [(1, 1, 8, 6, 544), (2, 3, 5, 4, 800), (1, 3, 64, 9, 768), (1, 1, 40, 3, 1056)])
+def test_wide_maps_whose_width_is_a_multiple_of_32(n, cin, cout, h, w):
+    """cin 1 and 3 run k_conv3x3's pipelined epilogue, which drops the per-lane store predicate when every 32-pixel tile lies inside
+    the row.  A width that is a multiple of 32 but not of the workgroup's 256 columns (544, 800, 1056) has tiles past the right edge
+    in the last workgroup of a row: their stores must stay masked -- unmasked they land at the start of the next row, and past the
+    tensor after the last one.  768 = 3 x 256 is the width that may go unmasked.  The output lies inside a NaN-filled buffer, which
+    must stay NaN around it."""
+    from cpu_vision_amd import _lib
+    x = philox_f32(7450 + w, (n, cin, h, w)) - 0.5
+    wt = (philox_f32(7451 + cout, (cout, cin, 3, 3)) - 0.5) * 0.5
+    b = philox_f32(7452, (cout,)) + 0.5
+    size, pad = n * cout * h * w, 1021  # an output off the 16-byte grid keeps cin 3 away from k_conv3x3_c3
+    buf = torch.full((pad + size + pad,), float("nan"), device="cuda")
+    out = buf[pad:pad + size].view(n, cout, h, w)
+    F.conv2d_bias_relu(dev(x), dev(wt), dev(b), out=out)
+    ks = 14 if cin == 3 else 5
+    assert _lib.last_kernel() == (f"k_conv3x3<ks{ks},fullw>" if w % 256 == 0 else f"k_conv3x3<ks{ks}>"), _lib.last_kernel()
+    np.testing.assert_array_equal(host(out), oracle_conv3x3(ref, x, wt, b))
+    assert bool(torch.isnan(buf[:pad]).all()) and bool(torch.isnan(buf[pad + size:]).all()), "stores outside the output"
 
 
 @pytest.mark.parametrize("group", ["1", "3", "64"])

@@ -455,3 +455,28 @@ def test_moved_code_reads_the_switches_from_functional(monkeypatch):
     assert F._use_separable(5, 5, image) is False
     monkeypatch.setattr(F, "INTEGER_BLUR_EXACT_2D", False)
     assert F._use_separable(5, 5, image) is True
+
+
+def test_large_offset_helpers_compare_both_sides_of_every_boundary():
+    """tests/_large.py, the bookkeeping of tests/test_gpu_large_offsets.py: which boundaries a tensor crosses, the rows picked around
+    them, and the assertion that the compared ranges straddle each one (it must fail when they do not)."""
+    from tests import _large as L
+    assert L.crossings(2 ** 31 + 5, 4) == {"element 2^31": 2 ** 31, "byte 2^31": 2 ** 29, "byte 2^32": 2 ** 30}
+    assert L.crossings(2 ** 31, 1) == {} and L.crossings(2 ** 30, 4) == {"byte 2^31": 2 ** 29}  # a boundary at the very end is not crossed
+    assert L.strips([5, 0, 1, 7, 6, 1]) == [(0, 2), (5, 8)]
+    assert L.rows_near(10 * 7, 7, 20) == [8, 9, 10, 11] and L.rows_near(20 * 7, 7, 20) == [0, 1, 18, 19]  # the seam between two planes
+    for planes, rin, win, rout, wout, scale, cut in ((3, 26760, 26760, 13380, 13380, 2, L.cut_pool2), (3, 26761, 26763, 13380, 13381, 2, L.cut_pool3s2),
+                                                      (3, 26761, 26760, 13381, 13380, 2, L.cut_pool3s2p1), (1, 16269437, 4, 16269437, 132, 1, L.cut_same)):
+        picks = L.pick_rows(planes, rin, win, 4, rout, wout, 4, scale)
+        text = L.assert_crossings_straddled(picks, cut, planes, rin, win, 4, rout, wout, 4)
+        assert "element 2^31" in text
+        for runs in picks.values():
+            for a, b in runs:
+                lo, hi, drop, first = cut(a, b, rin)
+                assert 0 <= lo <= first < hi <= rin and 0 <= a < b <= rout and drop in (0, 1)
+        with pytest.raises(AssertionError, match="does not cross"):
+            L.assert_crossings_straddled(picks, cut, planes, rin, win, 4, rout, wout, 4, need=("output byte 2^40",))
+    with pytest.raises(AssertionError, match="do not straddle"):
+        L.assert_straddles([(0, 2 ** 31)], 2 ** 31, "one side only")
+    # the cut of a padded 3 / 2 / 1 pool starts on an even row, so that its windows fall where the plane's do
+    assert L.cut_pool3s2p1(5, 7, 100) == (8, 14, 1, 9) and L.cut_pool3s2p1(0, 2, 100) == (0, 4, 0, 0) and L.cut_conv3(0, 3, 3) == (0, 3, 0, 0)
