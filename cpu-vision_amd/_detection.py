@@ -1,6 +1,7 @@
-"""The functional entries of the detection heads (models/detection/rpn.py, _utils.py BoxCoder): rpn_topk, rpn_decode and
-box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip).  float32, forward-only; the argument
-checks fire before a device is needed.  Every name here is re-exported by `functional`.
+"""The functional entries of the detection heads (models/detection/rpn.py, roi_heads.py, _utils.py BoxCoder): rpn_topk, rpn_decode
+and box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip), roi_detections over
+mv_roi_detections_f32 (csrc/roi_heads.hip).  float32, forward-only; the argument checks fire before a device is needed.  Every name
+here is re-exported by `functional`.
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ from . import _lib
 
 MAX_RPN_LEVELS = 8   # kMaxRpnLevels
 MAX_RPN_TOPK = 4096  # kRpnMaxK
+MAX_ROI_CLASSES = 2048  # kRoiMaxClasses
 BBOX_XFORM_CLIP = math.log(1000.0 / 16)
 
 
@@ -165,3 +167,64 @@ def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[floa
             _lib.launch(lib.mv_box_decode_f32, r, b.data_ptr(), r.data_ptr(), out.data_ptr(), m, c4 // 4, *[float(w) for w in weights],
                         float(bbox_xform_clip))
     return _lib.forward_only(out, "box_decode", boxes, rel_codes)
+
+
+def _rows(m: torch.Tensor) -> torch.Tensor:
+    """The matrix itself when its rows are dense (a column slice of a wider contiguous tensor is), else a contiguous copy."""
+    m = m.detach()
+    if m.stride(1) == 1 and (m.shape[0] <= 1 or m.stride(0) >= m.shape[1]):
+        return m
+    return m.contiguous()
+
+
+def roi_detections(class_logits: torch.Tensor, box_regression: torch.Tensor, rois: torch.Tensor, image_sizes,
+                   weights: Tuple[float, float, float, float] = (10.0, 10.0, 5.0, 5.0), bbox_xform_clip: float = BBOX_XFORM_CLIP,
+                   score_thresh: float = 0.05, min_size: float = 1e-2) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """RoIHeads.postprocess_detections (roi_heads.py) up to the per-image filters, ONE launch, one wave per roi: softmax of
+    class_logits (R, C), BoxCoder.decode_single of rois[:, 1:5] with box_regression (R, 4 C) and `weights`, clip_boxes_to_image with
+    image_sizes (N rows (h, w): a list, or an (N, 2) tensor) of image rois[:, 0], the background class dropped -> boxes (R, C - 1, 4),
+    scores (R, C - 1), labels (R, C - 1) int64 (column j - 1 holds class j), valid (R, C - 1) bool = score > score_thresh and both
+    sides >= min_size.  class_logits and box_regression may be column slices of one tensor: they are passed by their row strides."""
+    if not isinstance(class_logits, torch.Tensor) or class_logits.dim() != 2:
+        raise RuntimeError("roi_detections: class_logits should have shape (R, C)")
+    r, c = int(class_logits.shape[0]), int(class_logits.shape[1])
+    if not isinstance(box_regression, torch.Tensor) or tuple(box_regression.shape) != (r, 4 * c):
+        raise RuntimeError(f"roi_detections: box_regression should have shape ({r}, {4 * c}), got "
+                           f"{tuple(box_regression.shape) if isinstance(box_regression, torch.Tensor) else type(box_regression).__name__}")
+    if not isinstance(rois, torch.Tensor) or tuple(rois.shape) != (r, 5):
+        raise RuntimeError(f"roi_detections: rois should have shape ({r}, 5): (image index, x1, y1, x2, y2)")
+    if class_logits.dtype != torch.float32 or box_regression.dtype != torch.float32 or rois.dtype != torch.float32:
+        raise TypeError(f"roi_detections computes in float32. Got class_logits {class_logits.dtype}, box_regression {box_regression.dtype}, "
+                        f"rois {rois.dtype}")
+    if c < 2:
+        raise ValueError(f"roi_detections: at least 2 classes (the background and one more), got {c}")
+    if c > MAX_ROI_CLASSES:
+        raise _lib.Mi355VisionError(f"roi_detections: up to {MAX_ROI_CLASSES} classes, got {c}")
+    if r * c >= 2 ** 31:
+        raise _lib.Mi355VisionError(f"roi_detections: {r} rois x {c} classes exceed the 32-bit index")
+    if len(weights) != 4:
+        raise ValueError(f"roi_detections: four weights (wx, wy, ww, wh), got {weights!r}")
+    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
+                                                                                 dtype=torch.float32).reshape(-1, 2)
+    if sizes.dim() != 2 or sizes.shape[1] != 2 or (r > 0 and sizes.shape[0] < 1):
+        raise RuntimeError(f"roi_detections: image_sizes should hold at least one row (height, width), got {tuple(sizes.shape)}")
+    for m in (class_logits, box_regression, rois):
+        _lib.require_device(m, "roi_detections input")
+    lib = _lib.load()
+    dev = class_logits.device
+    with _lib.on_device_of(class_logits):
+        lg, dl = _rows(class_logits), _rows(box_regression)
+        rs = rois.detach().to(dev).contiguous()
+        sizes = sizes.detach().to(dev, torch.float32).contiguous()
+        boxes = torch.empty((r, c - 1, 4), dtype=torch.float32, device=dev)
+        scores = torch.empty((r, c - 1), dtype=torch.float32, device=dev)
+        labels = torch.empty((r, c - 1), dtype=torch.int64, device=dev)
+        valid = torch.empty((r, c - 1), dtype=torch.uint8, device=dev)
+        if r:
+            _lib.launch(lib.mv_roi_detections_f32, lg, lg.data_ptr(), int(lg.stride(0)) if r > 1 else c, dl.data_ptr(),
+                        int(dl.stride(0)) if r > 1 else 4 * c, rs.data_ptr(), sizes.data_ptr(), r, c, int(sizes.shape[0]),
+                        *[float(w) for w in weights], float(bbox_xform_clip), float(score_thresh), float(min_size), boxes.data_ptr(),
+                        scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
+    deps = (class_logits, box_regression, rois)
+    return (_lib.forward_only(boxes, "roi_detections", *deps), _lib.forward_only(scores, "roi_detections", *deps), labels,
+            valid.view(torch.bool))

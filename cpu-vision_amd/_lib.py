@@ -133,6 +133,7 @@ SYMBOLS = {
     "mv_rpn_decode_f32": (_i, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip, _ip, _i, _vp, _vp, _vp, _i64, _i64]
                           + [_d] * 7 + [_vp] * 5),
     "mv_box_decode_f32": (_i, [_vp, _vp, _vp, _i64, _i] + [_d] * 5 + [_vp]),
+    "mv_roi_detections_f32": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i64] + [_d] * 7 + [_vp] * 5),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1340,6 +1340,41 @@ int mv_box_decode_f32(const float* boxes, const float* rel_codes, float* out, in
   return launch_box_decode(boxes, rel_codes, out, m, classes, coef, (hipStream_t)stream);
 }
 
+// ---- RoIHeads.postprocess_detections: roi_heads.hip -----------------------------------------------------------------------------------
+int mv_roi_detections_f32(const float* class_logits, int64_t logits_stride, const float* box_regression, int64_t regression_stride,
+                          const float* rois, const float* image_sizes, int64_t r, int classes, int64_t n, double wx, double wy, double ww,
+                          double wh, double clip, double score_thresh, double min_size, float* boxes, float* scores, int64_t* labels,
+                          unsigned char* valid, void* stream) {
+  if (r < 0 || n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: bad shape r=%lld, n=%lld", (long long)r, (long long)n);
+  if (classes < 2)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: at least 2 classes (the background and one more), got %d", classes);
+  if (classes > kRoiMaxClasses) return set_error(MV_ERR_UNSUPPORTED, "roi_detections: up to %d classes, got %d", kRoiMaxClasses, classes);
+  if (logits_stride < classes || regression_stride < 4LL * classes)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: row strides (%lld, %lld), the rows have %d and %d elements",
+                     (long long)logits_stride, (long long)regression_stride, classes, 4 * classes);
+  if (r > 0x7fffffffLL / classes)
+    return set_error(MV_ERR_UNSUPPORTED, "roi_detections: %lld rois x %d classes exceed the 32-bit index", (long long)r, classes);
+  if (r == 0) return MV_OK;
+  if (n < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: %lld rois and no image", (long long)r);
+  if (logits_stride > 0x7fffffffffffLL / r || regression_stride > 0x7fffffffffffLL / r)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: row strides (%lld, %lld) of %lld rows exceed the address space",
+                     (long long)logits_stride, (long long)regression_stride, (long long)r);
+  if (!class_logits || !box_regression || !rois || !image_sizes || !boxes || !scores || !labels || !valid)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: null pointer");
+  if ((uintptr_t)labels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: labels must be 8-byte aligned");
+  const int64_t cells = r * (classes - 1);
+  const ByteRange ins[4] = {{class_logits, ((r - 1) * logits_stride + classes) * 4},
+                            {box_regression, ((r - 1) * regression_stride + 4LL * classes) * 4},
+                            {rois, r * 20},
+                            {image_sizes, n * 8}};
+  const ByteRange outs[4] = {{boxes, cells * 16}, {scores, cells * 4}, {labels, cells * 8}, {valid, cells}};
+  if (!outputs_clear(outs, 4, ins, 4))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: the outputs must not overlap an input or each other");
+  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
+  return launch_roi_detections(class_logits, logits_stride, box_regression, regression_stride, rois, image_sizes, r, classes, n, coef,
+                               (float)score_thresh, (float)min_size, boxes, scores, labels, valid, (hipStream_t)stream);
+}
+
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------
 // The checks the three entry points share, in the order of mv_roi_align_f32: 0 launch, 1 nothing to do, < 0 the error.
 static int roi_pool_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, const int* second,

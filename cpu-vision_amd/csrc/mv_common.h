@@ -331,6 +331,12 @@ int launch_rpn_decode(const float* const* logits, const float* const* deltas, co
                       float min_size, float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid,
                       hipStream_t s);
 int launch_box_decode(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, const float* coef5, hipStream_t s);
+// RoIHeads.postprocess_detections up to the per-image filters (roi_heads.hip; semantics in mi355vision.h mv_roi_detections_f32).  The
+// entry point has checked the arguments, the extents and the grid; r and n are positive, 2 <= classes <= kRoiMaxClasses.
+constexpr int kRoiMaxClasses = 2048;  // a workgroup parks four rows of exponentials in LDS: 32 KiB at this size
+int launch_roi_detections(const float* logits, int64_t logit_stride, const float* deltas, int64_t delta_stride, const float* rois,
+                          const float* image_sizes, int64_t r, int classes, int64_t n, const float* coef5, float score_thresh, float min_size,
+                          float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

@@ -1,0 +1,142 @@
+"""RoIHeads inference on the MI355X kernels: pooler -> box head -> box predictor -> postprocess_detections.
+
+Mirrors models/detection/roi_heads.py of the reference the way rpn.py mirrors models/detection/rpn.py: the same class, constructor
+arguments, child names (box_roi_pool, box_head, box_predictor) and state-dict keys.  Only `forward` differs.  The reference's
+postprocess_detections runs a softmax, BoxCoder.decode over every class, clip_boxes_to_image, three slices that drop the background
+column, three reshapes and two filter passes per image; here F.roi_detections does all of it for the whole batch in ONE launch and
+writes dense (R, C - 1) boxes / scores / labels with a validity flag.  What is left per image is what rpn.filter_proposals_detailed
+also does: the boolean indexing by `valid` (one read-back), ops.batched_nms and the slice.
+
+Numerics: DESIGN.md 3.25 and mi355vision.h mv_roi_detections_f32 -- every float operation is the reference's float32 operation,
+rounded once; exp is the correctly rounded float32 exp and the softmax sum is one ascending chain.  Inference only, float32 only:
+the matcher, the sampler and the losses of the reference are not built, the mask and keypoint branches are not implemented.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import torch
+from torch import nn, Tensor
+
+from . import _lib
+from . import functional as F
+from . import ops as box_ops
+from .rpn import BoxCoder
+
+__all__ = ["RoIHeads", "postprocess_detections_detailed"]
+
+
+def postprocess_detections_detailed(class_logits: Tensor, box_regression: Tensor, proposals: List[Tensor], image_shapes: List[Tuple[int, int]],
+                                    box_coder: BoxCoder, score_thresh: float, nms_thresh: float, detections_per_img: int,
+                                    min_size: float = 1e-2) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
+    """roi_heads.py postprocess_detections -> (boxes, scores, labels) per image: one F.roi_detections call for the whole batch, then
+    per image the boolean indexing by `valid` (the one read-back besides the nms's count), ops.batched_nms per class and the slice."""
+    boxes_per_image = [int(boxes_in_image.shape[0]) for boxes_in_image in proposals]
+    rois = box_ops._convert_to_roi_format([p.to(class_logits.dtype) for p in proposals])
+    boxes, scores, labels, valid = F.roi_detections(class_logits, box_regression, rois, image_shapes, box_coder.weights,
+                                                    box_coder.bbox_xform_clip, score_thresh, min_size)
+    all_boxes, all_scores, all_labels = [], [], []
+    for b, s, lab, v in zip(boxes.split(boxes_per_image, 0), scores.split(boxes_per_image, 0), labels.split(boxes_per_image, 0),
+                            valid.split(boxes_per_image, 0)):
+        # batch everything, by making every class prediction be a separate instance; low scores and empty boxes are `valid`'s zeros
+        b, s, lab = b[v], s[v], lab[v]
+        # non-maximum suppression, independently done per class
+        keep = box_ops.batched_nms(b, s, lab, nms_thresh)
+        # keep only topk scoring predictions
+        keep = keep[:detections_per_img]
+        all_boxes.append(b[keep])
+        all_scores.append(s[keep])
+        all_labels.append(lab[keep])
+    return all_boxes, all_scores, all_labels
+
+
+class RoIHeads(nn.Module):
+    """roi_heads.py:496-876, inference: forward(features, proposals, image_shapes) -> ([{boxes, labels, scores}] per image, {}).  The
+    training arguments are kept as given; a mask or keypoint module raises NotImplementedError."""
+
+    __annotations__ = {"box_coder": BoxCoder}
+
+    def __init__(self, box_roi_pool, box_head, box_predictor,
+                 # Faster R-CNN training
+                 fg_iou_thresh, bg_iou_thresh, batch_size_per_image, positive_fraction, bbox_reg_weights,
+                 # Faster R-CNN inference
+                 score_thresh, nms_thresh, detections_per_img,
+                 # Mask
+                 mask_roi_pool=None, mask_head=None, mask_predictor=None, keypoint_roi_pool=None, keypoint_head=None,
+                 keypoint_predictor=None):
+        super().__init__()
+        for name, module in (("mask_roi_pool", mask_roi_pool), ("mask_head", mask_head), ("mask_predictor", mask_predictor),
+                             ("keypoint_roi_pool", keypoint_roi_pool), ("keypoint_head", keypoint_head),
+                             ("keypoint_predictor", keypoint_predictor)):
+            if module is not None:
+                raise NotImplementedError(f"RoIHeads: {name} is given, and the mask and keypoint branches are not on the MI355X path "
+                                          "(the box branch is)")
+        self.box_similarity = box_ops.box_iou
+        # used during training (kept as given: the matcher and the sampler are not built)
+        self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
+        self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
+
+        if bbox_reg_weights is None:
+            bbox_reg_weights = (10.0, 10.0, 5.0, 5.0)
+        self.box_coder = BoxCoder(bbox_reg_weights)
+
+        self.box_roi_pool = box_roi_pool
+        self.box_head = box_head
+        self.box_predictor = box_predictor
+
+        self.score_thresh = score_thresh
+        self.nms_thresh = nms_thresh
+        self.detections_per_img = detections_per_img
+
+        self.mask_roi_pool = mask_roi_pool
+        self.mask_head = mask_head
+        self.mask_predictor = mask_predictor
+
+        self.keypoint_roi_pool = keypoint_roi_pool
+        self.keypoint_head = keypoint_head
+        self.keypoint_predictor = keypoint_predictor
+        self.eval()
+
+    def has_mask(self):
+        if self.mask_roi_pool is None:
+            return False
+        if self.mask_head is None:
+            return False
+        if self.mask_predictor is None:
+            return False
+        return True
+
+    def has_keypoint(self):
+        if self.keypoint_roi_pool is None:
+            return False
+        if self.keypoint_head is None:
+            return False
+        if self.keypoint_predictor is None:
+            return False
+        return True
+
+    def postprocess_detections(self, class_logits: Tensor, box_regression: Tensor, proposals: List[Tensor],
+                               image_shapes: List[Tuple[int, int]]) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
+        return postprocess_detections_detailed(class_logits, box_regression, proposals, image_shapes, self.box_coder, self.score_thresh,
+                                               self.nms_thresh, self.detections_per_img)
+
+    def forward(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]],
+                targets: Optional[List[Dict[str, Tensor]]] = None) -> Tuple[List[Dict[str, Tensor]], Dict[str, Tensor]]:
+        if self.training or targets is not None:
+            raise RuntimeError("the MI355X RoIHeads is inference only: call .eval() and pass no targets")
+        if self.has_mask() or self.has_keypoint():
+            raise NotImplementedError("RoIHeads: the mask and keypoint branches are not on the MI355X path")
+        for f in features.values():
+            if f.dtype != torch.float32:
+                raise TypeError(f"RoIHeads computes in float32. Got features {f.dtype}")
+        with torch.no_grad():  # no autograd bookkeeping per launch; the results are marked once (their backward raises)
+            box_features = self.box_roi_pool(features, proposals, image_shapes)
+            box_features = self.box_head(box_features)
+            class_logits, box_regression = self.box_predictor(box_features)
+            boxes, scores, labels = self.postprocess_detections(class_logits, box_regression, proposals, image_shapes)
+        deps = (*features.values(), *proposals, *self.box_head.parameters(), *self.box_predictor.parameters())
+        result: List[Dict[str, Tensor]] = []
+        for i in range(len(boxes)):
+            result.append({"boxes": _lib.forward_only(boxes[i], "RoIHeads.forward", *deps), "labels": labels[i],
+                           "scores": _lib.forward_only(scores[i], "RoIHeads.forward", *deps)})
+        return result, {}

@@ -1,0 +1,132 @@
+"""models/detection/transform.py: GeneralizedRCNNTransform, the normalisation and batching in front of a detection model and the
+box rescaling behind it.
+
+`normalize` is the package's F.normalize (one launch per image); `batch_images` is the reference's new_full + copy_ on the device;
+`postprocess` / `resize_boxes` is the reference's float32 composition.  `resize` is NOT here: the reference resizes with the
+non-antialiased bilinear `interpolate`, and the library has only the antialiased mv_resize_bilinear_aa_*.  The reference's private
+keyword `_skip_resize=True` is therefore the one way through `forward` (the reference honours it in training mode only; here it
+also stands for inference on images that already have their final size); without it `forward` raises NotImplementedError.
+"""
+from __future__ import annotations
+
+import math
+from typing import Any, Dict, List, Optional, Tuple
+
+import torch
+from torch import nn, Tensor
+
+from . import functional as F
+from .image_list import ImageList
+
+__all__ = ["GeneralizedRCNNTransform", "resize_boxes"]
+
+
+class GeneralizedRCNNTransform(nn.Module):
+    """transform.py:78-285.  forward(images, targets=None) -> (ImageList, targets): normalise each (C, H, W) image, pad them into
+    one batch whose sides are multiples of `size_divisible`."""
+
+    def __init__(self, min_size: int, max_size: int, image_mean: List[float], image_std: List[float], size_divisible: int = 32,
+                 fixed_size: Optional[Tuple[int, int]] = None, **kwargs: Any):
+        super().__init__()
+        if not isinstance(min_size, (list, tuple)):
+            min_size = (min_size,)
+        self.min_size = min_size
+        self.max_size = max_size
+        self.image_mean = image_mean
+        self.image_std = image_std
+        self.size_divisible = size_divisible
+        self.fixed_size = fixed_size
+        self._skip_resize = kwargs.pop("_skip_resize", False)
+        self.eval()
+
+    def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None) -> Tuple[ImageList, Optional[List[Dict[str, Tensor]]]]:
+        if self.training or targets is not None:
+            raise RuntimeError("the MI355X GeneralizedRCNNTransform is inference only: call .eval() and pass no targets")
+        images = [img for img in images]
+        for i in range(len(images)):
+            image = images[i]
+            if image.dim() != 3:
+                raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {image.shape}")
+            image = self.normalize(image)
+            image = self.resize(image)
+            images[i] = image
+
+        image_sizes = [img.shape[-2:] for img in images]
+        images = self.batch_images(images, size_divisible=self.size_divisible)
+        image_sizes_list: List[Tuple[int, int]] = []
+        for image_size in image_sizes:
+            torch._assert(len(image_size) == 2, f"Input tensors expected to have in the last two elements H and W, instead got {image_size}")
+            image_sizes_list.append((image_size[0], image_size[1]))
+
+        image_list = ImageList(images, image_sizes_list)
+        return image_list, targets
+
+    def normalize(self, image: Tensor) -> Tensor:
+        if not image.is_floating_point():
+            raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), but found type {image.dtype} instead")
+        if image.dtype != torch.float32:
+            raise TypeError(f"GeneralizedRCNNTransform computes in float32. Got {image.dtype}")
+        return F.normalize(image, list(self.image_mean), list(self.image_std))
+
+    def resize(self, image: Tensor) -> Tensor:
+        if self._skip_resize:
+            return image
+        raise NotImplementedError("GeneralizedRCNNTransform.resize: the non-antialiased bilinear `interpolate` of the reference's resize is not "
+                                  "in the library yet (it has the antialiased mv_resize_bilinear_aa_* only); construct the model with "
+                                  "_skip_resize=True and pass images of their final size")
+
+    def max_by_axis(self, the_list: List[List[int]]) -> List[int]:
+        maxes = the_list[0]
+        for sublist in the_list[1:]:
+            for index, item in enumerate(sublist):
+                maxes[index] = max(maxes[index], item)
+        return maxes
+
+    def batch_images(self, images: List[Tensor], size_divisible: int = 32) -> Tensor:
+        max_size = self.max_by_axis([list(img.shape) for img in images])
+        stride = float(size_divisible)
+        max_size = list(max_size)
+        max_size[1] = int(math.ceil(float(max_size[1]) / stride) * stride)
+        max_size[2] = int(math.ceil(float(max_size[2]) / stride) * stride)
+
+        batch_shape = [len(images)] + max_size
+        batched_imgs = images[0].new_full(batch_shape, 0)
+        for i in range(batched_imgs.shape[0]):
+            img = images[i]
+            batched_imgs[i, : img.shape[0], : img.shape[1], : img.shape[2]].copy_(img)
+
+        return batched_imgs
+
+    def postprocess(self, result: List[Dict[str, Tensor]], image_shapes: List[Tuple[int, int]],
+                    original_image_sizes: List[Tuple[int, int]]) -> List[Dict[str, Tensor]]:
+        if self.training:
+            return result
+        for i, (pred, im_s, o_im_s) in enumerate(zip(result, image_shapes, original_image_sizes)):
+            boxes = pred["boxes"]
+            boxes = resize_boxes(boxes, im_s, o_im_s)
+            result[i]["boxes"] = boxes
+        return result
+
+    def __repr__(self) -> str:
+        format_string = f"{self.__class__.__name__}("
+        _indent = "\n    "
+        format_string += f"{_indent}Normalize(mean={self.image_mean}, std={self.image_std})"
+        format_string += f"{_indent}Resize(min_size={self.min_size}, max_size={self.max_size}, mode='bilinear')"
+        format_string += "\n)"
+        return format_string
+
+
+def resize_boxes(boxes: Tensor, original_size: List[int], new_size: List[int]) -> Tensor:
+    """transform.py:301-313"""
+    ratios = [
+        torch.tensor(s, dtype=torch.float32, device=boxes.device) / torch.tensor(s_orig, dtype=torch.float32, device=boxes.device)
+        for s, s_orig in zip(new_size, original_size)
+    ]
+    ratio_height, ratio_width = ratios
+    xmin, ymin, xmax, ymax = boxes.unbind(1)
+
+    xmin = xmin * ratio_width
+    xmax = xmax * ratio_width
+    ymin = ymin * ratio_height
+    ymax = ymax * ratio_height
+    return torch.stack((xmin, ymin, xmax, ymax), dim=1)

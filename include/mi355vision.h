@@ -764,6 +764,38 @@ int mv_rpn_decode_f32(const float* const* logits, const float* const* deltas, co
 int mv_box_decode_f32(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, double wx, double wy, double ww,
                       double wh, double clip, void* stream);
 
+/* ---- RoIHeads.postprocess_detections up to the per-image filters (models/detection/roi_heads.py): softmax over the classes,
+ * BoxCoder.decode of every class, clip_boxes_to_image, the background column dropped, the score and small-box tests -- ONE launch,
+ * one wave64 per roi, lanes striding over the classes.
+ *
+ * All tensors are DEVICE float32.  class_logits (r, classes) and box_regression (r, 4 classes): row i starts logits_stride /
+ * regression_stride ELEMENTS after row 0 (>= the row's width: a column slice of a wider tensor can be passed, as img_strides in
+ * mv_rpn_topk_f32).  rois (r, 5) rows (image index, x1, y1, x2, y2), the layout of mv_roi_align_f32; image_sizes (n, 2) rows
+ * (height, width) as in mv_rpn_decode_f32.  2 <= classes <= 2048 (MV_ERR_UNSUPPORTED above); r * classes < 2^31
+ * (MV_ERR_UNSUPPORTED otherwise).  The outputs are dense, the background class 0 dropped; cell (i, j - 1) belongs to class j >= 1:
+ *   boxes (r, classes - 1, 4) float32;  scores (r, classes - 1) float32;  labels (r, classes - 1) int64 = j (8-byte aligned);
+ *   valid (r, classes - 1) uint8 = (score > (float)score_thresh) & (x2 - x1 >= (float)min_size) & (y2 - y1 >= (float)min_size)
+ * -- the score test is STRICT, as torch.where(scores > score_thresh) of the reference (mv_rpn_decode_f32's is not).
+ *
+ * Numerics: every operation rounded once to float32, nothing fused, the divisions correctly rounded.
+ *   softmax of row i:  m = max_j x_j (a NaN wins);  e_j = E(x_j - m), E the correctly rounded float32 exponential of
+ *     mv_rpn_decode_f32;  s = ((e_0 + e_1) + e_2) + ... , ONE float32 chain in ascending class order, the background included;
+ *     score_j = e_j / s.  NaN and +-inf behave as these formulas say: a row of all -inf, or a row that contains +inf or a NaN, gives
+ *     NaN scores (and valid 0).  torch's CPU softmax uses a 1-ulp vector exp and a summation order that depends on the vector width,
+ *     which no kernel reproduces bit for bit; this is the library's statement of the value.
+ *   box (i, j):  decode_single (above) of rois[i, 1:5] with the codes box_regression[i, 4 j .. 4 j + 3], weights and clip as (float);
+ *     then x clamped to [0, width] and y to [0, height] of image (int)rois[i, 0] (a NaN stays).
+ * An image index outside [0, n) cannot be reported without a read-back: the row's boxes, scores and labels are zeros, valid 0, and
+ * nothing is read through the index.
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a null pointer, classes < 2, a row stride below the row's width,
+ * n < 1 with r > 0, a negative r or n, an output that overlaps an input or another output (byte ranges), a misaligned labels.
+ * r == 0 is a no-op that touches no pointer.  Nothing is allocated or read back. */
+int mv_roi_detections_f32(const float* class_logits, int64_t logits_stride, const float* box_regression, int64_t regression_stride,
+                          const float* rois, const float* image_sizes, int64_t r, int classes, int64_t n, double wx, double wy, double ww,
+                          double wh, double clip, double score_thresh, double min_size, float* boxes, float* scores, int64_t* labels,
+                          unsigned char* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
