@@ -1,6 +1,7 @@
-"""The functional entries of the detection heads (models/detection/rpn.py, roi_heads.py, _utils.py BoxCoder): rpn_topk, rpn_decode
-and box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip), roi_detections over
-mv_roi_detections_f32 (csrc/roi_heads.hip).  float32, forward-only; the argument checks fire before a device is needed.  Every name
+"""The functional entries of the detection heads (models/detection/rpn.py, roi_heads.py, retinanet.py, _utils.py BoxCoder): rpn_topk,
+rpn_decode and box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip), roi_detections over
+mv_roi_detections_f32 (csrc/roi_heads.hip), retinanet_topk and retinanet_decode over mv_retinanet_topk_f32 / mv_retinanet_decode_f32
+(csrc/retinanet.hip).  float32, forward-only; the argument checks fire before a device is needed.  Every name
 here is re-exported by `functional`.
 """
 from __future__ import annotations
@@ -142,6 +143,107 @@ def rpn_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx: torc
                         scores.data_ptr(), levels.data_ptr(), valid.data_ptr())
     deps = (*logits, *deltas)
     return (_lib.forward_only(boxes, "rpn_decode", *deps), _lib.forward_only(scores, "rpn_decode", *deps), levels, valid.view(torch.bool))
+
+
+def _class_maps(name: str, logits, num_classes):
+    """The checks of RetinaNet's per-level class maps ((n, A_l * num_classes, H_l, W_l) float32) -> [(n, A_l, H_l, W_l)]."""
+    if not isinstance(num_classes, int) or isinstance(num_classes, bool) or num_classes < 1:
+        raise ValueError(f"{name}: num_classes must be a positive int, got {num_classes!r}")
+    shapes = _level_maps(name, logits, "logits", num_classes)
+    if sum(a * h * w for _, a, h, w in shapes) * num_classes >= 2 ** 31:
+        raise _lib.Mi355VisionError(f"{name}: the anchors of all levels x {num_classes} classes exceed the 32-bit index")
+    return shapes
+
+
+def retinanet_topk(logits: List[torch.Tensor], num_classes: int, k: int, score_thresh: float) -> torch.Tensor:
+    """postprocess_detections' sigmoid, `> score_thresh` and per-level topk (retinanet.py) on the head's own NCHW class maps:
+    logits[l] (N, A_l * num_classes, H_l, W_l) -> idx (N, Ktot) int32, Ktot = sum_l min(k, A_l H_l W_l num_classes): per image, level
+    after level, the flat indices ((y, x, a) anchor index of the concatenated layout) * num_classes + class of the level's
+    min(k, passing) greatest scores in stable descending order (equal scores by ascending flat index), then -1.  One (image, level)
+    is spread over many workgroups; nothing is read back."""
+    shapes = _class_maps("retinanet_topk", logits, num_classes)
+    if not isinstance(k, int) or k < 1:
+        raise ValueError(f"retinanet_topk: k must be a positive int, got {k!r}")
+    if k > MAX_RPN_TOPK:
+        raise _lib.Mi355VisionError(f"retinanet_topk: k up to {MAX_RPN_TOPK}, got {k}")
+    score_thresh = float(score_thresh)
+    for m in logits:
+        _lib.require_device(m, "logits")
+    lib = _lib.load()
+    l0 = logits[0]
+    n = shapes[0][0]
+    total = sum(min(k, a * h * w * num_classes) for _, a, h, w in shapes)
+    with _lib.on_device_of(l0):
+        maps = [_dense_images(m) for m in logits]
+        idx = torch.empty((n, total), dtype=torch.int32, device=l0.device)
+        if n:
+            hs, ws, as_ = _tables(shapes)
+            nbytes = int(lib.mv_retinanet_topk_workspace_bytes(n, hs, ws, as_, len(maps), num_classes, k))
+            if not nbytes:
+                raise _lib.Mi355VisionError(f"retinanet_topk: {n} images are more than one call takes")
+            buf, ws_ptr, nbytes = _lib.workspace(nbytes, l0.device)
+            _lib.launch(lib.mv_retinanet_topk_f32, l0, _lib.pointer_table(maps), hs, ws, as_, _img_strides(maps), len(maps), num_classes, n, k,
+                        score_thresh, idx.data_ptr(), ws_ptr, nbytes)
+    return idx
+
+
+def retinanet_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx: torch.Tensor, cell_anchors: List[torch.Tensor],
+                     strides: Sequence[Tuple[int, int]], image_sizes, num_classes: int,
+                     weights: Tuple[float, float, float, float] = (1.0, 1.0, 1.0, 1.0),
+                     clip: float = BBOX_XFORM_CLIP) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The rest of postprocess_detections before the nms for the candidates idx (N, K) of retinanet_topk, ONE launch, one lane per
+    candidate: anchor idx // num_classes from cell_anchors[l] (A_l, 4) and strides[l] = (stride_h, stride_w), label idx % num_classes,
+    BoxCoder.decode_single with `weights` and `clip`, clip_boxes_to_image with image_sizes (N rows (h, w): a list, or an (N, 2)
+    tensor), the sigmoid -> boxes (N, K, 4), scores (N, K), labels (N, K) int64, valid (N, K) bool (False, with zeros, for the -1
+    padding and any other index outside the pyramid)."""
+    shapes = _class_maps("retinanet_decode", logits, num_classes)
+    anchors = [a for _, a, _, _ in shapes]
+    dshapes = _level_maps("retinanet_decode", deltas, "deltas", 4, anchors) if isinstance(deltas, (list, tuple)) and len(deltas) == len(logits) else None
+    if dshapes is None or any(d[2:] != s[2:] or d[0] != s[0] for d, s in zip(dshapes, shapes)):
+        raise RuntimeError("retinanet_decode: deltas should hold one map per level of logits, of the same batch and size with 4 channels per anchor")
+    num, n = len(shapes), shapes[0][0]
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
+        raise RuntimeError(f"retinanet_decode: idx should be an int32 tensor of shape ({n}, K)")
+    if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or \
+            any(tuple(c.shape) != (a, 4) for c, a in zip(cell_anchors, anchors)):
+        raise RuntimeError(f"retinanet_decode: cell_anchors should hold one (A, 4) tensor per level, A = {anchors}")
+    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
+        raise RuntimeError(f"retinanet_decode: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
+    if len(weights) != 4:
+        raise ValueError(f"retinanet_decode: four weights (wx, wy, ww, wh), got {weights!r}")
+    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
+                                                                                 dtype=torch.float32).reshape(-1, 2)
+    if tuple(sizes.shape) != (n, 2):
+        raise RuntimeError(f"retinanet_decode: image_sizes should hold {n} rows (height, width), got {tuple(sizes.shape)}")
+    for m in (*logits, *deltas, idx):
+        _lib.require_device(m, "retinanet_decode input")
+    lib = _lib.load()
+    l0 = logits[0]
+    k = int(idx.shape[1])
+    with _lib.on_device_of(l0):
+        lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
+        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
+        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
+        ix = idx.contiguous()
+        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
+        labels = torch.empty((n, k), dtype=torch.int64, device=l0.device)
+        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
+        if n and k:
+            hs, ws, as_ = _tables(shapes)
+            sh = (C.c_int * num)(*[int(s[0]) for s in strides])
+            sw = (C.c_int * num)(*[int(s[1]) for s in strides])
+            _lib.launch(lib.mv_retinanet_decode_f32, l0, _lib.pointer_table(lmaps), _lib.pointer_table(dmaps), hs, ws, as_, _img_strides(lmaps),
+                        _img_strides(dmaps), sh, sw, num, num_classes, base.data_ptr(), sizes.data_ptr(), ix.data_ptr(), n, k,
+                        *[float(w) for w in weights], float(clip), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
+    deps = (*logits, *deltas)
+    return (_lib.forward_only(boxes, "retinanet_decode", *deps), _lib.forward_only(scores, "retinanet_decode", *deps), labels,
+            valid.view(torch.bool))
+
+
+def retinanet_topk_chunk() -> int:
+    """The elements of an (image, level) class map one stage-1 workgroup of retinanet_topk reads (mv_retinanet_topk_chunk)."""
+    return int(_lib.load().mv_retinanet_topk_chunk())
 
 
 def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[float, float, float, float],

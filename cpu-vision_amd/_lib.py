@@ -133,6 +133,11 @@ SYMBOLS = {
     "mv_rpn_decode_f32": (_i, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip, _ip, _i, _vp, _vp, _vp, _i64, _i64]
                           + [_d] * 7 + [_vp] * 5),
     "mv_box_decode_f32": (_i, [_vp, _vp, _vp, _i64, _i] + [_d] * 5 + [_vp]),
+    "mv_retinanet_topk_chunk": (_i, []),
+    "mv_retinanet_topk_workspace_bytes": (_i64, [_i64, _ip, _ip, _ip, _i, _i, _i]),
+    "mv_retinanet_topk_f32": (_i, [_vp, _ip, _ip, _ip, C.POINTER(C.c_int64), _i, _i, _i64, _i, _d, _vp, _vp, _i64, _vp]),
+    "mv_retinanet_decode_f32": (_i, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip, _ip, _i, _i, _vp, _vp, _vp,
+                                     _i64, _i64] + [_d] * 5 + [_vp] * 5),
     "mv_roi_detections_f32": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i64] + [_d] * 7 + [_vp] * 5),
 }
 

@@ -1375,6 +1375,108 @@ int mv_roi_detections_f32(const float* class_logits, int64_t logits_stride, cons
                                (float)score_thresh, (float)min_size, boxes, scores, labels, valid, (hipStream_t)stream);
 }
 
+// ---- RetinaNet threshold + top-k / decode: retinanet.hip -------------------------------------------------------------------------------
+// The level tables of the retinanet entries: rpn_levels_check, and classes >= 1 with anchors * classes < 2^31.  taken: sum of
+// min(k, a * h * w * classes).
+static int retinanet_levels_check(const char* op, const int* hs, const int* ws, const int* as, int levels, int classes, int k,
+                                  int64_t* anchors, int64_t* taken) {
+  int64_t unused;
+  if (int rc = rpn_levels_check(op, hs, ws, as, levels, 1, anchors, &unused)) return rc;
+  if (classes < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: classes must be positive, got %d", op, classes);
+  if (*anchors * classes > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld anchors x %d classes exceed the 32-bit index", op, (long long)*anchors, classes);
+  int64_t take = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
+    take += nl < k ? nl : k;
+  }
+  *taken = take;
+  return MV_OK;
+}
+
+int mv_retinanet_topk_chunk(void) { return kRetChunk; }
+
+int64_t mv_retinanet_topk_workspace_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k) {
+  int64_t anchors, taken;
+  if (n <= 0 || n > 65535 || k < 1 || k > kRpnMaxK || retinanet_levels_check("retinanet_topk", hs, ws, as, levels, classes, k, &anchors, &taken))
+    return 0;
+  return retinanet_plan(n, hs, ws, as, levels, classes, k).bytes;
+}
+
+int mv_retinanet_topk_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                          int classes, int64_t n, int k, double score_thresh, int* idx, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: bad image count %lld", (long long)n);
+  if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: k must be positive, got %d", k);
+  int64_t anchors, taken;
+  if (int rc = retinanet_levels_check("retinanet_topk", hs, ws, as, levels, classes, k, &anchors, &taken)) return rc;
+  if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "retinanet_topk: k up to %d, got %d", kRpnMaxK, k);
+  if (n == 0) return MV_OK;
+  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "retinanet_topk: %lld images exceed the launch grid", (long long)n);
+  if (!logits || !img_strides || !idx) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: null pointer");
+  const int64_t need = retinanet_plan(n, hs, ws, as, levels, classes, k).bytes;
+  ByteRange ins[kMaxRpnLevels];
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
+    if (!logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: null pointer (level %d)", l);
+    if (img_strides[l] < nl || img_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: image stride %lld of level %d, its map has %lld elements",
+                       (long long)img_strides[l], l, (long long)nl);
+    ins[l] = {logits[l], ((n - 1) * img_strides[l] + nl) * 4};
+  }
+  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: needs a workspace");
+  if (workspace_bytes < need)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: workspace of %lld bytes, need %lld (mv_retinanet_topk_workspace_bytes)",
+                     (long long)workspace_bytes, (long long)need);
+  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: the workspace must be 16-byte aligned");
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: idx must be 4-byte aligned");
+  const ByteRange outs[2] = {{idx, n * taken * 4}, {workspace, need}};
+  if (!outputs_clear(outs, 2, ins, levels))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: idx and the workspace must not overlap an input or each other");
+  return launch_retinanet_topk(logits, hs, ws, as, img_strides, levels, classes, (int)n, k, (float)score_thresh, idx, workspace,
+                               (hipStream_t)stream);
+}
+
+int mv_retinanet_decode_f32(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                            const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w,
+                            int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
+                            int64_t k, double wx, double wy, double ww, double wh, double clip, float* boxes, float* scores,
+                            int64_t* labels, unsigned char* valid, void* stream) {
+  if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: bad shape n=%lld, k=%lld", (long long)n, (long long)k);
+  int64_t anchors, taken;
+  if (int rc = retinanet_levels_check("retinanet_decode", hs, ws, as, levels, classes, 1, &anchors, &taken)) return rc;
+  if (!strides_h || !strides_w) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: null level table");
+  for (int l = 0; l < levels; ++l)
+    if (strides_h[l] < 0 || strides_w[l] < 0 || (int64_t)strides_h[l] * hs[l] > 0x7fffffffLL || (int64_t)strides_w[l] * ws[l] > 0x7fffffffLL)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: bad strides (%d, %d) of level %d", strides_h[l], strides_w[l], l);
+  if (n == 0 || k == 0) return MV_OK;
+  if (n > 0x7fffffffLL || k > (0x7fffffffLL * 256) / n)
+    return set_error(MV_ERR_UNSUPPORTED, "retinanet_decode: %lld x %lld candidates exceed the launch grid", (long long)n, (long long)k);
+  if (!logits || !deltas || !logit_strides || !delta_strides || !base_anchors || !image_sizes || !idx || !boxes || !scores || !labels || !valid)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: null pointer");
+  if ((uintptr_t)labels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: labels must be 8-byte aligned");
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: idx must be 4-byte aligned");
+  ByteRange ins[2 * kMaxRpnLevels + 3];
+  int64_t base_rows = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t al = (int64_t)as[l] * hs[l] * ws[l], nl = al * classes;
+    if (!logits[l] || !deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: null pointer (level %d)", l);
+    if (logit_strides[l] < nl || delta_strides[l] < 4 * al || logit_strides[l] > 0x7fffffffffffLL / n || delta_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: image strides (%lld, %lld) of level %d, its maps have %lld and %lld elements",
+                       (long long)logit_strides[l], (long long)delta_strides[l], l, (long long)nl, (long long)(4 * al));
+    ins[2 * l] = {logits[l], ((n - 1) * logit_strides[l] + nl) * 4};
+    ins[2 * l + 1] = {deltas[l], ((n - 1) * delta_strides[l] + 4 * al) * 4};
+    base_rows += as[l];
+  }
+  ins[2 * levels] = {base_anchors, base_rows * 16}, ins[2 * levels + 1] = {image_sizes, n * 8}, ins[2 * levels + 2] = {idx, n * k * 4};
+  const ByteRange outs[4] = {{boxes, n * k * 16}, {scores, n * k * 4}, {labels, n * k * 8}, {valid, n * k}};
+  if (!outputs_clear(outs, 4, ins, 2 * levels + 3))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: the outputs must not overlap an input or each other");
+  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
+  return launch_retinanet_decode(logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, classes,
+                                 base_anchors, image_sizes, idx, n, k, coef, boxes, scores, labels, valid, (hipStream_t)stream);
+}
+
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------
 // The checks the three entry points share, in the order of mv_roi_align_f32: 0 launch, 1 nothing to do, < 0 the error.
 static int roi_pool_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, const int* second,

@@ -337,6 +337,21 @@ constexpr int kRoiMaxClasses = 2048;  // a workgroup parks four rows of exponent
 int launch_roi_detections(const float* logits, int64_t logit_stride, const float* deltas, int64_t delta_stride, const float* rois,
                           const float* image_sizes, int64_t r, int classes, int64_t n, const float* coef5, float score_thresh, float min_size,
                           float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
+// RetinaNet's threshold + top-k and decode (retinanet.hip; semantics in mi355vision.h mv_retinanet_topk_f32 and below).  The entry
+// points have checked the arguments, the extents, the workspace and the grids; the tables are as for the rpn launchers.
+constexpr int kRetChunk = 16384;  // elements of an (image, level) map per stage-1 workgroup: 16 per thread, in registers
+struct RetinanetPlan {           // the workspace of launch_retinanet_topk: counts, then per image the pools of its levels
+  int64_t chunks[kMaxRpnLevels], pool_start[kMaxRpnLevels];
+  int64_t total_chunks, pool_per_image, counts_bytes, bytes;
+};
+RetinanetPlan retinanet_plan(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k);
+int launch_retinanet_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                          int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s);
+int launch_retinanet_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                            const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w,
+                            int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
+                            int64_t k, const float* coef5, float* boxes, float* scores, int64_t* labels, unsigned char* valid,
+                            hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

@@ -1,0 +1,335 @@
+// retinanet.hip -- the inference half of torchvision's RetinaNet.postprocess_detections (models/detection/retinanet.py) up to the nms
+// on gfx950.  Per image and level the reference applies a sigmoid to every (anchor, class) logit of a permuted copy, masks
+// `> score_thresh`, torch.where, topk, divides and gathers, decodes and clips; here the selection runs on the head's own NCHW maps,
+// spread over many workgroups, and only the selected candidates are decoded.
+//
+// A candidate is (anchor, class): logit channel a K + c at (y, x), flat index f = (start_l + (y W + x) A + a) K + c.  Its key is
+// the 64-bit (score bits << 32 | ~f): scores are in [0, 1], so their bit patterns order as the scores do, and ~f puts the smaller
+// flat index first among equal SCORES.  Keys of distinct candidates differ, so "the k greatest keys" is ONE set whatever the order
+// in which the candidates are visited, and the stable descending order is the descending order of the keys.  A candidate that fails
+// `score > thresh` (a NaN fails) has the key 0, which no passing candidate has (f < 2^31: ~f != 0).
+//
+// k_retinanet_chunks   stage 1, one workgroup per chunk of kRetChunk consecutive ELEMENTS of an (image, level) map, read in memory
+//                      order (coalesced) and once: score, threshold, key, all in registers.  The chunk's own min(k, passing) greatest
+//                      keys (select_keys below) are appended to the (image, level)'s pool in the workspace: one global atomicAdd per
+//                      chunk reserves the room, so the pool's ORDER varies from run to run and its content does not.  A pool has room
+//                      for min(k, kRetChunk) keys of every chunk: nothing is dropped, whatever passes.
+// k_retinanet_rank     stage 2, one workgroup per (image, level): select_keys over the pool, the <= k <= 4096 selected keys into
+//                      LDS, ranked pairwise there (position = #{greater keys}); idx[rank] = f, the rest of the segment -1.
+// select_keys          radix select of the k-th greatest key, 8 bits per pass from the top, a 256-bin histogram in LDS per pass
+//                      (hist_add of k_rpn_topk).  It stops as soon as the answer is known: after the first pass when at most k
+//                      keys pass at all, after any pass when the bin of the k-th key is taken whole; at most 8 passes.
+// k_retinanet_decode   one lane per idx[i, j]: anchor f / K and label f % K, the anchor in registers (anchor_at of mv_boxcoder.h,
+//                      shared with k_rpn_decode), decode_single, clip to the image, the score recomputed.
+//
+// Every float operation is written with __f*_rn and exp is the correctly rounded float32 exp, as in rpn.hip.
+#include "mv_boxcoder.h"
+#include "mv_common.h"
+#include "mv_topk.h"
+
+namespace mv {
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int kRetThreads = 1024;
+constexpr int kRetLoads = kRetChunk / kRetThreads;  // elements of a chunk per thread, in registers
+constexpr int kRankLoads = 4;                       // pool keys a thread loads before it works on them
+static_assert(kRetChunk % kRetThreads == 0, "a chunk is a whole number of elements per thread");
+
+// The k greatest of the non-zero keys that `each` visits (it calls f(key) for every key of this thread, the same number of times
+// in every thread of the workgroup; 0 = no key).  Returns T and sets *take = min(k, keys): the selected keys are those >= T.
+template <typename Each>
+__device__ inline u64 select_keys(const Each& each, unsigned k, unsigned* hist, unsigned* sel, int tid, int lane, unsigned* take) {
+  u64 prefix = 0;
+  unsigned rem = k;  // how many of the keys that share `prefix` are taken
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = 56 - 8 * pass;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    each([&](u64 key) { hist_add(hist, key != 0 && (pass == 0 || ((key >> shift) >> 8) == prefix), (unsigned)(key >> shift) & 255u, lane); });
+    __syncthreads();
+    if (tid < 256) {
+      unsigned above = 0;
+      for (int j = tid + 1; j < 256; ++j) above += hist[j];
+      const unsigned mine = hist[tid];
+      if (tid == 0) sel[3] = above + mine;  // every key counted in this pass
+      if (above < rem && above + mine >= rem) sel[0] = (unsigned)tid, sel[1] = rem - above, sel[2] = mine;  // at most one digit
+    }
+    __syncthreads();  // hist and sel are next written behind the first barrier of the next pass
+    if (pass == 0 && sel[3] <= k) {
+      *take = sel[3];
+      return 1;
+    }
+    prefix = (prefix << 8) | sel[0];
+    rem = sel[1];
+    if (sel[2] == rem) return *take = k, prefix << shift;  // the whole bin is taken: no need to look inside it
+  }
+  *take = k;
+  return prefix;
+}
+
+// The key of element e (memory order: channel a K + c, position pos) of a level's map with the logit x: 0 when it does not pass.
+__device__ inline u64 candidate_key(unsigned e, float x, int hw, int A, int K, int level_start, float thresh) {
+  const float s = sigmoid_cr(x);
+  const unsigned ch = e / (unsigned)hw, pos = e - ch * (unsigned)hw, a = ch / (unsigned)K, c = ch - a * (unsigned)K;
+  const unsigned f = ((unsigned)level_start + pos * (unsigned)A + a) * (unsigned)K + c;
+  return s > thresh ? ((u64)__float_as_uint(s) << 32) | (unsigned)~f : 0ull;
+}
+
+struct RetTopkArgs {
+  const float* logits[kMaxRpnLevels];
+  long long img_stride[kMaxRpnLevels];
+  int hw[kMaxRpnLevels], a[kMaxRpnLevels];
+  int level_start[kMaxRpnLevels];   // anchors of the levels before
+  int chunk_start[kMaxRpnLevels];   // first stage-1 block of the level
+  long long pool_start[kMaxRpnLevels];  // first pool entry of the level within an image's pools
+  int out_start[kMaxRpnLevels];     // position of the level's segment in a row of idx
+  int seg[kMaxRpnLevels];           // min(k, a * hw * classes)
+  int levels, classes, k, k_total;
+  long long pool_per_image;
+  float thresh;
+  unsigned* counts;  // (n, levels): keys in the pool
+  u64* pool;
+  int* idx;
+};
+
+__global__ __launch_bounds__(256) void k_retinanet_zero(unsigned* __restrict__ counts, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) counts[i] = 0;
+}
+
+__global__ __launch_bounds__(kRetThreads) void k_retinanet_chunks(const RetTopkArgs T) {
+  const int img = blockIdx.y;
+  int level = 0;
+#pragma unroll
+  for (int l = 1; l < kMaxRpnLevels; ++l)
+    if (l < T.levels && (int)blockIdx.x >= T.chunk_start[l]) level = l;
+  const float* p = nullptr;
+  long long img_stride = 0, pool_start = 0;
+  int hw = 1, A = 1, level_start = 0, chunk_start = 0;
+#pragma unroll
+  for (int l = 0; l < kMaxRpnLevels; ++l)
+    if (l == level)
+      p = T.logits[l], img_stride = T.img_stride[l], pool_start = T.pool_start[l], hw = T.hw[l], A = T.a[l], level_start = T.level_start[l],
+      chunk_start = T.chunk_start[l];
+  p += (size_t)img * img_stride;
+  const int K = T.classes;
+  const long long nl = (long long)A * K * hw;  // < 2^31
+  const long long base = (long long)((int)blockIdx.x - chunk_start) * kRetChunk;
+
+  __shared__ unsigned hist[256];
+  __shared__ unsigned sel[4];
+  __shared__ unsigned n_out, room;
+  const int tid = threadIdx.x, lane = tid & 63;
+
+  float x[kRetLoads];
+#pragma unroll
+  for (int u = 0; u < kRetLoads; ++u) {
+    const long long o = base + u * kRetThreads + tid;
+    x[u] = o < nl ? p[o] : 0.f;
+  }
+  u64 key[kRetLoads];
+#pragma unroll
+  for (int u = 0; u < kRetLoads; ++u) {
+    const long long o = base + u * kRetThreads + tid;
+    key[u] = o < nl ? candidate_key((unsigned)o, x[u], hw, A, K, level_start, T.thresh) : 0ull;
+  }
+
+  unsigned take;
+  const u64 thr = select_keys(
+      [&](auto f) {
+#pragma unroll
+        for (int u = 0; u < kRetLoads; ++u) f(key[u]);
+      },
+      (unsigned)T.k, hist, sel, tid, lane, &take);
+  if (take == 0) return;  // the same in every thread
+  if (tid == 0) n_out = 0, room = atomicAdd(&T.counts[img * T.levels + level], take);
+  __syncthreads();
+  u64* const pool = T.pool + (size_t)img * T.pool_per_image + pool_start + room;
+#pragma unroll
+  for (int u = 0; u < kRetLoads; ++u)
+    if (key[u] >= thr && key[u] != 0) {  // exactly `take` keys
+      const unsigned slot = atomicAdd(&n_out, 1u);
+      if (slot < take) pool[slot] = key[u];
+    }
+}
+
+// DIRECT: the keys come from the level's map itself, computed anew in every pass, in place of the pool -- the whole (image, level)
+// in ONE workgroup, without stage 1.  Instantiated in -DMV_TUNING builds only, for tools/perf_retinanet.py to measure what stage 1 buys.
+template <bool DIRECT>
+__global__ __launch_bounds__(kRetThreads) void k_retinanet_rank(const RetTopkArgs T) {
+  const int level = blockIdx.x, img = blockIdx.y;
+  const float* p = nullptr;
+  long long pool_start = 0, img_stride = 0;
+  int out_start = 0, seg = 0, hw = 1, A = 1, level_start = 0;
+#pragma unroll
+  for (int l = 0; l < kMaxRpnLevels; ++l)
+    if (l == level)
+      pool_start = T.pool_start[l], out_start = T.out_start[l], seg = T.seg[l], p = T.logits[l], img_stride = T.img_stride[l], hw = T.hw[l],
+      A = T.a[l], level_start = T.level_start[l];
+  const u64* const pool = T.pool + (size_t)img * T.pool_per_image + pool_start;
+  p += (size_t)img * img_stride;
+  const int K = T.classes;
+  const long long total = DIRECT ? (long long)A * K * hw : (long long)T.counts[img * T.levels + level];
+
+  __shared__ unsigned hist[256];
+  __shared__ unsigned sel[4];
+  __shared__ unsigned n_out;
+  __shared__ u64 cand[kRpnMaxK];
+  const int tid = threadIdx.x, lane = tid & 63;
+
+  const auto key_at = [&](long long i) -> u64 {
+    if (i >= total) return 0ull;
+    if (DIRECT) return candidate_key((unsigned)i, p[i], hw, A, K, level_start, T.thresh);
+    return pool[i];
+  };
+  const auto each = [&](auto f) {
+    for (long long b = 0; b < total; b += kRetThreads * kRankLoads) {
+      u64 key[kRankLoads];
+#pragma unroll
+      for (int u = 0; u < kRankLoads; ++u) key[u] = key_at(b + u * kRetThreads + tid);
+#pragma unroll
+      for (int u = 0; u < kRankLoads; ++u) f(key[u]);
+    }
+  };
+  unsigned take_u;
+  const u64 thr = select_keys(each, (unsigned)T.k, hist, sel, tid, lane, &take_u);
+  const int take = (int)take_u;
+  if (tid == 0) n_out = 0;
+  __syncthreads();
+  for (long long i = tid; i < total; i += kRetThreads) {
+    const u64 key = key_at(i);
+    if (key >= thr) {  // exactly `take` keys, each != 0
+      const unsigned slot = atomicAdd(&n_out, 1u);
+      if (slot < take_u) cand[slot] = key;
+    }
+  }
+  __syncthreads();
+  int* const out = T.idx + (size_t)img * T.k_total + out_start;
+  for (int i = tid; i < seg; i += kRetThreads) {
+    if (i >= take) {
+      out[i] = -1;
+      continue;
+    }
+    const u64 ki = cand[i];
+    int rank = 0;
+    for (int j = 0; j < take; ++j) rank += cand[j] > ki ? 1 : 0;
+    out[rank] = (int)~(unsigned)ki;
+  }
+}
+
+struct RetDecodeArgs {
+  const float* logits[kMaxRpnLevels];
+  const float* deltas[kMaxRpnLevels];
+  long long logit_stride[kMaxRpnLevels], delta_stride[kMaxRpnLevels];
+  AnchorLevels lv;
+  int classes;
+  const float* image_sizes;
+  const int* idx;
+  long long count, k;  // n * k candidates
+  DecodeCoef coef;
+  float* boxes;
+  float* scores;
+  long long* labels;
+  unsigned char* valid;
+};
+
+__global__ __launch_bounds__(256) void k_retinanet_decode(const RetDecodeArgs R) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= R.count) return;
+  const long long img = t / R.k;
+  const int f = R.idx[t];
+  if (f < 0 || f / R.classes >= R.lv.total) {  // not a candidate of this pyramid (the -1 padding): nothing is read for it
+    for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = 0.f;
+    R.scores[t] = 0.f, R.labels[t] = 0, R.valid[t] = 0;
+    return;
+  }
+  const int v = f / R.classes, c = f - v * R.classes;
+  const AnchorAt an = anchor_at(R.lv, v);
+  const float* lg = nullptr;
+  const float* dl = nullptr;
+  long long ls = 0, ds = 0;
+#pragma unroll
+  for (int l = 0; l < kMaxRpnLevels; ++l)
+    if (l == an.level) lg = R.logits[l], dl = R.deltas[l], ls = R.logit_stride[l], ds = R.delta_stride[l];
+  const size_t hw = an.hw;
+  const float logit = lg[(size_t)img * ls + ((size_t)an.a * R.classes + c) * hw + an.s];
+  const float* const d = dl + (size_t)img * ds + (size_t)(4 * an.a) * hw + an.s;
+  float box[4];
+  decode_single(an.x1, an.y1, an.x2, an.y2, d[0], d[hw], d[2 * hw], d[3 * hw], R.coef, box);
+  const float ih = R.image_sizes[img * 2], iw = R.image_sizes[img * 2 + 1];
+  box[0] = clamp0(box[0], iw), box[1] = clamp0(box[1], ih), box[2] = clamp0(box[2], iw), box[3] = clamp0(box[3], ih);
+  for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = box[q];
+  R.scores[t] = sigmoid_cr(logit);
+  R.labels[t] = c;
+  R.valid[t] = 1;
+}
+
+}  // namespace
+
+// The layout of the workspace of mv_retinanet_topk_f32: counts (n, levels) uint32 rounded up to 16 bytes, then per image the pools
+// of its levels, chunks_l * min(k, kRetChunk) keys of 8 bytes each.
+RetinanetPlan retinanet_plan(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k) {
+  RetinanetPlan p = {};
+  const int64_t per_chunk = k < kRetChunk ? k : kRetChunk;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
+    p.chunks[l] = (nl + kRetChunk - 1) / kRetChunk;
+    p.pool_start[l] = p.pool_per_image;
+    p.pool_per_image += p.chunks[l] * per_chunk;
+    p.total_chunks += p.chunks[l];
+  }
+  p.counts_bytes = (n * levels * 4 + 15) / 16 * 16;
+  p.bytes = p.counts_bytes + n * p.pool_per_image * 8;
+  return p;
+}
+
+int launch_retinanet_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                          int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s) {
+  const RetinanetPlan plan = retinanet_plan(n, hs, ws, as, levels, classes, k);
+  RetTopkArgs t = {};
+  int start = 0, out = 0, chunk = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
+    t.logits[l] = logits[l], t.img_stride[l] = img_strides[l], t.hw[l] = hs[l] * ws[l], t.a[l] = as[l];
+    t.level_start[l] = start, t.chunk_start[l] = chunk, t.pool_start[l] = plan.pool_start[l], t.out_start[l] = out;
+    t.seg[l] = nl < k ? (int)nl : k;
+    start += as[l] * hs[l] * ws[l], out += t.seg[l], chunk += (int)plan.chunks[l];
+  }
+  t.levels = levels, t.classes = classes, t.k = k, t.k_total = out, t.pool_per_image = plan.pool_per_image, t.thresh = score_thresh;
+  t.counts = static_cast<unsigned*>(workspace);
+  t.pool = reinterpret_cast<u64*>(static_cast<char*>(workspace) + plan.counts_bytes);
+  t.idx = idx;
+#ifdef MV_TUNING
+  if (tune_env("MV_RETINANET_ONE_WORKGROUP")) {  // tools/perf_retinanet.py: stage 2 alone, on the maps (not in the product library)
+    hipLaunchKernelGGL(k_retinanet_rank<true>, dim3(levels, n), dim3(kRetThreads), 0, s, t);
+    return check_launchf("k_retinanet_rank<direct,levels%d,k%d>", levels, k);
+  }
+#endif
+  // a kernel rather than hipMemsetAsync: see k_zero_hist (autoaug.hip)
+  hipLaunchKernelGGL(k_retinanet_zero, dim3((unsigned)((n * levels + 255) / 256)), dim3(256), 0, s, t.counts, n * levels);
+  if (int rc = check_launch("k_retinanet_zero")) return rc;
+  hipLaunchKernelGGL(k_retinanet_chunks, dim3((unsigned)plan.total_chunks, n), dim3(kRetThreads), 0, s, t);
+  if (int rc = check_launchf("k_retinanet_chunks<levels%d,k%d>", levels, k)) return rc;
+  hipLaunchKernelGGL(k_retinanet_rank<false>, dim3(levels, n), dim3(kRetThreads), 0, s, t);
+  return check_launchf("k_retinanet_rank<levels%d,k%d>", levels, k);
+}
+
+int launch_retinanet_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                            const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w,
+                            int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
+                            int64_t k, const float* coef5, float* boxes, float* scores, int64_t* labels, unsigned char* valid,
+                            hipStream_t s) {
+  RetDecodeArgs r = {};
+  for (int l = 0; l < levels; ++l)
+    r.logits[l] = logits[l], r.deltas[l] = deltas[l], r.logit_stride[l] = logit_strides[l], r.delta_stride[l] = delta_strides[l];
+  fill_anchor_levels(r.lv, hs, ws, as, strides_h, strides_w, levels, base_anchors);
+  r.classes = classes, r.image_sizes = image_sizes, r.idx = idx, r.count = n * k, r.k = k;
+  r.coef = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
+  r.boxes = boxes, r.scores = scores, r.labels = reinterpret_cast<long long*>(labels), r.valid = valid;
+  hipLaunchKernelGGL(k_retinanet_decode, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r);
+  return check_launchf("k_retinanet_decode<levels%d>", levels);
+}
+
+}  // namespace mv

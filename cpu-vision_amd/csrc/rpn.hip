@@ -22,6 +22,7 @@
 // implementation reproduces, so the library states the one value that does not depend on an implementation.
 #include "mv_boxcoder.h"
 #include "mv_common.h"
+#include "mv_topk.h"
 
 namespace mv {
 namespace {
@@ -51,19 +52,6 @@ struct TopkArgs {
   u64* cand;  // (n, k_total)
   int k_total;
 };
-
-// hist[digit] += 1 for every lane with `on`, one LDS atomic per distinct digit of the wave: logits of one map share their top
-// byte(s), and 64 adds to one address would serialise.  Called by whole waves.
-__device__ inline void hist_add(unsigned* hist, bool on, unsigned digit, int lane) {
-  u64 live = __ballot(on);
-  while (live) {
-    const int leader = __builtin_amdgcn_readfirstlane(__builtin_ctzll(live));
-    const unsigned d = (unsigned)__builtin_amdgcn_readlane((int)digit, leader);
-    const u64 same = __ballot(on && digit == d);
-    if (lane == leader) atomicAdd(&hist[d], (unsigned)__popcll(same));
-    live &= ~same;
-  }
-}
 
 __global__ __launch_bounds__(kTopkThreads) void k_rpn_topk(const TopkArgs T) {
   const int level = blockIdx.x, img = blockIdx.y;
@@ -180,12 +168,7 @@ struct RpnDecodeArgs {
   const float* logits[kMaxRpnLevels];
   const float* deltas[kMaxRpnLevels];
   long long logit_stride[kMaxRpnLevels], delta_stride[kMaxRpnLevels];
-  int h[kMaxRpnLevels], w[kMaxRpnLevels], a[kMaxRpnLevels];
-  int start[kMaxRpnLevels];     // flat index of the level's first anchor
-  int base_off[kMaxRpnLevels];  // row of the level's first base anchor
-  int stride_h[kMaxRpnLevels], stride_w[kMaxRpnLevels];
-  int levels, total;            // total: anchors of all levels
-  const float* base_anchors;
+  AnchorLevels lv;
   const float* image_sizes;
   const int* idx;
   long long count, k;           // n * k candidates
@@ -202,40 +185,30 @@ __global__ __launch_bounds__(256) void k_rpn_decode(const RpnDecodeArgs R) {
   if (t >= R.count) return;
   const long long img = t / R.k;
   const int v = R.idx[t];
-  if (v < 0 || v >= R.total) {  // not an anchor of this pyramid: nothing is read for it
+  if (v < 0 || v >= R.lv.total) {  // not an anchor of this pyramid: nothing is read for it
     for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = 0.f;
     R.scores[t] = 0.f, R.levels_out[t] = -1, R.valid[t] = 0;
     return;
   }
-  int level = 0;
-#pragma unroll
-  for (int l = 1; l < kMaxRpnLevels; ++l)
-    if (l < R.levels && v >= R.start[l]) level = l;
+  const AnchorAt an = anchor_at(R.lv, v);
   const float* lg = nullptr;
   const float* dl = nullptr;
   long long ls = 0, ds = 0;
-  int H = 1, W = 1, A = 1, start = 0, base_off = 0, sh = 0, sw = 0;
 #pragma unroll
   for (int l = 0; l < kMaxRpnLevels; ++l)
-    if (l == level)
-      lg = R.logits[l], dl = R.deltas[l], ls = R.logit_stride[l], ds = R.delta_stride[l], H = R.h[l], W = R.w[l], A = R.a[l],
-      start = R.start[l], base_off = R.base_off[l], sh = R.stride_h[l], sw = R.stride_w[l];
-  const int flat = v - start, a = flat % A, s = flat / A, y = s / W, x = s % W;
-  const size_t hw = (size_t)H * W;
-  const float logit = lg[(size_t)img * ls + (size_t)a * hw + s];
-  const float* const d = dl + (size_t)img * ds + (size_t)(4 * a) * hw + s;
-  const float* const b = R.base_anchors + (size_t)(base_off + a) * 4;
-  const float fx = (float)(x * sw), fy = (float)(y * sh);  // the reference's int32 shifts, converted as its int + float add does
+    if (l == an.level) lg = R.logits[l], dl = R.deltas[l], ls = R.logit_stride[l], ds = R.delta_stride[l];
+  const size_t hw = an.hw;
+  const float logit = lg[(size_t)img * ls + (size_t)an.a * hw + an.s];
+  const float* const d = dl + (size_t)img * ds + (size_t)(4 * an.a) * hw + an.s;
   float box[4];
-  decode_single(__fadd_rn(fx, b[0]), __fadd_rn(fy, b[1]), __fadd_rn(fx, b[2]), __fadd_rn(fy, b[3]), d[0], d[hw], d[2 * hw], d[3 * hw],
-                R.coef, box);
+  decode_single(an.x1, an.y1, an.x2, an.y2, d[0], d[hw], d[2 * hw], d[3 * hw], R.coef, box);
   const float ih = R.image_sizes[img * 2], iw = R.image_sizes[img * 2 + 1];
   box[0] = clamp0(box[0], iw), box[1] = clamp0(box[1], ih), box[2] = clamp0(box[2], iw), box[3] = clamp0(box[3], ih);
-  const float score = __fdiv_rn(1.f, __fadd_rn(1.f, exp_cr(-logit)));
+  const float score = sigmoid_cr(logit);
   const float bw = __fsub_rn(box[2], box[0]), bh = __fsub_rn(box[3], box[1]);
   for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = box[q];
   R.scores[t] = score;
-  R.levels_out[t] = level;
+  R.levels_out[t] = an.level;
   R.valid[t] = (bw >= R.min_size && bh >= R.min_size && score >= R.score_thresh) ? 1 : 0;
 }
 
@@ -274,15 +247,10 @@ int launch_rpn_decode(const float* const* logits, const float* const* deltas, co
                       float min_size, float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid,
                       hipStream_t s) {
   RpnDecodeArgs r = {};
-  int start = 0, base = 0;
-  for (int l = 0; l < levels; ++l) {
+  for (int l = 0; l < levels; ++l)
     r.logits[l] = logits[l], r.deltas[l] = deltas[l], r.logit_stride[l] = logit_strides[l], r.delta_stride[l] = delta_strides[l];
-    r.h[l] = hs[l], r.w[l] = ws[l], r.a[l] = as[l], r.start[l] = start, r.base_off[l] = base;
-    r.stride_h[l] = strides_h[l], r.stride_w[l] = strides_w[l];
-    start += as[l] * hs[l] * ws[l], base += as[l];
-  }
-  r.levels = levels, r.total = start;
-  r.base_anchors = base_anchors, r.image_sizes = image_sizes, r.idx = idx, r.count = n * k, r.k = k;
+  fill_anchor_levels(r.lv, hs, ws, as, strides_h, strides_w, levels, base_anchors);
+  r.image_sizes = image_sizes, r.idx = idx, r.count = n * k, r.k = k;
   r.coef = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
   r.min_size = min_size, r.score_thresh = score_thresh;
   r.boxes = boxes, r.scores = scores, r.levels_out = reinterpret_cast<long long*>(levels_out), r.valid = valid;

@@ -19,7 +19,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
   _crop       pad / crop / flips / resized_crop / erase and their kernels
   _mix        mixup_image / cutmix_image / mixup_labels
   _detection  rpn_topk / rpn_decode / box_decode (models/detection/rpn.py filter_proposals up to the nms, _utils.py
-              BoxCoder.decode_single), roi_detections (roi_heads.py postprocess_detections up to the per-image filters)
+              BoxCoder.decode_single), roi_detections (roi_heads.py postprocess_detections up to the per-image filters),
+              retinanet_topk / retinanet_decode (retinanet.py postprocess_detections up to the nms)
 The switches (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION, CONV2D_*) are set on this module only; the code behind it reads them
 here at call time (_lib.switch).
 
@@ -52,8 +53,8 @@ from ._geometry import (affine, _affine_coeffs, affine_image, affine_mask, _affi
                         _perspective_coefficients, _perspective_grid_coeffs, perspective_image, perspective_mask,
                         perspective_video, _PIL_INTERPOLATION, rotate, rotate_image, rotate_mask, rotate_video,
                         _warp, _WARP_KINDS)
-from ._detection import (BBOX_XFORM_CLIP, box_decode, MAX_ROI_CLASSES, MAX_RPN_LEVELS, MAX_RPN_TOPK, roi_detections,  # noqa: F401
-                         rpn_decode, rpn_topk)
+from ._detection import (BBOX_XFORM_CLIP, box_decode, MAX_ROI_CLASSES, MAX_RPN_LEVELS, MAX_RPN_TOPK, retinanet_decode,  # noqa: F401
+                         retinanet_topk, retinanet_topk_chunk, roi_detections, rpn_decode, rpn_topk)
 from ._filters import (_adjust_sharpness_image_pil, adjust_sharpness, adjust_sharpness_frames, adjust_sharpness_image,  # noqa: F401
                        adjust_sharpness_video, _blur_with_taps, _border, box_filter, _check_gaussian_args, _compute_dtype,
                        depthwise_conv2d, _DIRECT_2D_MAX_TAPS, _filter_f32_u8, _frames_call, gaussian_blur,

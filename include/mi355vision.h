@@ -796,6 +796,55 @@ int mv_roi_detections_f32(const float* class_logits, int64_t logits_stride, cons
                           double wh, double clip, double score_thresh, double min_size, float* boxes, float* scores, int64_t* labels,
                           unsigned char* valid, void* stream);
 
+/* ---- RetinaNet inference (models/detection/retinanet.py postprocess_detections up to the nms): sigmoid, `> score_thresh`, the top k
+ * per (image, level) over every (anchor, class) pair, then the decoding of what was selected -- on the head's own NCHW maps.
+ *
+ * The level tables are those of mv_rpn_topk_f32 (HOST arrays, 1 <= levels <= 8) with `classes` = K >= 1 more: logits[l] is a DEVICE
+ * map (n, as[l] K, hs[l], ws[l]) float32, deltas[l] one of (n, 4 as[l], hs[l], ws[l]), the image strides in ELEMENTS (64-bit, >= the
+ * map's size).  The logit of anchor (y, x, a) and class c is channel a K + c; the candidate's flat index is
+ *   f = (start_l + (y ws[l] + x) as[l] + a) K + c,   start_l the anchors of the levels before it
+ * -- the reference's view(N, -1, K, H, W).permute(0, 3, 4, 1, 2).reshape(N, -1, K) and the concatenation over levels.  The anchors of
+ * all levels times K number less than 2^31 (MV_ERR_UNSUPPORTED otherwise).
+ *
+ * The score of both entries is  s = 1 / (1 + E(-x)),  E the correctly rounded float32 exponential of mv_rpn_decode_f32, every
+ * operation rounded once to float32, the division correctly rounded.
+ *
+ * mv_retinanet_topk_f32: idx (n, Ktot) int32, Ktot = sum_l min(k, as[l] hs[l] ws[l] K).  For every (image, level) the candidates with
+ * s > (float)score_thresh pass (strict, in float32; a NaN score does not pass); the level's segment of idx receives the flat indices
+ * of its min(k, passing) greatest scores in STABLE DESCENDING order -- greater score first, equal SCORES (not logits: every logit
+ * above about 17 has the score 1) by ascending flat index -- and -1 in the rest of the segment.  This is the first k of
+ * torch.sort(stable=True, descending=True) of the passing scores and one of torch.topk's valid answers.  k <= 4096
+ * (MV_ERR_UNSUPPORTED above), n <= 65535.
+ *   Stage 1: one workgroup per chunk of mv_retinanet_topk_chunk() consecutive elements of an (image, level) map, read once and in
+ *   memory order; the chunk's own min(k, passing) greatest (score, index) keys go to the level's pool in `workspace`.  Stage 2: one
+ *   workgroup per (image, level) selects the k greatest keys of the pool and ranks them.  The keys of distinct candidates differ, so
+ *   the result is exact and the same on every run for every input; a pool holds min(k, chunk) keys per chunk, so nothing is dropped.
+ * `workspace`: a 16-byte aligned DEVICE buffer of mv_retinanet_topk_workspace_bytes(n, hs, ws, as, levels, classes, k) bytes (0 for
+ * arguments the entry refuses), any content.  Nothing is allocated or read back.
+ *
+ * mv_retinanet_decode_f32: one lane per idx[i, j] (idx (n, k) int32, k any count per image).  An index outside [0, anchors K) -- the
+ * -1 padding -- gives a zero box, score 0, label 0 and valid 0, and nothing is read through it.  Otherwise anchor f / K, label f % K,
+ * the anchor built as in mv_rpn_decode_f32 from base_anchors and the strides, decode_single with the weights and clip given
+ * (RetinaNet: 1, 1, 1, 1 and log(1000 / 16)) on the deltas of channels 4 a + q, x clamped to [0, width] and y to [0, height] of the
+ * image (a NaN stays), the score recomputed from the logit:
+ *   boxes (n, k, 4) float32;  scores (n, k) float32;  labels (n, k) int64 (8-byte aligned);  valid (n, k) uint8 = 1.
+ * There is no small-box test: the reference's RetinaNet has none.
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a null pointer or table, levels outside 1 .. 8 (above 8:
+ * MV_ERR_UNSUPPORTED), a non-positive h, w, a or classes, k < 1 (topk), an image stride below the map's size, a negative stride_h /
+ * stride_w, an output that overlaps an input or another output, a workspace that is missing, too small or misaligned, a misaligned
+ * labels.  n == 0 (k == 0 for decode) is a no-op that touches no pointer. */
+int mv_retinanet_topk_chunk(void);
+int64_t mv_retinanet_topk_workspace_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k);
+int mv_retinanet_topk_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                          int classes, int64_t n, int k, double score_thresh, int* idx, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+int mv_retinanet_decode_f32(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                            const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w,
+                            int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
+                            int64_t k, double wx, double wy, double ww, double wh, double clip, float* boxes, float* scores,
+                            int64_t* labels, unsigned char* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
