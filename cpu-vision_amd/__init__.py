@@ -19,7 +19,7 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   roi_heads       RoIHeads: pooler -> box head -> predictor -> softmax + decode + clip + filters of every (roi, class) in one launch,
                   then batched_nms per class
   faster_rcnn     FasterRCNN, TwoMLPHead, FastRCNNPredictor (cls_score + bbox_pred as one linear launch), fasterrcnn_resnet50_fpn;
-                  generalized_rcnn: GeneralizedRCNN; transform: GeneralizedRCNNTransform (normalize + batch, no resize yet)
+                  generalized_rcnn: GeneralizedRCNN; transform: GeneralizedRCNNTransform (normalize + resize + batch as one launch)
   retinanet       RetinaNetClassificationHead / RetinaNetRegressionHead / RetinaNetHead (the towers' first convs as one launch),
                   RetinaNet: threshold + top-k over every (anchor, class) of the heads' NCHW maps, many workgroups per (image,
                   level), then decode + clip + sigmoid of the selected candidates only, then batched_nms; retinanet_resnet50_fpn

@@ -1732,4 +1732,53 @@ int mv_equalize_u8(const uint8_t* x, uint8_t* y, int64_t planes, int h, int w, v
   return equalize(x, y, true, planes, h, w, workspace, workspace_bytes, stream);
 }
 
+// ---- F.interpolate(bilinear) and the detection transform's front end: interp.hip --------------------------------------------------------
+int mv_interpolate_bilinear_f32(const float* x, float* y, int64_t planes, int h, int w, int oh, int ow, void* stream) {
+  if (planes < 0 || h < 1 || w < 1 || oh < 1 || ow < 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate: bad shape planes=%lld, (%d, %d) -> (%d, %d)", (long long)planes, h, w, oh, ow);
+  if (planes == 0) return MV_OK;
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate: null pointer");
+  if (planes > 0x7fffffffffffLL / ((int64_t)h * w) || planes > 0x7fffffffffffLL / ((int64_t)oh * ow))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate: %lld planes exceed the address space", (long long)planes);
+  const ByteRange in = {x, planes * h * w * 4}, out = {y, planes * oh * ow * 4};
+  if (!outputs_clear(&out, 1, &in, 1)) return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate: the output must not overlap the input");
+  if (!interp_grid_fits(planes, oh, ow))
+    return set_error(MV_ERR_UNSUPPORTED, "interpolate: %lld planes of (%d, %d) exceed the launch grid", (long long)planes, oh, ow);
+  return launch_interp_batch(&x, &h, &w, &oh, &ow, 1, (int)planes, nullptr, nullptr, y, oh, ow, (hipStream_t)stream);
+}
+
+int mv_detection_batch_f32(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int64_t n, int c,
+                           const float* mean, const float* stdv, float* y, int hp, int wp, void* stream) {
+  if (n < 0 || c < 1 || hp < 1 || wp < 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: bad shape n=%lld, c=%d, batch (%d, %d)", (long long)n, c, hp, wp);
+  if (c > 16) return set_error(MV_ERR_UNSUPPORTED, "detection_batch: up to 16 channels, got %d", c);
+  if (n == 0) return MV_OK;
+  if (!xs || !hs || !ws || !ohs || !ows || !mean || !stdv || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: null pointer");
+  for (int i = 0; i < c; ++i)
+    if (stdv[i] == 0.f) return set_error(MV_ERR_INVALID_ARGUMENT, "std evaluated to zero, leading to division by zero.");
+  const int64_t plane = (int64_t)hp * wp;
+  if (n > 0x7fffffffffffLL / (plane * c)) return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: %lld images exceed the address space", (long long)n);
+  const ByteRange out = {y, n * c * plane * 4};
+  for (int64_t i = 0; i < n; ++i) {
+    if (!xs[i]) return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: null pointer (image %lld)", (long long)i);
+    if (hs[i] < 1 || ws[i] < 1 || ohs[i] < 1 || ows[i] < 1)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: bad size (%d, %d) -> (%d, %d) of image %lld", hs[i], ws[i], ohs[i], ows[i],
+                       (long long)i);
+    if (ohs[i] > hp || ows[i] > wp)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: image %lld resized to (%d, %d) does not fit the batch (%d, %d)", (long long)i,
+                       ohs[i], ows[i], hp, wp);
+    const ByteRange in = {xs[i], (int64_t)c * hs[i] * ws[i] * 4};
+    if (!outputs_clear(&out, 1, &in, 1))
+      return set_error(MV_ERR_INVALID_ARGUMENT, "detection_batch: the output must not overlap an input (image %lld)", (long long)i);
+  }
+  if (!interp_grid_fits((int64_t)kMaxDetImages * c, hp, wp))
+    return set_error(MV_ERR_UNSUPPORTED, "detection_batch: a batch of (%d, %d) exceeds the launch grid", hp, wp);
+  for (int64_t i = 0; i < n; i += kMaxDetImages) {  // one launch per kMaxDetImages images: the table is a kernel argument
+    const int m = (int)(n - i < kMaxDetImages ? n - i : kMaxDetImages);
+    if (int rc = launch_interp_batch(xs + i, hs + i, ws + i, ohs + i, ows + i, m, c, mean, stdv, y + i * c * plane, hp, wp, (hipStream_t)stream))
+      return rc;
+  }
+  return MV_OK;
+}
+
 }  // extern "C"

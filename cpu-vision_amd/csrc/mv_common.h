@@ -352,6 +352,14 @@ int launch_retinanet_decode(const float* const* logits, const float* const* delt
                             int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
                             int64_t k, const float* coef5, float* boxes, float* scores, int64_t* labels, unsigned char* valid,
                             hipStream_t s);
+// F.interpolate(bilinear) and the detection transform's fused normalize + resize + batch (interp.hip; semantics in mi355vision.h
+// mv_interpolate_bilinear_f32, mv_detection_batch_f32).  The tables are HOST arrays of n <= kMaxDetImages entries, copied into the kernel
+// arguments; mean / stdv: c <= 16 host floats, or both null (no normalisation).  The entry points have checked the arguments, the
+// extents and the grid (interp_grid_fits).
+constexpr int kMaxDetImages = 64;  // 64 x 32 B = 2 KiB of the 4 KiB kernel-argument segment; longer lists go in several launches
+bool interp_grid_fits(int64_t planes, int hp, int wp);
+int launch_interp_batch(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int n, int c,
+                        const float* mean, const float* stdv, float* y, int hp, int wp, hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

@@ -38,7 +38,9 @@ def _default_anchorgen():
 
 class FasterRCNN(GeneralizedRCNN):
     """faster_rcnn.py:44-297.  forward(images: List[Tensor (C, H, W) float32 in 0..1]) -> List[{boxes (N, 4) as (x1, y1, x2, y2),
-    labels (N,) int64, scores (N,)}].  `**kwargs` go to GeneralizedRCNNTransform (pass _skip_resize=True: transform.py)."""
+    labels (N,) int64, scores (N,)}], the boxes in the coordinates of the images as given.  The images may have any sizes: the
+    transform resizes them to min_size / max_size (transform.py).  `**kwargs` go to GeneralizedRCNNTransform (`_skip_resize=True`
+    for images that already have their final size)."""
 
     def __init__(self, backbone, num_classes=None,
                  # transform parameters

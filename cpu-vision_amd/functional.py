@@ -21,6 +21,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
   _detection  rpn_topk / rpn_decode / box_decode (models/detection/rpn.py filter_proposals up to the nms, _utils.py
               BoxCoder.decode_single), roi_detections (roi_heads.py postprocess_detections up to the per-image filters),
               retinanet_topk / retinanet_decode (retinanet.py postprocess_detections up to the nms)
+  _interp     interpolate (torch.nn.functional.interpolate, plain bilinear) and detection_batch, the fused normalize + resize +
+              batch_images in front of a detection model (models/detection/transform.py)
 The switches (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION, CONV2D_*) are set on this module only; the code behind it reads them
 here at call time (_lib.switch).
 
@@ -61,6 +63,7 @@ from ._filters import (_adjust_sharpness_image_pil, adjust_sharpness, adjust_sha
                        gaussian_blur_frames, gaussian_blur_image, _gaussian_blur_image_pil, gaussian_blur_video,
                        gaussian_sobel, _get_gaussian_kernel1d, _get_gaussian_kernel2d, _host_taps, _pair_f32, _planes,
                        _same_frames, separable_gaussian_blur, _sharpness, sobel, _taps_dtype, _use_separable)
+from ._interp import detection_batch, interpolate, interpolate_output_size, MAX_NORMALIZE_CHANNELS  # noqa: F401
 from ._layers import (_ACT_CODES, adaptive_avg_pool2d, _AFFINE_CODES, conv1x1_k_slices, conv1x1_upsample_add,  # noqa: F401
                       conv2d_affine_act, conv2d_bias_act, conv2d_bias_relu,
                       conv3x3_k_slices, conv_norm_act, _CONV_WORKSPACE_BYTES, fold_batchnorm, inverted_residual,

@@ -235,7 +235,9 @@ class RetinaNetHead(nn.Module):
 
 class RetinaNet(nn.Module):
     """retinanet.py:291-669.  forward(images: List[Tensor (C, H, W) float32 in 0..1]) -> List[{boxes (N, 4) as (x1, y1, x2, y2),
-    scores (N,), labels (N,) int64}].  `**kwargs` go to GeneralizedRCNNTransform (pass _skip_resize=True: transform.py).  The
+    scores (N,), labels (N,) int64}], the boxes in the coordinates of the images as given.  The images may have any sizes: the
+    transform resizes them to min_size / max_size (transform.py).  `**kwargs` go to GeneralizedRCNNTransform (`_skip_resize=True`
+    for images that already have their final size).  The
     matcher and the losses of the reference are training-only and not built; `proposal_matcher` is kept as given."""
 
     __annotations__ = {

@@ -1,11 +1,13 @@
 """models/detection/transform.py: GeneralizedRCNNTransform, the normalisation and batching in front of a detection model and the
 box rescaling behind it.
 
-`normalize` is the package's F.normalize (one launch per image); `batch_images` is the reference's new_full + copy_ on the device;
-`postprocess` / `resize_boxes` is the reference's float32 composition.  `resize` is NOT here: the reference resizes with the
-non-antialiased bilinear `interpolate`, and the library has only the antialiased mv_resize_bilinear_aa_*.  The reference's private
-keyword `_skip_resize=True` is therefore the one way through `forward` (the reference honours it in training mode only; here it
-also stands for inference on images that already have their final size); without it `forward` raises NotImplementedError.
+`forward` computes the resized sizes on the host (`resized_size`) and makes ONE launch, F.detection_batch: normalize, the reference's
+non-antialiased bilinear `interpolate` and the zero-padded batch in one pass over the pixels.  The pieces stay
+callable on their own and give the same bits: `normalize` is the package's F.normalize, `resize` is F.interpolate at the size
+`resized_size` gives (device tensors only), `batch_images` is the reference's new_full + copy_ on the device; `postprocess` /
+`resize_boxes` is the reference's float32 composition.  With the reference's private keyword `_skip_resize=True` (the reference
+honours it in training mode only; here it also stands for inference on images that already have their final size) `forward` runs
+those pieces one by one and does not resize.
 """
 from __future__ import annotations
 
@@ -18,12 +20,26 @@ from torch import nn, Tensor
 from . import functional as F
 from .image_list import ImageList
 
-__all__ = ["GeneralizedRCNNTransform", "resize_boxes"]
+__all__ = ["GeneralizedRCNNTransform", "resize_boxes", "resized_size"]
+
+
+def resized_size(h: int, w: int, min_size: int, max_size: int, fixed_size: Optional[Tuple[int, int]] = None) -> Tuple[int, int]:
+    """(oh, ow) of the reference's _resize_image_and_masks (transform.py:24-75) for an (h, w) image at inference.  With `fixed_size`
+    = (width, height) it is (fixed_size[1], fixed_size[0]).  Otherwise the reference's EAGER branch: scale_factor = min(min_size /
+    min(h, w), max_size / max(h, w)) in Python floats, then interpolate's recompute_scale_factor=True rule, floor(float(in) *
+    scale_factor) per axis.  The reference's scripted / tracing branch computes the scale in float32 tensors and gives another size
+    for some shapes (201 x 201 at 800 / 1333: 800 x 800 here, 799 x 799 there); the library implements the eager branch only."""
+    if fixed_size is not None:
+        return int(fixed_size[1]), int(fixed_size[0])
+    scale_factor = min(float(min_size) / float(min(h, w)), float(max_size) / float(max(h, w)))
+    oh, ow = F.interpolate_output_size((h, w), scale_factor=scale_factor)
+    return oh, ow
 
 
 class GeneralizedRCNNTransform(nn.Module):
-    """transform.py:78-285.  forward(images, targets=None) -> (ImageList, targets): normalise each (C, H, W) image, pad them into
-    one batch whose sides are multiples of `size_divisible`."""
+    """transform.py:78-285.  forward(images, targets=None) -> (ImageList, targets): normalise each (C, H, W) image, resize it so that
+    its shorter side is min_size unless the longer one would exceed max_size (or to `fixed_size`), pad them into one batch whose
+    sides are multiples of `size_divisible`; image_sizes are the resized sizes."""
 
     def __init__(self, min_size: int, max_size: int, image_mean: List[float], image_std: List[float], size_divisible: int = 32,
                  fixed_size: Optional[Tuple[int, int]] = None, **kwargs: Any):
@@ -43,6 +59,8 @@ class GeneralizedRCNNTransform(nn.Module):
         if self.training or targets is not None:
             raise RuntimeError("the MI355X GeneralizedRCNNTransform is inference only: call .eval() and pass no targets")
         images = [img for img in images]
+        if not self._skip_resize:
+            return self._forward_fused(images), targets
         for i in range(len(images)):
             image = images[i]
             if image.dim() != 3:
@@ -61,19 +79,35 @@ class GeneralizedRCNNTransform(nn.Module):
         image_list = ImageList(images, image_sizes_list)
         return image_list, targets
 
-    def normalize(self, image: Tensor) -> Tensor:
+    def _forward_fused(self, images: List[Tensor]) -> ImageList:
+        """normalize -> resize -> batch_images of every image as one F.detection_batch launch: the same checks, the same bits."""
+        for image in images:
+            if image.dim() != 3:
+                raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {image.shape}")
+            self._check_dtype(image)
+        sizes = [resized_size(int(img.shape[-2]), int(img.shape[-1]), self.min_size[-1], self.max_size, self.fixed_size) for img in images]
+        batch = F.detection_batch(images, sizes, list(self.image_mean), list(self.image_std), self.size_divisible)
+        return ImageList(batch, sizes)
+
+    def _check_dtype(self, image: Tensor) -> None:
         if not image.is_floating_point():
             raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), but found type {image.dtype} instead")
         if image.dtype != torch.float32:
             raise TypeError(f"GeneralizedRCNNTransform computes in float32. Got {image.dtype}")
+
+    def normalize(self, image: Tensor) -> Tensor:
+        self._check_dtype(image)
         return F.normalize(image, list(self.image_mean), list(self.image_std))
 
     def resize(self, image: Tensor) -> Tensor:
+        """_resize_image_and_masks for inference, the eager branch (resized_size), on a (C, H, W) float32 device tensor."""
         if self._skip_resize:
             return image
-        raise NotImplementedError("GeneralizedRCNNTransform.resize: the non-antialiased bilinear `interpolate` of the reference's resize is not "
-                                  "in the library yet (it has the antialiased mv_resize_bilinear_aa_* only); construct the model with "
-                                  "_skip_resize=True and pass images of their final size")
+        if not image.is_cuda:
+            raise NotImplementedError("GeneralizedRCNNTransform.resize: the non-antialiased bilinear interpolate runs on the device only "
+                                      f"(F.interpolate); the image lives on '{image.device}'")
+        size = resized_size(int(image.shape[-2]), int(image.shape[-1]), self.min_size[-1], self.max_size, self.fixed_size)
+        return F.interpolate(image[None], size=list(size), mode="bilinear", align_corners=False)[0]
 
     def max_by_axis(self, the_list: List[List[int]]) -> List[int]:
         maxes = the_list[0]

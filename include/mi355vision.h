@@ -845,6 +845,39 @@ int mv_retinanet_decode_f32(const float* const* logits, const float* const* delt
                             int64_t k, double wx, double wy, double ww, double wh, double clip, float* boxes, float* scores,
                             int64_t* labels, unsigned char* valid, void* stream);
 
+/* ---- torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False) and the front end of a detection model
+ * (models/detection/transform.py: normalize -> resize -> batch_images) on planar float32.
+ *
+ * mv_interpolate_bilinear_f32: x (planes, h, w) -> y (planes, oh, ow).  Per axis, with `in` and `out` its two sizes:
+ *   s   = float32(in) / float32(out)
+ *   src = max(fma(s, d + 0.5f, -0.5f), 0)                     for output index d
+ *   i0  = min((int)floor(src), in - 1),  i1 = min(i0 + 1, in - 1)
+ *   lam = clamp(src - (float)i0, 0, 1),  w0 = 1 - lam,  w1 = lam
+ * and with a, b the taps (y0, x0), (y0, x1) of the top row and c, d those of the bottom row
+ *   t = fma(wx0, a, wx1 * b),  u = fma(wx0, c, wx1 * d),  out = fma(wy0, t, wy1 * u)
+ * every product and every fma rounded once to float32.  NaN and +-inf follow from the formula (a zero weight times inf is NaN); with
+ * out == in, src == d exactly and the result is a + 0 * b per row, the input itself for finite values.
+ * This is bit for bit what torch 2.10's CPU kernel computes where it takes its vectorised channels-first loop (outputs of more than
+ * 3 264 elements, and not the channels-last kernel it picks for 3 channels on one thread); its other loops differ from it by a few
+ * 2^-24 max|x|.  The statement above is the library's own.
+ *
+ * mv_detection_batch_f32: ONE pass from n separately allocated images to the padded batch y (n, c, hp, wp).  xs is a HOST table of n
+ * DEVICE pointers, image i is (c, hs[i], ws[i]) and is resized to (ohs[i], ows[i]) <= (hp, wp) (hs, ws, ohs, ows HOST tables); mean and
+ * stdv are HOST arrays of c <= 16 floats (MV_ERR_UNSUPPORTED above).  Every element of y is written: inside (ohs[i], ows[i]) of image i
+ * the formula above on the NORMALISED taps, each (x - mean[ch]) / stdv[ch] with the subtraction rounded and the division correctly
+ * rounded (mv_normalize_f32's arithmetic); outside it +0.0.  The result has the bits of mv_normalize_f32 -> mv_interpolate_bilinear_f32
+ * -> new_full(0) + copy_.  ohs[i] == hs[i] and ows[i] == ws[i] (no resize) is normalise + pad.  The tables travel in the kernel
+ * arguments, 64 images per launch (longer lists take several launches); nothing is allocated or read back.
+ *
+ * y is stored 16 bytes at a time when its row pitch (ow, wp) is a multiple of 4 and y is 16-byte aligned, else element by element;
+ * x may start at any 4-byte address.  Element offsets are 64-bit.
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a null pointer or table, a non-positive size or channel count, a
+ * negative plane / image count, a resized size that exceeds the batch, a zero stdv, an output that overlaps an input, more workgroups
+ * than one launch grid holds (MV_ERR_UNSUPPORTED).  planes == 0 / n == 0 is a no-op that touches no pointer. */
+int mv_interpolate_bilinear_f32(const float* x, float* y, int64_t planes, int h, int w, int oh, int ow, void* stream);
+int mv_detection_batch_f32(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int64_t n, int c,
+                           const float* mean, const float* stdv, float* y, int hp, int wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
