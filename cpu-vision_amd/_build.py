@@ -25,7 +25,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 TUNING_INC = HERE.parent / "tools" / "tuning"
-SOURCES = ["abi.hip", "dw3x3.hip", "dw3x3_u8.hip", "dwk_u8.hip", "tiefix_u8.hip", "dwtile.hip", "dwf64.hip", "separable.hip", "sepfast.hip", "sepstream.hip", "conv3x3_mfma.hip", "conv3x3_c3.hip", "conv3x3_gen.hip", "cnn_ops.hip", "linear_mfma.hip", "resize.hip", "convnorm.hip", "conv_igemm.hip", "invres.hip", "deform.hip", "deform_fused.hip", "elastic.hip", "warp.hip", "color.hip", "autoaug.hip", "crop.hip", "batchmix.hip", "detect.hip", "roi_pool.hip", "boxes.hip", "rpn.hip", "roi_heads.hip", "retinanet.hip", "interp.hip"]
+SOURCES = ["abi.hip", "dw3x3.hip", "dw3x3_u8.hip", "dwk_u8.hip", "tiefix_u8.hip", "dwtile.hip", "dwf64.hip", "separable.hip", "sepfast.hip", "sepstream.hip", "conv3x3_mfma.hip", "conv3x3_c3.hip", "conv3x3_gen.hip", "cnn_ops.hip", "linear_mfma.hip", "resize.hip", "convnorm.hip", "conv_igemm.hip", "invres.hip", "deform.hip", "deform_fused.hip", "elastic.hip", "warp.hip", "color.hip", "autoaug.hip", "crop.hip", "batchmix.hip", "detect.hip", "roi_pool.hip", "boxes.hip", "rpn.hip", "roi_heads.hip", "retinanet.hip", "interp.hip", "mask.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -69,7 +69,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
     flags = list(FLAGS)
     if variant:
         flags += ["-DMV_TUNING", f"-I{TUNING_INC}", *extra_flags]
-    headers = [CSRC / "mv_common.h", HERE.parent / "include" / "mi355vision.h", CSRC / "mv_epilogue.h", CSRC / "mv_deform.h", CSRC / "mv_conv.h", CSRC / "mv_invres.h", CSRC / "mv_act.h", CSRC / "mv_gridsample.h", CSRC / "mv_vec16.h", CSRC / "mv_boxcoder.h", CSRC / "mv_topk.h"]
+    headers = [CSRC / "mv_common.h", HERE.parent / "include" / "mi355vision.h", CSRC / "mv_epilogue.h", CSRC / "mv_deform.h", CSRC / "mv_conv.h", CSRC / "mv_invres.h", CSRC / "mv_act.h", CSRC / "mv_gridsample.h", CSRC / "mv_vec16.h", CSRC / "mv_boxcoder.h", CSRC / "mv_topk.h", CSRC / "mv_bilinear.h"]
     if variant:
         headers.append(TUNING_INC / "mv_tuning.h")
     bid = build_id(flags)

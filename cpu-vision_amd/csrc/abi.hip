@@ -1781,4 +1781,54 @@ int mv_detection_batch_f32(const float* const* xs, const int* hs, const int* ws,
   return MV_OK;
 }
 
+// ---- the mask branch of Mask R-CNN: mask.hip, and convnorm.hip's pixel-shuffle instance of the pointwise kernel --------------------------
+int mv_paste_masks_f32(const float* masks, const float* boxes, float* y, int64_t r, int m, int padding, int h, int w, void* stream) {
+  if (r < 0 || m < 1 || padding < 0 || h < 1 || w < 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "paste_masks: bad shape r=%lld, m=%d, padding=%d, image (%d, %d)", (long long)r, m, padding, h, w);
+  if (padding > (0x7fffffff - m) / 2) return set_error(MV_ERR_INVALID_ARGUMENT, "paste_masks: padding=%d exceeds the index range", padding);
+  if (r == 0) return MV_OK;
+  if (!masks || !boxes || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "paste_masks: null pointer");
+  if (r > 0x7fffffffffffLL / ((int64_t)h * w) || r > 0x7fffffffffffLL / ((int64_t)m * m))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "paste_masks: %lld masks exceed the address space", (long long)r);
+  const ByteRange ins[2] = {{masks, r * m * m * 4}, {boxes, r * 16}}, out = {y, r * h * w * 4};
+  if (!outputs_clear(&out, 1, ins, 2)) return set_error(MV_ERR_INVALID_ARGUMENT, "paste_masks: the output must not overlap an input");
+  if (!paste_masks_grid_fits(r, h, w))
+    return set_error(MV_ERR_UNSUPPORTED, "paste_masks: %lld masks into (%d, %d) exceed the launch grid", (long long)r, h, w);
+  return launch_paste_masks(masks, boxes, y, r, m, padding, h, w, (hipStream_t)stream);
+}
+
+int mv_mask_probs_f32(const float* logits, const int64_t* labels, float* y, int64_t r, int classes, int mh, int mw, void* stream) {
+  if (r < 0 || classes < 1 || mh < 1 || mw < 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "mask_probs: bad shape r=%lld, classes=%d, (%d, %d)", (long long)r, classes, mh, mw);
+  if (r == 0) return MV_OK;
+  if (!logits || !labels || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "mask_probs: null pointer");
+  const int64_t plane = (int64_t)mh * mw;
+  if (r > 0x7fffffffffffLL / plane / classes) return set_error(MV_ERR_INVALID_ARGUMENT, "mask_probs: %lld rois exceed the address space", (long long)r);
+  if ((uintptr_t)labels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "mask_probs: labels must be 8-byte aligned");
+  const ByteRange ins[2] = {{logits, r * classes * plane * 4}, {labels, r * 8}}, out = {y, r * plane * 4};
+  if (!outputs_clear(&out, 1, ins, 2)) return set_error(MV_ERR_INVALID_ARGUMENT, "mask_probs: the output must not overlap an input");
+  if (!mask_probs_grid_fits(r, plane))
+    return set_error(MV_ERR_UNSUPPORTED, "mask_probs: %lld rois of (%d, %d) exceed the launch grid", (long long)r, mh, mw);
+  return launch_mask_probs(logits, labels, y, r, classes, plane, (hipStream_t)stream);
+}
+
+int mv_conv_transpose2x2_bias_act_f32(const float* x, const float* w4, const float* bias4, float* y, int64_t n, int cin, int h, int w,
+                                      int cout, int act, void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose2x2: bad shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, cin, cout, h, w);
+  if (act != MV_ACT_NONE && act != MV_ACT_RELU && act != MV_ACT_RELU6)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose2x2: bad activation code %d (none, ReLU and ReLU6 are supported)", act);
+  if (cout > 0x7fffffff / 4) return set_error(MV_ERR_UNSUPPORTED, "conv_transpose2x2: cout=%d exceeds the index range", cout);
+  if (n == 0) return MV_OK;
+  if (!x || !w4 || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose2x2: null pointer");
+  const int64_t hw = (int64_t)h * w;
+  if (n > 0x7fffffffffffLL / hw / cin || n > 0x7fffffffffffLL / hw / 4 / cout)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose2x2: %lld images exceed the address space", (long long)n);
+  const ByteRange ins[3] = {{x, n * cin * hw * 4}, {w4, (int64_t)cout * 16 * cin}, {bias4, bias4 ? (int64_t)cout * 16 : 0}};
+  const ByteRange out = {y, n * cout * hw * 16};
+  if (!outputs_clear(&out, 1, ins, 3)) return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose2x2: the output must not overlap an input");
+  const Epilogue e = {bias4, nullptr, nullptr, nullptr, MV_AFFINE_NONE, act};
+  return launch_conv_transpose2x2(x, w4, y, n, cin, h, w, cout, e, (hipStream_t)stream);
+}
+
 }  // extern "C"

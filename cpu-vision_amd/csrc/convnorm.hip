@@ -510,6 +510,9 @@ struct PwArgs {
   long long top_img_stride;  // cout * top_h * top_w
   int top_h, top_w, wdt;     // wdt: the output's row length (hw = h * wdt)
   float top_sy, top_sx;      // (float)top_h / (float)h and (float)top_w / (float)wdt: one float division each, on the host
+  // CT instances only (ConvTranspose2d(2, 2), launch_conv_transpose2x2): the cout = 4 * co + 2 * dy + dx channels are stored as the pixel
+  // shuffle y[img][co][2 i + dy][2 j + dx] of input pixel (i, j); wdt is the INPUT's row length there and vec_y says wdt is even
+  int shuffle;
 };
 
 
@@ -594,6 +597,72 @@ __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& 
   }
 }
 
+// CT: the tile's channels are q = 4 co + 2 dy + dx of a ConvTranspose2d(2, 2) and pixel p = i * wdt + j of the input lands at
+// y[img][co][2 i + dy][2 j + dx].  After the same transpose a lane reads the dx = 0 and dx = 1 rows of one (co, dy) -- channel rows
+// 2 (r0 + 8 j) and the one after -- for its four pixels and interleaves them: 8 consecutive floats of one output row, as two
+// 16-byte stores, one per pixel pair.  With wdt even a pair (p, p + 1), p even, never crosses a row end and its 4 outputs start at
+// column 2 j, a multiple of 4, in a row pitch 2 wdt that is one too: aligned whenever y is.  Otherwise element by element.
+// Epilogue: `+ bias` (per q) and none / ReLU / ReLU6; no norm, no residual.
+template <int NT>
+__device__ __forceinline__ void pw_store_shuffle(const f32x16 (&acc)[NT], const PwTile& T, const PwArgs& A, float* tb, int lane) {
+  const int M = A.cout, HW = A.hw, Wd = A.wdt;
+  const Clamp cl = make_clamp(A.e.act);
+  const int l31 = lane & 31, hf = lane >> 5;
+  const int r0 = lane >> 3, q = (lane & 7) * 4;  // after the transpose: channel rows 2 (r0 + 8 j) + {0, 1}, pixels q .. q + 3
+  float bias[2][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int d = 0; d < 2; ++d) bias[j][d] = A.e.bias ? A.e.bias[min(T.m + 2 * (r0 + 8 * j) + d, M - 1)] : 0.f;
+  const size_t pitch = 2 * (size_t)Wd;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t < T.ntiles) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<f32x4*>(tb + l31 * kTP + 8 * g + 4 * hf) =
+            (f32x4){acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+      const int p = T.p_base + 32 * t + q;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int row = 2 * (r0 + 8 * j);
+        const int m = T.m + row;  // even, and M is a multiple of 4: m + 1 < M whenever m < M
+        const f32x4 a = *reinterpret_cast<const f32x4*>(tb + row * kTP + q);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(tb + (row + 1) * kTP + q);
+        if (m < M && p < HW) {
+          const int co = m >> 2, dy = (m >> 1) & 1;
+          float* const yp = A.y + (size_t)T.img * A.y_img_stride + (size_t)co * 4 * HW;
+          float v0[4] = {a.x, a.y, a.z, a.w}, v1[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (A.e.bias) v0[i] = v0[i] + bias[j][0], v1[i] = v1[i] + bias[j][1];
+            v0[i] = epi_act<0>(v0[i], cl), v1[i] = epi_act<0>(v1[i], cl);
+          }
+          if (A.vec_y) {  // wdt even: HW even, p even, p + 1 < HW whenever p < HW
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const int pp = p + 2 * k;
+              if (pp < HW) {
+                const int iy = pp / Wd, ix = pp - iy * Wd;
+                *reinterpret_cast<f32x4*>(yp + (size_t)(2 * iy + dy) * pitch + 2 * (size_t)ix) =
+                    (f32x4){v0[2 * k], v1[2 * k], v0[2 * k + 1], v1[2 * k + 1]};
+              }
+            }
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (p + i < HW) {
+                const int iy = (p + i) / Wd, ix = (p + i) - iy * Wd;
+                float* const o = yp + (size_t)(2 * iy + dy) * pitch + 2 * (size_t)ix;
+                o[0] = v0[i], o[1] = v1[i];
+              }
+          }
+        }
+      }
+    }
+  }
+}
+
 // KS > 1: K SLICES INSIDE the workgroup (MobileNet's 7x7 / 14x14 layers: 256-512 workgroups, K up to 960).  Such a launch is one
 // or two workgroups per CU, each walking 12-30 chunks whose loads nothing else on the CU overlaps -- every wave waits half
 // its life (PMC).  Here the workgroup has KS x 4 waves: wave group s walks chunks [s * cps, (s + 1) * cps) with
@@ -602,7 +671,7 @@ __device__ __forceinline__ void pw_store(const f32x16 (&acc)[NT], const PwTile& 
 // second launch; the summation order -- one ascending-k chain per slice from +0, slices added in order -- is stated by
 // mv_conv1x1_k_slices() and restated by the oracle (orc_pointwise_sliced_affine_act_f32): bit-exact against that, within
 // 1e-6 relative of the single chain.
-template <int NT, int MW, int KS, bool UP = false>
+template <int NT, int MW, int KS, bool UP = false, bool CT = false>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwArgs A) {
   constexpr int PG = 4 / MW;              // pixel groups (waves along pixels)
   constexpr int PXB = PG * NT * 32;       // pixels per workgroup
@@ -779,6 +848,10 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
   if (!live) return;
   float* tb = xs + wave * (32 * kTP);
   const PwTile tile = {j0 + mt * 32, pw0, ntiles, img};
+  if constexpr (CT) {
+    pw_store_shuffle<NT>(acc, tile, A, tb, lane);
+    return;
+  }
   const bool res = UP || A.e.res != nullptr;  // UP instances always add `top`: their other halves fold away
   if (A.e.act <= 2 && A.e.affine == 2 && A.e.bias == nullptr) {
     res ? pw_store<NT, 0, true, true, UP>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, true, UP>(acc, tile, A, tb, lane);
@@ -848,6 +921,18 @@ static int pw_launch(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: problem too large for one launch");
   const dim3 grid((unsigned)nb, (unsigned)n);
   const bool up = a.top != nullptr;  // the same plan, the instances that gather their residual from `top`
+  if (a.shuffle) {  // the same plan, the instances whose store is ConvTranspose2d(2, 2)'s pixel shuffle
+    int ks = 1;
+    if constexpr (NT == 1) ks = p.ks;
+    if (ks == 2) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 2, false, true>), grid, dim3(512), 0, s, a);
+    } else if (ks == 4) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 4, false, true>), grid, dim3(1024), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_conv1x1<NT, MW, 1, false, true>), grid, dim3(256), 0, s, a);
+    }
+    return check_launchf("k_conv1x1_ct<%d,%d,ks%d,%s>", NT, MW, ks, a.vec_y ? "vec16" : "scalar");
+  }
   if constexpr (NT == 1) {
     if (p.ks > 1) {
       if (p.ks == 2) {
@@ -872,7 +957,8 @@ static int pw_pick_nt(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   return pw_launch<(MW == 1 ? 2 : 4), MW>(a, n, p, s);
 }
 
-// up: null, or the coarser map of launch_conv1x1_upsample_add (e.res is null then)
+// up: null, or the extra fields of an UP / CT instance: the coarser map of launch_conv1x1_upsample_add, or launch_conv_transpose2x2's
+// shuffle flag and input row length (e.res is null then)
 static int conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e, hipStream_t s,
                    int64_t x_img_stride, int64_t y_img_stride, bool allow_k_slices, const PwArgs* up) {
   // pixel indices are ints, and a workgroup's last tile (p0 + PXB, the epilogue's p + 3) may reach up to 1024 pixels past the plane
@@ -887,6 +973,7 @@ static int conv1x1(const float* x, const float* w, float* y, int64_t n, int cin,
   a.vec_w = (cin % 4 == 0) && ((uintptr_t)w % 16 == 0);
   a.vec_x = (hw % 4 == 0) && ((uintptr_t)x % 16 == 0);
   a.vec_y = (hw % 4 == 0) && ((uintptr_t)y % 16 == 0) && (e.res == nullptr || (uintptr_t)e.res % 16 == 0);
+  if (a.shuffle) a.vec_y = (a.wdt % 2 == 0) && ((uintptr_t)y % 16 == 0);
   if (n == 0 || hw == 0) return MV_OK;
   PwPlan p = pw_plan(n, cin, hw, cout);
   if (!allow_k_slices) p.ks = 1, p.cps = a.chunks;  // the im2col GEMMs keep the single chain their oracle states
@@ -908,6 +995,13 @@ int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top
   up.top_img_stride = (long long)cout * top_h * top_w;
   up.top_sy = (float)top_h / (float)h, up.top_sx = (float)top_w / (float)wd;
   return conv1x1(x, w, y, n, cin, (int64_t)h * wd, cout, e, s, 0, 0, true, &up);
+}
+
+int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,
+                             hipStream_t s) {
+  PwArgs ct = {};
+  ct.shuffle = 1, ct.wdt = wd;
+  return conv1x1(x, w4, y, n, cin, (int64_t)h * wd, 4 * cout, e, s, 0, 0, true, &ct);
 }
 
 }  // namespace mv

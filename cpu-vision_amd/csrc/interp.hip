@@ -14,6 +14,7 @@
 // Arithmetic (mi355vision.h, mv_interpolate_bilinear_f32): every product and every fma is written with __fmul_rn / __fmaf_rn, one
 // rounding each; NORM normalises each tap first as (x - mean[c]) / std[c], the subtraction rounded, the division correctly rounded
 // (k_to_float_normalize's arithmetic), so the fused result has the bits of normalize -> interpolate -> batch_images.
+#include "mv_bilinear.h"
 #include "mv_common.h"
 
 namespace mv {
@@ -40,21 +41,6 @@ struct InterpArgs {
   float mean[16], stdv[16];
 };
 
-// source index pair and weights of output index d: src = max(fma(s, d + 0.5, -0.5), 0)
-struct Tap {
-  int i0, i1;
-  float w0, w1;
-};
-__device__ inline Tap tap_of(int d, float s, int in) {
-  const float src = fmaxf(__fmaf_rn(s, (float)d + 0.5f, -0.5f), 0.f);
-  Tap t;
-  t.i0 = min((int)src, in - 1);  // src >= 0: the conversion truncates to the floor
-  t.i1 = min(t.i0 + 1, in - 1);
-  t.w1 = fminf(fmaxf(__fsub_rn(src, (float)t.i0), 0.f), 1.f);
-  t.w0 = __fsub_rn(1.f, t.w1);
-  return t;
-}
-
 template <bool NORM>
 __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_interp_batch(const InterpArgs A) {
   const unsigned xb = blockIdx.x % A.xblocks, t = blockIdx.x / A.xblocks;
@@ -65,14 +51,14 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void k_interp_batch(const In
   const DetImage I = A.img[n];
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   if (y < I.oh && x0 < I.ow) {
-    const Tap ty = tap_of(y, I.sy, I.h);
+    const BilinearTap ty = bilinear_tap(y, I.sy, I.h);
     const float* const r0 = I.x + ((size_t)ch * I.h + ty.i0) * I.w;
     const float* const r1 = I.x + ((size_t)ch * I.h + ty.i1) * I.w;
     const float m = NORM ? A.mean[ch] : 0.f, sd = NORM ? A.stdv[ch] : 1.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (x0 + j < I.ow) {
-        const Tap tx = tap_of(x0 + j, I.sx, I.w);
+        const BilinearTap tx = bilinear_tap(x0 + j, I.sx, I.w);
         float a = r0[tx.i0], b = r0[tx.i1], c = r1[tx.i0], d = r1[tx.i1];
         if (NORM) {
           a = __fdiv_rn(__fsub_rn(a, m), sd), b = __fdiv_rn(__fsub_rn(b, m), sd);

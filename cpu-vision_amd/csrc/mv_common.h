@@ -360,6 +360,16 @@ constexpr int kMaxDetImages = 64;  // 64 x 32 B = 2 KiB of the 4 KiB kernel-argu
 bool interp_grid_fits(int64_t planes, int hp, int wp);
 int launch_interp_batch(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int n, int c,
                         const float* mean, const float* stdv, float* y, int hp, int wp, hipStream_t s);
+// Mask R-CNN's paste_masks_in_image and maskrcnn_inference (mask.hip; semantics in mi355vision.h mv_paste_masks_f32,
+// mv_mask_probs_f32).  The entry points have checked the arguments, the extents and the grids (*_grid_fits); r is positive.
+bool paste_masks_grid_fits(int64_t r, int h, int w);
+int launch_paste_masks(const float* masks, const float* boxes, float* y, int64_t r, int m, int padding, int h, int w, hipStream_t s);
+bool mask_probs_grid_fits(int64_t r, int64_t plane);
+int launch_mask_probs(const float* logits, const int64_t* labels, float* y, int64_t r, int classes, int64_t plane, hipStream_t s);
+// ConvTranspose2d(kernel 2, stride 2) + bias + activation: launch_conv1x1 on the relaid (4 cout, cin) weight whose store is the pixel
+// shuffle (convnorm.hip, k_conv1x1_ct: the same plan, tiles and summation order; e.res must be null, e.affine 0)
+int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,
+                             hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

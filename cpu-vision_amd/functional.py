@@ -23,6 +23,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               retinanet_topk / retinanet_decode (retinanet.py postprocess_detections up to the nms)
   _interp     interpolate (torch.nn.functional.interpolate, plain bilinear) and detection_batch, the fused normalize + resize +
               batch_images in front of a detection model (models/detection/transform.py)
+  _mask       paste_masks_in_image / mask_probs (roi_heads.py paste_masks_in_image, maskrcnn_inference) and
+              conv_transpose2d_bias_act, ConvTranspose2d(kernel 2, stride 2) + bias + activation (mask_rcnn.py conv5_mask)
 The switches (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION, CONV2D_*) are set on this module only; the code behind it reads them
 here at call time (_lib.switch).
 
@@ -70,6 +72,7 @@ from ._layers import (_ACT_CODES, adaptive_avg_pool2d, _AFFINE_CODES, conv1x1_k_
                       inverted_residual_k_slices, _inverted_residual_workspace_bytes, linear_bias_relu, linear_k_slices,
                       max_pool2d, max_pool2d_2x2, normalized_conv2d_bias_relu)
 from ._lib import max_value as _max_value  # noqa: F401
+from ._mask import conv_transpose2d_bias_act, conv_transpose2x2_relayout, mask_probs, paste_masks_in_image  # noqa: F401
 from ._misc import (center_crop, center_crop_image, _mean_std, normalize, normalize_image, resize, resize_image,  # noqa: F401
                     resize_video, to_dtype, to_dtype_image, _to_dtype_tensor_dispatch, to_float_normalize)
 from ._registry import _get_kernel, _register_kernel_internal  # noqa: F401

@@ -9,7 +9,11 @@ also does: the boolean indexing by `valid` (one read-back), ops.batched_nms and 
 
 Numerics: DESIGN.md 3.25 and mi355vision.h mv_roi_detections_f32 -- every float operation is the reference's float32 operation,
 rounded once; exp is the correctly rounded float32 exp and the softmax sum is one ascending chain.  Inference only, float32 only:
-the matcher, the sampler and the losses of the reference are not built, the mask and keypoint branches are not implemented.
+the matcher, the sampler and the losses of the reference are not built, the keypoint branch is not implemented.
+
+With mask modules (mask_rcnn.py: this package's MultiScaleRoIAlign, MaskRCNNHeads and MaskRCNNPredictor) `forward` runs the
+reference's mask branch on the detected boxes and adds "masks" (N_i, 1, M, M) to every result: pooler -> mask head -> predictor ->
+F.mask_probs, which reads only the predicted label's plane of every roi.
 """
 from __future__ import annotations
 
@@ -51,8 +55,9 @@ def postprocess_detections_detailed(class_logits: Tensor, box_regression: Tensor
 
 
 class RoIHeads(nn.Module):
-    """roi_heads.py:496-876, inference: forward(features, proposals, image_shapes) -> ([{boxes, labels, scores}] per image, {}).  The
-    training arguments are kept as given; a mask or keypoint module raises NotImplementedError."""
+    """roi_heads.py:496-876, inference: forward(features, proposals, image_shapes) -> ([{boxes, labels, scores[, masks]}] per image,
+    {}).  The training arguments are kept as given; the mask modules must be this package's (mask_rcnn.py), any other object and
+    every keypoint module raises NotImplementedError."""
 
     __annotations__ = {"box_coder": BoxCoder}
 
@@ -65,12 +70,18 @@ class RoIHeads(nn.Module):
                  mask_roi_pool=None, mask_head=None, mask_predictor=None, keypoint_roi_pool=None, keypoint_head=None,
                  keypoint_predictor=None):
         super().__init__()
-        for name, module in (("mask_roi_pool", mask_roi_pool), ("mask_head", mask_head), ("mask_predictor", mask_predictor),
-                             ("keypoint_roi_pool", keypoint_roi_pool), ("keypoint_head", keypoint_head),
+        from .mask_rcnn import MaskRCNNHeads, MaskRCNNPredictor  # mask_rcnn imports faster_rcnn, which imports this module
+
+        for name, module, kind in (("mask_roi_pool", mask_roi_pool, box_ops.MultiScaleRoIAlign), ("mask_head", mask_head, MaskRCNNHeads),
+                                   ("mask_predictor", mask_predictor, MaskRCNNPredictor)):
+            if module is not None and not isinstance(module, kind):
+                raise NotImplementedError(f"RoIHeads: {name} is a {type(module).__name__}, and the mask branch on the MI355X path runs "
+                                          f"this package's {kind.__name__} only")
+        for name, module in (("keypoint_roi_pool", keypoint_roi_pool), ("keypoint_head", keypoint_head),
                              ("keypoint_predictor", keypoint_predictor)):
             if module is not None:
-                raise NotImplementedError(f"RoIHeads: {name} is given, and the mask and keypoint branches are not on the MI355X path "
-                                          "(the box branch is)")
+                raise NotImplementedError(f"RoIHeads: {name} is given, and the keypoint branch is not on the MI355X path "
+                                          "(the box and mask branches are)")
         self.box_similarity = box_ops.box_iou
         # used during training (kept as given: the matcher and the sampler are not built)
         self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
@@ -124,8 +135,8 @@ class RoIHeads(nn.Module):
                 targets: Optional[List[Dict[str, Tensor]]] = None) -> Tuple[List[Dict[str, Tensor]], Dict[str, Tensor]]:
         if self.training or targets is not None:
             raise RuntimeError("the MI355X RoIHeads is inference only: call .eval() and pass no targets")
-        if self.has_mask() or self.has_keypoint():
-            raise NotImplementedError("RoIHeads: the mask and keypoint branches are not on the MI355X path")
+        if self.has_keypoint():
+            raise NotImplementedError("RoIHeads: the keypoint branch is not on the MI355X path")
         for f in features.values():
             if f.dtype != torch.float32:
                 raise TypeError(f"RoIHeads computes in float32. Got features {f.dtype}")
@@ -139,4 +150,25 @@ class RoIHeads(nn.Module):
         for i in range(len(boxes)):
             result.append({"boxes": _lib.forward_only(boxes[i], "RoIHeads.forward", *deps), "labels": labels[i],
                            "scores": _lib.forward_only(scores[i], "RoIHeads.forward", *deps)})
+        if self.has_mask():
+            mask_deps = (*deps, *self.mask_head.parameters(), *self.mask_predictor.parameters())
+            for r, probs in zip(result, self.mask_branch(features, boxes, labels, image_shapes)):
+                r["masks"] = _lib.forward_only(probs, "RoIHeads.forward", *mask_deps)
         return result, {}
+
+    def mask_branch(self, features: Dict[str, Tensor], boxes: List[Tensor], labels: List[Tensor],
+                    image_shapes: List[Tuple[int, int]]) -> List[Tensor]:
+        """roi_heads.py:815-850, inference: mask_roi_pool on the detected boxes -> mask_head -> mask_predictor -> F.mask_probs on the
+        concatenated labels (maskrcnn_inference: one gather + sigmoid launch), split per image into (N_i, 1, M, M).  Without a
+        detection in the whole batch nothing is launched and every image gets an empty tensor."""
+        boxes_per_image = [int(b.shape[0]) for b in boxes]
+        with torch.no_grad():
+            if sum(boxes_per_image) == 0:
+                # MaskRCNNHeads keeps the pooled size, MaskRCNNPredictor's ConvTranspose2d(2, 2) doubles it
+                mh, mw = (2 * int(s) for s in self.mask_roi_pool.output_size)
+                return [b.new_empty((0, 1, mh, mw)) for b in boxes]
+            mask_features = self.mask_roi_pool(features, [b.detach() for b in boxes], image_shapes)
+            mask_features = self.mask_head(mask_features)
+            mask_logits = self.mask_predictor(mask_features)
+            probs = F.mask_probs(mask_logits, torch.cat(labels))
+        return list(probs.split(boxes_per_image, dim=0))

@@ -5,7 +5,8 @@ box rescaling behind it.
 non-antialiased bilinear `interpolate` and the zero-padded batch in one pass over the pixels.  The pieces stay
 callable on their own and give the same bits: `normalize` is the package's F.normalize, `resize` is F.interpolate at the size
 `resized_size` gives (device tensors only), `batch_images` is the reference's new_full + copy_ on the device; `postprocess` /
-`resize_boxes` is the reference's float32 composition.  With the reference's private keyword `_skip_resize=True` (the reference
+`resize_boxes` is the reference's float32 composition, and a prediction with "masks" (Mask R-CNN) has them pasted into the original
+image by ONE F.paste_masks_in_image launch per image, on the rescaled boxes as in the reference.  With the reference's private keyword `_skip_resize=True` (the reference
 honours it in training mode only; here it also stands for inference on images that already have their final size) `forward` runs
 those pieces one by one and does not resize.
 """
@@ -139,6 +140,10 @@ class GeneralizedRCNNTransform(nn.Module):
             boxes = pred["boxes"]
             boxes = resize_boxes(boxes, im_s, o_im_s)
             result[i]["boxes"] = boxes
+            if "masks" in pred:
+                masks = pred["masks"]
+                masks = F.paste_masks_in_image(masks, boxes, o_im_s)
+                result[i]["masks"] = masks
         return result
 
     def __repr__(self) -> str:

@@ -878,6 +878,52 @@ int mv_interpolate_bilinear_f32(const float* x, float* y, int64_t planes, int h,
 int mv_detection_batch_f32(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int64_t n, int c,
                            const float* mean, const float* stdv, float* y, int hp, int wp, void* stream);
 
+/* ---- The mask branch of Mask R-CNN (models/detection/roi_heads.py maskrcnn_inference, paste_masks_in_image; mask_rcnn.py's
+ * ConvTranspose2d(kernel 2, stride 2)).  All tensors DEVICE float32 unless said.
+ *
+ * mv_paste_masks_f32: masks (r, m, m), boxes (r, 4) rows (x1, y1, x2, y2) -> y (r, h, w), ONE launch that writes every element of y
+ * once.  Everything is float32 and every operation is rounded once.  Per roi (expand_boxes, in registers):
+ *   wh = (x2 - x1) * 0.5f,  hh = (y2 - y1) * 0.5f,  xc = (x2 + x1) * 0.5f,  yc = (y2 + y1) * 0.5f
+ *   wh = wh * scale,  hh = hh * scale,   scale = float32((double)(m + 2 padding) / m)      (m = 28, padding = 1: 1.0714285373687744)
+ *   (bx0, by0, bx1, by1) = trunc(xc - wh), trunc(yc - hh), trunc(xc + wh), trunc(yc + hh)   (toward zero, the reference's .to(int64))
+ *   bw = max(bx1 - bx0 + 1, 1),  bh = max(by1 - by0 + 1, 1)
+ * and y[r, Y, X] is element (Y - by0, X - bx0) of the bilinear resize of the zero-padded mask (m + 2 padding)^2 -> (bh, bw) when
+ * max(bx0, 0) <= X < min(bx1 + 1, w) and max(by0, 0) <= Y < min(by1 + 1, h), and +0.0 everywhere else.  The resize is exactly the
+ * formula of mv_interpolate_bilinear_f32 with s = float32(m + 2 padding) / float32(bw) (and bh), a correctly rounded division on the
+ * device.  The padded mask is never materialised: a tap in the padding ring reads as +0.0.  The boxes are read on the device; nothing
+ * is allocated, read back or synchronised, and r is only a grid extent.
+ *   Domain.  A roi with an expanded coordinate that is not finite or whose magnitude reaches 2^30 gives a zero plane (the reference's
+ *   conversion is undefined there).  The rule equals the reference's paste_mask_in_image wherever its slice bounds are non-negative and
+ *   inside the image; for a box wholly outside the image (bx1 < -1, bx0 > w, ...) the reference raises on a shape mismatch or applies
+ *   Python's negative-index slicing, and this entry writes what the rule says (zeros).  RoIHeads clips its boxes to the image, so the
+ *   model never meets that case.
+ * y is stored 16 bytes at a time when w is a multiple of 4 and y is 16-byte aligned, else element by element (mv_last_kernel says
+ * which); masks and boxes may start at any 4-byte address.  Element offsets are 64-bit.
+ *
+ * mv_mask_probs_f32: logits (r, classes, mh, mw), labels (r) int64 -> y (r, mh, mw) = s(logits[i, labels[i]]), s the sigmoid of
+ * mv_retinanet_topk_f32 (1 / (1 + E(-x)), E the correctly rounded float32 exponential, the division correctly rounded).  Only the
+ * selected plane of a roi is read.  A label outside [0, classes) gives a zero plane and nothing is read through it (the reference
+ * would raise; the library does not read labels back).
+ *
+ * mv_conv_transpose2x2_bias_act_f32: ConvTranspose2d(kernel_size 2, stride 2, padding 0, output_padding 0, groups 1, dilation 1) +
+ * bias + activation, x (n, cin, h, w) -> y (n, cout, 2 h, 2 w):
+ *   y[b, co, 2 i + dy, 2 j + dx] = act(bias4[q] + sum_ci x[b, ci, i, j] * w4[q, ci]),   q = 4 co + 2 dy + dx
+ * `w4` is the RELAID weight (4 cout, cin), row q = torch's weight[:, co, dy, dx]; `bias4` (4 cout) the bias with every entry
+ * repeated four times, or NULL.  It is the pointwise kernel of mv_conv_norm_act_f32 (MV_CONV_PW1X1) on 4 cout channels with the same
+ * plan, tiles, K chunks and K slices, whose store is the pixel shuffle: the summation order is, by construction, exactly the one
+ * mv_conv1x1_k_slices(n, cin, h, w, 4 cout) states, then `+ bias`, then the activation (MV_ACT_NONE / RELU / RELU6).  The
+ * (n, 4 cout, h, w) intermediate never reaches memory and y is written once, 16 bytes at a time when w is even and y is 16-byte
+ * aligned, else element by element (mv_last_kernel says which).
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: a null pointer (bias4 may be null), a non-positive
+ * m / h / w / classes / cin / cout, a negative r, n or padding, an activation code other than the three, an output that overlaps an
+ * input (byte ranges), sizes that exceed the address space, more workgroups than one launch grid holds (MV_ERR_UNSUPPORTED).
+ * r == 0 / n == 0 is a no-op that touches no pointer. */
+int mv_paste_masks_f32(const float* masks, const float* boxes, float* y, int64_t r, int m, int padding, int h, int w, void* stream);
+int mv_mask_probs_f32(const float* logits, const int64_t* labels, float* y, int64_t r, int classes, int mh, int mw, void* stream);
+int mv_conv_transpose2x2_bias_act_f32(const float* x, const float* w4, const float* bias4, float* y, int64_t n, int cin, int h, int w,
+                                      int cout, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
