@@ -63,33 +63,95 @@ def _img_strides(maps):
     return (C.c_int64 * len(maps))(*[int(m.stride(0)) if m.shape[0] > 1 else int(m[0].numel()) for m in maps])
 
 
-def rpn_topk(logits: List[torch.Tensor], k: int) -> torch.Tensor:
-    """filter_proposals' per-level top-k (rpn.py) on the head's own NCHW logits, ONE launch: logits[l] (N, A_l, H_l, W_l) -> idx
-    (N, K) int32, K = sum_l min(k, A_l H_l W_l): per image, level after level, the indices into the reference's concatenated
-    (y, x, a) layout of the level's greatest logits in stable descending order (equal logits by ascending index, NaN greatest)."""
-    shapes = _level_maps("rpn_topk", logits, "logits", 1)
+def _image_sizes(name: str, image_sizes, fits, rows: str) -> torch.Tensor:
+    """image_sizes (rows (h, w): a list, or an (N, 2) tensor) as a tensor; `fits(sizes)` is the caller's rule for the rows, `rows`
+    its words in the message."""
+    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
+                                                                                 dtype=torch.float32).reshape(-1, 2)
+    if not fits(sizes):
+        raise RuntimeError(f"{name}: image_sizes should hold {rows} (height, width), got {tuple(sizes.shape)}")
+    return sizes
+
+
+def _topk(name: str, logits, shapes, k, classes: Optional[int] = None, score_thresh=None) -> torch.Tensor:
+    """What rpn_topk and retinanet_topk share behind the checks of their maps: the checks of k, the workspace of
+    mv_<name>_workspace_bytes and the launch of mv_<name>_f32.  classes and score_thresh: retinanet's, arguments of its entries only."""
     if not isinstance(k, int) or k < 1:
-        raise ValueError(f"rpn_topk: k must be a positive int, got {k!r}")
+        raise ValueError(f"{name}: k must be a positive int, got {k!r}")
     if k > MAX_RPN_TOPK:
-        raise _lib.Mi355VisionError(f"rpn_topk: k up to {MAX_RPN_TOPK}, got {k}")
+        raise _lib.Mi355VisionError(f"{name}: k up to {MAX_RPN_TOPK}, got {k}")
+    per_anchor = 1 if classes is None else classes
+    classes, thresh = (() if classes is None else (classes,)), (() if score_thresh is None else (float(score_thresh),))
     for m in logits:
         _lib.require_device(m, "logits")
     lib = _lib.load()
     l0 = logits[0]
     n = shapes[0][0]
-    total = sum(min(k, a * h * w) for _, a, h, w in shapes)
+    total = sum(min(k, a * h * w * per_anchor) for _, a, h, w in shapes)
     with _lib.on_device_of(l0):
         maps = [_dense_images(m) for m in logits]
         idx = torch.empty((n, total), dtype=torch.int32, device=l0.device)
         if n:
             hs, ws, as_ = _tables(shapes)
-            nbytes = int(lib.mv_rpn_topk_workspace_bytes(n, hs, ws, as_, len(maps), k))
+            nbytes = int(getattr(lib, f"mv_{name}_workspace_bytes")(n, hs, ws, as_, len(maps), *classes, k))
             if not nbytes:
-                raise _lib.Mi355VisionError(f"rpn_topk: {n} images are more than one call takes")
+                raise _lib.Mi355VisionError(f"{name}: {n} images are more than one call takes")
             buf, ws_ptr, nbytes = _lib.workspace(nbytes, l0.device)
-            _lib.launch(lib.mv_rpn_topk_f32, l0, _lib.pointer_table(maps), hs, ws, as_, _img_strides(maps), len(maps), n, k, idx.data_ptr(),
-                        ws_ptr, nbytes)
+            _lib.launch(getattr(lib, f"mv_{name}_f32"), l0, _lib.pointer_table(maps), hs, ws, as_, _img_strides(maps), len(maps), *classes, n, k,
+                        *thresh, idx.data_ptr(), ws_ptr, nbytes)
     return idx
+
+
+def _decode(name: str, logits, shapes, deltas, idx, cell_anchors, strides, image_sizes, weights, clip, classes=(), filters=()):
+    """What rpn_decode and retinanet_decode share behind the checks of their logits: the checks of the other arguments, the staging
+    and the launch of mv_<name>_f32 -> boxes, scores, the entry's int64 output, valid.  classes: (num_classes,) for retinanet's
+    entry; filters: (min_size, score_thresh) for the rpn's."""
+    anchors = [a for _, a, _, _ in shapes]
+    dshapes = _level_maps(name, deltas, "deltas", 4, anchors) if isinstance(deltas, (list, tuple)) and len(deltas) == len(logits) else None
+    if dshapes is None or any(d[2:] != s[2:] or d[0] != s[0] for d, s in zip(dshapes, shapes)):
+        raise RuntimeError(f"{name}: deltas should hold one map per level of logits, of the same batch and size with 4 channels per anchor")
+    num, n = len(shapes), shapes[0][0]
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
+        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, K)")
+    if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or \
+            any(tuple(c.shape) != (a, 4) for c, a in zip(cell_anchors, anchors)):
+        raise RuntimeError(f"{name}: cell_anchors should hold one (A, 4) tensor per level, A = {anchors}")
+    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
+        raise RuntimeError(f"{name}: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
+    if len(weights) != 4:
+        raise ValueError(f"{name}: four weights (wx, wy, ww, wh), got {weights!r}")
+    sizes = _image_sizes(name, image_sizes, lambda t: tuple(t.shape) == (n, 2), f"{n} rows")
+    for m in (*logits, *deltas, idx):
+        _lib.require_device(m, f"{name} input")
+    lib = _lib.load()
+    l0 = logits[0]
+    k = int(idx.shape[1])
+    with _lib.on_device_of(l0):
+        lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
+        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
+        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
+        ix = idx.contiguous()
+        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
+        third = torch.empty((n, k), dtype=torch.int64, device=l0.device)
+        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
+        if n and k:
+            hs, ws, as_ = _tables(shapes)
+            sh = (C.c_int * num)(*[int(s[0]) for s in strides])
+            sw = (C.c_int * num)(*[int(s[1]) for s in strides])
+            _lib.launch(getattr(lib, f"mv_{name}_f32"), l0, _lib.pointer_table(lmaps), _lib.pointer_table(dmaps), hs, ws, as_,
+                        _img_strides(lmaps), _img_strides(dmaps), sh, sw, num, *classes, base.data_ptr(), sizes.data_ptr(), ix.data_ptr(), n, k,
+                        *[float(w) for w in weights], float(clip), *[float(f) for f in filters], boxes.data_ptr(), scores.data_ptr(),
+                        third.data_ptr(), valid.data_ptr())
+    deps = (*logits, *deltas)
+    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(scores, name, *deps), third, valid.view(torch.bool)
+
+
+def rpn_topk(logits: List[torch.Tensor], k: int) -> torch.Tensor:
+    """filter_proposals' per-level top-k (rpn.py) on the head's own NCHW logits, ONE launch: logits[l] (N, A_l, H_l, W_l) -> idx
+    (N, K) int32, K = sum_l min(k, A_l H_l W_l): per image, level after level, the indices into the reference's concatenated
+    (y, x, a) layout of the level's greatest logits in stable descending order (equal logits by ascending index, NaN greatest)."""
+    return _topk("rpn_topk", logits, _level_maps("rpn_topk", logits, "logits", 1), k)
 
 
 def rpn_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx: torch.Tensor, cell_anchors: List[torch.Tensor],
@@ -101,48 +163,8 @@ def rpn_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx: torc
     clip_boxes_to_image with image_sizes (N rows (h, w): a list, or an (N, 2) tensor), sigmoid -> boxes (N, K, 4), scores (N, K),
     levels (N, K) int64, valid (N, K) bool = both sides >= min_size and score >= score_thresh."""
     shapes = _level_maps("rpn_decode", logits, "logits", 1)
-    anchors = [a for _, a, _, _ in shapes]
-    dshapes = _level_maps("rpn_decode", deltas, "deltas", 4, anchors) if isinstance(deltas, (list, tuple)) and len(deltas) == len(logits) else None
-    if dshapes is None or any(d[2:] != s[2:] or d[0] != s[0] for d, s in zip(dshapes, shapes)):
-        raise RuntimeError("rpn_decode: deltas should hold one map per level of logits, of the same batch and size with 4 channels per anchor")
-    num, n = len(shapes), shapes[0][0]
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
-        raise RuntimeError(f"rpn_decode: idx should be an int32 tensor of shape ({n}, K)")
-    if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or \
-            any(tuple(c.shape) != (a, 4) for c, a in zip(cell_anchors, anchors)):
-        raise RuntimeError(f"rpn_decode: cell_anchors should hold one (A, 4) tensor per level, A = {anchors}")
-    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
-        raise RuntimeError(f"rpn_decode: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
-    if len(weights) != 4:
-        raise ValueError(f"rpn_decode: four weights (wx, wy, ww, wh), got {weights!r}")
-    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
-                                                                                 dtype=torch.float32).reshape(-1, 2)
-    if tuple(sizes.shape) != (n, 2):
-        raise RuntimeError(f"rpn_decode: image_sizes should hold {n} rows (height, width), got {tuple(sizes.shape)}")
-    for m in (*logits, *deltas, idx):
-        _lib.require_device(m, "rpn_decode input")
-    lib = _lib.load()
-    l0 = logits[0]
-    k = int(idx.shape[1])
-    with _lib.on_device_of(l0):
-        lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
-        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
-        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
-        ix = idx.contiguous()
-        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
-        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
-        levels = torch.empty((n, k), dtype=torch.int64, device=l0.device)
-        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
-        if n and k:
-            hs, ws, as_ = _tables(shapes)
-            sh = (C.c_int * num)(*[int(s[0]) for s in strides])
-            sw = (C.c_int * num)(*[int(s[1]) for s in strides])
-            _lib.launch(lib.mv_rpn_decode_f32, l0, _lib.pointer_table(lmaps), _lib.pointer_table(dmaps), hs, ws, as_, _img_strides(lmaps),
-                        _img_strides(dmaps), sh, sw, num, base.data_ptr(), sizes.data_ptr(), ix.data_ptr(), n, k,
-                        *[float(w) for w in weights], float(bbox_xform_clip), float(min_size), float(score_thresh), boxes.data_ptr(),
-                        scores.data_ptr(), levels.data_ptr(), valid.data_ptr())
-    deps = (*logits, *deltas)
-    return (_lib.forward_only(boxes, "rpn_decode", *deps), _lib.forward_only(scores, "rpn_decode", *deps), levels, valid.view(torch.bool))
+    return _decode("rpn_decode", logits, shapes, deltas, idx, cell_anchors, strides, image_sizes, weights, bbox_xform_clip,
+                   filters=(min_size, score_thresh))
 
 
 def _class_maps(name: str, logits, num_classes):
@@ -161,30 +183,7 @@ def retinanet_topk(logits: List[torch.Tensor], num_classes: int, k: int, score_t
     after level, the flat indices ((y, x, a) anchor index of the concatenated layout) * num_classes + class of the level's
     min(k, passing) greatest scores in stable descending order (equal scores by ascending flat index), then -1.  One (image, level)
     is spread over many workgroups; nothing is read back."""
-    shapes = _class_maps("retinanet_topk", logits, num_classes)
-    if not isinstance(k, int) or k < 1:
-        raise ValueError(f"retinanet_topk: k must be a positive int, got {k!r}")
-    if k > MAX_RPN_TOPK:
-        raise _lib.Mi355VisionError(f"retinanet_topk: k up to {MAX_RPN_TOPK}, got {k}")
-    score_thresh = float(score_thresh)
-    for m in logits:
-        _lib.require_device(m, "logits")
-    lib = _lib.load()
-    l0 = logits[0]
-    n = shapes[0][0]
-    total = sum(min(k, a * h * w * num_classes) for _, a, h, w in shapes)
-    with _lib.on_device_of(l0):
-        maps = [_dense_images(m) for m in logits]
-        idx = torch.empty((n, total), dtype=torch.int32, device=l0.device)
-        if n:
-            hs, ws, as_ = _tables(shapes)
-            nbytes = int(lib.mv_retinanet_topk_workspace_bytes(n, hs, ws, as_, len(maps), num_classes, k))
-            if not nbytes:
-                raise _lib.Mi355VisionError(f"retinanet_topk: {n} images are more than one call takes")
-            buf, ws_ptr, nbytes = _lib.workspace(nbytes, l0.device)
-            _lib.launch(lib.mv_retinanet_topk_f32, l0, _lib.pointer_table(maps), hs, ws, as_, _img_strides(maps), len(maps), num_classes, n, k,
-                        score_thresh, idx.data_ptr(), ws_ptr, nbytes)
-    return idx
+    return _topk("retinanet_topk", logits, _class_maps("retinanet_topk", logits, num_classes), k, num_classes, score_thresh)
 
 
 def retinanet_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx: torch.Tensor, cell_anchors: List[torch.Tensor],
@@ -197,48 +196,7 @@ def retinanet_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx
     tensor), the sigmoid -> boxes (N, K, 4), scores (N, K), labels (N, K) int64, valid (N, K) bool (False, with zeros, for the -1
     padding and any other index outside the pyramid)."""
     shapes = _class_maps("retinanet_decode", logits, num_classes)
-    anchors = [a for _, a, _, _ in shapes]
-    dshapes = _level_maps("retinanet_decode", deltas, "deltas", 4, anchors) if isinstance(deltas, (list, tuple)) and len(deltas) == len(logits) else None
-    if dshapes is None or any(d[2:] != s[2:] or d[0] != s[0] for d, s in zip(dshapes, shapes)):
-        raise RuntimeError("retinanet_decode: deltas should hold one map per level of logits, of the same batch and size with 4 channels per anchor")
-    num, n = len(shapes), shapes[0][0]
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
-        raise RuntimeError(f"retinanet_decode: idx should be an int32 tensor of shape ({n}, K)")
-    if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or \
-            any(tuple(c.shape) != (a, 4) for c, a in zip(cell_anchors, anchors)):
-        raise RuntimeError(f"retinanet_decode: cell_anchors should hold one (A, 4) tensor per level, A = {anchors}")
-    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
-        raise RuntimeError(f"retinanet_decode: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
-    if len(weights) != 4:
-        raise ValueError(f"retinanet_decode: four weights (wx, wy, ww, wh), got {weights!r}")
-    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
-                                                                                 dtype=torch.float32).reshape(-1, 2)
-    if tuple(sizes.shape) != (n, 2):
-        raise RuntimeError(f"retinanet_decode: image_sizes should hold {n} rows (height, width), got {tuple(sizes.shape)}")
-    for m in (*logits, *deltas, idx):
-        _lib.require_device(m, "retinanet_decode input")
-    lib = _lib.load()
-    l0 = logits[0]
-    k = int(idx.shape[1])
-    with _lib.on_device_of(l0):
-        lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
-        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
-        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
-        ix = idx.contiguous()
-        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
-        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
-        labels = torch.empty((n, k), dtype=torch.int64, device=l0.device)
-        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
-        if n and k:
-            hs, ws, as_ = _tables(shapes)
-            sh = (C.c_int * num)(*[int(s[0]) for s in strides])
-            sw = (C.c_int * num)(*[int(s[1]) for s in strides])
-            _lib.launch(lib.mv_retinanet_decode_f32, l0, _lib.pointer_table(lmaps), _lib.pointer_table(dmaps), hs, ws, as_, _img_strides(lmaps),
-                        _img_strides(dmaps), sh, sw, num, num_classes, base.data_ptr(), sizes.data_ptr(), ix.data_ptr(), n, k,
-                        *[float(w) for w in weights], float(clip), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
-    deps = (*logits, *deltas)
-    return (_lib.forward_only(boxes, "retinanet_decode", *deps), _lib.forward_only(scores, "retinanet_decode", *deps), labels,
-            valid.view(torch.bool))
+    return _decode("retinanet_decode", logits, shapes, deltas, idx, cell_anchors, strides, image_sizes, weights, clip, classes=(num_classes,))
 
 
 def retinanet_topk_chunk() -> int:
@@ -306,10 +264,8 @@ def roi_detections(class_logits: torch.Tensor, box_regression: torch.Tensor, roi
         raise _lib.Mi355VisionError(f"roi_detections: {r} rois x {c} classes exceed the 32-bit index")
     if len(weights) != 4:
         raise ValueError(f"roi_detections: four weights (wx, wy, ww, wh), got {weights!r}")
-    sizes = image_sizes if isinstance(image_sizes, torch.Tensor) else torch.tensor([[float(s[0]), float(s[1])] for s in image_sizes],
-                                                                                 dtype=torch.float32).reshape(-1, 2)
-    if sizes.dim() != 2 or sizes.shape[1] != 2 or (r > 0 and sizes.shape[0] < 1):
-        raise RuntimeError(f"roi_detections: image_sizes should hold at least one row (height, width), got {tuple(sizes.shape)}")
+    sizes = _image_sizes("roi_detections", image_sizes, lambda t: t.dim() == 2 and t.shape[1] == 2 and (r == 0 or t.shape[0] >= 1),
+                         "at least one row")
     for m in (class_logits, box_regression, rois):
         _lib.require_device(m, "roi_detections input")
     lib = _lib.load()

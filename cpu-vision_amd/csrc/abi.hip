@@ -1210,7 +1210,7 @@ int mv_masks_to_boxes_f32(const float* masks, float* boxes, int* empty_flag, int
   return masks_to_boxes(masks, true, boxes, empty_flag, n, h, w, workspace, workspace_bytes, stream);
 }
 
-// ---- RPN top-k / decode, BoxCoder.decode: rpn.hip -------------------------------------------------------------------------------------
+// ---- RPN top-k / decode, BoxCoder.decode: rpn.hip; the pyramid checks shared with the RetinaNet entries below ------------------------
 struct ByteRange {
   const void* p;
   long long bytes;
@@ -1230,61 +1230,137 @@ static bool outputs_clear(const ByteRange* outs, int n_out, const ByteRange* ins
   return true;
 }
 
-// The level tables of the three rpn entries: 0 and the totals, or the error.  anchors: sum of a * h * w (< 2^31); taken: sum of
-// min(k, a * h * w) (k < 1: not computed).
-static int rpn_levels_check(const char* op, const int* hs, const int* ws, const int* as, int levels, int k, int64_t* anchors, int64_t* taken) {
+// The rpn and retinanet entries are one set of checks: a pyramid of per-level maps with `classes` logit channels per anchor, the
+// rpn's with one (the two refusals that name the classes cannot fire then).  `op` names the entry in the messages.
+//
+// The level tables: 0 and taken = sum of min(k, a * h * w * classes) (k < 1: not computed), or the error.  The anchors of all
+// levels, sum of a * h * w, times the classes stay below 2^31.
+static int levels_check(const char* op, const int* hs, const int* ws, const int* as, int levels, int classes, int k, int64_t* taken) {
   if (levels < 1 || levels > kMaxRpnLevels)
     return set_error(levels > kMaxRpnLevels ? MV_ERR_UNSUPPORTED : MV_ERR_INVALID_ARGUMENT, "%s: 1 to %d levels per call, got %d", op,
                      kMaxRpnLevels, levels);
   if (!hs || !ws || !as) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null level table", op);
-  int64_t total = 0, take = 0;
+  int64_t anchors = 0;
   for (int l = 0; l < levels; ++l) {
     if (hs[l] < 1 || ws[l] < 1 || as[l] < 1)
       return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape (%d anchors, %d, %d) of level %d", op, as[l], hs[l], ws[l], l);
     const int64_t hw = (int64_t)hs[l] * ws[l];
-    if (hw > 0x7fffffffLL || hw * as[l] > 0x7fffffffLL || (total += hw * as[l]) > 0x7fffffffLL)
+    if (hw > 0x7fffffffLL || hw * as[l] > 0x7fffffffLL || (anchors += hw * as[l]) > 0x7fffffffLL)
       return set_error(MV_ERR_UNSUPPORTED, "%s: the anchors of all levels exceed the 32-bit index", op);
-    take += hw * as[l] < k ? hw * as[l] : k;
   }
-  *anchors = total, *taken = take;
+  if (classes < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: classes must be positive, got %d", op, classes);
+  if (anchors * classes > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld anchors x %d classes exceed the 32-bit index", op, (long long)anchors, classes);
+  *taken = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
+    *taken += nl < k ? nl : k;
+  }
   return MV_OK;
 }
 
+// The bytes of a top-k entry's workspace, the level tables checked (taken: levels_check's).  The rpn's: a 64-bit candidate per
+// index taken; retinanet's: retinanet_plan's.
+typedef int64_t (*TopkBytes)(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k, int64_t taken);
+static int64_t rpn_topk_bytes(int64_t n, const int*, const int*, const int*, int, int, int, int64_t taken) { return (n * taken * 8 + 15) / 16 * 16; }
+static int64_t retinanet_topk_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k, int64_t) {
+  return retinanet_plan(n, hs, ws, as, levels, classes, k).bytes;
+}
+// what the two *_topk_workspace_bytes entries answer: 0 for a call the launch entry refuses
+static int64_t topk_workspace_bytes(const char* op, TopkBytes bytes, int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes,
+                                    int k) {
+  int64_t taken;
+  if (n <= 0 || n > 65535 || k < 1 || k > kRpnMaxK || levels_check(op, hs, ws, as, levels, classes, k, &taken)) return 0;
+  return bytes(n, hs, ws, as, levels, classes, k, taken);
+}
+
+// The arguments of a top-k entry (m: topk_maps), in the order of the refusals: 0 launch, 1 nothing to do, < 0 the error.
+static PyramidMaps topk_maps(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels) {
+  PyramidMaps m = {};
+  m.logits = logits, m.hs = hs, m.ws = ws, m.as = as, m.logit_strides = img_strides, m.levels = levels;
+  return m;
+}
+static int topk_check(const char* op, TopkBytes bytes, const PyramidMaps& m, int classes, int64_t n, int k, const int* idx, const void* workspace,
+                      int64_t workspace_bytes) {
+  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad image count %lld", op, (long long)n);
+  if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: k must be positive, got %d", op, k);
+  int64_t taken;
+  if (int rc = levels_check(op, m.hs, m.ws, m.as, m.levels, classes, k, &taken)) return rc;
+  if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "%s: k up to %d, got %d", op, kRpnMaxK, k);
+  if (n == 0) return 1;
+  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images exceed the launch grid", op, (long long)n);
+  if (!m.logits || !m.logit_strides || !idx) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  const int64_t need = bytes(n, m.hs, m.ws, m.as, m.levels, classes, k, taken);
+  ByteRange ins[kMaxRpnLevels];
+  for (int l = 0; l < m.levels; ++l) {
+    const int64_t nl = (int64_t)m.as[l] * m.hs[l] * m.ws[l] * classes;
+    if (!m.logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+    if (m.logit_strides[l] < nl || m.logit_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of level %d, its map has %lld elements", op,
+                       (long long)m.logit_strides[l], l, (long long)nl);
+    ins[l] = {m.logits[l], ((n - 1) * m.logit_strides[l] + nl) * 4};
+  }
+  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: needs a workspace", op);
+  if (workspace_bytes < need)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: workspace of %lld bytes, need %lld (mv_%s_workspace_bytes)", op, (long long)workspace_bytes,
+                     (long long)need, op);
+  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", op);
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx must be 4-byte aligned", op);
+  const ByteRange outs[2] = {{idx, n * taken * 4}, {workspace, need}};
+  if (!outputs_clear(outs, 2, ins, m.levels))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx and the workspace must not overlap an input or each other", op);
+  return 0;
+}
+
+// The arguments of a decode entry, in the order of the refusals: 0 launch, 1 nothing to do, < 0 the error.  out64 is the int64
+// output, `out64_name` its word in the alignment message.
+static int decode_check(const char* op, const char* out64_name, const PyramidMaps& m, int classes, const float* image_sizes, const int* idx,
+                        int64_t n, int64_t k, const float* boxes, const float* scores, const int64_t* out64, const unsigned char* valid) {
+  if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld, k=%lld", op, (long long)n, (long long)k);
+  int64_t taken;
+  if (int rc = levels_check(op, m.hs, m.ws, m.as, m.levels, classes, 1, &taken)) return rc;
+  if (!m.strides_h || !m.strides_w) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null level table", op);
+  for (int l = 0; l < m.levels; ++l)
+    if (m.strides_h[l] < 0 || m.strides_w[l] < 0 || (int64_t)m.strides_h[l] * m.hs[l] > 0x7fffffffLL ||
+        (int64_t)m.strides_w[l] * m.ws[l] > 0x7fffffffLL)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad strides (%d, %d) of level %d", op, m.strides_h[l], m.strides_w[l], l);
+  if (n == 0 || k == 0) return 1;
+  if (n > 0x7fffffffLL || k > (0x7fffffffLL * 256) / n)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld x %lld candidates exceed the launch grid", op, (long long)n, (long long)k);
+  if (!m.logits || !m.deltas || !m.logit_strides || !m.delta_strides || !m.base_anchors || !image_sizes || !idx || !boxes || !scores || !out64 ||
+      !valid)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  if ((uintptr_t)out64 % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: %s must be 8-byte aligned", op, out64_name);
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx must be 4-byte aligned", op);
+  ByteRange ins[2 * kMaxRpnLevels + 3];
+  int64_t base_rows = 0;
+  for (int l = 0; l < m.levels; ++l) {
+    const int64_t al = (int64_t)m.as[l] * m.hs[l] * m.ws[l], nl = al * classes;
+    const int64_t ls = m.logit_strides[l], ds = m.delta_strides[l];
+    if (!m.logits[l] || !m.deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+    if (ls < nl || ds < 4 * al || ls > 0x7fffffffffffLL / n || ds > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image strides (%lld, %lld) of level %d, its maps have %lld and %lld elements", op,
+                       (long long)ls, (long long)ds, l, (long long)nl, (long long)(4 * al));
+    ins[2 * l] = {m.logits[l], ((n - 1) * ls + nl) * 4};
+    ins[2 * l + 1] = {m.deltas[l], ((n - 1) * ds + 4 * al) * 4};
+    base_rows += m.as[l];
+  }
+  ins[2 * m.levels] = {m.base_anchors, base_rows * 16}, ins[2 * m.levels + 1] = {image_sizes, n * 8}, ins[2 * m.levels + 2] = {idx, n * k * 4};
+  const ByteRange outs[4] = {{boxes, n * k * 16}, {scores, n * k * 4}, {out64, n * k * 8}, {valid, n * k}};
+  if (!outputs_clear(outs, 4, ins, 2 * m.levels + 3))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the outputs must not overlap an input or each other", op);
+  return 0;
+}
+
 int64_t mv_rpn_topk_workspace_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int k) {
-  int64_t anchors, taken;
-  if (n <= 0 || n > 65535 || k < 1 || k > kRpnMaxK || rpn_levels_check("rpn_topk", hs, ws, as, levels, k, &anchors, &taken)) return 0;
-  return (n * taken * 8 + 15) / 16 * 16;
+  return topk_workspace_bytes("rpn_topk", rpn_topk_bytes, n, hs, ws, as, levels, 1, k);
 }
 
 int mv_rpn_topk_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
                     int64_t n, int k, int* idx, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: bad image count %lld", (long long)n);
-  if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: k must be positive, got %d", k);
-  int64_t anchors, taken;
-  if (int rc = rpn_levels_check("rpn_topk", hs, ws, as, levels, k, &anchors, &taken)) return rc;
-  if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "rpn_topk: k up to %d, got %d", kRpnMaxK, k);
-  if (n == 0) return MV_OK;
-  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "rpn_topk: %lld images exceed the launch grid", (long long)n);
-  if (!logits || !img_strides || !idx) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: null pointer");
-  const int64_t need = (n * taken * 8 + 15) / 16 * 16;
-  ByteRange ins[kMaxRpnLevels];
-  for (int l = 0; l < levels; ++l) {
-    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l];
-    if (!logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: null pointer (level %d)", l);
-    if (img_strides[l] < nl || img_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: image stride %lld of level %d, its map has %lld elements", (long long)img_strides[l],
-                       l, (long long)nl);
-    ins[l] = {logits[l], ((n - 1) * img_strides[l] + nl) * 4};
-  }
-  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: needs a workspace");
-  if (workspace_bytes < need)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: workspace of %lld bytes, need %lld (mv_rpn_topk_workspace_bytes)",
-                     (long long)workspace_bytes, (long long)need);
-  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: the workspace must be 16-byte aligned");
-  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: idx must be 4-byte aligned");
-  const ByteRange outs[2] = {{idx, n * taken * 4}, {workspace, need}};
-  if (!outputs_clear(outs, 2, ins, levels)) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_topk: idx and the workspace must not overlap an input or each other");
-  return launch_rpn_topk(logits, hs, ws, as, img_strides, levels, (int)n, k, idx, workspace, (hipStream_t)stream);
+  const PyramidMaps m = topk_maps(logits, hs, ws, as, img_strides, levels);
+  if (int rc = topk_check("rpn_topk", rpn_topk_bytes, m, 1, n, k, idx, workspace, workspace_bytes)) return rc < 0 ? rc : MV_OK;
+  return launch_rpn_topk(m, (int)n, k, idx, workspace, (hipStream_t)stream);
 }
 
 int mv_rpn_decode_f32(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
@@ -1292,39 +1368,10 @@ int mv_rpn_decode_f32(const float* const* logits, const float* const* deltas, co
                       const float* base_anchors, const float* image_sizes, const int* idx, int64_t n, int64_t k, double wx, double wy,
                       double ww, double wh, double clip, double min_size, double score_thresh, float* boxes, float* scores,
                       int64_t* levels_out, unsigned char* valid, void* stream) {
-  if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: bad shape n=%lld, k=%lld", (long long)n, (long long)k);
-  int64_t anchors, taken;
-  if (int rc = rpn_levels_check("rpn_decode", hs, ws, as, levels, 1, &anchors, &taken)) return rc;
-  if (!strides_h || !strides_w) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: null level table");
-  for (int l = 0; l < levels; ++l)
-    if (strides_h[l] < 0 || strides_w[l] < 0 || (int64_t)strides_h[l] * hs[l] > 0x7fffffffLL || (int64_t)strides_w[l] * ws[l] > 0x7fffffffLL)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: bad strides (%d, %d) of level %d", strides_h[l], strides_w[l], l);
-  if (n == 0 || k == 0) return MV_OK;
-  if (n > 0x7fffffffLL || k > (0x7fffffffLL * 256) / n)
-    return set_error(MV_ERR_UNSUPPORTED, "rpn_decode: %lld x %lld candidates exceed the launch grid", (long long)n, (long long)k);
-  if (!logits || !deltas || !logit_strides || !delta_strides || !base_anchors || !image_sizes || !idx || !boxes || !scores || !levels_out || !valid)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: null pointer");
-  if ((uintptr_t)levels_out % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: levels must be 8-byte aligned");
-  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: idx must be 4-byte aligned");
-  ByteRange ins[2 * kMaxRpnLevels + 3];
-  int64_t base_rows = 0;
-  for (int l = 0; l < levels; ++l) {
-    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l];
-    if (!logits[l] || !deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: null pointer (level %d)", l);
-    if (logit_strides[l] < nl || delta_strides[l] < 4 * nl || logit_strides[l] > 0x7fffffffffffLL / n || delta_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: image strides (%lld, %lld) of level %d, its maps have %lld and %lld elements",
-                       (long long)logit_strides[l], (long long)delta_strides[l], l, (long long)nl, (long long)(4 * nl));
-    ins[2 * l] = {logits[l], ((n - 1) * logit_strides[l] + nl) * 4};
-    ins[2 * l + 1] = {deltas[l], ((n - 1) * delta_strides[l] + 4 * nl) * 4};
-    base_rows += as[l];
-  }
-  ins[2 * levels] = {base_anchors, base_rows * 16}, ins[2 * levels + 1] = {image_sizes, n * 8}, ins[2 * levels + 2] = {idx, n * k * 4};
-  const ByteRange outs[4] = {{boxes, n * k * 16}, {scores, n * k * 4}, {levels_out, n * k * 8}, {valid, n * k}};
-  if (!outputs_clear(outs, 4, ins, 2 * levels + 3))
-    return set_error(MV_ERR_INVALID_ARGUMENT, "rpn_decode: the outputs must not overlap an input or each other");
-  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
-  return launch_rpn_decode(logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, base_anchors, image_sizes,
-                           idx, n, k, coef, (float)min_size, (float)score_thresh, boxes, scores, levels_out, valid, (hipStream_t)stream);
+  const PyramidMaps m = {logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, base_anchors};
+  if (int rc = decode_check("rpn_decode", "levels", m, 1, image_sizes, idx, n, k, boxes, scores, levels_out, valid)) return rc < 0 ? rc : MV_OK;
+  return launch_rpn_decode(m, image_sizes, idx, n, k, decode_coef(wx, wy, ww, wh, clip), (float)min_size, (float)score_thresh, boxes, scores,
+                           levels_out, valid, (hipStream_t)stream);
 }
 
 int mv_box_decode_f32(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, double wx, double wy, double ww,
@@ -1336,8 +1383,7 @@ int mv_box_decode_f32(const float* boxes, const float* rel_codes, float* out, in
   if (!boxes || !rel_codes || !out) return set_error(MV_ERR_INVALID_ARGUMENT, "box_decode: null pointer");
   const ByteRange ins[2] = {{boxes, m * 16}, {rel_codes, m * classes * 16}}, outs[1] = {{out, m * classes * 16}};
   if (!outputs_clear(outs, 1, ins, 2)) return set_error(MV_ERR_INVALID_ARGUMENT, "box_decode: the output must not overlap an input");
-  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
-  return launch_box_decode(boxes, rel_codes, out, m, classes, coef, (hipStream_t)stream);
+  return launch_box_decode(boxes, rel_codes, out, m, classes, decode_coef(wx, wy, ww, wh, clip), (hipStream_t)stream);
 }
 
 // ---- RoIHeads.postprocess_detections: roi_heads.hip -----------------------------------------------------------------------------------
@@ -1370,71 +1416,26 @@ int mv_roi_detections_f32(const float* class_logits, int64_t logits_stride, cons
   const ByteRange outs[4] = {{boxes, cells * 16}, {scores, cells * 4}, {labels, cells * 8}, {valid, cells}};
   if (!outputs_clear(outs, 4, ins, 4))
     return set_error(MV_ERR_INVALID_ARGUMENT, "roi_detections: the outputs must not overlap an input or each other");
-  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
-  return launch_roi_detections(class_logits, logits_stride, box_regression, regression_stride, rois, image_sizes, r, classes, n, coef,
-                               (float)score_thresh, (float)min_size, boxes, scores, labels, valid, (hipStream_t)stream);
+  return launch_roi_detections(class_logits, logits_stride, box_regression, regression_stride, rois, image_sizes, r, classes, n,
+                               decode_coef(wx, wy, ww, wh, clip), (float)score_thresh, (float)min_size, boxes, scores, labels, valid,
+                               (hipStream_t)stream);
 }
 
 // ---- RetinaNet threshold + top-k / decode: retinanet.hip -------------------------------------------------------------------------------
-// The level tables of the retinanet entries: rpn_levels_check, and classes >= 1 with anchors * classes < 2^31.  taken: sum of
-// min(k, a * h * w * classes).
-static int retinanet_levels_check(const char* op, const int* hs, const int* ws, const int* as, int levels, int classes, int k,
-                                  int64_t* anchors, int64_t* taken) {
-  int64_t unused;
-  if (int rc = rpn_levels_check(op, hs, ws, as, levels, 1, anchors, &unused)) return rc;
-  if (classes < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: classes must be positive, got %d", op, classes);
-  if (*anchors * classes > 0x7fffffffLL)
-    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld anchors x %d classes exceed the 32-bit index", op, (long long)*anchors, classes);
-  int64_t take = 0;
-  for (int l = 0; l < levels; ++l) {
-    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
-    take += nl < k ? nl : k;
-  }
-  *taken = take;
-  return MV_OK;
-}
-
+// The checks are the rpn's, above (levels_check, topk_check, decode_check), with the class count.
 int mv_retinanet_topk_chunk(void) { return kRetChunk; }
 
 int64_t mv_retinanet_topk_workspace_bytes(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k) {
-  int64_t anchors, taken;
-  if (n <= 0 || n > 65535 || k < 1 || k > kRpnMaxK || retinanet_levels_check("retinanet_topk", hs, ws, as, levels, classes, k, &anchors, &taken))
-    return 0;
-  return retinanet_plan(n, hs, ws, as, levels, classes, k).bytes;
+  return topk_workspace_bytes("retinanet_topk", retinanet_topk_bytes, n, hs, ws, as, levels, classes, k);
 }
 
 int mv_retinanet_topk_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
                           int classes, int64_t n, int k, double score_thresh, int* idx, void* workspace, int64_t workspace_bytes,
                           void* stream) {
-  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: bad image count %lld", (long long)n);
-  if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: k must be positive, got %d", k);
-  int64_t anchors, taken;
-  if (int rc = retinanet_levels_check("retinanet_topk", hs, ws, as, levels, classes, k, &anchors, &taken)) return rc;
-  if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "retinanet_topk: k up to %d, got %d", kRpnMaxK, k);
-  if (n == 0) return MV_OK;
-  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "retinanet_topk: %lld images exceed the launch grid", (long long)n);
-  if (!logits || !img_strides || !idx) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: null pointer");
-  const int64_t need = retinanet_plan(n, hs, ws, as, levels, classes, k).bytes;
-  ByteRange ins[kMaxRpnLevels];
-  for (int l = 0; l < levels; ++l) {
-    const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
-    if (!logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: null pointer (level %d)", l);
-    if (img_strides[l] < nl || img_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: image stride %lld of level %d, its map has %lld elements",
-                       (long long)img_strides[l], l, (long long)nl);
-    ins[l] = {logits[l], ((n - 1) * img_strides[l] + nl) * 4};
-  }
-  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: needs a workspace");
-  if (workspace_bytes < need)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: workspace of %lld bytes, need %lld (mv_retinanet_topk_workspace_bytes)",
-                     (long long)workspace_bytes, (long long)need);
-  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: the workspace must be 16-byte aligned");
-  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: idx must be 4-byte aligned");
-  const ByteRange outs[2] = {{idx, n * taken * 4}, {workspace, need}};
-  if (!outputs_clear(outs, 2, ins, levels))
-    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_topk: idx and the workspace must not overlap an input or each other");
-  return launch_retinanet_topk(logits, hs, ws, as, img_strides, levels, classes, (int)n, k, (float)score_thresh, idx, workspace,
-                               (hipStream_t)stream);
+  const PyramidMaps m = topk_maps(logits, hs, ws, as, img_strides, levels);
+  if (int rc = topk_check("retinanet_topk", retinanet_topk_bytes, m, classes, n, k, idx, workspace, workspace_bytes))
+    return rc < 0 ? rc : MV_OK;
+  return launch_retinanet_topk(m, classes, (int)n, k, (float)score_thresh, idx, workspace, (hipStream_t)stream);
 }
 
 int mv_retinanet_decode_f32(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
@@ -1442,39 +1443,11 @@ int mv_retinanet_decode_f32(const float* const* logits, const float* const* delt
                             int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
                             int64_t k, double wx, double wy, double ww, double wh, double clip, float* boxes, float* scores,
                             int64_t* labels, unsigned char* valid, void* stream) {
-  if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: bad shape n=%lld, k=%lld", (long long)n, (long long)k);
-  int64_t anchors, taken;
-  if (int rc = retinanet_levels_check("retinanet_decode", hs, ws, as, levels, classes, 1, &anchors, &taken)) return rc;
-  if (!strides_h || !strides_w) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: null level table");
-  for (int l = 0; l < levels; ++l)
-    if (strides_h[l] < 0 || strides_w[l] < 0 || (int64_t)strides_h[l] * hs[l] > 0x7fffffffLL || (int64_t)strides_w[l] * ws[l] > 0x7fffffffLL)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: bad strides (%d, %d) of level %d", strides_h[l], strides_w[l], l);
-  if (n == 0 || k == 0) return MV_OK;
-  if (n > 0x7fffffffLL || k > (0x7fffffffLL * 256) / n)
-    return set_error(MV_ERR_UNSUPPORTED, "retinanet_decode: %lld x %lld candidates exceed the launch grid", (long long)n, (long long)k);
-  if (!logits || !deltas || !logit_strides || !delta_strides || !base_anchors || !image_sizes || !idx || !boxes || !scores || !labels || !valid)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: null pointer");
-  if ((uintptr_t)labels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: labels must be 8-byte aligned");
-  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: idx must be 4-byte aligned");
-  ByteRange ins[2 * kMaxRpnLevels + 3];
-  int64_t base_rows = 0;
-  for (int l = 0; l < levels; ++l) {
-    const int64_t al = (int64_t)as[l] * hs[l] * ws[l], nl = al * classes;
-    if (!logits[l] || !deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: null pointer (level %d)", l);
-    if (logit_strides[l] < nl || delta_strides[l] < 4 * al || logit_strides[l] > 0x7fffffffffffLL / n || delta_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: image strides (%lld, %lld) of level %d, its maps have %lld and %lld elements",
-                       (long long)logit_strides[l], (long long)delta_strides[l], l, (long long)nl, (long long)(4 * al));
-    ins[2 * l] = {logits[l], ((n - 1) * logit_strides[l] + nl) * 4};
-    ins[2 * l + 1] = {deltas[l], ((n - 1) * delta_strides[l] + 4 * al) * 4};
-    base_rows += as[l];
-  }
-  ins[2 * levels] = {base_anchors, base_rows * 16}, ins[2 * levels + 1] = {image_sizes, n * 8}, ins[2 * levels + 2] = {idx, n * k * 4};
-  const ByteRange outs[4] = {{boxes, n * k * 16}, {scores, n * k * 4}, {labels, n * k * 8}, {valid, n * k}};
-  if (!outputs_clear(outs, 4, ins, 2 * levels + 3))
-    return set_error(MV_ERR_INVALID_ARGUMENT, "retinanet_decode: the outputs must not overlap an input or each other");
-  const float coef[5] = {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
-  return launch_retinanet_decode(logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, classes,
-                                 base_anchors, image_sizes, idx, n, k, coef, boxes, scores, labels, valid, (hipStream_t)stream);
+  const PyramidMaps m = {logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, base_anchors};
+  if (int rc = decode_check("retinanet_decode", "labels", m, classes, image_sizes, idx, n, k, boxes, scores, labels, valid))
+    return rc < 0 ? rc : MV_OK;
+  return launch_retinanet_decode(m, classes, image_sizes, idx, n, k, decode_coef(wx, wy, ww, wh, clip), boxes, scores, labels, valid,
+                                 (hipStream_t)stream);
 }
 
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------

@@ -1,18 +1,15 @@
 // mv_boxcoder.h -- BoxCoder.decode_single (_utils.py) as one device function, shared by rpn.hip (k_rpn_decode, k_box_decode),
 // roi_heads.hip (k_roi_detections) and retinanet.hip (k_retinanet_decode); the anchor of a flat index, built in registers from the
-// level tables (anchor_at), and the sigmoid (sigmoid_cr), shared by k_rpn_decode and k_retinanet_decode.  Every float operation is written with __f*_rn: the reference is a chain of float32 torch ops,
-// one rounding each, never an fma.  exp is the CORRECTLY ROUNDED float32 exp, (float)exp((double)v): torch's CPU exp is a 1-ulp
-// vector routine whose bits no other implementation reproduces, so the library states the one value that does not depend on an
-// implementation (mi355vision.h, mv_rpn_decode_f32).
+// level tables (anchor_at), the sigmoid (sigmoid_cr) and the decode of one candidate of a pyramid (PyramidDecode, decode_candidate),
+// shared by k_rpn_decode and k_retinanet_decode.  Every float operation is written with __f*_rn: the reference is a chain of float32
+// torch ops, one rounding each, never an fma.  exp is the CORRECTLY ROUNDED float32 exp, (float)exp((double)v): torch's CPU exp is a
+// 1-ulp vector routine whose bits no other implementation reproduces, so the library states the one value that does not depend on
+// an implementation (mi355vision.h, mv_rpn_decode_f32).
 #pragma once
 
 #include "mv_common.h"
 
 namespace mv {
-
-struct DecodeCoef {
-  float wx, wy, ww, wh, clip;
-};
 
 __device__ inline float exp_cr(float v) { return (float)exp((double)v); }
 
@@ -46,15 +43,39 @@ struct AnchorLevels {
   int levels, total;            // total: anchors of all levels
   const float* base_anchors;
 };
-inline void fill_anchor_levels(AnchorLevels& t, const int* hs, const int* ws, const int* as, const int* strides_h, const int* strides_w,
-                               int levels, const float* base_anchors) {
+inline void fill_anchor_levels(AnchorLevels& t, const PyramidMaps& m) {
   int start = 0, base = 0;
-  for (int l = 0; l < levels; ++l) {
-    t.h[l] = hs[l], t.w[l] = ws[l], t.a[l] = as[l], t.start[l] = start, t.base_off[l] = base;
-    t.stride_h[l] = strides_h[l], t.stride_w[l] = strides_w[l];
-    start += as[l] * hs[l] * ws[l], base += as[l];
+  for (int l = 0; l < m.levels; ++l) {
+    t.h[l] = m.hs[l], t.w[l] = m.ws[l], t.a[l] = m.as[l], t.start[l] = start, t.base_off[l] = base;
+    t.stride_h[l] = m.strides_h[l], t.stride_w[l] = m.strides_w[l];
+    start += m.as[l] * m.hs[l] * m.ws[l], base += m.as[l];
   }
-  t.levels = levels, t.total = start, t.base_anchors = base_anchors;
+  t.levels = m.levels, t.total = start, t.base_anchors = m.base_anchors;
+}
+
+// What k_rpn_decode and k_retinanet_decode take alike, by value in the kernel arguments: the head's maps (logit channel
+// a * classes + c, delta channels 4 a .. 4 a + 3 of anchor a), the pyramid, the n * k candidates and the outputs both write.
+struct PyramidDecode {
+  const float* logits[kMaxRpnLevels];
+  const float* deltas[kMaxRpnLevels];
+  long long logit_stride[kMaxRpnLevels], delta_stride[kMaxRpnLevels];
+  AnchorLevels lv;
+  int classes;  // the rpn: 1
+  const float* image_sizes;
+  const int* idx;
+  long long count, k;  // n * k candidates
+  DecodeCoef coef;
+  float* boxes;
+  float* scores;
+  unsigned char* valid;
+};
+inline void fill_pyramid_decode(PyramidDecode& p, const PyramidMaps& m, int classes, const float* image_sizes, const int* idx, int64_t n,
+                                int64_t k, const DecodeCoef& coef, float* boxes, float* scores, unsigned char* valid) {
+  for (int l = 0; l < m.levels; ++l)
+    p.logits[l] = m.logits[l], p.deltas[l] = m.deltas[l], p.logit_stride[l] = m.logit_strides[l], p.delta_stride[l] = m.delta_strides[l];
+  fill_anchor_levels(p.lv, m);
+  p.classes = classes, p.image_sizes = image_sizes, p.idx = idx, p.count = n * k, p.k = k, p.coef = coef;
+  p.boxes = boxes, p.scores = scores, p.valid = valid;
 }
 
 // Anchor v (0 <= v < T.total) of the concatenated (y, x, a) layout: its level, its anchor a and position s = y W + x in the level's
@@ -78,6 +99,45 @@ __device__ inline AnchorAt anchor_at(const AnchorLevels& T, int v) {
   const float* const b = T.base_anchors + (size_t)(base_off + a) * 4;
   const float fx = (float)(x * sw), fy = (float)(y * sh);  // the reference's int32 shifts, converted as its int + float add does
   return {level, a, s, (size_t)H * W, __fadd_rn(fx, b[0]), __fadd_rn(fy, b[1]), __fadd_rn(fx, b[2]), __fadd_rn(fy, b[3])};
+}
+
+// Candidate t of P (0 <= t < P.count), flat index f = P.idx[t] = anchor * classes + class.  in_pyramid: f is a candidate of this
+// pyramid (f >= 0 and its anchor not past the last); a kernel reads nothing but the index for one that is not.  decode_candidate,
+// for one that is: its level, its class, its logit and decode_single of its anchor with its four deltas, clipped to its image.
+// CLASSES: the class count where the kernel knows it (the rpn's 1: no division is left), 0 = P.classes.
+struct Candidate {
+  int level, label;
+  float logit, box[4];
+};
+template <int CLASSES>
+__device__ inline bool in_pyramid(const PyramidDecode& P, long long t) {
+  const int K = CLASSES ? CLASSES : P.classes;
+  const int f = P.idx[t];
+  return f >= 0 && f / K < P.lv.total;
+}
+template <int CLASSES>
+__device__ inline Candidate decode_candidate(const PyramidDecode& P, long long t) {
+  Candidate out;
+  const int K = CLASSES ? CLASSES : P.classes;
+  const long long img = t / P.k;
+  const int f = P.idx[t];
+  const int v = f / K, c = f - v * K;
+  const AnchorAt an = anchor_at(P.lv, v);
+  const float* lg = nullptr;
+  const float* dl = nullptr;
+  long long ls = 0, ds = 0;
+#pragma unroll
+  for (int l = 0; l < kMaxRpnLevels; ++l)
+    if (l == an.level) lg = P.logits[l], dl = P.deltas[l], ls = P.logit_stride[l], ds = P.delta_stride[l];
+  const size_t hw = an.hw;
+  out.level = an.level, out.label = c;
+  out.logit = lg[(size_t)img * ls + ((size_t)an.a * K + c) * hw + an.s];
+  const float* const d = dl + (size_t)img * ds + (size_t)(4 * an.a) * hw + an.s;
+  decode_single(an.x1, an.y1, an.x2, an.y2, d[0], d[hw], d[2 * hw], d[3 * hw], P.coef, out.box);
+  const float ih = P.image_sizes[img * 2], iw = P.image_sizes[img * 2 + 1];
+  out.box[0] = clamp0(out.box[0], iw), out.box[1] = clamp0(out.box[1], ih);
+  out.box[2] = clamp0(out.box[2], iw), out.box[3] = clamp0(out.box[3], ih);
+  return out;
 }
 
 }  // namespace mv

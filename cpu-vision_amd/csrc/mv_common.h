@@ -319,39 +319,48 @@ bool masks_to_boxes_grid_fits(int64_t n, int h);
 int launch_masks_to_boxes(const void* masks, bool f32, float* boxes, int* empty_flag, int64_t n, int h, int w, void* workspace,
                           hipStream_t s);
 // RegionProposalNetwork's top-k and decode, BoxCoder.decode (rpn.hip; semantics in mi355vision.h mv_rpn_topk_f32 and below).  The
-// entry points have checked the arguments, the extents, the workspace and the grids; the tables are HOST arrays of `levels` <=
-// kMaxRpnLevels entries, copied into the kernel arguments; coef5 = {wx, wy, ww, wh, clip} as floats.
+// entry points have checked the arguments, the extents, the workspace and the grids.
 constexpr int kMaxRpnLevels = 8;
 constexpr int kRpnMaxK = 4096;  // the candidates of a level are ranked pairwise: k^2 comparisons per (image, level)
-int launch_rpn_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels, int n,
-                    int k, int* idx, void* workspace, hipStream_t s);
-int launch_rpn_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
-                      const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w, int levels,
-                      const float* base_anchors, const float* image_sizes, const int* idx, int64_t n, int64_t k, const float* coef5,
-                      float min_size, float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid,
-                      hipStream_t s);
-int launch_box_decode(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, const float* coef5, hipStream_t s);
+// A head's per-level NCHW maps as the rpn and retinanet entry points receive them: HOST arrays of `levels` <= kMaxRpnLevels
+// entries, copied into the kernel arguments.  The top-k launchers read logits, hs, ws, as and logit_strides; the rest is null there.
+struct PyramidMaps {
+  const float* const* logits;
+  const float* const* deltas;
+  const int *hs, *ws, *as;
+  const int64_t *logit_strides, *delta_strides;  // elements between the images of a level's map
+  const int *strides_h, *strides_w;              // the anchor grid's steps
+  int levels;
+  const float* base_anchors;  // DEVICE: the (sum of as, 4) cell anchors, level after level
+};
+// BoxCoder's weights and clip as the kernels take them (decode_single, mv_boxcoder.h)
+struct DecodeCoef {
+  float wx, wy, ww, wh, clip;
+};
+inline DecodeCoef decode_coef(double wx, double wy, double ww, double wh, double clip) {
+  return {(float)wx, (float)wy, (float)ww, (float)wh, (float)clip};
+}
+int launch_rpn_topk(const PyramidMaps& m, int n, int k, int* idx, void* workspace, hipStream_t s);
+int launch_rpn_decode(const PyramidMaps& m, const float* image_sizes, const int* idx, int64_t n, int64_t k, const DecodeCoef& coef, float min_size,
+                      float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid, hipStream_t s);
+int launch_box_decode(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, const DecodeCoef& coef, hipStream_t s);
 // RoIHeads.postprocess_detections up to the per-image filters (roi_heads.hip; semantics in mi355vision.h mv_roi_detections_f32).  The
 // entry point has checked the arguments, the extents and the grid; r and n are positive, 2 <= classes <= kRoiMaxClasses.
 constexpr int kRoiMaxClasses = 2048;  // a workgroup parks four rows of exponentials in LDS: 32 KiB at this size
 int launch_roi_detections(const float* logits, int64_t logit_stride, const float* deltas, int64_t delta_stride, const float* rois,
-                          const float* image_sizes, int64_t r, int classes, int64_t n, const float* coef5, float score_thresh, float min_size,
+                          const float* image_sizes, int64_t r, int classes, int64_t n, const DecodeCoef& coef, float score_thresh, float min_size,
                           float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
 // RetinaNet's threshold + top-k and decode (retinanet.hip; semantics in mi355vision.h mv_retinanet_topk_f32 and below).  The entry
-// points have checked the arguments, the extents, the workspace and the grids; the tables are as for the rpn launchers.
+// points have checked the arguments, the extents, the workspace and the grids; PyramidMaps is as for the rpn launchers.
 constexpr int kRetChunk = 16384;  // elements of an (image, level) map per stage-1 workgroup: 16 per thread, in registers
 struct RetinanetPlan {           // the workspace of launch_retinanet_topk: counts, then per image the pools of its levels
   int64_t chunks[kMaxRpnLevels], pool_start[kMaxRpnLevels];
   int64_t total_chunks, pool_per_image, counts_bytes, bytes;
 };
 RetinanetPlan retinanet_plan(int64_t n, const int* hs, const int* ws, const int* as, int levels, int classes, int k);
-int launch_retinanet_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
-                          int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s);
-int launch_retinanet_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
-                            const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w,
-                            int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
-                            int64_t k, const float* coef5, float* boxes, float* scores, int64_t* labels, unsigned char* valid,
-                            hipStream_t s);
+int launch_retinanet_topk(const PyramidMaps& m, int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s);
+int launch_retinanet_decode(const PyramidMaps& m, int classes, const float* image_sizes, const int* idx, int64_t n, int64_t k,
+                            const DecodeCoef& coef, float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
 // F.interpolate(bilinear) and the detection transform's fused normalize + resize + batch (interp.hip; semantics in mi355vision.h
 // mv_interpolate_bilinear_f32, mv_detection_batch_f32).  The tables are HOST arrays of n <= kMaxDetImages entries, copied into the kernel
 // arguments; mean / stdv: c <= 16 host floats, or both null (no normalisation).  The entry points have checked the arguments, the

@@ -19,8 +19,8 @@
 // select_keys          radix select of the k-th greatest key, 8 bits per pass from the top, a 256-bin histogram in LDS per pass
 //                      (hist_add of k_rpn_topk).  It stops as soon as the answer is known: after the first pass when at most k
 //                      keys pass at all, after any pass when the bin of the k-th key is taken whole; at most 8 passes.
-// k_retinanet_decode   one lane per idx[i, j]: anchor f / K and label f % K, the anchor in registers (anchor_at of mv_boxcoder.h,
-//                      shared with k_rpn_decode), decode_single, clip to the image, the score recomputed.
+// k_retinanet_decode   one lane per idx[i, j]: anchor f / K and label f % K, the anchor in registers, decode_single, clip to the
+//                      image (decode_candidate of mv_boxcoder.h, shared with k_rpn_decode), the score recomputed.
 //
 // Every float operation is written with __f*_rn and exp is the correctly rounded float32 exp, as in rpn.hip.
 #include "mv_boxcoder.h"
@@ -219,51 +219,20 @@ __global__ __launch_bounds__(kRetThreads) void k_retinanet_rank(const RetTopkArg
   }
 }
 
-struct RetDecodeArgs {
-  const float* logits[kMaxRpnLevels];
-  const float* deltas[kMaxRpnLevels];
-  long long logit_stride[kMaxRpnLevels], delta_stride[kMaxRpnLevels];
-  AnchorLevels lv;
-  int classes;
-  const float* image_sizes;
-  const int* idx;
-  long long count, k;  // n * k candidates
-  DecodeCoef coef;
-  float* boxes;
-  float* scores;
-  long long* labels;
-  unsigned char* valid;
-};
-
-__global__ __launch_bounds__(256) void k_retinanet_decode(const RetDecodeArgs R) {
+// amdgpu_waves_per_eu(8): left alone the compiler keeps the tables of all eight levels in 102 SGPRs, which leaves a SIMD 7 waves
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_retinanet_decode(const PyramidDecode P, long long* labels) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= R.count) return;
-  const long long img = t / R.k;
-  const int f = R.idx[t];
-  if (f < 0 || f / R.classes >= R.lv.total) {  // not a candidate of this pyramid (the -1 padding): nothing is read for it
-    for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = 0.f;
-    R.scores[t] = 0.f, R.labels[t] = 0, R.valid[t] = 0;
+  if (t >= P.count) return;
+  if (!in_pyramid<0>(P, t)) {  // not a candidate of this pyramid (the -1 padding): nothing is read for it
+    for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = 0.f;
+    P.scores[t] = 0.f, labels[t] = 0, P.valid[t] = 0;
     return;
   }
-  const int v = f / R.classes, c = f - v * R.classes;
-  const AnchorAt an = anchor_at(R.lv, v);
-  const float* lg = nullptr;
-  const float* dl = nullptr;
-  long long ls = 0, ds = 0;
-#pragma unroll
-  for (int l = 0; l < kMaxRpnLevels; ++l)
-    if (l == an.level) lg = R.logits[l], dl = R.deltas[l], ls = R.logit_stride[l], ds = R.delta_stride[l];
-  const size_t hw = an.hw;
-  const float logit = lg[(size_t)img * ls + ((size_t)an.a * R.classes + c) * hw + an.s];
-  const float* const d = dl + (size_t)img * ds + (size_t)(4 * an.a) * hw + an.s;
-  float box[4];
-  decode_single(an.x1, an.y1, an.x2, an.y2, d[0], d[hw], d[2 * hw], d[3 * hw], R.coef, box);
-  const float ih = R.image_sizes[img * 2], iw = R.image_sizes[img * 2 + 1];
-  box[0] = clamp0(box[0], iw), box[1] = clamp0(box[1], ih), box[2] = clamp0(box[2], iw), box[3] = clamp0(box[3], ih);
-  for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = box[q];
-  R.scores[t] = sigmoid_cr(logit);
-  R.labels[t] = c;
-  R.valid[t] = 1;
+  const Candidate c = decode_candidate<0>(P, t);
+  for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = c.box[q];
+  P.scores[t] = sigmoid_cr(c.logit);
+  labels[t] = c.label;
+  P.valid[t] = 1;
 }
 
 }  // namespace
@@ -285,14 +254,14 @@ RetinanetPlan retinanet_plan(int64_t n, const int* hs, const int* ws, const int*
   return p;
 }
 
-int launch_retinanet_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
-                          int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s) {
+int launch_retinanet_topk(const PyramidMaps& m, int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s) {
+  const int *const hs = m.hs, *const ws = m.ws, *const as = m.as, levels = m.levels;
   const RetinanetPlan plan = retinanet_plan(n, hs, ws, as, levels, classes, k);
   RetTopkArgs t = {};
   int start = 0, out = 0, chunk = 0;
   for (int l = 0; l < levels; ++l) {
     const int64_t nl = (int64_t)as[l] * hs[l] * ws[l] * classes;
-    t.logits[l] = logits[l], t.img_stride[l] = img_strides[l], t.hw[l] = hs[l] * ws[l], t.a[l] = as[l];
+    t.logits[l] = m.logits[l], t.img_stride[l] = m.logit_strides[l], t.hw[l] = hs[l] * ws[l], t.a[l] = as[l];
     t.level_start[l] = start, t.chunk_start[l] = chunk, t.pool_start[l] = plan.pool_start[l], t.out_start[l] = out;
     t.seg[l] = nl < k ? (int)nl : k;
     start += as[l] * hs[l] * ws[l], out += t.seg[l], chunk += (int)plan.chunks[l];
@@ -316,20 +285,12 @@ int launch_retinanet_topk(const float* const* logits, const int* hs, const int* 
   return check_launchf("k_retinanet_rank<levels%d,k%d>", levels, k);
 }
 
-int launch_retinanet_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
-                            const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w,
-                            int levels, int classes, const float* base_anchors, const float* image_sizes, const int* idx, int64_t n,
-                            int64_t k, const float* coef5, float* boxes, float* scores, int64_t* labels, unsigned char* valid,
-                            hipStream_t s) {
-  RetDecodeArgs r = {};
-  for (int l = 0; l < levels; ++l)
-    r.logits[l] = logits[l], r.deltas[l] = deltas[l], r.logit_stride[l] = logit_strides[l], r.delta_stride[l] = delta_strides[l];
-  fill_anchor_levels(r.lv, hs, ws, as, strides_h, strides_w, levels, base_anchors);
-  r.classes = classes, r.image_sizes = image_sizes, r.idx = idx, r.count = n * k, r.k = k;
-  r.coef = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
-  r.boxes = boxes, r.scores = scores, r.labels = reinterpret_cast<long long*>(labels), r.valid = valid;
-  hipLaunchKernelGGL(k_retinanet_decode, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r);
-  return check_launchf("k_retinanet_decode<levels%d>", levels);
+int launch_retinanet_decode(const PyramidMaps& m, int classes, const float* image_sizes, const int* idx, int64_t n, int64_t k,
+                            const DecodeCoef& coef, float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s) {
+  PyramidDecode p = {};
+  fill_pyramid_decode(p, m, classes, image_sizes, idx, n, k, coef, boxes, scores, valid);
+  hipLaunchKernelGGL(k_retinanet_decode, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, reinterpret_cast<long long*>(labels));
+  return check_launchf("k_retinanet_decode<levels%d>", m.levels);
 }
 
 }  // namespace mv

@@ -115,12 +115,11 @@ __global__ __launch_bounds__(kRoiWaves* kWave) void k_roi_detections(const RoiDe
 }  // namespace
 
 int launch_roi_detections(const float* logits, int64_t logit_stride, const float* deltas, int64_t delta_stride, const float* rois,
-                          const float* image_sizes, int64_t r, int classes, int64_t n, const float* coef5, float score_thresh, float min_size,
+                          const float* image_sizes, int64_t r, int classes, int64_t n, const DecodeCoef& coef, float score_thresh, float min_size,
                           float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s) {
   RoiDetArgs a = {};
   a.logits = logits, a.deltas = deltas, a.rois = rois, a.image_sizes = image_sizes;
-  a.logit_stride = logit_stride, a.delta_stride = delta_stride, a.r = r, a.n = n, a.classes = classes;
-  a.coef = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
+  a.logit_stride = logit_stride, a.delta_stride = delta_stride, a.r = r, a.n = n, a.classes = classes, a.coef = coef;
   a.score_thresh = score_thresh, a.min_size = min_size;
   a.boxes = boxes, a.scores = scores, a.labels = reinterpret_cast<long long*>(labels), a.valid = valid;
   const unsigned blocks = (unsigned)((r + kRoiWaves - 1) / kRoiWaves);

@@ -163,53 +163,22 @@ __global__ __launch_bounds__(kTopkThreads) void k_rpn_topk(const TopkArgs T) {
   }
 }
 
-// ---- BoxCoder.decode_single: mv_boxcoder.h (shared with roi_heads.hip) --------------------------------------------------------------
-struct RpnDecodeArgs {
-  const float* logits[kMaxRpnLevels];
-  const float* deltas[kMaxRpnLevels];
-  long long logit_stride[kMaxRpnLevels], delta_stride[kMaxRpnLevels];
-  AnchorLevels lv;
-  const float* image_sizes;
-  const int* idx;
-  long long count, k;           // n * k candidates
-  DecodeCoef coef;
-  float min_size, score_thresh;
-  float* boxes;
-  float* scores;
-  long long* levels_out;
-  unsigned char* valid;
-};
-
-__global__ __launch_bounds__(256) void k_rpn_decode(const RpnDecodeArgs R) {
+// ---- the decode of a candidate: decode_candidate of mv_boxcoder.h (shared with retinanet.hip), here with one class -----------------
+__global__ __launch_bounds__(256) void k_rpn_decode(const PyramidDecode P, long long* levels_out, float min_size, float score_thresh) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= R.count) return;
-  const long long img = t / R.k;
-  const int v = R.idx[t];
-  if (v < 0 || v >= R.lv.total) {  // not an anchor of this pyramid: nothing is read for it
-    for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = 0.f;
-    R.scores[t] = 0.f, R.levels_out[t] = -1, R.valid[t] = 0;
+  if (t >= P.count) return;
+  if (!in_pyramid<1>(P, t)) {  // not an anchor of this pyramid: nothing is read for it
+    for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = 0.f;
+    P.scores[t] = 0.f, levels_out[t] = -1, P.valid[t] = 0;
     return;
   }
-  const AnchorAt an = anchor_at(R.lv, v);
-  const float* lg = nullptr;
-  const float* dl = nullptr;
-  long long ls = 0, ds = 0;
-#pragma unroll
-  for (int l = 0; l < kMaxRpnLevels; ++l)
-    if (l == an.level) lg = R.logits[l], dl = R.deltas[l], ls = R.logit_stride[l], ds = R.delta_stride[l];
-  const size_t hw = an.hw;
-  const float logit = lg[(size_t)img * ls + (size_t)an.a * hw + an.s];
-  const float* const d = dl + (size_t)img * ds + (size_t)(4 * an.a) * hw + an.s;
-  float box[4];
-  decode_single(an.x1, an.y1, an.x2, an.y2, d[0], d[hw], d[2 * hw], d[3 * hw], R.coef, box);
-  const float ih = R.image_sizes[img * 2], iw = R.image_sizes[img * 2 + 1];
-  box[0] = clamp0(box[0], iw), box[1] = clamp0(box[1], ih), box[2] = clamp0(box[2], iw), box[3] = clamp0(box[3], ih);
-  const float score = sigmoid_cr(logit);
-  const float bw = __fsub_rn(box[2], box[0]), bh = __fsub_rn(box[3], box[1]);
-  for (int q = 0; q < 4; ++q) R.boxes[t * 4 + q] = box[q];
-  R.scores[t] = score;
-  R.levels_out[t] = an.level;
-  R.valid[t] = (bw >= R.min_size && bh >= R.min_size && score >= R.score_thresh) ? 1 : 0;
+  const Candidate c = decode_candidate<1>(P, t);
+  const float score = sigmoid_cr(c.logit);
+  const float bw = __fsub_rn(c.box[2], c.box[0]), bh = __fsub_rn(c.box[3], c.box[1]);
+  for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = c.box[q];
+  P.scores[t] = score;
+  levels_out[t] = c.level;
+  P.valid[t] = (bw >= min_size && bh >= min_size && score >= score_thresh) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void k_box_decode(const float* __restrict__ boxes, const float* __restrict__ codes, float* __restrict__ out,
@@ -226,42 +195,32 @@ __global__ __launch_bounds__(256) void k_box_decode(const float* __restrict__ bo
 
 }  // namespace
 
-int launch_rpn_topk(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels, int n,
-                    int k, int* idx, void* workspace, hipStream_t s) {
+int launch_rpn_topk(const PyramidMaps& m, int n, int k, int* idx, void* workspace, hipStream_t s) {
   TopkArgs t = {};
   int start = 0, out = 0;
-  for (int l = 0; l < levels; ++l) {
-    const int nl = as[l] * hs[l] * ws[l];
-    t.logits[l] = logits[l], t.img_stride[l] = img_strides[l], t.hw[l] = hs[l] * ws[l], t.a[l] = as[l];
+  for (int l = 0; l < m.levels; ++l) {
+    const int nl = m.as[l] * m.hs[l] * m.ws[l];
+    t.logits[l] = m.logits[l], t.img_stride[l] = m.logit_strides[l], t.hw[l] = m.hs[l] * m.ws[l], t.a[l] = m.as[l];
     t.level_start[l] = start, t.out_start[l] = out, t.take[l] = nl < k ? nl : k;
     start += nl, out += t.take[l];
   }
   t.idx = idx, t.cand = static_cast<u64*>(workspace), t.k_total = out;
-  hipLaunchKernelGGL(k_rpn_topk, dim3(levels, n), dim3(kTopkThreads), 0, s, t);
-  return check_launchf("k_rpn_topk<levels%d,k%d>", levels, k);
+  hipLaunchKernelGGL(k_rpn_topk, dim3(m.levels, n), dim3(kTopkThreads), 0, s, t);
+  return check_launchf("k_rpn_topk<levels%d,k%d>", m.levels, k);
 }
 
-int launch_rpn_decode(const float* const* logits, const float* const* deltas, const int* hs, const int* ws, const int* as,
-                      const int64_t* logit_strides, const int64_t* delta_strides, const int* strides_h, const int* strides_w, int levels,
-                      const float* base_anchors, const float* image_sizes, const int* idx, int64_t n, int64_t k, const float* coef5,
-                      float min_size, float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid,
-                      hipStream_t s) {
-  RpnDecodeArgs r = {};
-  for (int l = 0; l < levels; ++l)
-    r.logits[l] = logits[l], r.deltas[l] = deltas[l], r.logit_stride[l] = logit_strides[l], r.delta_stride[l] = delta_strides[l];
-  fill_anchor_levels(r.lv, hs, ws, as, strides_h, strides_w, levels, base_anchors);
-  r.image_sizes = image_sizes, r.idx = idx, r.count = n * k, r.k = k;
-  r.coef = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
-  r.min_size = min_size, r.score_thresh = score_thresh;
-  r.boxes = boxes, r.scores = scores, r.levels_out = reinterpret_cast<long long*>(levels_out), r.valid = valid;
-  hipLaunchKernelGGL(k_rpn_decode, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r);
-  return check_launchf("k_rpn_decode<levels%d>", levels);
+int launch_rpn_decode(const PyramidMaps& m, const float* image_sizes, const int* idx, int64_t n, int64_t k, const DecodeCoef& coef, float min_size,
+                      float score_thresh, float* boxes, float* scores, int64_t* levels_out, unsigned char* valid, hipStream_t s) {
+  PyramidDecode p = {};
+  fill_pyramid_decode(p, m, 1, image_sizes, idx, n, k, coef, boxes, scores, valid);
+  hipLaunchKernelGGL(k_rpn_decode, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, reinterpret_cast<long long*>(levels_out), min_size,
+                     score_thresh);
+  return check_launchf("k_rpn_decode<levels%d>", m.levels);
 }
 
-int launch_box_decode(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, const float* coef5, hipStream_t s) {
-  const DecodeCoef k = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
+int launch_box_decode(const float* boxes, const float* rel_codes, float* out, int64_t m, int classes, const DecodeCoef& coef, hipStream_t s) {
   const long long count = (long long)m * classes;
-  hipLaunchKernelGGL(k_box_decode, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, boxes, rel_codes, out, count, classes, k);
+  hipLaunchKernelGGL(k_box_decode, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, boxes, rel_codes, out, count, classes, coef);
   return check_launch("k_box_decode");
 }
 

@@ -1,6 +1,7 @@
 """Shared helpers for the test-suite: seeded inputs, golden loading, the parity tolerance."""
 from __future__ import annotations
 
+import ctypes as C
 from functools import lru_cache
 from pathlib import Path
 
@@ -21,6 +22,23 @@ def philox_u8(seed: int, shape) -> np.ndarray:
 @lru_cache(maxsize=None)
 def golden(name: str):
     return np.load(GOLDEN / f"{name}.npz", allow_pickle=False)
+
+
+# ---- host tables for calls into the C ABI (tests/test_rpn_host.py, tests/test_retinanet_host.py) -------------------------------------
+def c_ints(*v):
+    return (C.c_int * len(v))(*v)
+
+
+def c_i64s(*v):
+    return (C.c_int64 * len(v))(*v)
+
+
+def c_ptrs(*arrays):
+    """A table of pointers: each entry a numpy array (its data), an address or None."""
+    t = (C.c_void_p * len(arrays))()
+    for i, a in enumerate(arrays):
+        t[i] = a if a is None or isinstance(a, int) else a.ctypes.data
+    return t
 
 
 def conv_tol(ref: np.ndarray, w_abs_sum: float, x_abs_max: float, rel: float = 1e-5, floor: float = 1e-6):

@@ -2,7 +2,6 @@
 version-1 key renaming, defaults and argument errors, the paths that are not built, every refusal of mv_retinanet_topk_f32 /
 mv_retinanet_decode_f32 with host pointers (refusals come before any launch), the Python-side checks, and the two references of
 tests/_retinanet_ref.py against each other."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -15,6 +14,8 @@ from cpu_vision_amd import functional as F
 from tests import _fpn_ref as PF
 from tests import _retinanet_ref as R
 from tests import _rpn_ref as P
+from tests import test_rpn_host as RH  # its fixtures and refusal tables, for the comparison of the two families
+from tests._util import c_i64s as _i64s, c_ints as _ints, c_ptrs as _ptrs
 
 
 def _equal_state(a, b):
@@ -212,32 +213,18 @@ INVALID, UNSUPPORTED = -1, -2
 SENT = -7.25
 
 
-def _ints(*v):
-    return (C.c_int * len(v))(*v)
-
-
-def _i64s(*v):
-    return (C.c_int64 * len(v))(*v)
-
-
-def _ptrs(*arrays):
-    t = (C.c_void_p * len(arrays))()
-    for i, a in enumerate(arrays):
-        t[i] = a if a is None or isinstance(a, int) else a.ctypes.data
-    return t
-
-
 class _Topk:
-    """One level (1, 3 * 2, 5, 7), k = 4, everything in host memory: valid arguments that single tests spoil."""
+    """One level (1, 3 * classes, 5, 7), k = 4, everything in host memory: valid arguments that single tests spoil."""
 
-    def __init__(self):
-        self.need = int(_lib.load().mv_retinanet_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 2, 4))
-        self.logits = np.zeros(210, np.float32)
+    def __init__(self, classes=2):
+        self.numel = 105 * classes
+        self.need = int(_lib.load().mv_retinanet_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, classes, 4))
+        self.logits = np.zeros(self.numel, np.float32)
         self.idx = np.full(4, 0x5AA5C33C, np.int32)
         self.ws = np.full(self.need + 16, 0xA5, np.uint8)
         self.ws_ptr = self.ws.ctypes.data + (-self.ws.ctypes.data) % 16
-        self.kw = dict(logits=_ptrs(self.logits), hs=_ints(5), ws=_ints(7), as_=_ints(3), strides=_i64s(210), levels=1, classes=2, n=1, k=4,
-                       thresh=0.05, idx=self.idx.ctypes.data, wsp=self.ws_ptr, nbytes=self.need)
+        self.kw = dict(logits=_ptrs(self.logits), hs=_ints(5), ws=_ints(7), as_=_ints(3), strides=_i64s(self.numel), levels=1, classes=classes,
+                       n=1, k=4, thresh=0.05, idx=self.idx.ctypes.data, wsp=self.ws_ptr, nbytes=self.need)
 
     def call(self, **over):
         a = {**self.kw, **over}
@@ -261,9 +248,9 @@ def test_topk_workspace_and_chunk():
     assert int(lib.mv_retinanet_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 9, 2, 4)) == 0
 
 
-def test_topk_refusals():
-    t = _Topk()
-    cases = [
+def _topk_cases(t):
+    """(spoiled arguments, status, part of the message), written on the fixture t (test_rpn_host._topk_cases)."""
+    return [
         (dict(logits=None), INVALID, "null pointer"),
         (dict(logits=_ptrs(None)), INVALID, "null pointer (level 0)"),
         (dict(idx=None), INVALID, "null pointer"),
@@ -279,7 +266,7 @@ def test_topk_refusals():
         (dict(k=0), INVALID, "k must be positive"),
         (dict(k=4097, nbytes=1 << 20), UNSUPPORTED, "k up to 4096"),
         (dict(n=-1), INVALID, "bad image count"),
-        (dict(strides=_i64s(209)), INVALID, "image stride"),
+        (dict(strides=_i64s(t.numel - 1)), INVALID, "image stride"),
         (dict(hs=_ints(1 << 15), ws=_ints(1 << 15), as_=_ints(2)), UNSUPPORTED, "32-bit index"),
         (dict(hs=_ints(1 << 10), ws=_ints(1 << 10), classes=1 << 10), UNSUPPORTED, "32-bit index"),
         (dict(wsp=None), INVALID, "needs a workspace"),
@@ -288,21 +275,28 @@ def test_topk_refusals():
         (dict(idx=t.logits.ctypes.data + 4 * 50), INVALID, "must not overlap"),
         (dict(wsp=(t.logits.ctypes.data + 15) // 16 * 16), INVALID, "must not overlap"),
     ]
-    for over, status, text in cases:
+
+
+def test_topk_refusals():
+    t = _Topk()
+    for over, status, text in _topk_cases(t):
         rc, msg = t.call(**over)
         assert rc == status and text in msg, (over.keys(), rc, msg)
     assert t.call(n=0, logits=None, idx=None, wsp=None, nbytes=0)[0] == 0
 
 
 class _Decode:
-    def __init__(self):
-        self.logits, self.deltas = np.zeros(210, np.float32), np.zeros(420, np.float32)
+    out64 = "lb"  # the key of the int64 output in `kw`
+
+    def __init__(self, classes=2):
+        self.numel = 105 * classes  # the elements of the logit map
+        self.logits, self.deltas = np.zeros(self.numel, np.float32), np.zeros(420, np.float32)
         self.base, self.sizes = np.zeros(12, np.float32), np.array([20.0, 28.0], np.float32)
         self.idx = np.zeros(4, np.int32)
         self.boxes, self.scores = np.full(16, SENT, np.float32), np.full(4, SENT, np.float32)
         self.labels, self.valid = np.full(4, 0x5AA5C33C, np.int64), np.full(4, 0xA5, np.uint8)
-        self.kw = dict(logits=_ptrs(self.logits), deltas=_ptrs(self.deltas), hs=_ints(5), ws=_ints(7), as_=_ints(3), ls=_i64s(210), ds=_i64s(420),
-                       sh=_ints(4), sw=_ints(4), levels=1, classes=2, base=self.base.ctypes.data, sizes=self.sizes.ctypes.data,
+        self.kw = dict(logits=_ptrs(self.logits), deltas=_ptrs(self.deltas), hs=_ints(5), ws=_ints(7), as_=_ints(3), ls=_i64s(self.numel),
+                       ds=_i64s(420), sh=_ints(4), sw=_ints(4), levels=1, classes=classes, base=self.base.ctypes.data, sizes=self.sizes.ctypes.data,
                        idx=self.idx.ctypes.data, n=1, k=4, boxes=self.boxes.ctypes.data, scores=self.scores.ctypes.data,
                        lb=self.labels.ctypes.data, valid=self.valid.ctypes.data)
 
@@ -316,11 +310,11 @@ class _Decode:
         return rc, _lib.load().mv_last_error().decode()
 
 
-def test_decode_refusals():
-    d = _Decode()
+def _decode_cases(d):
+    """As _topk_cases, for the fixture d of a decode entry."""
     cases = [(dict(**{name: None}), INVALID, "null") for name in ("logits", "deltas", "hs", "ws", "as_", "ls", "ds", "sh", "sw", "base", "sizes",
-                                                                  "idx", "boxes", "scores", "lb", "valid")]
-    cases += [
+                                                                  "idx", "boxes", "scores", d.out64, "valid")]
+    return cases + [
         (dict(deltas=_ptrs(None)), INVALID, "null pointer (level 0)"),
         (dict(levels=0), INVALID, "1 to 8 levels"),
         (dict(levels=9), UNSUPPORTED, "1 to 8 levels"),
@@ -330,21 +324,51 @@ def test_decode_refusals():
         (dict(sh=_ints(-4)), INVALID, "bad strides"),
         (dict(n=-1), INVALID, "bad shape"),
         (dict(k=-1), INVALID, "bad shape"),
-        (dict(ls=_i64s(209)), INVALID, "image strides"),
+        (dict(ls=_i64s(d.numel - 1)), INVALID, "image strides"),
         (dict(ds=_i64s(419)), INVALID, "image strides"),
         (dict(hs=_ints(1 << 10), ws=_ints(1 << 10), classes=1 << 10), UNSUPPORTED, "32-bit index"),
-        (dict(lb=d.labels.ctypes.data + 4), INVALID, "8-byte aligned"),
+        ({d.out64: d.kw[d.out64] + 4}, INVALID, "8-byte aligned"),
         (dict(boxes=d.deltas.ctypes.data), INVALID, "must not overlap"),
-        (dict(scores=d.logits.ctypes.data + 4 * 209), INVALID, "must not overlap"),
+        (dict(scores=d.logits.ctypes.data + 4 * (d.numel - 1)), INVALID, "must not overlap"),
         (dict(scores=d.boxes.ctypes.data + 4 * 15), INVALID, "must not overlap"),
         (dict(valid=d.idx.ctypes.data), INVALID, "must not overlap"),
-        (dict(lb=d.base.ctypes.data), INVALID, "must not overlap"),
+        ({d.out64: d.base.ctypes.data}, INVALID, "must not overlap"),
     ]
-    for over, status, text in cases:
+
+
+def test_decode_refusals():
+    d = _Decode()
+    for over, status, text in _decode_cases(d):
         rc, msg = d.call(**over)
         assert rc == status and text in msg, (list(over), rc, msg)
     assert d.call(n=0, logits=None, boxes=None)[0] == 0
     assert d.call(k=0, idx=None, boxes=None, scores=None, lb=None, valid=None)[0] == 0
+
+
+def test_rpn_entries_refuse_as_the_one_class_retinanet_entries():
+    """The rpn entries and the retinanet entries with classes = 1 answer every spoiled call alike: the same status, and the same
+    message once `retinanet_` reads `rpn_` and `labels must` reads `levels must`.  The spoils are every case of the four refusal
+    tables (this file's and test_rpn_host's) that does not set `classes`, each written on the fixture it runs on (105 logits here),
+    and an image count and a candidate count past the launch grid.  The size of the workspace is each entry's own (32 bytes
+    against 48 here), so the one message that prints it is compared with the sizes of its own fixture written in."""
+    lib = _lib.load()
+    assert int(lib.mv_retinanet_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 1, 4)) > 0
+    assert int(lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 4)) == 32
+    grid = "exceed the launch grid"
+    pairs = [(RH._Topk(), _Topk(classes=1), (RH._topk_cases, _topk_cases), (dict(n=70000), UNSUPPORTED, grid)),
+             (RH._Decode(), _Decode(classes=1), (RH._decode_cases, _decode_cases), (dict(n=1 << 33, k=1 << 33), UNSUPPORTED, grid))]
+    for rpn, ret, tables, extra in pairs:
+        spoils = lambda fixture: [c for table in tables for c in table(fixture) if "classes" not in c[0]] + [extra]  # noqa: E731
+        on_rpn, on_ret = spoils(rpn), spoils(ret)
+        assert len(on_rpn) == len(on_ret) >= 40
+        for (over_rpn, status, text), (over_ret, _, _) in zip(on_rpn, on_ret):
+            rc_rpn, msg_rpn = rpn.call(**over_rpn)
+            rc_ret, msg_ret = ret.call(**over_ret)
+            msg_ret = msg_ret.replace("retinanet_", "rpn_").replace("labels must", "levels must")
+            if "nbytes" in over_ret and "k" not in over_ret:
+                assert f"workspace of {ret.need - 1} bytes, need {ret.need} " in msg_ret
+                msg_ret = msg_ret.replace(f"of {ret.need - 1} bytes, need {ret.need} ", f"of {rpn.need - 1} bytes, need {rpn.need} ")
+            assert rc_rpn == rc_ret == status and msg_rpn == msg_ret and text in msg_rpn, (list(over_rpn), rc_rpn, msg_rpn, rc_ret, msg_ret)
 
 
 # ---- the Python checks fire before a device is needed ---------------------------------------------------------------------------------

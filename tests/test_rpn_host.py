@@ -1,7 +1,6 @@
 """RPN without a GPU: the two references of tests/_rpn_ref.py against each other, AnchorGenerator / RPNHead / RegionProposalNetwork
 against the replica (values, state, initialisation), every refusal of mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 with
 host pointers (refusals come before any launch), and the Python-side checks."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -12,6 +11,7 @@ import cpu_vision_amd as mv
 from cpu_vision_amd import _lib, anchor_utils, image_list, rpn
 from cpu_vision_amd import functional as F
 from tests import _rpn_ref as P
+from tests._util import c_i64s as _i64s, c_ints as _ints, c_ptrs as _ptrs
 
 
 # ---- replica (a) against restatement (b) ----------------------------------------------------------------------------------------------
@@ -213,25 +213,11 @@ INVALID, UNSUPPORTED = -1, -2
 SENT = -7.25
 
 
-def _ints(*v):
-    return (C.c_int * len(v))(*v)
-
-
-def _i64s(*v):
-    return (C.c_int64 * len(v))(*v)
-
-
-def _ptrs(*arrays):
-    t = (C.c_void_p * len(arrays))()
-    for i, a in enumerate(arrays):
-        t[i] = a if a is None or isinstance(a, int) else a.ctypes.data
-    return t
-
-
 class _Topk:
     """One level (1, 3, 5, 7), k = 4, everything in host memory: valid arguments that single tests spoil."""
 
     def __init__(self):
+        self.numel, self.need = 105, 32  # the elements of the map, the bytes of the workspace
         self.logits = np.zeros(105, np.float32)
         self.idx = np.full(4, 0x5AA5C33C, np.int32)
         self.ws = np.full(32 + 16, 0xA5, np.uint8)
@@ -248,15 +234,9 @@ class _Topk:
         return rc, _lib.load().mv_last_error().decode()
 
 
-def test_topk_refusals():
-    t = _Topk()
-    lib = _lib.load()
-    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 4) == 32
-    assert lib.mv_rpn_topk_workspace_bytes(2, _ints(5, 1), _ints(7, 1), _ints(3, 1), 2, 4) == 2 * 5 * 8
-    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 1000) == 848  # 105 candidates of 8 bytes, rounded up to 16
-    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 4097) == 0
-    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 9, 4) == 0
-    cases = [
+def _topk_cases(t):
+    """(spoiled arguments, status, part of the message), written on the fixture t: test_retinanet_host runs them on its own too."""
+    return [
         (dict(logits=None), INVALID, "null pointer"),
         (dict(logits=_ptrs(None)), INVALID, "null pointer (level 0)"),
         (dict(idx=None), INVALID, "null pointer"),
@@ -270,21 +250,33 @@ def test_topk_refusals():
         (dict(k=0), INVALID, "k must be positive"),
         (dict(k=4097, nbytes=1 << 20), UNSUPPORTED, "k up to 4096"),
         (dict(n=-1), INVALID, "bad image count"),
-        (dict(strides=_i64s(104)), INVALID, "image stride"),
+        (dict(strides=_i64s(t.numel - 1)), INVALID, "image stride"),
         (dict(hs=_ints(1 << 15), ws=_ints(1 << 15), as_=_ints(2)), UNSUPPORTED, "32-bit index"),
         (dict(wsp=None), INVALID, "needs a workspace"),
-        (dict(nbytes=31), INVALID, "workspace of 31 bytes, need 32"),
+        (dict(nbytes=t.need - 1), INVALID, f"workspace of {t.need - 1} bytes, need {t.need}"),
         (dict(wsp=t.ws_ptr + 4), INVALID, "16-byte aligned"),
         (dict(idx=t.logits.ctypes.data + 4 * 50), INVALID, "must not overlap"),
         (dict(wsp=(t.logits.ctypes.data + 15) // 16 * 16), INVALID, "must not overlap"),
     ]
-    for over, status, text in cases:
+
+
+def test_topk_refusals():
+    t = _Topk()
+    lib = _lib.load()
+    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 4) == 32
+    assert lib.mv_rpn_topk_workspace_bytes(2, _ints(5, 1), _ints(7, 1), _ints(3, 1), 2, 4) == 2 * 5 * 8
+    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 1000) == 848  # 105 candidates of 8 bytes, rounded up to 16
+    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 1, 4097) == 0
+    assert lib.mv_rpn_topk_workspace_bytes(1, _ints(5), _ints(7), _ints(3), 9, 4) == 0
+    for over, status, text in _topk_cases(t):
         rc, msg = t.call(**over)
         assert rc == status and text in msg, (over.keys(), rc, msg)
     assert t.call(n=0, logits=None, idx=None, wsp=None, nbytes=0)[0] == 0
 
 
 class _Decode:
+    numel, out64 = 105, "lv"  # the elements of the logit map; the key of the int64 output in `kw`
+
     def __init__(self):
         self.logits, self.deltas = np.zeros(105, np.float32), np.zeros(420, np.float32)
         self.base, self.sizes = np.zeros(12, np.float32), np.array([20.0, 28.0], np.float32)
@@ -305,11 +297,11 @@ class _Decode:
         return rc, _lib.load().mv_last_error().decode()
 
 
-def test_decode_refusals():
-    d = _Decode()
+def _decode_cases(d):
+    """As _topk_cases, for the fixture d of a decode entry."""
     cases = [(dict(**{name: None}), INVALID, "null") for name in ("logits", "deltas", "hs", "ws", "as_", "ls", "ds", "sh", "sw", "base", "sizes",
-                                                                  "idx", "boxes", "scores", "lv", "valid")]
-    cases += [
+                                                                  "idx", "boxes", "scores", d.out64, "valid")]
+    return cases + [
         (dict(deltas=_ptrs(None)), INVALID, "null pointer (level 0)"),
         (dict(levels=0), INVALID, "1 to 8 levels"),
         (dict(levels=9), UNSUPPORTED, "1 to 8 levels"),
@@ -318,17 +310,21 @@ def test_decode_refusals():
         (dict(sh=_ints(-4)), INVALID, "bad strides"),
         (dict(n=-1), INVALID, "bad shape"),
         (dict(k=-1), INVALID, "bad shape"),
-        (dict(ls=_i64s(104)), INVALID, "image strides"),
+        (dict(ls=_i64s(d.numel - 1)), INVALID, "image strides"),
         (dict(ds=_i64s(419)), INVALID, "image strides"),
         (dict(hs=_ints(1 << 15), ws=_ints(1 << 15), as_=_ints(2)), UNSUPPORTED, "32-bit index"),
-        (dict(lv=d.levels.ctypes.data + 4), INVALID, "8-byte aligned"),
+        ({d.out64: d.kw[d.out64] + 4}, INVALID, "8-byte aligned"),
         (dict(boxes=d.deltas.ctypes.data), INVALID, "must not overlap"),
-        (dict(scores=d.logits.ctypes.data + 4 * 104), INVALID, "must not overlap"),
+        (dict(scores=d.logits.ctypes.data + 4 * (d.numel - 1)), INVALID, "must not overlap"),
         (dict(scores=d.boxes.ctypes.data + 4 * 15), INVALID, "must not overlap"),
         (dict(valid=d.idx.ctypes.data), INVALID, "must not overlap"),
-        (dict(lv=d.base.ctypes.data), INVALID, "must not overlap"),
+        ({d.out64: d.base.ctypes.data}, INVALID, "must not overlap"),
     ]
-    for over, status, text in cases:
+
+
+def test_decode_refusals():
+    d = _Decode()
+    for over, status, text in _decode_cases(d):
         rc, msg = d.call(**over)
         assert rc == status and text in msg, (list(over), rc, msg)
     assert d.call(n=0, logits=None, boxes=None)[0] == 0
