@@ -69,7 +69,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
     flags = list(FLAGS)
     if variant:
         flags += ["-DMV_TUNING", f"-I{TUNING_INC}", *extra_flags]
-    headers = [CSRC / "mv_common.h", HERE.parent / "include" / "mi355vision.h", CSRC / "mv_epilogue.h", CSRC / "mv_deform.h", CSRC / "mv_conv.h", CSRC / "mv_invres.h", CSRC / "mv_act.h", CSRC / "mv_gridsample.h", CSRC / "mv_vec16.h", CSRC / "mv_boxcoder.h", CSRC / "mv_topk.h", CSRC / "mv_bilinear.h"]
+    headers = [CSRC / "mv_common.h", HERE.parent / "include" / "mi355vision.h", CSRC / "mv_epilogue.h", CSRC / "mv_deform.h", CSRC / "mv_conv.h", CSRC / "mv_invres.h", CSRC / "mv_act.h", CSRC / "mv_gridsample.h", CSRC / "mv_vec16.h", CSRC / "mv_boxcoder.h", CSRC / "mv_topk.h", CSRC / "mv_bilinear.h", CSRC / "mv_roi.h"]
     if variant:
         headers.append(TUNING_INC / "mv_tuning.h")
     bid = build_id(flags)

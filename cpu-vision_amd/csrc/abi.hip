@@ -1112,20 +1112,40 @@ int mv_nms_f32(const float* boxes, const float* scores, int64_t n, double iou_th
   return launch_nms(boxes, scores, (int)n, iou_threshold, keep_out, keep_count_out, workspace, (hipStream_t)stream);
 }
 
+// One lane per output element in workgroups of 256: k rois x c_out channels x (pooled_h, pooled_w) must fit the launch grid.
+static int roi_grid_check(const char* op, int64_t k, int c_out, int pooled_h, int pooled_w) {
+  if (k > ((0x7fffffffLL * 256) / c_out) / pooled_h / pooled_w)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid", op, (long long)k, c_out,
+                     pooled_h, pooled_w);
+  return 0;
+}
+
+// The checks roi_align, roi_pool, ps_roi_pool and ps_roi_align share: 0 launch, 1 nothing to do, < 0 the error.  has_second:
+// the op writes a second output (argmax or channel_mapping), which must be there and alias nothing.
+static int roi_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, bool has_second,
+                     const int* second, int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w) {
+  if (n < 0 || c < 0 || h < 0 || w < 0 || k < 0 || pooled_h < 0 || pooled_w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld c=%d (%d, %d), k=%lld, output (%d, %d)", op, (long long)n, c, h, w,
+                     (long long)k, pooled_h, pooled_w);
+  if (k == 0 || c == 0 || pooled_h == 0 || pooled_w == 0) return 1;
+  if (position_sensitive && c % ((int64_t)pooled_h * pooled_w))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: input channels must be a multiple of pooling height * pooling width, got %d for (%d, %d)",
+                     op, c, pooled_h, pooled_w);
+  if (n > 0 && (h == 0 || w == 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: empty (%d, %d) feature map", op, h, w);
+  if (n > 0x7fffffffLL || (int64_t)h * w > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images of %d x %d exceed the 32-bit plane index", op, (long long)n, h, w);
+  if (int rc = roi_grid_check(op, k, position_sensitive ? c / (pooled_h * pooled_w) : c, pooled_h, pooled_w)) return rc;
+  if (!rois || !y || (has_second && !second) || (n > 0 && !x)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  const void* const s = second;
+  if (x == y || rois == y || (has_second && (x == s || rois == s || y == s)))
+    return set_error(MV_ERR_INVALID_ARGUMENT,
+                     has_second ? "output must not alias input or the other output" : "output must not alias input");
+  return 0;
+}
+
 int mv_roi_align_f32(const float* x, const float* rois, float* y, int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w,
                      double spatial_scale, int sampling_ratio, int aligned, void* stream) {
-  if (n < 0 || c < 0 || h < 0 || w < 0 || k < 0 || pooled_h < 0 || pooled_w < 0)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "roi_align: bad shape n=%lld c=%d (%d, %d), k=%lld, output (%d, %d)", (long long)n, c, h, w,
-                     (long long)k, pooled_h, pooled_w);
-  if (k == 0 || c == 0 || pooled_h == 0 || pooled_w == 0) return MV_OK;
-  if (n > 0 && (h == 0 || w == 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_align: empty (%d, %d) feature map", h, w);
-  if (n > 0x7fffffffLL || (int64_t)h * w > 0x7fffffffLL)
-    return set_error(MV_ERR_UNSUPPORTED, "roi_align: %lld images of %d x %d exceed the 32-bit plane index", (long long)n, h, w);
-  if (k > ((0x7fffffffLL * 256) / c) / pooled_h / pooled_w)
-    return set_error(MV_ERR_UNSUPPORTED, "roi_align: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid", (long long)k, c,
-                     pooled_h, pooled_w);
-  if (!rois || !y || (n > 0 && !x)) return set_error(MV_ERR_INVALID_ARGUMENT, "roi_align: null pointer");
-  if (x == y || rois == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  if (int rc = roi_check("roi_align", false, x, rois, y, false, nullptr, n, c, h, w, k, pooled_h, pooled_w)) return rc < 0 ? rc : MV_OK;
   return launch_roi_align(x, rois, y, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, sampling_ratio, aligned ? 1 : 0,
                           (hipStream_t)stream);
 }
@@ -1149,9 +1169,7 @@ int mv_multiscale_roi_align_f32(const float* const* xs, const int* hs, const int
       return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: feature map %d of %d x %d exceeds the 32-bit plane index", l, hs[l], ws[l]);
   }
   if (n > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: %lld images exceed the 32-bit plane index", (long long)n);
-  if (k > ((0x7fffffffLL * 256) / c) / pooled_h / pooled_w)
-    return set_error(MV_ERR_UNSUPPORTED, "multiscale_roi_align: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid",
-                     (long long)k, c, pooled_h, pooled_w);
+  if (int rc = roi_grid_check("multiscale_roi_align", k, c, pooled_h, pooled_w)) return rc;
   if (!rois || !roi_levels || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: null pointer");
   if (rois == y || (const void*)roi_levels == (const void*)y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
   if ((uintptr_t)roi_levels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "multiscale_roi_align: roi_levels must be 8-byte aligned");
@@ -1451,46 +1469,23 @@ int mv_retinanet_decode_f32(const float* const* logits, const float* const* delt
 }
 
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------
-// The checks the three entry points share, in the order of mv_roi_align_f32: 0 launch, 1 nothing to do, < 0 the error.
-static int roi_pool_check(const char* op, bool position_sensitive, const float* x, const float* rois, const float* y, const int* second,
-                          int64_t n, int c, int h, int w, int64_t k, int pooled_h, int pooled_w) {
-  if (n < 0 || c < 0 || h < 0 || w < 0 || k < 0 || pooled_h < 0 || pooled_w < 0)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld c=%d (%d, %d), k=%lld, output (%d, %d)", op, (long long)n, c, h, w,
-                     (long long)k, pooled_h, pooled_w);
-  if (k == 0 || c == 0 || pooled_h == 0 || pooled_w == 0) return 1;
-  if (position_sensitive && c % ((int64_t)pooled_h * pooled_w))
-    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: input channels must be a multiple of pooling height * pooling width, got %d for (%d, %d)",
-                     op, c, pooled_h, pooled_w);
-  if (n > 0 && (h == 0 || w == 0)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: empty (%d, %d) feature map", op, h, w);
-  if (n > 0x7fffffffLL || (int64_t)h * w > 0x7fffffffLL)
-    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images of %d x %d exceed the 32-bit plane index", op, (long long)n, h, w);
-  const int c_out = position_sensitive ? c / (pooled_h * pooled_w) : c;
-  if (k > ((0x7fffffffLL * 256) / c_out) / pooled_h / pooled_w)
-    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld rois x %d channels x (%d, %d) outputs exceed the launch grid", op, (long long)k, c_out,
-                     pooled_h, pooled_w);
-  if (!rois || !y || !second || (n > 0 && !x)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
-  if (x == y || rois == y || (const void*)x == (const void*)second || (const void*)rois == (const void*)second ||
-      (const void*)y == (const void*)second)
-    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input or the other output");
-  return 0;
-}
-
+// (the checks: roi_check, with mv_roi_align_f32)
 int mv_roi_pool_f32(const float* x, const float* rois, float* y, int* argmax, int64_t n, int c, int h, int w, int64_t k, int pooled_h,
                     int pooled_w, double spatial_scale, void* stream) {
-  if (int rc = roi_pool_check("roi_pool", false, x, rois, y, argmax, n, c, h, w, k, pooled_h, pooled_w)) return rc < 0 ? rc : MV_OK;
+  if (int rc = roi_check("roi_pool", false, x, rois, y, true, argmax, n, c, h, w, k, pooled_h, pooled_w)) return rc < 0 ? rc : MV_OK;
   return launch_roi_pool(x, rois, y, argmax, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, (hipStream_t)stream);
 }
 
 int mv_ps_roi_pool_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
                        int pooled_h, int pooled_w, double spatial_scale, void* stream) {
-  if (int rc = roi_pool_check("ps_roi_pool", true, x, rois, y, channel_mapping, n, c, h, w, k, pooled_h, pooled_w))
+  if (int rc = roi_check("ps_roi_pool", true, x, rois, y, true, channel_mapping, n, c, h, w, k, pooled_h, pooled_w))
     return rc < 0 ? rc : MV_OK;
   return launch_ps_roi_pool(x, rois, y, channel_mapping, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, (hipStream_t)stream);
 }
 
 int mv_ps_roi_align_f32(const float* x, const float* rois, float* y, int* channel_mapping, int64_t n, int c, int h, int w, int64_t k,
                         int pooled_h, int pooled_w, double spatial_scale, int sampling_ratio, void* stream) {
-  if (int rc = roi_pool_check("ps_roi_align", true, x, rois, y, channel_mapping, n, c, h, w, k, pooled_h, pooled_w))
+  if (int rc = roi_check("ps_roi_align", true, x, rois, y, true, channel_mapping, n, c, h, w, k, pooled_h, pooled_w))
     return rc < 0 ? rc : MV_OK;
   return launch_ps_roi_align(x, rois, y, channel_mapping, (int)n, c, h, w, k, pooled_h, pooled_w, (float)spatial_scale, sampling_ratio,
                              (hipStream_t)stream);

@@ -16,9 +16,11 @@
 //                words of the bitset -- those loads do not depend on each other, unlike a walk box by box.
 //
 // roi_align: one lane per output element (k, c, ph, pw), pw fastest; the lane recomputes its roi's geometry (a few dozen flops)
-// and walks its samples in ascending (iy, ix) order (roi_align_element).  k_multiscale_roi_align (ops/poolers.py MultiScaleRoIAlign)
-// is the same element function on the feature map of the roi's level: one launch over all levels, no read-back.
+// and sums its bin's samples (roi_align_element; the element index, the batch-index rule, the grid size and the sampling loop are
+// mv_roi.h's, shared with roi_pool.hip).  k_multiscale_roi_align (ops/poolers.py MultiScaleRoIAlign) is the same element function
+// on the feature map of the roi's level: one launch over all levels, no read-back.
 #include "mv_common.h"
+#include "mv_roi.h"
 
 namespace mv {
 namespace {
@@ -160,18 +162,13 @@ struct RoiAlignArgs {
 // Output element idx of roi_align on the map A.x (A.h x A.w, A.spatial_scale): k_roi_align hands over its arguments as they are,
 // k_multiscale_roi_align the map of the roi's level.
 __device__ inline void roi_align_element(const RoiAlignArgs& A, long long idx) {
-  const int pw = (int)(idx % A.pooled_w);
-  const int ph = (int)((idx / A.pooled_w) % A.pooled_h);
-  const long long kc = idx / ((long long)A.pooled_w * A.pooled_h);
-  const int ch = (int)(kc % A.c);
-  const long long k = kc / A.c;
-  const float* const roi = A.rois + k * 5;
-  const float bf = roi[0];
-  if (!(bf > -1.f && bf < (float)A.n)) {  // a batch index that does not truncate into [0, n) (or NaN): zeros, nothing is read
+  const RoiElem e = roi_elem(idx, A.pooled_h, A.pooled_w, A.c);
+  const float* const roi = A.rois + e.k * 5;
+  int b;
+  if (!roi_image(roi[0], A.n, &b)) {
     A.y[idx] = 0.f;
     return;
   }
-  const int b = (int)bf;
   const float offset = A.aligned ? 0.5f : 0.f;
   const float start_w = __fsub_rn(__fmul_rn(roi[1], A.spatial_scale), offset);
   const float start_h = __fsub_rn(__fmul_rn(roi[2], A.spatial_scale), offset);
@@ -180,48 +177,11 @@ __device__ inline void roi_align_element(const RoiAlignArgs& A, long long idx) {
   float roi_w = __fsub_rn(end_w, start_w), roi_h = __fsub_rn(end_h, start_h);
   if (!A.aligned) roi_w = ref_max(roi_w, 1.f), roi_h = ref_max(roi_h, 1.f);
   const float bin_h = __fdiv_rn(roi_h, (float)A.pooled_h), bin_w = __fdiv_rn(roi_w, (float)A.pooled_w);
-  const int grid_h = A.sampling_ratio > 0 ? A.sampling_ratio : (int)ceilf(__fdiv_rn(roi_h, (float)A.pooled_h));
-  const int grid_w = A.sampling_ratio > 0 ? A.sampling_ratio : (int)ceilf(__fdiv_rn(roi_w, (float)A.pooled_w));
-  const float count = (float)max(grid_h * grid_w, 1);
-  const float* const plane = A.x + ((size_t)b * A.c + ch) * ((size_t)A.h * A.w);
-  const float base_y = __fadd_rn(start_h, __fmul_rn((float)ph, bin_h)), base_x = __fadd_rn(start_w, __fmul_rn((float)pw, bin_w));
-  const float fh = (float)A.h, fw = (float)A.w;
-  float out = 0.f;
-  for (int iy = 0; iy < grid_h; ++iy) {
-    float yy = __fadd_rn(base_y, __fdiv_rn(__fmul_rn(__fadd_rn((float)iy, .5f), bin_h), (float)grid_h));
-    const bool y_out = yy < -1.f || yy > fh;
-    if (y_out || yy <= 0.f) yy = 0.f;  // (an outside row's weights are not used)
-    int y_low = (int)yy, y_high;
-    if (y_low >= A.h - 1) {
-      y_high = y_low = A.h - 1;
-      yy = (float)y_low;
-    } else {
-      y_high = y_low + 1;
-    }
-    const float ly = __fsub_rn(yy, (float)y_low), hy = __fsub_rn(1.f, ly);
-    for (int ix = 0; ix < grid_w; ++ix) {
-      float xx = __fadd_rn(base_x, __fdiv_rn(__fmul_rn(__fadd_rn((float)ix, .5f), bin_w), (float)grid_w));
-      float w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f;
-      int p1 = 0, p2 = 0, p3 = 0, p4 = 0;  // a sample outside [-1, h] x [-1, w]: zero weights on element 0, as pre_calc does
-      if (!(y_out || xx < -1.f || xx > fw)) {
-        if (xx <= 0.f) xx = 0.f;
-        int x_low = (int)xx, x_high;
-        if (x_low >= A.w - 1) {
-          x_high = x_low = A.w - 1;
-          xx = (float)x_low;
-        } else {
-          x_high = x_low + 1;
-        }
-        const float lx = __fsub_rn(xx, (float)x_low), hx = __fsub_rn(1.f, lx);
-        w1 = __fmul_rn(hy, hx), w2 = __fmul_rn(hy, lx), w3 = __fmul_rn(ly, hx), w4 = __fmul_rn(ly, lx);
-        p1 = y_low * A.w + x_low, p2 = y_low * A.w + x_high, p3 = y_high * A.w + x_low, p4 = y_high * A.w + x_high;
-      }
-      const float s = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w1, plane[p1]), __fmul_rn(w2, plane[p2])), __fmul_rn(w3, plane[p3])),
-                                __fmul_rn(w4, plane[p4]));
-      out = __fadd_rn(out, s);
-    }
-  }
-  A.y[idx] = __fdiv_rn(out, count);
+  const int grid_h = roi_grid(A.sampling_ratio, roi_h, A.pooled_h), grid_w = roi_grid(A.sampling_ratio, roi_w, A.pooled_w);
+  const float count = (float)max(grid_h * grid_w, 1);  // an empty adaptive grid: 0 / 1 = 0
+  const float* const plane = A.x + ((size_t)b * A.c + e.ch) * ((size_t)A.h * A.w);
+  const float base_y = __fadd_rn(start_h, __fmul_rn((float)e.ph, bin_h)), base_x = __fadd_rn(start_w, __fmul_rn((float)e.pw, bin_w));
+  A.y[idx] = __fdiv_rn(roi_bin_sum(plane, A.h, A.w, base_y, base_x, bin_h, bin_w, grid_h, grid_w), count);
 }
 
 __global__ __launch_bounds__(256) void k_roi_align(const RoiAlignArgs A) {
@@ -245,8 +205,7 @@ struct MultiScaleArgs {
 __global__ __launch_bounds__(256) void k_multiscale_roi_align(const MultiScaleArgs M) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= M.roi.total) return;
-  const long long k = idx / ((long long)M.roi.pooled_w * M.roi.pooled_h * M.roi.c);
-  const long long level = M.roi_levels[k];
+  const long long level = M.roi_levels[roi_elem(idx, M.roi.pooled_h, M.roi.pooled_w, M.roi.c).k];
   if (level < 0 || level >= M.levels) {
     M.roi.y[idx] = 0.f;
     return;

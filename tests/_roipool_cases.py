@@ -50,5 +50,23 @@ def pool_reference(op, shape, cfg, extra=0):
     return _frozen(*f32), _frozen(*f64), rois
 
 
+def same_as_aligned_roi_align(y, mapping, full, ratio, what):
+    """Asserts the relation the shared bin sampler (csrc/mv_roi.h) embodies: ps_roi_align's float32 output `y` is, bit for bit,
+    the output `full` of roi_align(aligned=True) on the same map and rois, gathered along channels by `mapping`.  Excluded are only
+    the elements of the DEGENERATE_ROIS rows that ps_roi_align makes NaN with an adaptive grid (ratio <= 0): there the divisor
+    differs by contract, the bare grid_h * grid_w against roi_align's max(.., 1).  The zero-size roi is such a row at every output
+    size."""
+    y, full = np.ascontiguousarray(y), np.ascontiguousarray(full)
+    assert y.dtype == full.dtype == np.float32 and full.shape[1] == y.shape[1] * y.shape[2] * y.shape[3], what
+    gathered = np.ascontiguousarray(np.take_along_axis(full, mapping.astype(np.int64), axis=1))
+    excluded = np.zeros(y.shape, bool)
+    if ratio <= 0:
+        excluded[list(DEGENERATE_ROIS)] = np.isnan(y[list(DEGENERATE_ROIS)])
+        assert excluded[DEGENERATE_ROIS[0]].all(), f"{what}: the zero-size roi is not NaN throughout"
+    assert np.isnan(y[excluded]).all()
+    differ = (y.view(np.uint32) != gathered.view(np.uint32)) & ~excluded
+    assert not differ.any(), f"{what}: {int(differ.sum())} of {y.size} elements differ, in rois {np.flatnonzero(differ.any((1, 2, 3))).tolist()}"
+
+
 def configs(op):
     return PS_ALIGN_CONFIGS if op == "ps_roi_align" else POOL_CONFIGS

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 from cpu_vision_amd import _lib, ops  # noqa: E402
 from tests import _detect_ref as R  # noqa: E402
 from tests import _roipool_ref as P  # noqa: E402
-from tests._roipool_cases import OPS, configs, pool_input, pool_reference  # noqa: E402
+from tests._detect_cases import roi_rois  # noqa: E402
+from tests._roipool_cases import OPS, configs, pool_input, pool_reference, same_as_aligned_roi_align  # noqa: E402
 
 try:
     import torchvision.ops as tv_ops
@@ -74,6 +75,18 @@ def test_equals_the_float32_restatement(op):
             if tv_ops is not None:
                 assert np.array_equal(got[0].cpu().numpy(), _tv(op, pool_input(op, shape, cfg[0]), rois, cfg), equal_nan=True), \
                     f"{op} {shape} {cfg}: differs from torchvision's CPU op"
+
+
+@pytest.mark.parametrize("ratio", (-1, 2))
+@pytest.mark.parametrize("scale", (1.0, 0.25))
+@pytest.mark.parametrize("out", ((2, 3), (7, 7)), ids=str)
+def test_ps_roi_align_is_aligned_roi_align_gathered_by_channel_mapping(out, scale, ratio):
+    """k_ps_roi_align and k_roi_align sum a bin with the same device function: on the same map their outputs are the same bits."""
+    x, r = _dev(pool_input("ps_roi_align", "main", out)), _dev(roi_rois("main", scale))
+    y, mapping = ops._ps_roi_align_impl(x, r, float(scale), out[0], out[1], ratio)
+    assert torch.equal(ops.ps_roi_align(x, r, out, scale, ratio).nan_to_num(7.0), y.nan_to_num(7.0))
+    full = ops.roi_align(x, r, out, scale, ratio, aligned=True)
+    same_as_aligned_roi_align(y.cpu().numpy(), mapping.cpu().numpy(), full.cpu().numpy(), ratio, f"ps_roi_align {(out, scale, ratio)}")
 
 
 @pytest.mark.parametrize("op", OPS)

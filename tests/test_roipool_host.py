@@ -6,10 +6,11 @@ import pytest
 import torch
 
 from cpu_vision_amd import _lib, ops
+from tests import _detect_ref as R
 from tests import _roipool_ref as P
 from tests._detect_cases import roi_rois
 from tests._roipool_cases import (DEGENERATE_ROIS, OPS, OUTPUTS, POOL_CONFIGS, PS_ALIGN_CONFIGS, SCALES, SHAPES, input_shape,
-                                  pool_reference)
+                                  pool_input, pool_reference, same_as_aligned_roi_align)
 
 F32 = np.float32
 FLT_MAX = np.finfo(np.float32).max
@@ -112,17 +113,19 @@ def test_reprs_and_exports():
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("op", ("roi_align",) + OPS)
 def test_abi_validates_on_the_host(op):
-    """Every rejection happens before a launch (the pointers are made up); k == 0, c == 0 and a zero output side succeed without one."""
+    """Every rejection happens before a launch (the pointers are made up); k == 0, c == 0 and a zero output side succeed without one.
+    The four entry points share one set of checks; roi_align has no second output, so `second` is not passed on."""
     lib = _lib.load()
     fn = getattr(lib, f"mv_{op}_f32")
-    ps = op != "roi_pool"
-    tail = (-1, None) if op == "ps_roi_align" else (None,)
+    ps = op in ("ps_roi_pool", "ps_roi_align")
+    pair = op != "roi_align"
+    tail = {"roi_align": (-1, 0, None), "ps_roi_align": (-1, None)}.get(op, (None,))
     c = 98 if ps else 3  # 2 * 7 * 7
 
     def call(x=16, rois=32, y=64, second=128, n=2, c=c, h=8, w=8, k=1, ph=7, pw=7):
-        return fn(x, rois, y, second, n, c, h, w, k, ph, pw, 1.0, *tail)
+        return fn(x, rois, y, *((second,) if pair else ()), n, c, h, w, k, ph, pw, 1.0, *tail)
 
     assert call(None, None, None, None, k=0) == 0
     assert call(None, None, None, None, c=0) == 0
@@ -134,10 +137,11 @@ def test_abi_validates_on_the_host(op):
     assert call(w=0) == -1 and b"empty" in lib.mv_last_error()
     assert call(h=65536, w=65536) == -2 and b"plane index" in lib.mv_last_error()
     assert call(c=(1 << 20) * (49 if ps else 1), k=1 << 40) == -2 and b"launch grid" in lib.mv_last_error()
-    for null in (dict(x=None), dict(rois=None), dict(y=None), dict(second=None)):
+    for null in (dict(x=None), dict(rois=None), dict(y=None)) + ((dict(second=None),) if pair else ()):
         assert call(**null) == -1 and b"null pointer" in lib.mv_last_error(), null
-    for alias in (dict(y=16), dict(y=32), dict(second=16), dict(second=32), dict(second=64)):
-        assert call(**alias) == -1 and b"alias" in lib.mv_last_error(), alias
+    message = b"output must not alias input or the other output" if pair else b"output must not alias input"
+    for alias in (dict(y=16), dict(y=32)) + ((dict(second=16), dict(second=32), dict(second=64)) if pair else ()):
+        assert call(**alias) == -1 and lib.mv_last_error() == message, alias
     if ps:
         for c_bad in (97, 99, 1, 48):
             assert call(c=c_bad) == -1 and b"input channels must be a multiple of pooling height * pooling width" in lib.mv_last_error()
@@ -246,6 +250,15 @@ def test_ps_roi_align_is_nan_exactly_where_the_adaptive_grid_has_no_sample_count
     for ratio in (1, 2):
         (y, _), _, _ = pool_reference("ps_roi_align", "main", (out, scale, ratio), 51)
         assert np.isfinite(y).all()
+
+
+@pytest.mark.parametrize("cfg", PS_ALIGN_CONFIGS, ids=str)
+def test_ps_roi_align_is_aligned_roi_align_gathered_by_channel_mapping(cfg):
+    """The two restatements agree bit for bit wherever the divisor is the same: what lets the kernels share one bin sampler."""
+    out, scale, ratio = cfg
+    (y, mapping), _, rois = pool_reference("ps_roi_align", "main", cfg)
+    full = R.roi_align_ref(pool_input("ps_roi_align", "main", out), rois, out, scale, ratio, True)
+    same_as_aligned_roi_align(y, mapping, full, ratio, f"ps_roi_align_ref {cfg}")
 
 
 # ---- the conditions under which the float64 yardstick means something ----------------------------------------------------------------
