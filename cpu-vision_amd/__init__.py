@@ -22,6 +22,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
                   generalized_rcnn: GeneralizedRCNN; transform: GeneralizedRCNNTransform (normalize + resize + batch as one launch)
   mask_rcnn       MaskRCNN, MaskRCNNHeads, MaskRCNNPredictor (ConvTranspose2d(2, 2) + ReLU as one pixel-shuffling pointwise launch),
                   maskrcnn_resnet50_fpn; _mask: mask_probs (gather + sigmoid) and paste_masks_in_image (one launch per image)
+  keypoint_rcnn   KeypointRCNN, KeypointRCNNHeads, KeypointRCNNPredictor (ConvTranspose2d(4, stride 2, padding 1) as one implicit-GEMM
+                  launch with a transposed store, then the x2 bilinear interpolate), keypointrcnn_resnet50_fpn; _keypoint:
+                  heatmaps_to_keypoints (bicubic resize + argmax of every (roi, keypoint) in one launch, nothing materialised)
   retinanet       RetinaNetClassificationHead / RetinaNetRegressionHead / RetinaNetHead (the towers' first convs as one launch),
                   RetinaNet: threshold + top-k over every (anchor, class) of the heads' NCHW maps, many workgroups per (image,
                   level), then decode + clip + sigmoid of the selected candidates only, then batched_nms; retinanet_resnet50_fpn
@@ -39,7 +42,7 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
 The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias package at the repo root).
 """
 from . import (anchor_utils, backbone_utils, faster_rcnn, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
-               mask_rcnn, mobilenet, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, transform, transforms, tv_tensors)
+               keypoint_rcnn, mask_rcnn, mobilenet, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, transform, transforms, tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
 from .backbone_utils import BackboneWithFPN, IntermediateLayerGetter, resnet_fpn_backbone  # noqa: F401
@@ -52,6 +55,7 @@ from .transform import GeneralizedRCNNTransform  # noqa: F401
 from .generalized_rcnn import GeneralizedRCNN  # noqa: F401
 from .faster_rcnn import FasterRCNN, FastRCNNPredictor, TwoMLPHead, fasterrcnn_resnet50_fpn  # noqa: F401
 from .mask_rcnn import MaskRCNN, MaskRCNNHeads, MaskRCNNPredictor, maskrcnn_resnet50_fpn  # noqa: F401
+from .keypoint_rcnn import KeypointRCNN, KeypointRCNNHeads, KeypointRCNNPredictor, keypointrcnn_resnet50_fpn  # noqa: F401
 from .retinanet import (RetinaNet, RetinaNetClassificationHead, RetinaNetHead, RetinaNetRegressionHead,  # noqa: F401
                         retinanet_resnet50_fpn)
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401

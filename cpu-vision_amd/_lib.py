@@ -144,6 +144,8 @@ SYMBOLS = {
     "mv_paste_masks_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_mask_probs_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "mv_conv_transpose2x2_bias_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "mv_conv_transpose4x4s2_bias_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "mv_heatmaps_to_keypoints_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

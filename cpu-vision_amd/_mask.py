@@ -1,7 +1,8 @@
 """The mask branch of Mask R-CNN behind the mask head: paste_masks_in_image and mask_probs (models/detection/roi_heads.py
 paste_masks_in_image / maskrcnn_inference) and conv_transpose2d_bias_act, nn.ConvTranspose2d(kernel 2, stride 2) + bias + activation
-(mask_rcnn.py's conv5_mask) -- ONE launch each (csrc/mask.hip, the pixel-shuffle instance of csrc/convnorm.hip's pointwise kernel;
-arithmetic in mi355vision.h, mv_paste_masks_f32 and below).
+(mask_rcnn.py's conv5_mask; the kernel 4, stride 2, padding 1 geometry of Keypoint R-CNN goes on to _keypoint.py) -- ONE launch each
+(csrc/mask.hip, the pixel-shuffle instance of csrc/convnorm.hip's pointwise kernel; arithmetic in mi355vision.h, mv_paste_masks_f32
+and below).
 
 Every name here is re-exported by `functional`, which is where the rest of the package, the tests and tools/ find it.
 """
@@ -12,6 +13,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._keypoint import conv_transpose4x4s2
 from ._layers import _ACT_CODES
 
 
@@ -93,22 +95,27 @@ def conv_transpose2x2_relayout(weight: torch.Tensor, bias: Optional[torch.Tensor
 def conv_transpose2d_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, activation: Optional[str] = None,
                               stride=2, padding=0, output_padding=0, groups: int = 1, dilation=1,
                               relaid: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None) -> torch.Tensor:
-    """nn.ConvTranspose2d(kernel_size=2, stride=2) + bias + activation (None / "relu" / "relu6") as ONE launch: x (N, Cin, H, W) and
-    torch's weight (Cin, Cout, 2, 2) -> (N, Cout, 2 H, 2 W).  With kernel == stride the four taps never overlap, so this is a
-    pointwise conv with 4 Cout channels whose store is a pixel shuffle; the summation order is the one
-    conv1x1_k_slices(N, Cin, H, W, 4 Cout) states.  Any other geometry raises NotImplementedError naming the argument.  `relaid`:
-    the result of conv_transpose2x2_relayout for this weight and bias, when the caller caches it."""
+    """nn.ConvTranspose2d + bias + activation (None / "relu" / "relu6") as ONE launch, x (N, Cin, H, W) and torch's weight (Cin, Cout,
+    k, k) -> (N, Cout, 2 H, 2 W), in exactly two geometries:
+      kernel 2, stride 2, padding 0   the four taps never overlap, so this is a pointwise conv with 4 Cout channels whose store is a
+                                      pixel shuffle; the summation order is the one conv1x1_k_slices(N, Cin, H, W, 4 Cout) states;
+      kernel 4, stride 2, padding 1   every output phase (py, px) is a 2x2 convolution of the input, so this is the implicit-GEMM
+                                      conv2d_bias_act(x, w2, bias4, padding=1) with 4 Cout channels whose store keeps each phase's
+                                      window positions (_keypoint.py); the summation order is conv2d_bias_act's single chain.
+    Any other geometry raises NotImplementedError naming the argument.  `relaid`: the result of conv_transpose2x2_relayout /
+    conv_transpose4x4_relayout for this weight and bias, when the caller caches it."""
     if x.ndim != 4 or weight.ndim != 4:
         raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
-    for name, value, want in (("stride", _pair(stride), (2, 2)), ("padding", _pair(padding), (0, 0)),
+    four = weight.ndim == 4 and tuple(weight.shape[2:]) == (4, 4)
+    for name, value, want in (("stride", _pair(stride), (2, 2)), ("padding", _pair(padding), (1, 1) if four else (0, 0)),
                               ("output_padding", _pair(output_padding), (0, 0)), ("dilation", _pair(dilation), (1, 1))):
         if value != want:
             raise NotImplementedError(f"conv_transpose2d_bias_act: {name}={value} is not on the MI355X path ({name}={want} is)")
     if groups != 1:
         raise NotImplementedError(f"conv_transpose2d_bias_act: groups={groups} is not on the MI355X path (groups=1 is)")
-    if tuple(weight.shape[2:]) != (2, 2):
+    if not four and tuple(weight.shape[2:]) != (2, 2):
         raise NotImplementedError(f"conv_transpose2d_bias_act: kernel_size={tuple(weight.shape[2:])} is not on the MI355X path "
-                                  "(kernel_size=(2, 2) is)")
+                                  "(kernel_size=(2, 2) with padding 0 and (4, 4) with padding 1 are)")
     if activation not in (None, "none", "relu", "relu6"):
         raise NotImplementedError(f"conv_transpose2d_bias_act: activation={activation!r} is not on the MI355X path (None, 'relu' and "
                                   "'relu6' are)")
@@ -122,6 +129,9 @@ def conv_transpose2d_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: Optio
         raise RuntimeError(f"conv_transpose2d_bias_act: an input of shape {tuple(x.shape)} has no pixels")
     _lib.require_f32_layer("conv_transpose2d_bias_act", x, weight)
     _lib.require_device(x)
+    if four:
+        y = conv_transpose4x4s2(x, weight, bias, _ACT_CODES[activation], relaid)
+        return _lib.forward_only(y, "conv_transpose2d_bias_act", x, weight, bias)
     w4, b4 = relaid if relaid is not None else conv_transpose2x2_relayout(weight, bias, x.device)
     y = torch.empty((n, cout, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
     if n == 0:

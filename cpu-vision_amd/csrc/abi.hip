@@ -1799,4 +1799,45 @@ int mv_conv_transpose2x2_bias_act_f32(const float* x, const float* w4, const flo
   return launch_conv_transpose2x2(x, w4, y, n, cin, h, w, cout, e, (hipStream_t)stream);
 }
 
+// ---- the keypoint branch of Keypoint R-CNN: conv_igemm.hip's transposed store, keypoint.hip ---------------------------------------------
+int mv_conv_transpose4x4s2_bias_act_f32(const float* x, const float* w2, const float* bias4, float* y, int64_t n, int cin, int h, int w,
+                                        int cout, int act, void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose4x4s2: bad shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, cin, cout, h, w);
+  if (act != MV_ACT_NONE && act != MV_ACT_RELU && act != MV_ACT_RELU6)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose4x4s2: bad activation code %d (none, ReLU and ReLU6 are supported)", act);
+  // what the implicit-GEMM kernel's 32-bit indices cover: K = 4 cin, the (h + 1) x (w + 1) window positions, one image of x and of y
+  const int64_t hw = (int64_t)h * w, positions = ((int64_t)h + 1) * ((int64_t)w + 1);
+  if (cout > 0x7fffffff / 4 || cin >= 65536 / 4 || w + 1 >= 4096 || positions >= (1 << 20) || cin * hw >= (1LL << 30) || n > 65535)
+    return set_error(MV_ERR_UNSUPPORTED, "conv_transpose4x4s2: n=%lld cin=%d cout=%d h=%d w=%d exceeds the kernel's index range",
+                     (long long)n, cin, cout, h, w);
+  if (n == 0) return MV_OK;
+  if (!x || !w2 || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose4x4s2: null pointer");
+  if (n > 0x7fffffffffffLL / hw / cin || n > 0x7fffffffffffLL / hw / 4 / cout)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose4x4s2: %lld images exceed the address space", (long long)n);
+  const ByteRange ins[3] = {{x, n * cin * hw * 4}, {w2, (int64_t)cout * 64 * cin}, {bias4, bias4 ? (int64_t)cout * 16 : 0}};
+  const ByteRange out = {y, n * cout * hw * 16};
+  if (!outputs_clear(&out, 1, ins, 3)) return set_error(MV_ERR_INVALID_ARGUMENT, "conv_transpose4x4s2: the output must not overlap an input");
+  const Epilogue e = {bias4, nullptr, nullptr, nullptr, MV_AFFINE_NONE, act};
+  return launch_conv_transpose4x4s2(x, w2, y, n, cin, h, w, cout, e, (hipStream_t)stream);
+}
+
+int mv_heatmaps_to_keypoints_f32(const float* maps, const float* rois, float* xy, float* scores, int64_t r, int k, int mh, int mw,
+                                 void* stream) {
+  if (r < 0 || k < 1 || mh < 1 || mw < 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "heatmaps_to_keypoints: bad shape r=%lld, k=%d, (%d, %d)", (long long)r, k, mh, mw);
+  const int64_t plane = (int64_t)mh * mw;
+  if (plane > kKpMaxPlane)
+    return set_error(MV_ERR_UNSUPPORTED, "heatmaps_to_keypoints: heatmaps of (%d, %d) exceed %d elements", mh, mw, kKpMaxPlane);
+  if (r == 0) return MV_OK;
+  if (!maps || !rois || !xy || !scores) return set_error(MV_ERR_INVALID_ARGUMENT, "heatmaps_to_keypoints: null pointer");
+  if (r > 0x7fffffffffffLL / plane / k) return set_error(MV_ERR_INVALID_ARGUMENT, "heatmaps_to_keypoints: %lld rois exceed the address space", (long long)r);
+  const ByteRange ins[2] = {{maps, r * k * plane * 4}, {rois, r * 16}}, outs[2] = {{xy, r * k * 12}, {scores, r * k * 4}};
+  if (!outputs_clear(outs, 2, ins, 2))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "heatmaps_to_keypoints: the outputs must not overlap an input or each other");
+  if (!heatmaps_to_keypoints_grid_fits(r, k))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "heatmaps_to_keypoints: %lld rois of %d keypoints exceed the launch grid", (long long)r, k);
+  return launch_heatmaps_to_keypoints(maps, rois, xy, scores, r, k, mh, mw, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -29,6 +29,12 @@
 // residual pointer allows it, else four guarded scalars -- nothing past HW or past channel mg.  FULL is a compile-time switch; the
 // bias + activation instances (FULL = false, kernel argument IgArgs) compile to the instructions and the registers they had
 // before it existed.
+//
+// mv_conv_transpose4x4s2_bias_act_f32 (Keypoint R-CNN's kps_score_lowres, ConvTranspose2d(kernel 4, stride 2, padding 1)) runs the
+// same kernel with the TR store, k_conv_igemm<CT, PT, false, true> ("k_conv_igemm_tr"): the GEMM is the 2x2 convolution with padding 1
+// of the relaid weight (4 cout rows, q = 4 co + 2 py + px) on the (h + 1) x (w + 1) grid of window positions, and the epilogue
+// stores row q's value at position (m + py, n + px) to y[co, 2 m + py, 2 n + px], dropping the positions no phase keeps.  Only the
+// epilogue's addressing and validity test differ; TR is a compile-time switch like FULL and the other instances do not see it.
 #include <cstdlib>
 
 #include "mv_common.h"
@@ -82,13 +88,16 @@ __device__ __forceinline__ unsigned ig_div(unsigned n, unsigned d, unsigned m) {
 // FULL = false: + bias, activation (mv_conv2d_bias_act_f32; the kernel argument is IgArgs and every `if constexpr (FULL)` below is
 // discarded: the function the compiler sees is the one it saw before FULL existed).  FULL = true: + bias -> folded norm ->
 // + residual -> activation, in mv_epilogue.h's order (epi_norm, `res + v`, epi_act) -- orc_conv2d_affine_act_f32's.
-template <int CT, int PT, bool FULL = false>
+// TR = true (FULL = false only): the transposed-conv store.  A is the 2x2 / padding 1 convolution's IgArgs (ih x iw the input, ow =
+// iw + 1, HW = (ih + 1) * (iw + 1), mg = 4 cout) with y the (cout, 2 ih, 2 iw) output and y_img_stride its image stride.
+template <int CT, int PT, bool FULL = false, bool TR = false>
 __global__ __launch_bounds__(256, 2) void k_conv_igemm(const typename IgArgsOf<FULL>::type A) {
   constexpr int MB = kIgTile * CT, PB = kIgTile * PT;    // workgroup tile: channels x pixels
   constexpr int WU = MB / 32;                  // float4 of W per thread and chunk (MB rows x 8 float4)
   constexpr int XU = PB / 8;                   // gathered X elements per thread and chunk (32 k x PB pixels / 256)
   constexpr int XROWS = 256 / PB > 0 ? 256 / PB : 1;  // k rows covered by the 256 threads at once (PB <= 256)
   static_assert(PB == 64 || PB == 128 || PB == 256, "pixel tile");
+  static_assert(!(FULL && TR), "the transposed store has the bias + activation epilogue only");
   __shared__ __attribute__((aligned(16))) float ws[MB * kIgP];
   __shared__ __attribute__((aligned(16))) float xs[PB * kIgP > 4 * 32 * kIgP ? PB * kIgP : 4 * 32 * kIgP];  // also 4 transpose buffers
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -279,6 +288,18 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const typename IgArgsOf<F
             v[r] = (A.act == 3) ? epi_act<1>(v[r], cl) : ((A.act == 4) ? epi_act<2>(v[r], cl) : epi_act<0>(v[r], cl));
           }
         }
+        if constexpr (TR) {  // row co = 4 c + 2 py + px keeps window position (m + py, n + px) as y[c, 2 m + py, 2 n + px]
+          const int py = (co >> 1) & 1, px = co & 1;
+          float* const plane = Y + (size_t)(co >> 2) * 4 * A.ih * A.iw;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if (pq + r >= HW) continue;
+            const unsigned wy = ig_div((unsigned)(pq + r), (unsigned)A.ow, A.m_ow);
+            const int m = (int)wy - py, n = (pq + r) - (int)wy * A.ow - px;
+            if ((unsigned)m < (unsigned)A.ih && (unsigned)n < (unsigned)A.iw) plane[(size_t)(2 * m + py) * (2 * A.iw) + 2 * n + px] = v[r];
+          }
+          continue;
+        }
         float* dst = Y + (size_t)co * HW + pq;
         if (A.vec_y && pq + 3 < HW) {
           *reinterpret_cast<f32x4*>(dst) = (f32x4){v[0], v[1], v[2], v[3]};
@@ -294,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const typename IgArgsOf<F
 
 // e == nullptr: the bias + activation instances; else the instances with the full epilogue
 template <int CT, int PT>
-static int ig_launch(IgArgs& a, const IgEpi* e, int64_t n, hipStream_t s) {
+static int ig_launch(IgArgs& a, const IgEpi* e, int64_t n, hipStream_t s, bool tr = false) {
   a.mblocks = (a.mg + 64 * CT - 1) / (64 * CT);
   const long long pblocks = (a.HW + 64 * PT - 1) / (64 * PT);
   const long long nb = a.mblocks * pblocks;
@@ -306,8 +327,40 @@ static int ig_launch(IgArgs& a, const IgEpi* e, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL((k_conv_igemm<CT, PT, true>), dim3((unsigned)nb, (unsigned)n), dim3(256), 0, s, f);
     return check_launchf("k_conv_igemm_full<%dch,%dpx,implicit %dx%d>", 64 * CT, 64 * PT, a.taps / a.kw, a.kw);
   }
+  if (tr) {
+    hipLaunchKernelGGL((k_conv_igemm<CT, PT, false, true>), dim3((unsigned)nb, (unsigned)n), dim3(256), 0, s, a);
+    return check_launchf("k_conv_igemm_tr<%dch,%dpx,transposed 4x4 s2>", 64 * CT, 64 * PT);
+  }
   hipLaunchKernelGGL((k_conv_igemm<CT, PT>), dim3((unsigned)nb, (unsigned)n), dim3(256), 0, s, a);
   return check_launchf("k_conv_igemm<%dch,%dpx,implicit %dx%d>", 64 * CT, 64 * PT, a.taps / a.kw, a.kw);
+}
+
+static unsigned ig_magic(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
+
+// the tile for a (mg channels, HW pixels, n images) problem, and its launch
+static int ig_dispatch(IgArgs& a, const IgEpi* ep, int64_t n, hipStream_t s, bool tr) {
+  const int mg = a.mg;
+  // channel tile: 64, 128 or 192 channels per workgroup, whichever pads the least (ties: the larger -- every gathered element
+  // then feeds more channels); pixel tile: 256 pixels with one channel tile per wave, else 128; small problems take 64-pixel
+  // tiles so that the grid still covers the chip
+  auto padded = [](long long v, long long t) { return (v + t - 1) / t * t; };
+  int ct = 3;
+  long long best = padded(mg, 192);
+  if (padded(mg, 128) < best) ct = 2, best = padded(mg, 128);
+  if (padded(mg, 64) < best) ct = 1, best = padded(mg, 64);
+  if (const char* ev = tune_env("MV_IG_CT")) ct = atoi(ev) >= 1 && atoi(ev) <= 3 ? atoi(ev) : ct;
+  const long long wgs256 = padded(mg, 64 * ct) / (64 * ct) * ((a.HW + 255) / 256) * n;
+  if (ct == 1) {
+    if (wgs256 >= 512 || a.HW > 4096) return ig_launch<1, 4>(a, ep, n, s, tr);
+    if (padded(mg, 64) / 64 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<1, 2>(a, ep, n, s, tr);
+    return ig_launch<1, 1>(a, ep, n, s, tr);
+  }
+  if (ct == 2) {
+    if (padded(mg, 128) / 128 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<2, 2>(a, ep, n, s, tr);
+    return ig_launch<2, 1>(a, ep, n, s, tr);
+  }
+  if (padded(mg, 192) / 192 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<3, 2>(a, ep, n, s, tr);
+  return ig_launch<3, 1>(a, ep, n, s, tr);
 }
 
 // kFormColumns: sizes the implicit kernel's index arithmetic does not cover (and A/B in the tuning build: MV_CONV_COLUMNS).
@@ -345,8 +398,7 @@ int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, 
   a.x_img_stride = (int64_t)g.cin * g.h * g.w, a.y_img_stride = y_img_stride;
   a.mg = mg, a.K = cg * g.kh * kw, a.HW = g.oh * g.ow;
   a.ih = g.h, a.iw = g.w, a.ow = g.ow, a.kw = kw, a.taps = g.kh * kw, a.sh = g.sh, a.sw = g.sw, a.ph = g.ph, a.pw = g.pw, a.dh = g.dh, a.dw = g.dw;
-  auto magic = [](unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; };
-  a.m_taps = magic((unsigned)a.taps), a.m_kw = magic((unsigned)kw), a.m_ow = magic((unsigned)g.ow);
+  a.m_taps = ig_magic((unsigned)a.taps), a.m_kw = ig_magic((unsigned)kw), a.m_ow = ig_magic((unsigned)g.ow);
   a.chunks = (a.K + kIgK - 1) / kIgK;
   a.act = e.act;
   a.vec_w = (a.K % 4 == 0) && ((uintptr_t)w % 16 == 0);
@@ -354,27 +406,23 @@ int launch_conv2d_implicit(const float* x, const float* w, float* y, int64_t n, 
   IgEpi epi = {e.alpha, e.beta, e.res, e.affine, a.vec_y && ((uintptr_t)e.res % 16 == 0)};  // the residual's image stride is y's
   const IgEpi* ep = full ? &epi : nullptr;
   if (n == 0 || a.HW == 0) return MV_OK;
-  // channel tile: 64, 128 or 192 channels per workgroup, whichever pads the least (ties: the larger -- every gathered element
-  // then feeds more channels); pixel tile: 256 pixels with one channel tile per wave, else 128; small problems take 64-pixel
-  // tiles so that the grid still covers the chip
-  auto padded = [](long long v, long long t) { return (v + t - 1) / t * t; };
-  int ct = 3;
-  long long best = padded(mg, 192);
-  if (padded(mg, 128) < best) ct = 2, best = padded(mg, 128);
-  if (padded(mg, 64) < best) ct = 1, best = padded(mg, 64);
-  if (const char* ev = tune_env("MV_IG_CT")) ct = atoi(ev) >= 1 && atoi(ev) <= 3 ? atoi(ev) : ct;
-  const long long wgs256 = padded(mg, 64 * ct) / (64 * ct) * ((a.HW + 255) / 256) * n;
-  if (ct == 1) {
-    if (wgs256 >= 512 || a.HW > 4096) return ig_launch<1, 4>(a, ep, n, s);
-    if (padded(mg, 64) / 64 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<1, 2>(a, ep, n, s);
-    return ig_launch<1, 1>(a, ep, n, s);
-  }
-  if (ct == 2) {
-    if (padded(mg, 128) / 128 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<2, 2>(a, ep, n, s);
-    return ig_launch<2, 1>(a, ep, n, s);
-  }
-  if (padded(mg, 192) / 192 * ((a.HW + 127) / 128) * n >= 256) return ig_launch<3, 2>(a, ep, n, s);
-  return ig_launch<3, 1>(a, ep, n, s);
+  return ig_dispatch(a, ep, n, s, false);
+}
+
+int launch_conv_transpose4x4s2(const float* x, const float* w2, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,
+                               hipStream_t s) {
+  // the 2x2 / padding 1 convolution of the relaid weight on the (h + 1) x (wd + 1) window positions; y is the transposed conv's output
+  IgArgs a = {};
+  a.x = x, a.w = w2, a.bias = e.bias, a.y = y;
+  a.x_img_stride = (int64_t)cin * h * wd, a.y_img_stride = (int64_t)cout * 4 * h * wd;
+  a.mg = 4 * cout, a.K = cin * 4, a.HW = (h + 1) * (wd + 1);
+  a.ih = h, a.iw = wd, a.ow = wd + 1, a.kw = 2, a.taps = 4, a.sh = 1, a.sw = 1, a.ph = 1, a.pw = 1, a.dh = 1, a.dw = 1;
+  a.m_taps = ig_magic(4u), a.m_kw = ig_magic(2u), a.m_ow = ig_magic((unsigned)a.ow);
+  a.chunks = (a.K + kIgK - 1) / kIgK;
+  a.act = e.act;
+  a.vec_w = (uintptr_t)w2 % 16 == 0;  // K = 4 cin
+  a.vec_y = 0;                        // the TR store is element by element
+  return ig_dispatch(a, nullptr, n, s, true);
 }
 
 }  // namespace mv

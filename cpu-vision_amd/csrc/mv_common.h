@@ -379,6 +379,17 @@ int launch_mask_probs(const float* logits, const int64_t* labels, float* y, int6
 // shuffle (convnorm.hip, k_conv1x1_ct: the same plan, tiles and summation order; e.res must be null, e.affine 0)
 int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,
                              hipStream_t s);
+// ConvTranspose2d(kernel 4, stride 2, padding 1) + bias + activation: the implicit-GEMM kernel on the relaid (4 cout, cin, 2, 2) weight
+// whose store keeps, per phase, the window positions of that phase (conv_igemm.hip, k_conv_igemm<.., TR>: the summation order of
+// mv_conv2d_bias_act_f32; only e.bias and e.act are used).  The entry point has checked the extents the kernel's indices cover.
+int launch_conv_transpose4x4s2(const float* x, const float* w2, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,
+                               hipStream_t s);
+// Keypoint R-CNN's heatmaps_to_keypoints (keypoint.hip; semantics in mi355vision.h mv_heatmaps_to_keypoints_f32).  The entry point has
+// checked the arguments, the extents and the grid; r is positive and mh * mw <= kKpMaxPlane.
+constexpr int kKpMaxPlane = 16384;  // the heatmap is staged in LDS: 64 KiB
+bool heatmaps_to_keypoints_grid_fits(int64_t r, int k);
+int launch_heatmaps_to_keypoints(const float* maps, const float* rois, float* xy, float* scores, int64_t r, int k, int mh, int mw,
+                                 hipStream_t s);
 // ops.roi_pool / ps_roi_pool / ps_roi_align (roi_pool.hip; semantics in mi355vision.h).  Checked by the entry points as for
 // launch_roi_align; for the two position-sensitive ops c is a multiple of pooled_h * pooled_w.
 int launch_roi_pool(const float* x, const float* rois, float* y, int* argmax, int n, int c, int h, int w, int64_t k, int pooled_h,

@@ -25,6 +25,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               batch_images in front of a detection model (models/detection/transform.py)
   _mask       paste_masks_in_image / mask_probs (roi_heads.py paste_masks_in_image, maskrcnn_inference) and
               conv_transpose2d_bias_act, ConvTranspose2d(kernel 2, stride 2) + bias + activation (mask_rcnn.py conv5_mask)
+  _keypoint   heatmaps_to_keypoints (roi_heads.py) and conv_transpose2d_bias_act's kernel 4, stride 2, padding 1 geometry
+              (keypoint_rcnn.py kps_score_lowres) with its conv_transpose4x4_relayout
 The switches (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION, CONV2D_*) are set on this module only; the code behind it reads them
 here at call time (_lib.switch).
 
@@ -71,6 +73,7 @@ from ._layers import (_ACT_CODES, adaptive_avg_pool2d, _AFFINE_CODES, conv1x1_k_
                       conv3x3_k_slices, conv_norm_act, _CONV_WORKSPACE_BYTES, fold_batchnorm, inverted_residual,
                       inverted_residual_k_slices, _inverted_residual_workspace_bytes, linear_bias_relu, linear_k_slices,
                       max_pool2d, max_pool2d_2x2, normalized_conv2d_bias_relu)
+from ._keypoint import conv_transpose4x4_relayout, heatmaps_to_keypoints, MAX_HEATMAP_ELEMENTS  # noqa: F401
 from ._lib import max_value as _max_value  # noqa: F401
 from ._mask import conv_transpose2d_bias_act, conv_transpose2x2_relayout, mask_probs, paste_masks_in_image  # noqa: F401
 from ._misc import (center_crop, center_crop_image, _mean_std, normalize, normalize_image, resize, resize_image,  # noqa: F401

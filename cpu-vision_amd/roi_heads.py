@@ -9,11 +9,16 @@ also does: the boolean indexing by `valid` (one read-back), ops.batched_nms and 
 
 Numerics: DESIGN.md 3.25 and mi355vision.h mv_roi_detections_f32 -- every float operation is the reference's float32 operation,
 rounded once; exp is the correctly rounded float32 exp and the softmax sum is one ascending chain.  Inference only, float32 only:
-the matcher, the sampler and the losses of the reference are not built, the keypoint branch is not implemented.
+the matcher, the sampler and the losses of the reference are not built.
 
 With mask modules (mask_rcnn.py: this package's MultiScaleRoIAlign, MaskRCNNHeads and MaskRCNNPredictor) `forward` runs the
 reference's mask branch on the detected boxes and adds "masks" (N_i, 1, M, M) to every result: pooler -> mask head -> predictor ->
 F.mask_probs, which reads only the predicted label's plane of every roi.
+
+With keypoint modules (keypoint_rcnn.py: this package's MultiScaleRoIAlign, KeypointRCNNHeads and KeypointRCNNPredictor, all three
+or none) `forward` then runs the reference's keypoint branch on the detected boxes and adds "keypoints" (N_i, K, 3) and
+"keypoints_scores" (N_i, K): pooler -> keypoint head -> predictor -> ONE F.heatmaps_to_keypoints launch on the concatenated boxes of
+the whole batch, where the reference loops over the detections with a bicubic interpolate and two read-backs each.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ from . import functional as F
 from . import ops as box_ops
 from .rpn import BoxCoder
 
-__all__ = ["RoIHeads", "postprocess_detections_detailed"]
+__all__ = ["RoIHeads", "postprocess_detections_detailed", "check_keypoint_modules"]
 
 
 def postprocess_detections_detailed(class_logits: Tensor, box_regression: Tensor, proposals: List[Tensor], image_shapes: List[Tuple[int, int]],
@@ -54,10 +59,30 @@ def postprocess_detections_detailed(class_logits: Tensor, box_regression: Tensor
     return all_boxes, all_scores, all_labels
 
 
+def check_keypoint_modules(keypoint_roi_pool, keypoint_head, keypoint_predictor) -> None:
+    """The keypoint modules RoIHeads runs: this package's MultiScaleRoIAlign, KeypointRCNNHeads and KeypointRCNNPredictor, all three
+    or none.  Anything else raises NotImplementedError naming the argument -- another object would compute on another path, and one
+    module without the others would silently run no keypoint branch (as it does in the reference)."""
+    from .keypoint_rcnn import KeypointRCNNHeads, KeypointRCNNPredictor  # keypoint_rcnn imports faster_rcnn, which imports this module
+
+    given = (("keypoint_roi_pool", keypoint_roi_pool, box_ops.MultiScaleRoIAlign), ("keypoint_head", keypoint_head, KeypointRCNNHeads),
+             ("keypoint_predictor", keypoint_predictor, KeypointRCNNPredictor))
+    for name, module, kind in given:
+        if module is not None and not isinstance(module, kind):
+            raise NotImplementedError(f"RoIHeads: {name} is a {type(module).__name__}, and the keypoint branch on the MI355X path runs "
+                                      f"this package's {kind.__name__} only")
+    missing = [name for name, module, _ in given if module is None]
+    if 0 < len(missing) < 3:
+        present = [name for name, module, _ in given if module is not None]
+        raise NotImplementedError(f"RoIHeads: {', '.join(present)} given without {', '.join(missing)}: the keypoint branch on the MI355X "
+                                  "path takes its three modules together")
+
+
 class RoIHeads(nn.Module):
-    """roi_heads.py:496-876, inference: forward(features, proposals, image_shapes) -> ([{boxes, labels, scores[, masks]}] per image,
-    {}).  The training arguments are kept as given; the mask modules must be this package's (mask_rcnn.py), any other object and
-    every keypoint module raises NotImplementedError."""
+    """roi_heads.py:496-876, inference: forward(features, proposals, image_shapes) -> ([{boxes, labels, scores[, masks][, keypoints,
+    keypoints_scores]}] per image, {}).  The training arguments are kept as given; the mask modules must be this package's
+    (mask_rcnn.py) and the keypoint modules this package's, all three together (keypoint_rcnn.py); any other object raises
+    NotImplementedError."""
 
     __annotations__ = {"box_coder": BoxCoder}
 
@@ -77,11 +102,7 @@ class RoIHeads(nn.Module):
             if module is not None and not isinstance(module, kind):
                 raise NotImplementedError(f"RoIHeads: {name} is a {type(module).__name__}, and the mask branch on the MI355X path runs "
                                           f"this package's {kind.__name__} only")
-        for name, module in (("keypoint_roi_pool", keypoint_roi_pool), ("keypoint_head", keypoint_head),
-                             ("keypoint_predictor", keypoint_predictor)):
-            if module is not None:
-                raise NotImplementedError(f"RoIHeads: {name} is given, and the keypoint branch is not on the MI355X path "
-                                          "(the box and mask branches are)")
+        check_keypoint_modules(keypoint_roi_pool, keypoint_head, keypoint_predictor)
         self.box_similarity = box_ops.box_iou
         # used during training (kept as given: the matcher and the sampler are not built)
         self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
@@ -135,8 +156,6 @@ class RoIHeads(nn.Module):
                 targets: Optional[List[Dict[str, Tensor]]] = None) -> Tuple[List[Dict[str, Tensor]], Dict[str, Tensor]]:
         if self.training or targets is not None:
             raise RuntimeError("the MI355X RoIHeads is inference only: call .eval() and pass no targets")
-        if self.has_keypoint():
-            raise NotImplementedError("RoIHeads: the keypoint branch is not on the MI355X path")
         for f in features.values():
             if f.dtype != torch.float32:
                 raise TypeError(f"RoIHeads computes in float32. Got features {f.dtype}")
@@ -154,6 +173,12 @@ class RoIHeads(nn.Module):
             mask_deps = (*deps, *self.mask_head.parameters(), *self.mask_predictor.parameters())
             for r, probs in zip(result, self.mask_branch(features, boxes, labels, image_shapes)):
                 r["masks"] = _lib.forward_only(probs, "RoIHeads.forward", *mask_deps)
+        if self.has_keypoint():
+            check_keypoint_modules(self.keypoint_roi_pool, self.keypoint_head, self.keypoint_predictor)
+            kp_deps = (*deps, *self.keypoint_head.parameters(), *self.keypoint_predictor.parameters())
+            for r, (kps, kp_scores) in zip(result, self.keypoint_branch(features, boxes, image_shapes)):
+                r["keypoints"] = _lib.forward_only(kps, "RoIHeads.forward", *kp_deps)
+                r["keypoints_scores"] = _lib.forward_only(kp_scores, "RoIHeads.forward", *kp_deps)
         return result, {}
 
     def mask_branch(self, features: Dict[str, Tensor], boxes: List[Tensor], labels: List[Tensor],
@@ -172,3 +197,21 @@ class RoIHeads(nn.Module):
             mask_logits = self.mask_predictor(mask_features)
             probs = F.mask_probs(mask_logits, torch.cat(labels))
         return list(probs.split(boxes_per_image, dim=0))
+
+    def keypoint_branch(self, features: Dict[str, Tensor], boxes: List[Tensor],
+                        image_shapes: List[Tuple[int, int]]) -> List[Tuple[Tensor, Tensor]]:
+        """roi_heads.py:852-874, inference: keypoint_roi_pool on the detected boxes -> keypoint_head -> keypoint_predictor -> ONE
+        F.heatmaps_to_keypoints call on the concatenated boxes (keypointrcnn_inference calls it per image, and it loops over the
+        detections), split per image into ((N_i, K, 3), (N_i, K)).  Without a detection in the whole batch nothing is launched and
+        every image gets empty tensors."""
+        boxes_per_image = [int(b.shape[0]) for b in boxes]
+        with torch.no_grad():
+            if sum(boxes_per_image) == 0:
+                k = int(self.keypoint_predictor.out_channels)
+                return [(b.new_empty((0, k, 3)), b.new_empty((0, k))) for b in boxes]
+            rois = [b.detach() for b in boxes]
+            keypoint_features = self.keypoint_roi_pool(features, rois, image_shapes)
+            keypoint_features = self.keypoint_head(keypoint_features)
+            keypoint_logits = self.keypoint_predictor(keypoint_features)
+            xy, scores = F.heatmaps_to_keypoints(keypoint_logits, torch.cat(rois))
+        return list(zip(xy.split(boxes_per_image, dim=0), scores.split(boxes_per_image, dim=0)))

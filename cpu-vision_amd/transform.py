@@ -144,6 +144,10 @@ class GeneralizedRCNNTransform(nn.Module):
                 masks = pred["masks"]
                 masks = F.paste_masks_in_image(masks, boxes, o_im_s)
                 result[i]["masks"] = masks
+            if "keypoints" in pred:
+                keypoints = pred["keypoints"]
+                keypoints = resize_keypoints(keypoints, im_s, o_im_s)
+                result[i]["keypoints"] = keypoints
         return result
 
     def __repr__(self) -> str:
@@ -153,6 +157,19 @@ class GeneralizedRCNNTransform(nn.Module):
         format_string += f"{_indent}Resize(min_size={self.min_size}, max_size={self.max_size}, mode='bilinear')"
         format_string += "\n)"
         return format_string
+
+
+def resize_keypoints(keypoints: Tensor, original_size: List[int], new_size: List[int]) -> Tensor:
+    """transform.py:284-298, the eager branch: a torch composition, as resize_boxes"""
+    ratios = [
+        torch.tensor(s, dtype=torch.float32, device=keypoints.device) / torch.tensor(s_orig, dtype=torch.float32, device=keypoints.device)
+        for s, s_orig in zip(new_size, original_size)
+    ]
+    ratio_h, ratio_w = ratios
+    resized_data = keypoints.clone()
+    resized_data[..., 0] *= ratio_w
+    resized_data[..., 1] *= ratio_h
+    return resized_data
 
 
 def resize_boxes(boxes: Tensor, original_size: List[int], new_size: List[int]) -> Tensor:

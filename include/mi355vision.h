@@ -924,6 +924,57 @@ int mv_mask_probs_f32(const float* logits, const int64_t* labels, float* y, int6
 int mv_conv_transpose2x2_bias_act_f32(const float* x, const float* w4, const float* bias4, float* y, int64_t n, int cin, int h, int w,
                                       int cout, int act, void* stream);
 
+/* ---- The keypoint branch of Keypoint R-CNN (models/detection/keypoint_rcnn.py's ConvTranspose2d(kernel 4, stride 2, padding 1);
+ * roi_heads.py heatmaps_to_keypoints).  All tensors DEVICE float32.
+ *
+ * mv_conv_transpose4x4s2_bias_act_f32: ConvTranspose2d(kernel_size 4, stride 2, padding 1, output_padding 0, groups 1, dilation 1) +
+ * bias + activation, x (n, cin, h, w) -> y (n, cout, 2 h, 2 w).  With xp the input zero-padded by one pixel on every side:
+ *   y[b, co, 2 m + py, 2 n + px] = act(bias4[q] + sum_ci sum_ty sum_tx xp[b, ci, m + py + ty, n + px + tx] * w2[q, ci, ty, tx])
+ *   q = 4 co + 2 py + px,   py, px, ty, tx in {0, 1}
+ * `w2` is the RELAID weight (4 cout, cin, 2, 2), w2[q, ci, ty, tx] = torch's weight[ci, co, 3 - py - 2 ty, 3 - px - 2 tx]; `bias4`
+ * (4 cout) the bias with every entry repeated four times, or NULL.  This is the 2x2 convolution with padding 1 of w2, evaluated on
+ * the (h + 1) x (w + 1) grid of window positions, of which phase (py, px) keeps position (m + py, n + px).  The summation order is
+ * mv_conv2d_bias_act_f32's: one accumulator per output, ascending (ci, ty, tx) from +0, then `+ bias`, then the activation
+ * (MV_ACT_NONE / RELU / RELU6) -- bit for bit mv_conv2d_bias_act_f32(x, w2, bias4, padding 1) followed by that strided gather.  ONE
+ * launch of the implicit-GEMM kernel with a transposed store: the (n, 4 cout, h + 1, w + 1) intermediate never reaches memory and y is
+ * written once, element by element; x, w2 and y may start at any 4-byte address.  Element offsets are 64-bit.
+ * MV_ERR_UNSUPPORTED beyond the kernel's index range: cin >= 16384, w + 1 >= 4096, (h + 1) (w + 1) >= 2^20, cin h w >= 2^30,
+ * cout > (2^31 - 1) / 4 or n > 65535.
+ *
+ * mv_heatmaps_to_keypoints_f32: maps (r, k, mh, mw), rois (r, 4) rows (x1, y1, x2, y2) -> xy (r, k, 3) rows (x, y, visibility) and
+ * scores (r, k), ONE launch, one workgroup per (roi, keypoint).  Every operation is rounded once to float32 and never contracted,
+ * except the one fma named below.  Per roi:
+ *   w  = max(x2 - x1, 1),  h = max(y2 - y1, 1),   rw = (int)ceil(w),  rh = (int)ceil(h)
+ *   cx = w / float32(rw),  cy = h / float32(rh)                                    (correctly rounded divisions)
+ *   roi_map[k] = bicubic(maps[r, k]; (mh, mw) -> (rh, rw))                          (never materialised)
+ *   pos = the first row-major index of the maximum of roi_map[k]; a NaN counts as larger than every number and the first NaN wins
+ *         (torch's CPU argmax); -0.0 and +0.0 are equal;  yi = pos / rw,  xi = pos % rw
+ *   xy[r, k] = ((float)xi + 0.5f) * cx + x1,  ((float)yi + 0.5f) * cy + y1,  1.0f;    scores[r, k] = roi_map[k][yi, xi]
+ * The bicubic resize is the library's own statement of interpolate(mode="bicubic", align_corners=False, antialias=False), A = -0.75.
+ * Per axis, with `in` and `out` its two sizes and d the output index:
+ *   s    = float32(in) / float32(out)
+ *   real = fma(s, d + 0.5f, -0.5f)                        (the one fma, as in mv_interpolate_bilinear_f32; NOT clamped at 0)
+ *   i0   = min((int)floor(real), in - 1),   t = clamp(real - (float)i0, 0, 1)
+ *   taps clamp(i0 - 1 + j, 0, in - 1), j = 0 .. 3, with the weights c2(t + 1), c1(t), c1(1 - t), c2((1 - t) + 1)
+ *   c1(x) = ((A + 2) x - (A + 3)) x x + 1,   c2(x) = ((A x - 5 A) x + 8 A) x - 4 A      (left to right, every operation rounded)
+ * and the value is sum_i wy_i * (sum_j wx_j * src[y_i, x_j]): the inner sum first, each sum from its first product with the next three
+ * added in order, every product and every sum rounded.  With out == in, real == d, t == 0 and the weights are 0, 1, 0, 0: the map
+ * itself for finite values.  NaN and +-inf follow from the formula.  torch's CPU kernel differs from this statement by a few
+ * 2^-24 max|x| (DESIGN.md 3.29 has the bound).
+ *   Domain.  A roi with a coordinate that is not finite, or with rw or rh above 2^15, gives the row +0.0 (x, y, visibility and score)
+ *   and nothing is read through it (the reference would fail or try to allocate the resized map).  mh * mw > 16384 (the heatmap is
+ *   staged in LDS) is MV_ERR_UNSUPPORTED.
+ * The rois are read on the device; nothing is allocated, read back or synchronised, and r is only a grid extent.
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: a null pointer (bias4 may be null), a non-positive
+ * k / mh / mw / cin / cout / h / w, a negative r or n, an activation code other than the three, an output that overlaps an input or
+ * the other output (byte ranges), sizes that exceed the address space, more workgroups than one launch grid holds.
+ * r == 0 / n == 0 is a no-op that touches no pointer. */
+int mv_conv_transpose4x4s2_bias_act_f32(const float* x, const float* w2, const float* bias4, float* y, int64_t n, int cin, int h, int w,
+                                        int cout, int act, void* stream);
+int mv_heatmaps_to_keypoints_f32(const float* maps, const float* rois, float* xy, float* scores, int64_t r, int k, int mh, int mw,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
