@@ -6,7 +6,8 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   _layers         conv+ReLU, pools, linear, conv_norm_act, inverted_residual (what nn and mobilenet run on)
   _misc           resize / center_crop / to_dtype / normalize (+ kernels), to_float_normalize
   _detection      rpn_topk / rpn_decode / box_decode (what rpn runs on), roi_detections (what roi_heads runs on), retinanet_topk /
-                  retinanet_decode (what retinanet runs on)
+                  retinanet_decode (what retinanet runs on), fcos_topk / fcos_decode (what fcos runs on)
+  _norm           group_norm_act: GroupNorm (+ ReLU), float64 statistics, two launches
   _crop, _mix     pad / crop / flip / erase / resized_crop; MixUp / CutMix on a batch
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
@@ -28,6 +29,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   retinanet       RetinaNetClassificationHead / RetinaNetRegressionHead / RetinaNetHead (the towers' first convs as one launch),
                   RetinaNet: threshold + top-k over every (anchor, class) of the heads' NCHW maps, many workgroups per (image,
                   level), then decode + clip + sigmoid of the selected candidates only, then batched_nms; retinanet_resnet50_fpn
+  fcos            FCOSClassificationHead / FCOSRegressionHead / FCOSHead (towers of conv, then GroupNorm + ReLU: _norm.group_norm_act),
+                  FCOS: threshold + top-k on sqrt(sigmoid(cls) * sigmoid(centerness)), BoxLinearCoder's linear decode of the selected
+                  candidates only, then batched_nms; fcos_resnet50_fpn
   ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
                   ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*); box_iou / generalized_box_iou /
                   distance_box_iou, masks_to_boxes, MultiScaleRoIAlign, box_area / box_convert / clip_boxes_to_image /
@@ -41,7 +45,7 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
 
 The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias package at the repo root).
 """
-from . import (anchor_utils, backbone_utils, faster_rcnn, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
+from . import (anchor_utils, backbone_utils, faster_rcnn, fcos, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
                keypoint_rcnn, mask_rcnn, mobilenet, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, transform, transforms, tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
@@ -58,6 +62,7 @@ from .mask_rcnn import MaskRCNN, MaskRCNNHeads, MaskRCNNPredictor, maskrcnn_resn
 from .keypoint_rcnn import KeypointRCNN, KeypointRCNNHeads, KeypointRCNNPredictor, keypointrcnn_resnet50_fpn  # noqa: F401
 from .retinanet import (RetinaNet, RetinaNetClassificationHead, RetinaNetHead, RetinaNetRegressionHead,  # noqa: F401
                         retinanet_resnet50_fpn)
+from .fcos import FCOS, FCOSClassificationHead, FCOSHead, FCOSRegressionHead, fcos_resnet50_fpn  # noqa: F401
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
                   generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401

@@ -1,7 +1,8 @@
 """The functional entries of the detection heads (models/detection/rpn.py, roi_heads.py, retinanet.py, _utils.py BoxCoder): rpn_topk,
 rpn_decode and box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip), roi_detections over
 mv_roi_detections_f32 (csrc/roi_heads.hip), retinanet_topk and retinanet_decode over mv_retinanet_topk_f32 / mv_retinanet_decode_f32
-(csrc/retinanet.hip).  float32, forward-only; the argument checks fire before a device is needed.  Every name
+(csrc/retinanet.hip), fcos_topk and fcos_decode over mv_fcos_topk_f32 / mv_fcos_decode_f32 (the same file: fcos.py's centerness score and
+BoxLinearCoder.decode).  float32, forward-only; the argument checks fire before a device is needed.  Every name
 here is re-exported by `functional`.
 """
 from __future__ import annotations
@@ -202,6 +203,95 @@ def retinanet_decode(logits: List[torch.Tensor], deltas: List[torch.Tensor], idx
 def retinanet_topk_chunk() -> int:
     """The elements of an (image, level) class map one stage-1 workgroup of retinanet_topk reads (mv_retinanet_topk_chunk)."""
     return int(_lib.load().mv_retinanet_topk_chunk())
+
+
+def _fcos_maps(name: str, cls_logits, ctrness, num_classes):
+    """The checks of FCOS's per-level class maps (n, num_classes, H_l, W_l) and centerness maps (n, 1, H_l, W_l): one anchor per
+    location -> the shapes [(n, 1, H_l, W_l)]."""
+    shapes = _class_maps(name, cls_logits, num_classes)
+    if any(a != 1 for _, a, _, _ in shapes):
+        raise RuntimeError(f"{name}: one anchor per location: cls_logits[l] should have {num_classes} channels, got "
+                           f"{[int(m.shape[1]) for m in cls_logits]}")
+    cshapes = _level_maps(name, ctrness, "ctrness", 1) if isinstance(ctrness, (list, tuple)) and len(ctrness) == len(cls_logits) else None
+    if cshapes is None or cshapes != shapes:
+        raise RuntimeError(f"{name}: ctrness should hold one map per level of cls_logits, of the same batch and size with one channel")
+    return shapes
+
+
+def fcos_topk(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], num_classes: int, k: int, score_thresh: float) -> torch.Tensor:
+    """FCOS.postprocess_detections' score sqrt(sigmoid(cls) * sigmoid(centerness)), `> score_thresh` and per-level topk (fcos.py) on the
+    head's own NCHW maps: cls_logits[l] (N, num_classes, H_l, W_l), ctrness[l] (N, 1, H_l, W_l) -> idx (N, Ktot) int32,
+    Ktot = sum_l min(k, H_l W_l num_classes), as retinanet_topk: per image, level after level, the flat indices position * num_classes +
+    class (offset by the positions of the levels before) of the min(k, passing) greatest scores in stable descending order, then -1."""
+    shapes = _fcos_maps("fcos_topk", cls_logits, ctrness, num_classes)
+    if not isinstance(k, int) or k < 1:
+        raise ValueError(f"fcos_topk: k must be a positive int, got {k!r}")
+    if k > MAX_RPN_TOPK:
+        raise _lib.Mi355VisionError(f"fcos_topk: k up to {MAX_RPN_TOPK}, got {k}")
+    for m in (*cls_logits, *ctrness):
+        _lib.require_device(m, "fcos_topk input")
+    lib = _lib.load()
+    l0, n = cls_logits[0], shapes[0][0]
+    total = sum(min(k, h * w * num_classes) for _, _, h, w in shapes)
+    with _lib.on_device_of(l0):
+        maps, cmaps = [_dense_images(m) for m in cls_logits], [_dense_images(m) for m in ctrness]
+        idx = torch.empty((n, total), dtype=torch.int32, device=l0.device)
+        if n:
+            hs, ws, as_ = _tables(shapes)
+            nbytes = int(lib.mv_retinanet_topk_workspace_bytes(n, hs, ws, as_, len(maps), num_classes, k))
+            if not nbytes:
+                raise _lib.Mi355VisionError(f"fcos_topk: {n} images are more than one call takes")
+            buf, ws_ptr, nbytes = _lib.workspace(nbytes, l0.device)
+            _lib.launch(lib.mv_fcos_topk_f32, l0, _lib.pointer_table(maps), _lib.pointer_table(cmaps), hs, ws, as_, _img_strides(maps),
+                        _img_strides(cmaps), len(maps), num_classes, n, k, float(score_thresh), idx.data_ptr(), ws_ptr, nbytes)
+    return idx
+
+
+def fcos_decode(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], bbox_regression: List[torch.Tensor], idx: torch.Tensor,
+                cell_anchors: List[torch.Tensor], strides: Sequence[Tuple[int, int]], image_sizes,
+                num_classes: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The rest of FCOS.postprocess_detections before the nms for the candidates idx (N, K) of fcos_topk, ONE launch, one lane per
+    candidate: the anchor of position idx // num_classes from cell_anchors[l] (1, 4) and strides[l], label idx % num_classes,
+    BoxLinearCoder(normalize_by_size=True).decode with max(bbox_regression, 0) (the head's ReLU), clip_boxes_to_image, the score
+    recomputed -> boxes (N, K, 4), scores (N, K), labels (N, K) int64, valid (N, K) bool (False, with zeros, for the -1 padding and any
+    other index outside the pyramid)."""
+    name = "fcos_decode"
+    shapes = _fcos_maps(name, cls_logits, ctrness, num_classes)
+    dshapes = _level_maps(name, bbox_regression, "bbox_regression", 4, [1] * len(shapes)) \
+        if isinstance(bbox_regression, (list, tuple)) and len(bbox_regression) == len(cls_logits) else None
+    if dshapes is None or dshapes != shapes:
+        raise RuntimeError(f"{name}: bbox_regression should hold one map per level of cls_logits, of the same batch and size with 4 channels")
+    num, n = len(shapes), shapes[0][0]
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
+        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, K)")
+    if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or any(tuple(c.shape) != (1, 4) for c in cell_anchors):
+        raise RuntimeError(f"{name}: cell_anchors should hold one (1, 4) tensor per level")
+    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
+        raise RuntimeError(f"{name}: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
+    sizes = _image_sizes(name, image_sizes, lambda t: tuple(t.shape) == (n, 2), f"{n} rows")
+    for m in (*cls_logits, *ctrness, *bbox_regression, idx):
+        _lib.require_device(m, f"{name} input")
+    lib = _lib.load()
+    l0 = cls_logits[0]
+    k = int(idx.shape[1])
+    with _lib.on_device_of(l0):
+        lmaps, cmaps, dmaps = ([_dense_images(m) for m in maps] for maps in (cls_logits, ctrness, bbox_regression))
+        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
+        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
+        ix = idx.contiguous()
+        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
+        labels = torch.empty((n, k), dtype=torch.int64, device=l0.device)
+        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
+        if n and k:
+            hs, ws, as_ = _tables(shapes)
+            sh = (C.c_int * num)(*[int(s[0]) for s in strides])
+            sw = (C.c_int * num)(*[int(s[1]) for s in strides])
+            _lib.launch(lib.mv_fcos_decode_f32, l0, _lib.pointer_table(lmaps), _lib.pointer_table(cmaps), _lib.pointer_table(dmaps), hs, ws, as_,
+                        _img_strides(lmaps), _img_strides(cmaps), _img_strides(dmaps), sh, sw, num, num_classes, base.data_ptr(),
+                        sizes.data_ptr(), ix.data_ptr(), n, k, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
+    deps = (*cls_logits, *ctrness, *bbox_regression)
+    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(scores, name, *deps), labels, valid.view(torch.bool)
 
 
 def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[float, float, float, float],

@@ -1298,18 +1298,40 @@ static PyramidMaps topk_maps(const float* const* logits, const int* hs, const in
   m.logits = logits, m.hs = hs, m.ws = ws, m.as = as, m.logit_strides = img_strides, m.levels = levels;
   return m;
 }
+// ctr: the entry takes centerness maps too (FCOS): one anchor per location, m.ctrness[l] a map (n, 1, hs[l], ws[l]).
+static int one_anchor_check(const char* op, const PyramidMaps& m) {
+  for (int l = 0; l < m.levels; ++l)
+    if (m.as[l] != 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: one anchor per location, level %d has %d", op, l, m.as[l]);
+  return MV_OK;
+}
+static int ctr_check(const char* op, const PyramidMaps& m, int64_t n, ByteRange* ins) {
+  if (!m.ctrness || !m.ctr_strides) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  for (int l = 0; l < m.levels; ++l) {
+    const int64_t hw = (int64_t)m.hs[l] * m.ws[l];
+    if (!m.ctrness[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+    if (m.ctr_strides[l] < hw || m.ctr_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of the centerness of level %d, its map has %lld elements", op,
+                       (long long)m.ctr_strides[l], l, (long long)hw);
+    ins[l] = {m.ctrness[l], ((n - 1) * m.ctr_strides[l] + hw) * 4};
+  }
+  return MV_OK;
+}
 static int topk_check(const char* op, TopkBytes bytes, const PyramidMaps& m, int classes, int64_t n, int k, const int* idx, const void* workspace,
-                      int64_t workspace_bytes) {
+                      int64_t workspace_bytes, bool ctr = false) {
   if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad image count %lld", op, (long long)n);
   if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: k must be positive, got %d", op, k);
   int64_t taken;
   if (int rc = levels_check(op, m.hs, m.ws, m.as, m.levels, classes, k, &taken)) return rc;
+  if (ctr)
+    if (int rc = one_anchor_check(op, m)) return rc;
   if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "%s: k up to %d, got %d", op, kRpnMaxK, k);
   if (n == 0) return 1;
   if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images exceed the launch grid", op, (long long)n);
   if (!m.logits || !m.logit_strides || !idx) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
   const int64_t need = bytes(n, m.hs, m.ws, m.as, m.levels, classes, k, taken);
-  ByteRange ins[kMaxRpnLevels];
+  ByteRange ins[2 * kMaxRpnLevels];
+  if (ctr)
+    if (int rc = ctr_check(op, m, n, ins + m.levels)) return rc;
   for (int l = 0; l < m.levels; ++l) {
     const int64_t nl = (int64_t)m.as[l] * m.hs[l] * m.ws[l] * classes;
     if (!m.logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
@@ -1325,7 +1347,7 @@ static int topk_check(const char* op, TopkBytes bytes, const PyramidMaps& m, int
   if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned", op);
   if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx must be 4-byte aligned", op);
   const ByteRange outs[2] = {{idx, n * taken * 4}, {workspace, need}};
-  if (!outputs_clear(outs, 2, ins, m.levels))
+  if (!outputs_clear(outs, 2, ins, ctr ? 2 * m.levels : m.levels))
     return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx and the workspace must not overlap an input or each other", op);
   return 0;
 }
@@ -1333,10 +1355,13 @@ static int topk_check(const char* op, TopkBytes bytes, const PyramidMaps& m, int
 // The arguments of a decode entry, in the order of the refusals: 0 launch, 1 nothing to do, < 0 the error.  out64 is the int64
 // output, `out64_name` its word in the alignment message.
 static int decode_check(const char* op, const char* out64_name, const PyramidMaps& m, int classes, const float* image_sizes, const int* idx,
-                        int64_t n, int64_t k, const float* boxes, const float* scores, const int64_t* out64, const unsigned char* valid) {
+                        int64_t n, int64_t k, const float* boxes, const float* scores, const int64_t* out64, const unsigned char* valid,
+                        bool ctr = false) {
   if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld, k=%lld", op, (long long)n, (long long)k);
   int64_t taken;
   if (int rc = levels_check(op, m.hs, m.ws, m.as, m.levels, classes, 1, &taken)) return rc;
+  if (ctr)
+    if (int rc = one_anchor_check(op, m)) return rc;
   if (!m.strides_h || !m.strides_w) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null level table", op);
   for (int l = 0; l < m.levels; ++l)
     if (m.strides_h[l] < 0 || m.strides_w[l] < 0 || (int64_t)m.strides_h[l] * m.hs[l] > 0x7fffffffLL ||
@@ -1350,7 +1375,12 @@ static int decode_check(const char* op, const char* out64_name, const PyramidMap
     return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
   if ((uintptr_t)out64 % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: %s must be 8-byte aligned", op, out64_name);
   if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx must be 4-byte aligned", op);
-  ByteRange ins[2 * kMaxRpnLevels + 3];
+  ByteRange ins[3 * kMaxRpnLevels + 3];
+  int n_in = 2 * m.levels + 3;
+  if (ctr) {
+    if (int rc = ctr_check(op, m, n, ins + n_in)) return rc;
+    n_in += m.levels;
+  }
   int64_t base_rows = 0;
   for (int l = 0; l < m.levels; ++l) {
     const int64_t al = (int64_t)m.as[l] * m.hs[l] * m.ws[l], nl = al * classes;
@@ -1365,7 +1395,7 @@ static int decode_check(const char* op, const char* out64_name, const PyramidMap
   }
   ins[2 * m.levels] = {m.base_anchors, base_rows * 16}, ins[2 * m.levels + 1] = {image_sizes, n * 8}, ins[2 * m.levels + 2] = {idx, n * k * 4};
   const ByteRange outs[4] = {{boxes, n * k * 16}, {scores, n * k * 4}, {out64, n * k * 8}, {valid, n * k}};
-  if (!outputs_clear(outs, 4, ins, 2 * m.levels + 3))
+  if (!outputs_clear(outs, 4, ins, n_in))
     return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the outputs must not overlap an input or each other", op);
   return 0;
 }
@@ -1466,6 +1496,84 @@ int mv_retinanet_decode_f32(const float* const* logits, const float* const* delt
     return rc < 0 ? rc : MV_OK;
   return launch_retinanet_decode(m, classes, image_sizes, idx, n, k, decode_coef(wx, wy, ww, wh, clip), boxes, scores, labels, valid,
                                  (hipStream_t)stream);
+}
+
+// ---- FCOS threshold + top-k / decode: retinanet.hip ------------------------------------------------------------------------------------
+// RetinaNet's checks with the centerness maps (topk_check / decode_check with ctr); the workspace is
+// mv_retinanet_topk_workspace_bytes'.
+int mv_fcos_topk_f32(const float* const* logits, const float* const* ctrness, const int* hs, const int* ws, const int* as,
+                     const int64_t* img_strides, const int64_t* ctr_strides, int levels, int classes, int64_t n, int k, double score_thresh,
+                     int* idx, void* workspace, int64_t workspace_bytes, void* stream) {
+  PyramidMaps m = topk_maps(logits, hs, ws, as, img_strides, levels);
+  m.ctrness = ctrness, m.ctr_strides = ctr_strides;
+  if (int rc = topk_check("fcos_topk", retinanet_topk_bytes, m, classes, n, k, idx, workspace, workspace_bytes, true)) return rc < 0 ? rc : MV_OK;
+  return launch_fcos_topk(m, classes, (int)n, k, (float)score_thresh, idx, workspace, (hipStream_t)stream);
+}
+
+int mv_fcos_decode_f32(const float* const* logits, const float* const* ctrness, const float* const* deltas, const int* hs, const int* ws,
+                       const int* as, const int64_t* logit_strides, const int64_t* ctr_strides, const int64_t* delta_strides,
+                       const int* strides_h, const int* strides_w, int levels, int classes, const float* base_anchors,
+                       const float* image_sizes, const int* idx, int64_t n, int64_t k, float* boxes, float* scores, int64_t* labels,
+                       unsigned char* valid, void* stream) {
+  const PyramidMaps m = {logits, deltas, hs, ws, as, logit_strides, delta_strides, strides_h, strides_w, levels, base_anchors, ctrness, ctr_strides};
+  if (int rc = decode_check("fcos_decode", "labels", m, classes, image_sizes, idx, n, k, boxes, scores, labels, valid, true))
+    return rc < 0 ? rc : MV_OK;
+  return launch_fcos_decode(m, classes, image_sizes, idx, n, k, boxes, scores, labels, valid, (hipStream_t)stream);
+}
+
+// ---- GroupNorm (+ ReLU): groupnorm.hip ---------------------------------------------------------------------------------------------
+int mv_group_norm_chunk(void) { return kGnChunk; }
+
+// 0 and the slabs' extent, or the error: the shape, the groups and the launch grid
+static int group_norm_shape(int64_t n, int c, int h, int w, int groups, int64_t* m, int64_t* blocks) {
+  if (n < 0 || c < 0 || h < 0 || w < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: negative size (n=%lld c=%d h=%d w=%d)", (long long)n, c, h, w);
+  if (groups < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: groups must be positive, got %d", groups);
+  if (c % groups) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: %d channels are not divisible by %d groups", c, groups);
+  *m = (int64_t)(c / groups) * h * w;
+  if ((int64_t)h * w > 0x7fffffffLL || *m > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "group_norm_act: a group of %lld elements exceeds the 32-bit index", (long long)*m);
+  *blocks = *m ? n * groups * group_norm_chunks(*m) : 0;
+  if (n > 0x7fffffffLL || *blocks > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "group_norm_act: %lld workgroups exceed the launch grid", (long long)*blocks);
+  return MV_OK;
+}
+
+int64_t mv_group_norm_workspace_bytes(int64_t n, int c, int h, int w, int groups) {
+  int64_t m, blocks;
+  if (group_norm_shape(n, c, h, w, groups, &m, &blocks)) return 0;
+  return blocks * 16;
+}
+
+int mv_group_norm_act_f32(const float* x, float* y, const float* weight, const float* bias, int64_t n, int c, int h, int w, int groups,
+                          int64_t x_stride, int64_t y_stride, double eps, int relu, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+  int64_t m, blocks;
+  if (int rc = group_norm_shape(n, c, h, w, groups, &m, &blocks)) return rc;
+  if (!(eps > 0) || eps > 3.0e38 || !((float)eps > 0.f))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: eps must be positive and finite in float32, got %g", eps);
+  if (blocks == 0) return MV_OK;
+  const int64_t image = (int64_t)c * h * w;
+  if (x_stride < image || y_stride < image || x_stride > 0x7fffffffffffLL / n || y_stride > 0x7fffffffffffLL / n)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: image strides (%lld, %lld), an image has %lld elements", (long long)x_stride,
+                     (long long)y_stride, (long long)image);
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: null pointer");
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: x and y must be 4-byte aligned");
+  const ByteRange xr = {x, ((n - 1) * x_stride + image) * 4}, yr = {y, ((n - 1) * y_stride + image) * 4};
+  // in place exactly (the same pointer and stride) or apart
+  if (!(x == y && x_stride == y_stride) && ranges_overlap(xr, yr))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: y must be x itself (in place) or must not overlap it");
+  if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: needs a workspace");
+  if (workspace_bytes < blocks * 16)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: workspace of %lld bytes, need %lld (mv_group_norm_workspace_bytes)",
+                     (long long)workspace_bytes, (long long)(blocks * 16));
+  if ((uintptr_t)workspace % 16) return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: the workspace must be 16-byte aligned");
+  const ByteRange wr = {workspace, blocks * 16};
+  const ByteRange params[2] = {{weight, weight ? c * 4LL : 0}, {bias, bias ? c * 4LL : 0}};
+  if (ranges_overlap(wr, xr) || ranges_overlap(wr, yr) || ranges_overlap(wr, params[0]) || ranges_overlap(wr, params[1]) ||
+      ranges_overlap(yr, params[0]) || ranges_overlap(yr, params[1]))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: the workspace and y must not overlap an input or each other");
+  return launch_group_norm_act(x, y, weight, bias, n, c, h, w, groups, x_stride, y_stride, (float)eps, relu != 0, workspace,
+                               (hipStream_t)stream);
 }
 
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------

@@ -34,6 +34,24 @@ __device__ inline float clamp0(float v, float hi) { return v != v ? v : (v < 0.f
 // 1 / (1 + E(-x)), every operation rounded once to float32, the division correctly rounded
 __device__ inline float sigmoid_cr(float x) { return __fdiv_rn(1.f, __fadd_rn(1.f, exp_cr(-x))); }
 
+// The correctly rounded float32 square root, through float64 as exp_cr (53 >= 2 * 24 + 2 bits: the second rounding is innocuous).
+// __fsqrt_rn is the native 1-ulp instruction unless the headers are built with rounded operations.
+__device__ inline float sqrt_cr(float v) { return (float)__builtin_sqrt((double)v); }
+
+// FCOS's score of a candidate (fcos.py postprocess_detections): sqrt(sigmoid(cls) * sigmoid(centerness)), each operation rounded once
+__device__ inline float fcos_score(float cls, float ctr) { return sqrt_cr(__fmul_rn(sigmoid_cr(cls), sigmoid_cr(ctr))); }
+
+// BoxLinearCoder(normalize_by_size=True).decode (_utils.py) of one anchor with the four distances r (left, top, right, bottom in
+// units of the anchor's sides): linear in the anchor's size, no exp.  max(r, 0) first -- the head's ReLU, the same bits on a map
+// that is rectified already (a NaN stays).
+__device__ inline void decode_linear(float x1, float y1, float x2, float y2, float r0, float r1, float r2, float r3, float (&out)[4]) {
+  r0 = r0 < 0.f ? 0.f : r0, r1 = r1 < 0.f ? 0.f : r1, r2 = r2 < 0.f ? 0.f : r2, r3 = r3 < 0.f ? 0.f : r3;
+  const float ctr_x = __fmul_rn(0.5f, __fadd_rn(x1, x2)), ctr_y = __fmul_rn(0.5f, __fadd_rn(y1, y2));
+  const float w = __fsub_rn(x2, x1), h = __fsub_rn(y2, y1);
+  out[0] = __fsub_rn(ctr_x, __fmul_rn(r0, w)), out[1] = __fsub_rn(ctr_y, __fmul_rn(r1, h));
+  out[2] = __fadd_rn(ctr_x, __fmul_rn(r2, w)), out[3] = __fadd_rn(ctr_y, __fmul_rn(r3, h));
+}
+
 // The pyramid of an anchor generator, by value in the kernel arguments (kMaxRpnLevels entries, `levels` used).
 struct AnchorLevels {
   int h[kMaxRpnLevels], w[kMaxRpnLevels], a[kMaxRpnLevels];

@@ -332,6 +332,9 @@ struct PyramidMaps {
   const int *strides_h, *strides_w;              // the anchor grid's steps
   int levels;
   const float* base_anchors;  // DEVICE: the (sum of as, 4) cell anchors, level after level
+  // FCOS only (null elsewhere): the per-level centerness maps (n, 1, hs[l], ws[l]) and their image strides
+  const float* const* ctrness;
+  const int64_t* ctr_strides;
 };
 // BoxCoder's weights and clip as the kernels take them (decode_single, mv_boxcoder.h)
 struct DecodeCoef {
@@ -361,6 +364,18 @@ RetinanetPlan retinanet_plan(int64_t n, const int* hs, const int* ws, const int*
 int launch_retinanet_topk(const PyramidMaps& m, int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s);
 int launch_retinanet_decode(const PyramidMaps& m, int classes, const float* image_sizes, const int* idx, int64_t n, int64_t k,
                             const DecodeCoef& coef, float* boxes, float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
+// FCOS's threshold + top-k and decode (retinanet.hip: the select / rank body of RetinaNet's with the centerness map read at the
+// candidate's position; semantics in mi355vision.h mv_fcos_topk_f32 and below).  m.ctrness / m.ctr_strides are set, every as[l] is 1;
+// the workspace is retinanet_plan's.
+int launch_fcos_topk(const PyramidMaps& m, int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s);
+int launch_fcos_decode(const PyramidMaps& m, int classes, const float* image_sizes, const int* idx, int64_t n, int64_t k, float* boxes,
+                       float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
+// GroupNorm (+ ReLU) (groupnorm.hip; semantics in mi355vision.h mv_group_norm_act_f32).  The entry point has checked the arguments,
+// the extents, the workspace and the grid; n, c, h, w are positive and m = (c / groups) h w < 2^31.
+constexpr int kGnChunk = 4096;  // elements of a slab per workgroup of the statistics and of the apply launch: 16 per thread
+inline int64_t group_norm_chunks(int64_t m) { return (m + kGnChunk - 1) / kGnChunk; }
+int launch_group_norm_act(const float* x, float* y, const float* gamma, const float* beta, int64_t n, int c, int h, int w, int groups,
+                          int64_t x_stride, int64_t y_stride, float eps, int relu, void* workspace, hipStream_t s);
 // F.interpolate(bilinear) and the detection transform's fused normalize + resize + batch (interp.hip; semantics in mi355vision.h
 // mv_interpolate_bilinear_f32, mv_detection_batch_f32).  The tables are HOST arrays of n <= kMaxDetImages entries, copied into the kernel
 // arguments; mean / stdv: c <= 16 host floats, or both null (no normalisation).  The entry points have checked the arguments, the

@@ -845,6 +845,65 @@ int mv_retinanet_decode_f32(const float* const* logits, const float* const* delt
                             int64_t k, double wx, double wy, double ww, double wh, double clip, float* boxes, float* scores,
                             int64_t* labels, unsigned char* valid, void* stream);
 
+/* ---- FCOS inference (models/detection/fcos.py postprocess_detections up to the nms) on the head's own NCHW maps: RetinaNet's two
+ * entries above with another score and another box coder.  FCOS has ONE anchor per location: every as[l] is 1 (refused otherwise),
+ * logits[l] is (n, K, hs[l], ws[l]), ctrness[l] (n, 1, hs[l], ws[l]), deltas[l] (n, 4, hs[l], ws[l]), each with its image stride in
+ * elements; the flat index of position pos = y ws[l] + x and class c is f = (start_l + pos) K + c.
+ *
+ * The score of both entries is  s = sqrt(fl(sig(cls) * sig(ctr))),  sig the sigmoid of mv_retinanet_topk_f32, ctr the centerness at the
+ * candidate's position, the product and the correctly rounded square root each rounded once to float32.
+ *
+ * mv_fcos_topk_f32: mv_retinanet_topk_f32 with that score -- s > (float)score_thresh passes (a NaN in either map does not), stable
+ * descending order, -1 in the rest of a segment, the same two stages, exact and the same on every run.  `workspace`:
+ * mv_retinanet_topk_workspace_bytes(n, hs, ws, as, levels, classes, k) bytes; the stage-1 chunk is mv_retinanet_topk_chunk().
+ *
+ * mv_fcos_decode_f32: one lane per idx[i, j]; outside the pyramid: zeros and valid 0, as above.  Otherwise the anchor (x1, y1, x2, y2)
+ * of position f / K built as in mv_rpn_decode_f32, label f % K, r_q = max(deltas channel q, 0) (the head's ReLU; a NaN stays) and
+ * BoxLinearCoder(normalize_by_size=True).decode, every operation rounded once to float32:
+ *   cx = 0.5 (x1 + x2), cy = 0.5 (y1 + y2), w = x2 - x1, h = y2 - y1
+ *   box = (cx - r0 w, cy - r1 h, cx + r2 w, cy + r3 h)
+ * clamped to the image as in mv_retinanet_decode_f32, the score recomputed.  The outputs and the refusals are RetinaNet's, the
+ * centerness maps checked like the logits. */
+int mv_fcos_topk_f32(const float* const* logits, const float* const* ctrness, const int* hs, const int* ws, const int* as,
+                     const int64_t* img_strides, const int64_t* ctr_strides, int levels, int classes, int64_t n, int k, double score_thresh,
+                     int* idx, void* workspace, int64_t workspace_bytes, void* stream);
+int mv_fcos_decode_f32(const float* const* logits, const float* const* ctrness, const float* const* deltas, const int* hs, const int* ws,
+                       const int* as, const int64_t* logit_strides, const int64_t* ctr_strides, const int64_t* delta_strides,
+                       const int* strides_h, const int* strides_w, int levels, int classes, const float* base_anchors,
+                       const float* image_sizes, const int* idx, int64_t n, int64_t k, float* boxes, float* scores, int64_t* labels,
+                       unsigned char* valid, void* stream);
+
+/* ---- torch.nn.GroupNorm (+ ReLU) on float32 NCHW: x (n, c, h, w) -> y of the same shape, image i at x + i x_stride / y + i y_stride
+ * (elements, >= c h w: a channel slice of a wider tensor is passed as it is), each image dense.  The slab of (image, group g) is the
+ * contiguous span of m = (c / groups) h w elements at channel g c / groups.  Two launches, nothing read back:
+ *
+ *   statistics  per chunk of mv_group_norm_chunk() = 4096 consecutive elements of a slab (the last one shorter), in float64:
+ *               thread t of 256 adds its 16 elements  e = 1024 u + 4 t + q  (u = 0 .. 3 outer, q = 0 .. 3 inner; an element past the
+ *               slab's end counts as +0), one after the other, to (s, s2) = (0, 0): s += x, s2 += x x (exact in float64);  the 64
+ *               threads 64 v .. 64 v + 63 are folded by halves, a[l] += a[l ^ 32], then ^ 16, 8, 4, 2, 1;  the four folds are
+ *               added in ascending v.
+ *   apply       S, S2 = the chunks' sums added in ascending chunk order to 0;  in float64  mean = S / m,
+ *               var = max(S2 / m - mean mean, 0) (a NaN stays),  rstd = 1 / sqrt(var + (double)(float)eps);  mean32, rstd32 their
+ *               roundings to float32;  y = fl(fl(fl(fl(x - mean32) rstd32) weight[ch]) + bias[ch])  -- the multiplication is left
+ *               out when weight is null, the addition when bias is null, never an fma -- and then, when relu != 0,
+ *               y < 0 ? 0 : y (a NaN stays).
+ * The result of a slab is a function of the slab's values, m, weight, bias, eps and relu alone: not of n, of the slab's place or
+ * alignment, or of the launch.  A NaN or an infinity in a slab makes the whole slab NaN and touches no other slab.
+ * Domain: the sums carry 53 bits for 24-bit data, so S2 / m - mean^2 keeps about 29 - 2 log2(|mean| / std) bits; the statistics
+ * are good to float32 for |mean| / std up to about 2^12 (tests/_fcos_ref.py measures against torch's float64 GroupNorm).
+ *
+ * `workspace`: a 16-byte aligned DEVICE buffer of mv_group_norm_workspace_bytes(n, c, h, w, groups) bytes (16 per chunk of every slab;
+ * 0 for arguments the entry refuses or for empty work), any content.  y may be x itself with the same stride (in place).
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a negative size, groups < 1, c not divisible by groups, eps that is
+ * not positive and finite as a float32, an image stride below c h w, a null or misaligned x / y, y overlapping x other than exactly, a
+ * workspace that is missing, too small, misaligned or overlaps a tensor; a slab or a grid beyond 2^31 - 1 (MV_ERR_UNSUPPORTED).
+ * n c h w == 0 is a no-op that touches no pointer. */
+int mv_group_norm_chunk(void);
+int64_t mv_group_norm_workspace_bytes(int64_t n, int c, int h, int w, int groups);
+int mv_group_norm_act_f32(const float* x, float* y, const float* weight, const float* bias, int64_t n, int c, int h, int w, int groups,
+                          int64_t x_stride, int64_t y_stride, double eps, int relu, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 /* ---- torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False) and the front end of a detection model
  * (models/detection/transform.py: normalize -> resize -> batch_images) on planar float32.
  *
