@@ -7,14 +7,15 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   _misc           resize / center_crop / to_dtype / normalize (+ kernels), to_float_normalize
   _detection      rpn_topk / rpn_decode / box_decode (what rpn runs on), roi_detections (what roi_heads runs on), retinanet_topk /
                   retinanet_decode (what retinanet runs on), fcos_topk / fcos_decode (what fcos runs on)
-  _norm           group_norm_act: GroupNorm (+ ReLU), float64 statistics, two launches
+  _norm           group_norm_act: GroupNorm (+ ReLU), float64 statistics, two launches; l2_normalize_scale: weight * F.normalize over the
+                  channels (SSD's conv4_3), float64 sum of squares, one launch
   _crop, _mix     pad / crop / flip / erase / resized_crop; MixUp / CutMix on a batch
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
   resnet          BasicBlock / Bottleneck / ResNet, resnet18 ... resnet152, wide_resnet50_2 / 101_2: one launch per conv + norm (+ add) + ReLU
   fpn             FeaturePyramidNetwork, LastLevelMaxPool, LastLevelP6P7: lateral 1x1 conv + nearest upsample + add in one launch
   backbone_utils  IntermediateLayerGetter, BackboneWithFPN, resnet_fpn_backbone
-  anchor_utils    AnchorGenerator; image_list: ImageList
+  anchor_utils    AnchorGenerator, DefaultBoxGenerator (SSD's default boxes); image_list: ImageList
   rpn             BoxCoder (decode), RPNHead (cls_logits + bbox_pred as one pointwise launch), RegionProposalNetwork: top-k on the
                   head's NCHW maps, then anchors + decode + clip + sigmoid of the selected candidates only, then batched_nms
   roi_heads       RoIHeads: pooler -> box head -> predictor -> softmax + decode + clip + filters of every (roi, class) in one launch,
@@ -32,6 +33,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   fcos            FCOSClassificationHead / FCOSRegressionHead / FCOSHead (towers of conv, then GroupNorm + ReLU: _norm.group_norm_act),
                   FCOS: threshold + top-k on sqrt(sigmoid(cls) * sigmoid(centerness)), BoxLinearCoder's linear decode of the selected
                   candidates only, then batched_nms; fcos_resnet50_fpn
+  ssd             SSDFeatureExtractorVGG (VGG16 with the ceil-mode third pool, conv4_3 rescaled by _norm.l2_normalize_scale, the dilated
+                  fc6), SSDHead (one conv launch per level and head), SSD: softmax into a class-major matrix, per-class threshold +
+                  top-k on its rows, default boxes + decode of the selected candidates only, then batched_nms; ssd300_vgg16
   ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
                   ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*); box_iou / generalized_box_iou /
                   distance_box_iou, masks_to_boxes, MultiScaleRoIAlign, box_area / box_convert / clip_boxes_to_image /
@@ -46,12 +50,13 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
 The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias package at the repo root).
 """
 from . import (anchor_utils, backbone_utils, faster_rcnn, fcos, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
-               keypoint_rcnn, mask_rcnn, mobilenet, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, transform, transforms, tv_tensors)
+               keypoint_rcnn, mask_rcnn, mobilenet, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, ssd, transform, transforms,
+               tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
 from .backbone_utils import BackboneWithFPN, IntermediateLayerGetter, resnet_fpn_backbone  # noqa: F401
 from .fpn import ExtraFPNBlock, FeaturePyramidNetwork, LastLevelMaxPool, LastLevelP6P7  # noqa: F401
-from .anchor_utils import AnchorGenerator  # noqa: F401
+from .anchor_utils import AnchorGenerator, DefaultBoxGenerator  # noqa: F401
 from .image_list import ImageList  # noqa: F401
 from .rpn import BoxCoder, RegionProposalNetwork, RPNHead  # noqa: F401
 from .roi_heads import RoIHeads  # noqa: F401
@@ -63,6 +68,8 @@ from .keypoint_rcnn import KeypointRCNN, KeypointRCNNHeads, KeypointRCNNPredicto
 from .retinanet import (RetinaNet, RetinaNetClassificationHead, RetinaNetHead, RetinaNetRegressionHead,  # noqa: F401
                         retinanet_resnet50_fpn)
 from .fcos import FCOS, FCOSClassificationHead, FCOSHead, FCOSRegressionHead, fcos_resnet50_fpn  # noqa: F401
+from .ssd import (SSD, SSDClassificationHead, SSDFeatureExtractorVGG, SSDHead, SSDRegressionHead, SSDScoringHead,  # noqa: F401
+                  ssd300_vgg16)
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
                   generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401

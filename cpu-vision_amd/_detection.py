@@ -2,7 +2,8 @@
 rpn_decode and box_decode over mv_rpn_topk_f32 / mv_rpn_decode_f32 / mv_box_decode_f32 (csrc/rpn.hip), roi_detections over
 mv_roi_detections_f32 (csrc/roi_heads.hip), retinanet_topk and retinanet_decode over mv_retinanet_topk_f32 / mv_retinanet_decode_f32
 (csrc/retinanet.hip), fcos_topk and fcos_decode over mv_fcos_topk_f32 / mv_fcos_decode_f32 (the same file: fcos.py's centerness score and
-BoxLinearCoder.decode).  float32, forward-only; the argument checks fire before a device is needed.  Every name
+BoxLinearCoder.decode), ssd_scores, ssd_topk and ssd_decode over mv_ssd_scores_f32 / mv_ssd_topk_f32 / mv_ssd_decode_f32 (csrc/ssd.hip:
+ssd.py's softmax, per-class top-k and default boxes).  float32, forward-only; the argument checks fire before a device is needed.  Every name
 here is re-exported by `functional`.
 """
 from __future__ import annotations
@@ -292,6 +293,128 @@ def fcos_decode(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], bbo
                         sizes.data_ptr(), ix.data_ptr(), n, k, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
     deps = (*cls_logits, *ctrness, *bbox_regression)
     return _lib.forward_only(boxes, name, *deps), _lib.forward_only(scores, name, *deps), labels, valid.view(torch.bool)
+
+
+def ssd_scores(cls_logits: List[torch.Tensor], num_classes: int) -> torch.Tensor:
+    """SSD.postprocess_detections' softmax (ssd.py) on the head's own NCHW class maps, ONE launch for all levels and images:
+    cls_logits[l] (N, A_l * num_classes, H_l, W_l) -> scores (N, num_classes, V) float32, CLASS-MAJOR: scores[i, c, v] is the softmax
+    over the classes of anchor v = start_l + (y W_l + x) A_l + a of the reference's concatenated layout (channel a * num_classes + c).
+    Maximum and exponentials as roi_detections', the sum one ascending float64 chain (mi355vision.h, mv_ssd_scores_f32)."""
+    shapes = _class_maps("ssd_scores", cls_logits, num_classes)
+    if num_classes < 2:
+        raise ValueError(f"ssd_scores: at least 2 classes (the background and one more), got {num_classes}")
+    for m in cls_logits:
+        _lib.require_device(m, "ssd_scores input")
+    lib = _lib.load()
+    l0, n = cls_logits[0], shapes[0][0]
+    total = sum(a * h * w for _, a, h, w in shapes)
+    with _lib.on_device_of(l0):
+        maps = [_dense_images(m) for m in cls_logits]
+        scores = torch.empty((n, num_classes, total), dtype=torch.float32, device=l0.device)
+        if n:
+            hs, ws, as_ = _tables(shapes)
+            _lib.launch(lib.mv_ssd_scores_f32, l0, _lib.pointer_table(maps), hs, ws, as_, _img_strides(maps), len(maps), num_classes, n,
+                        scores.data_ptr())
+    return _lib.forward_only(scores, "ssd_scores", *cls_logits)
+
+
+def ssd_topk(scores: torch.Tensor, k: int, score_thresh: float) -> torch.Tensor:
+    """SSD.postprocess_detections' loop over the labels (ssd.py) as ONE launch, one workgroup per (image, class >= 1): scores
+    (N, K, V) of ssd_scores -> idx (N, (K - 1) * k) int32.  Segment (c - 1) * k holds the flat indices v * K + c of the
+    min(k, passing) anchors with the greatest scores[i, c, v] > score_thresh in stable descending order (equal scores by ascending
+    anchor), then -1.  Nothing is read back."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 3:
+        raise RuntimeError("ssd_topk: scores should be a 3-D tensor (N, K, V)")
+    if scores.dtype != torch.float32:
+        raise TypeError(f"ssd_topk computes in float32. Got scores {scores.dtype}")
+    n, classes, v = (int(d) for d in scores.shape)
+    if classes < 2:
+        raise ValueError(f"ssd_topk: at least 2 classes (the background and one more), got {classes}")
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+        raise ValueError(f"ssd_topk: k must be a positive int, got {k!r}")
+    if k > MAX_RPN_TOPK:
+        raise _lib.Mi355VisionError(f"ssd_topk: k up to {MAX_RPN_TOPK}, got {k}")
+    if v * classes >= 2 ** 31:
+        raise _lib.Mi355VisionError(f"ssd_topk: {v} anchors x {classes} classes exceed the 32-bit index")
+    _lib.require_device(scores, "scores")
+    lib = _lib.load()
+    with _lib.on_device_of(scores):
+        sc = scores.detach().contiguous()
+        idx = torch.empty((n, (classes - 1) * k), dtype=torch.int32, device=scores.device)
+        if n:
+            _lib.launch(lib.mv_ssd_topk_f32, sc, sc.data_ptr(), n, classes, v, k, float(score_thresh), idx.data_ptr())
+    return idx
+
+
+def ssd_decode(scores: torch.Tensor, bbox_regression: List[torch.Tensor], idx: torch.Tensor, wh_pairs: List[torch.Tensor],
+               steps: Optional[Sequence[float]], batch_size: Tuple[int, int], image_sizes,
+               weights: Tuple[float, float, float, float] = (10.0, 10.0, 5.0, 5.0), clip: bool = True,
+               bbox_xform_clip: float = BBOX_XFORM_CLIP) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The rest of SSD.postprocess_detections before the nms for the candidates idx (N, M) of ssd_topk, ONE launch, one lane per
+    candidate: anchor idx // K and label idx % K; the default box of DefaultBoxGenerator built in registers from wh_pairs[l]
+    ((A_l, 2): the generator's _wh_pairs, clamped to [0, 1] here when `clip`), steps (the generator's, or None: the grid's own size)
+    and batch_size = (H, W) of the batch tensor; BoxCoder.decode_single with bbox_regression[l] (N, 4 A_l, H_l, W_l) and `weights`,
+    clip_boxes_to_image with image_sizes (N rows (h, w): a list, or an (N, 2) tensor), the score from the matrix -> boxes (N, M, 4),
+    scores (N, M), labels (N, M) int64, valid (N, M) bool (False, with zeros, for the -1 padding and any other index outside the
+    pyramid)."""
+    name = "ssd_decode"
+    if not isinstance(wh_pairs, (list, tuple)) or not wh_pairs or \
+            any(not isinstance(p, torch.Tensor) or p.dim() != 2 or p.shape[1] != 2 or p.shape[0] < 1 for p in wh_pairs):
+        raise RuntimeError(f"{name}: wh_pairs should hold one (A, 2) tensor per level")
+    anchors = [int(p.shape[0]) for p in wh_pairs]
+    dshapes = _level_maps(name, bbox_regression, "bbox_regression", 4, anchors) \
+        if isinstance(bbox_regression, (list, tuple)) and len(bbox_regression) == len(wh_pairs) else None
+    if dshapes is None:
+        raise RuntimeError(f"{name}: bbox_regression should hold one map per level of wh_pairs, with 4 channels per anchor")
+    num, n = len(dshapes), dshapes[0][0]
+    total = sum(a * h * w for _, a, h, w in dshapes)
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 3 or int(scores.shape[0]) != n or int(scores.shape[2]) != total:
+        raise RuntimeError(f"{name}: scores should have shape ({n}, K, {total})")
+    if scores.dtype != torch.float32:
+        raise TypeError(f"{name} computes in float32. Got scores {scores.dtype}")
+    classes = int(scores.shape[1])
+    if classes < 2:
+        raise ValueError(f"{name}: at least 2 classes (the background and one more), got {classes}")
+    if total * classes >= 2 ** 31:
+        raise _lib.Mi355VisionError(f"{name}: the anchors of all levels x {classes} classes exceed the 32-bit index")
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
+        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, M)")
+    if steps is not None and (len(steps) != num or any(not float(s) > 0 for s in steps)):
+        raise ValueError(f"{name}: steps should hold one positive step per level, got {steps!r}")
+    if len(batch_size) != 2 or int(batch_size[0]) < 1 or int(batch_size[1]) < 1:
+        raise ValueError(f"{name}: batch_size should be the (height, width) of the batch tensor, got {batch_size!r}")
+    if len(weights) != 4:
+        raise ValueError(f"{name}: four weights (wx, wy, ww, wh), got {weights!r}")
+    sizes = _image_sizes(name, image_sizes, lambda t: tuple(t.shape) == (n, 2), f"{n} rows")
+    for m in (scores, *bbox_regression, idx):
+        _lib.require_device(m, f"{name} input")
+    lib = _lib.load()
+    d0 = bbox_regression[0]
+    m_ = int(idx.shape[1])
+    bh, bw = int(batch_size[0]), int(batch_size[1])
+    with _lib.on_device_of(d0):
+        dmaps = [_dense_images(m) for m in bbox_regression]
+        pairs = torch.cat([p.detach().to(torch.float32) for p in wh_pairs])
+        if clip:
+            pairs = pairs.clamp(min=0, max=1)
+        pairs = pairs.to(d0.device).contiguous()
+        sc = scores.detach().contiguous()
+        sizes = sizes.detach().to(d0.device, torch.float32).contiguous()
+        ix = idx.contiguous()
+        boxes = torch.empty((n, m_, 4), dtype=torch.float32, device=d0.device)
+        out_scores = torch.empty((n, m_), dtype=torch.float32, device=d0.device)
+        labels = torch.empty((n, m_), dtype=torch.int64, device=d0.device)
+        valid = torch.empty((n, m_), dtype=torch.uint8, device=d0.device)
+        if n and m_:
+            hs, ws, as_ = _tables(dshapes)
+            # the reference divides a float32 tensor by the Python double image side / step (or by the grid's int side)
+            x_f = (C.c_float * num)(*[bw / steps[l] if steps is not None else float(dshapes[l][3]) for l in range(num)])
+            y_f = (C.c_float * num)(*[bh / steps[l] if steps is not None else float(dshapes[l][2]) for l in range(num)])
+            _lib.launch(lib.mv_ssd_decode_f32, d0, sc.data_ptr(), _lib.pointer_table(dmaps), hs, ws, as_, _img_strides(dmaps), num, classes,
+                        pairs.data_ptr(), x_f, y_f, bh, bw, sizes.data_ptr(), ix.data_ptr(), n, m_, *[float(w) for w in weights],
+                        float(bbox_xform_clip), boxes.data_ptr(), out_scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
+    deps = (scores, *bbox_regression)
+    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(out_scores, name, *deps), labels, valid.view(torch.bool)
 
 
 def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[float, float, float, float],

@@ -80,10 +80,14 @@ def max_pool2d_2x2(x: torch.Tensor) -> torch.Tensor:
                           out_dtype=torch.float32)
 
 
-def max_pool2d(x: torch.Tensor, kernel_size: int, stride: Optional[int] = None, padding: int = 0) -> torch.Tensor:
-    """nn.MaxPool2d(kernel_size, stride, padding), floor mode, dilation 1 on (..., H, W): without padding AlexNet's 3, 2
+def max_pool2d(x: torch.Tensor, kernel_size: int, stride: Optional[int] = None, padding: int = 0, *, ceil_mode: bool = False) -> torch.Tensor:
+    """nn.MaxPool2d(kernel_size, stride, padding), dilation 1 on (..., H, W): without padding AlexNet's 3, 2
     (models/alexnet.py:24); with padding (0 < padding <= kernel_size // 2: ResNet's stem, 3, 2, 1; models/resnet.py:201) the padded
-    positions never win and NaN propagates as in torch's CPU kernel (mv_maxpool2d_pad_f32)."""
+    positions never win and NaN propagates as in torch's CPU kernel (mv_maxpool2d_pad_f32).  ceil_mode=True (SSD's third VGG pool,
+    75 -> 38): the output side is ceil((in + 2 padding - kernel_size) / stride) + 1, less one when the last window would start in the
+    right padding; windows are clipped to the input (mv_maxpool2d_ceil_f32)."""
+    if ceil_mode:
+        return _max_pool2d_ceil(x, int(kernel_size), int(kernel_size if stride is None else stride), int(padding))
     stride = kernel_size if stride is None else stride
     if padding != 0:
         return _max_pool2d_padded(x, int(kernel_size), int(stride), int(padding))
@@ -111,6 +115,28 @@ def _max_pool2d_padded(x: torch.Tensor, kernel_size: int, stride: int, padding: 
         raise RuntimeError(f"max_pool2d: kernel {kernel_size} exceeds the {h}x{w} input padded by {padding}")
     out_shape = tuple(x.shape[:-2]) + ((h + 2 * padding - kernel_size) // stride + 1, (w + 2 * padding - kernel_size) // stride + 1)
     return _lib.launch_xy(_lib.load().mv_maxpool2d_pad_f32, x, (planes, h, w, kernel_size, stride, padding), out_shape=out_shape,
+                          out_dtype=torch.float32)
+
+
+def _ceil_pool_out(size: int, kernel_size: int, stride: int, padding: int) -> int:
+    """torch's pooling_output_shape with ceil_mode=True."""
+    o = -((size + 2 * padding - kernel_size) // -stride) + 1
+    return o - 1 if (o - 1) * stride >= size + padding else o
+
+
+def _max_pool2d_ceil(x: torch.Tensor, kernel_size: int, stride: int, padding: int) -> torch.Tensor:
+    if x.dtype != torch.float32:
+        raise TypeError(f"max_pool2d computes in float32. Got {x.dtype}")
+    if kernel_size <= 0 or stride <= 0:
+        raise RuntimeError(f"max_pool2d: kernel_size and stride must be positive, got {kernel_size}, {stride}")
+    if padding < 0 or padding > kernel_size // 2:
+        raise RuntimeError(f"pad should be at most half of effective kernel size, but got pad={padding}, kernel_size={kernel_size}")
+    planes, h, w = _planes(x)
+    if h + 2 * padding < kernel_size or w + 2 * padding < kernel_size:
+        raise RuntimeError(f"max_pool2d: kernel {kernel_size} exceeds the {h}x{w} input padded by {padding}")
+    _lib.require_device(x)
+    out_shape = tuple(x.shape[:-2]) + (_ceil_pool_out(h, kernel_size, stride, padding), _ceil_pool_out(w, kernel_size, stride, padding))
+    return _lib.launch_xy(_lib.load().mv_maxpool2d_ceil_f32, x, (planes, h, w, kernel_size, stride, padding), out_shape=out_shape,
                           out_dtype=torch.float32)
 
 

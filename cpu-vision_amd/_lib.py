@@ -81,6 +81,7 @@ SYMBOLS = {
     "mv_maxpool2d_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_conv2d_affine_act_f32": (_i, [_vp] * 7 + [_i64] + [_i] * 15 + [_vp, _i64, _vp]),
     "mv_maxpool2d_pad_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "mv_maxpool2d_ceil_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "mv_resize_workspace_bytes": (_i64, [_i64, _i, _i, _i, _i, _i, _i, _i, _i]),
     "mv_resize_bilinear_aa_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "mv_resize_bilinear_aa_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
@@ -141,9 +142,14 @@ SYMBOLS = {
     "mv_fcos_topk_f32": (_i, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i, _i, _i64, _i, _d, _vp, _vp, _i64, _vp]),
     "mv_fcos_decode_f32": (_i, [_vp, _vp, _vp, _ip, _ip, _ip] + [C.POINTER(C.c_int64)] * 3 + [_ip, _ip, _i, _i, _vp, _vp, _vp, _i64, _i64]
                            + [_vp] * 5),
+    "mv_ssd_scores_f32": (_i, [_vp, _ip, _ip, _ip, C.POINTER(C.c_int64), _i, _i, _i64, _vp, _vp]),
+    "mv_ssd_topk_f32": (_i, [_vp, _i64, _i, _i64, _i, _d, _vp, _vp]),
+    "mv_ssd_decode_f32": (_i, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_int64), _i, _i, _vp, _fp, _fp, _i, _i, _vp, _vp, _i64, _i64] + [_d] * 5
+                          + [_vp] * 5),
     "mv_group_norm_chunk": (_i, []),
     "mv_group_norm_workspace_bytes": (_i64, [_i64, _i, _i, _i, _i]),
     "mv_group_norm_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i64, _i64, _d, _i, _vp, _i64, _vp]),
+    "mv_l2_normalize_scale_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _i64, _d, _vp]),
     "mv_roi_detections_f32": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i64] + [_d] * 7 + [_vp] * 5),
     "mv_interpolate_bilinear_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_detection_batch_f32": (_i, [_vp, _ip, _ip, _ip, _ip, _i64, _i, _fp, _fp, _vp, _i, _i, _vp]),

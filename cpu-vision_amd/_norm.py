@@ -1,5 +1,6 @@
 """torch.nn.functional.group_norm (+ ReLU) over mv_group_norm_act_f32 (csrc/groupnorm.hip): the `GroupNorm -> ReLU` of the FCOS towers
-and of the v2 detection heads.  float32, forward-only; the argument checks fire before a device is needed.  Every name here is
+and of the v2 detection heads; weight * torch.nn.functional.normalize over mv_l2_normalize_scale_f32 (csrc/l2norm.hip): SSD's
+rescaling of conv4_3.  float32, forward-only; the argument checks fire before a device is needed.  Every name here is
 re-exported by `functional`.
 """
 from __future__ import annotations
@@ -68,3 +69,44 @@ def group_norm_act(x: torch.Tensor, num_groups: int, weight: Optional[torch.Tens
     if out is not None:
         return x
     return _lib.forward_only(y, "group_norm_act", x, weight, bias)
+
+
+def l2_normalize_scale(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-12, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """weight.view(1, -1, 1, 1) * torch.nn.functional.normalize(x, p=2, dim=1, eps=eps) as ONE launch: x (N, C, H, W) float32 ->
+    (N, C, H, W), weight (C,).  A channel slice of a wider contiguous tensor is read as it is.  out: `x` itself for the in-place form
+    (then x is dense NCHW).  The arithmetic is stated in mi355vision.h (mv_l2_normalize_scale_f32): the squares are summed in float64,
+    and a pixel's result depends on its own C values only."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise RuntimeError("l2_normalize_scale: x should be a 4-D tensor (N, C, H, W)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"l2_normalize_scale computes in float32. Got x {x.dtype}")
+    n, c, h, w = (int(d) for d in x.shape)
+    if not isinstance(weight, torch.Tensor) or tuple(weight.shape) != (c,):
+        raise RuntimeError(f"l2_normalize_scale: weight should have shape ({c},), got "
+                           f"{tuple(weight.shape) if isinstance(weight, torch.Tensor) else type(weight).__name__}")
+    if weight.dtype != torch.float32:
+        raise TypeError(f"l2_normalize_scale computes in float32. Got weight {weight.dtype}")
+    eps = float(eps)
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"l2_normalize_scale: eps must be positive and finite, got {eps!r}")
+    if out is not None and out is not x:
+        raise ValueError("l2_normalize_scale: out is x itself (in place) or None")
+    _lib.require_device(x, "x")
+    lib = _lib.load()
+    with _lib.on_device_of(x):
+        xs = _dense_images(x)
+        if out is not None:
+            if xs.data_ptr() != x.data_ptr():  # _dense_images made a copy
+                raise ValueError("l2_normalize_scale: the in-place form needs dense images")
+            y = xs
+        else:
+            y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+        if n and c and h and w:
+            scale = _lib.f32_on(weight, x.device)
+            image = c * h * w
+            x_stride = int(xs.stride(0)) if n > 1 else image
+            _lib.launch(lib.mv_l2_normalize_scale_f32, xs, xs.data_ptr(), y.data_ptr(), scale.data_ptr(), n, c, h, w, x_stride,
+                        x_stride if out is not None else image, eps)
+    if out is not None:
+        return x
+    return _lib.forward_only(y, "l2_normalize_scale", x, weight)

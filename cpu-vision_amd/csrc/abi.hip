@@ -849,6 +849,18 @@ int mv_maxpool2d_pad_f32(const float* x, float* y, int64_t planes, int h, int wd
   return launch_maxpool2d_pad(x, y, planes, h, wdt, k, stride, pad, (hipStream_t)stream);
 }
 
+int mv_maxpool2d_ceil_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, int pad, void* stream) {
+  if (planes < 0 || h <= 0 || wdt <= 0 || k <= 0 || stride <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad pooling shape planes=%lld (%d, %d) k=%d stride=%d", (long long)planes, h, wdt, k, stride);
+  if (pad < 0 || pad > k / 2) return set_error(MV_ERR_INVALID_ARGUMENT, "pad should be at most half of effective kernel size, but got pad=%d, kernel_size=%d", pad, k);
+  if ((long long)h + 2 * pad < k || (long long)wdt + 2 * pad < k)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "Output size is too small: (%d, %d) with k=%d pad=%d", h, wdt, k, pad);
+  if (planes == 0) return MV_OK;
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  return launch_maxpool2d_ceil(x, y, planes, h, wdt, k, stride, pad, (hipStream_t)stream);
+}
+
 int mv_maxpool2d_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, void* stream) {
   if (planes < 0 || h <= 0 || wdt <= 0 || k <= 0 || stride <= 0 || k > h || k > wdt)
     return set_error(MV_ERR_INVALID_ARGUMENT, "bad pooling shape planes=%lld (%d, %d) k=%d stride=%d", (long long)planes, h, wdt, k, stride);
@@ -1521,6 +1533,100 @@ int mv_fcos_decode_f32(const float* const* logits, const float* const* ctrness, 
   return launch_fcos_decode(m, classes, image_sizes, idx, n, k, boxes, scores, labels, valid, (hipStream_t)stream);
 }
 
+// ---- SSD: ssd.hip ------------------------------------------------------------------------------------------------------------------
+int mv_ssd_scores_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                      int classes, int64_t n, float* scores, void* stream) {
+  const char* const op = "ssd_scores";
+  if (n < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad image count %lld", op, (long long)n);
+  int64_t taken;
+  if (int rc = levels_check(op, hs, ws, as, levels, classes, 1, &taken)) return rc;
+  if (classes < 2) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: at least 2 classes (the background and one more), got %d", op, classes);
+  if (n == 0) return MV_OK;
+  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images exceed the launch grid", op, (long long)n);
+  if (!logits || !img_strides || !scores) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  if ((uintptr_t)scores % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: scores must be 4-byte aligned", op);
+  ByteRange ins[kMaxRpnLevels];
+  int64_t anchors = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t al = (int64_t)as[l] * hs[l] * ws[l], nl = al * classes;
+    if (!logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+    if ((uintptr_t)logits[l] % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the maps must be 4-byte aligned (level %d)", op, l);
+    if (img_strides[l] < nl || img_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of level %d, its map has %lld elements", op, (long long)img_strides[l], l,
+                       (long long)nl);
+    ins[l] = {logits[l], ((n - 1) * img_strides[l] + nl) * 4};
+    anchors += al;
+  }
+  const ByteRange out = {scores, n * anchors * classes * 4};
+  if (!outputs_clear(&out, 1, ins, levels)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: scores must not overlap an input", op);
+  const PyramidMaps m = topk_maps(logits, hs, ws, as, img_strides, levels);
+  return launch_ssd_scores(m, classes, (int)n, scores, (hipStream_t)stream);
+}
+
+int mv_ssd_topk_f32(const float* scores, int64_t n, int classes, int64_t v, int k, double score_thresh, int* idx, void* stream) {
+  const char* const op = "ssd_topk";
+  if (n < 0 || v < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld, v=%lld", op, (long long)n, (long long)v);
+  if (k < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: k must be positive, got %d", op, k);
+  if (classes < 2) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: at least 2 classes (the background and one more), got %d", op, classes);
+  if (v > 0x7fffffffLL / classes)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld anchors x %d classes exceed the 32-bit index", op, (long long)v, classes);
+  if (k > kRpnMaxK) return set_error(MV_ERR_UNSUPPORTED, "%s: k up to %d, got %d", op, kRpnMaxK, k);
+  if (n == 0) return MV_OK;
+  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "%s: %lld images exceed the launch grid", op, (long long)n);
+  if (!idx || (v > 0 && !scores)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  if ((uintptr_t)scores % 4 || (uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: scores and idx must be 4-byte aligned", op);
+  const ByteRange in = {scores, n * classes * v * 4}, out = {idx, n * (classes - 1) * (int64_t)k * 4};
+  if (!outputs_clear(&out, 1, &in, 1)) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx must not overlap scores", op);
+  return launch_ssd_topk(scores, (int)n, classes, (int)v, k, (float)score_thresh, idx, (hipStream_t)stream);
+}
+
+int mv_ssd_decode_f32(const float* scores, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                      const int64_t* delta_strides, int levels, int classes, const float* wh_pairs, const float* x_f, const float* y_f,
+                      int batch_h, int batch_w, const float* image_sizes, const int* idx, int64_t n, int64_t k, double wx, double wy,
+                      double ww, double wh, double clip, float* boxes, float* scores_out, int64_t* labels, unsigned char* valid,
+                      void* stream) {
+  const char* const op = "ssd_decode";
+  if (n < 0 || k < 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad shape n=%lld, k=%lld", op, (long long)n, (long long)k);
+  int64_t taken;
+  if (int rc = levels_check(op, hs, ws, as, levels, classes, 1, &taken)) return rc;
+  if (classes < 2) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: at least 2 classes (the background and one more), got %d", op, classes);
+  if (!x_f || !y_f) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null level table", op);
+  for (int l = 0; l < levels; ++l)
+    if (!(x_f[l] > 0.f) || !(y_f[l] > 0.f) || x_f[l] > 3.0e38f || y_f[l] > 3.0e38f)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad grid divisors (%g, %g) of level %d", op, (double)x_f[l], (double)y_f[l], l);
+  if (batch_h < 1 || batch_w < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: bad batch size (%d, %d)", op, batch_h, batch_w);
+  if (n == 0 || k == 0) return MV_OK;
+  if (n > 0x7fffffffLL || k > (0x7fffffffLL * 256) / n)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: %lld x %lld candidates exceed the launch grid", op, (long long)n, (long long)k);
+  if (!scores || !deltas || !delta_strides || !wh_pairs || !image_sizes || !idx || !boxes || !scores_out || !labels || !valid)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  if ((uintptr_t)labels % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: labels must be 8-byte aligned", op);
+  if ((uintptr_t)idx % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: idx must be 4-byte aligned", op);
+  if ((uintptr_t)scores % 4 || (uintptr_t)wh_pairs % 4 || (uintptr_t)image_sizes % 4 || (uintptr_t)boxes % 4 || (uintptr_t)scores_out % 4)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the float tensors must be 4-byte aligned", op);
+  ByteRange ins[kMaxRpnLevels + 4];
+  int64_t anchors = 0, pairs = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int64_t al = (int64_t)as[l] * hs[l] * ws[l];
+    if (!deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+    if ((uintptr_t)deltas[l] % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the maps must be 4-byte aligned (level %d)", op, l);
+    if (delta_strides[l] < 4 * al || delta_strides[l] > 0x7fffffffffffLL / n)
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of level %d, its map has %lld elements", op, (long long)delta_strides[l],
+                       l, (long long)(4 * al));
+    ins[l] = {deltas[l], ((n - 1) * delta_strides[l] + 4 * al) * 4};
+    anchors += al, pairs += as[l];
+  }
+  ins[levels] = {scores, n * anchors * classes * 4}, ins[levels + 1] = {wh_pairs, pairs * 8}, ins[levels + 2] = {image_sizes, n * 8};
+  ins[levels + 3] = {idx, n * k * 4};
+  const ByteRange outs[4] = {{boxes, n * k * 16}, {scores_out, n * k * 4}, {labels, n * k * 8}, {valid, n * k}};
+  if (!outputs_clear(outs, 4, ins, levels + 4))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the outputs must not overlap an input or each other", op);
+  PyramidMaps m = {};
+  m.deltas = deltas, m.hs = hs, m.ws = ws, m.as = as, m.delta_strides = delta_strides, m.levels = levels;
+  return launch_ssd_decode(scores, m, classes, wh_pairs, x_f, y_f, batch_h, batch_w, image_sizes, idx, n, k, decode_coef(wx, wy, ww, wh, clip),
+                           boxes, scores_out, labels, valid, (hipStream_t)stream);
+}
+
 // ---- GroupNorm (+ ReLU): groupnorm.hip ---------------------------------------------------------------------------------------------
 int mv_group_norm_chunk(void) { return kGnChunk; }
 
@@ -1574,6 +1680,34 @@ int mv_group_norm_act_f32(const float* x, float* y, const float* weight, const f
     return set_error(MV_ERR_INVALID_ARGUMENT, "group_norm_act: the workspace and y must not overlap an input or each other");
   return launch_group_norm_act(x, y, weight, bias, n, c, h, w, groups, x_stride, y_stride, (float)eps, relu != 0, workspace,
                                (hipStream_t)stream);
+}
+
+// ---- weight * F.normalize(x, dim=1): l2norm.hip ------------------------------------------------------------------------------------
+int mv_l2_normalize_scale_f32(const float* x, float* y, const float* weight, int64_t n, int c, int h, int w, int64_t x_stride,
+                              int64_t y_stride, double eps, void* stream) {
+  if (n < 0 || c < 0 || h < 0 || w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: negative size (n=%lld c=%d h=%d w=%d)", (long long)n, c, h, w);
+  const int64_t hw = (int64_t)h * w, image = (int64_t)c * hw;
+  if (hw > 0x7fffffffLL || image > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "l2_normalize_scale: an image of %d x %d x %d elements exceeds the 32-bit index", c, h, w);
+  const int64_t blocks = n * l2_normalize_blocks(hw);
+  if (n > 0x7fffffffLL || blocks > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "l2_normalize_scale: %lld workgroups exceed the launch grid", (long long)blocks);
+  if (!(eps > 0) || eps > 3.0e38 || !((float)eps > 0.f))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: eps must be positive and finite in float32, got %g", eps);
+  if (n == 0 || image == 0) return MV_OK;
+  if (x_stride < image || y_stride < image || x_stride > 0x7fffffffffffLL / n || y_stride > 0x7fffffffffffLL / n)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: image strides (%lld, %lld), an image has %lld elements",
+                     (long long)x_stride, (long long)y_stride, (long long)image);
+  if (!x || !y || !weight) return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: null pointer");
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4 || (uintptr_t)weight % 4)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: x, y and weight must be 4-byte aligned");
+  const ByteRange xr = {x, ((n - 1) * x_stride + image) * 4}, yr = {y, ((n - 1) * y_stride + image) * 4}, wr = {weight, c * 4LL};
+  // in place exactly (the same pointer and stride) or apart
+  if (!(x == y && x_stride == y_stride) && ranges_overlap(xr, yr))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: y must be x itself (in place) or must not overlap it");
+  if (ranges_overlap(yr, wr)) return set_error(MV_ERR_INVALID_ARGUMENT, "l2_normalize_scale: y must not overlap weight");
+  return launch_l2_normalize_scale(x, y, weight, n, c, h, w, x_stride, y_stride, (float)eps, (hipStream_t)stream);
 }
 
 // ---- roi_pool / ps_roi_pool / ps_roi_align: roi_pool.hip ---------------------------------------------------------------------------

@@ -250,4 +250,16 @@ int launch_maxpool2d_pad(const float* x, float* y, int64_t planes, int h, int w,
   return check_launch("k_maxpool2d_pad");
 }
 
+// nn.MaxPool2d(k, stride, pad, ceil_mode=True) (SSD's third VGG pool, 75 -> 38; models/detection/ssd.py): k_maxpool2d_pad over the
+// larger output.  Its windows are clipped to the image already, and the rule that drops an output whose window would start in the
+// right padding ((o - 1) stride < in + pad) with pad <= k / 2 keeps every window non-empty: it starts before `in` and ends after 0.
+int launch_maxpool2d_ceil(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s) {
+  const int oh = maxpool_ceil_out(h, k, stride, pad), ow = maxpool_ceil_out(w, k, stride, pad);
+  const long long total = (long long)planes * oh * ow;
+  if (total > 256LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "maxpool2d: batch too large for one launch");
+  if (total == 0) return MV_OK;
+  hipLaunchKernelGGL(k_maxpool2d_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, total, h, w, oh, ow, k, stride, pad);
+  return check_launch("k_maxpool2d_pad<ceil>");
+}
+
 }  // namespace mv

@@ -31,6 +31,9 @@ __device__ inline void decode_single(float x1, float y1, float x2, float y2, flo
 // torch.clamp(v, min=0, max=hi): a NaN stays
 __device__ inline float clamp0(float v, float hi) { return v != v ? v : (v < 0.f ? 0.f : (v > hi ? hi : v)); }
 
+// torch.max over a row: any NaN makes the result NaN
+__device__ inline float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
+
 // 1 / (1 + E(-x)), every operation rounded once to float32, the division correctly rounded
 __device__ inline float sigmoid_cr(float x) { return __fdiv_rn(1.f, __fadd_rn(1.f, exp_cr(-x))); }
 

@@ -265,6 +265,13 @@ int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top
 // nn.Conv2d of any geometry and deform_conv2d: mv_conv.h, mv_deform.h
 int launch_maxpool2d(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, hipStream_t s);
 int launch_maxpool2d_pad(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s);
+// ceil_mode=True: the output side of one axis (torch's pooling_output_shape) and the launch; 0 <= pad <= k / 2, in + 2 pad >= k
+inline int maxpool_ceil_out(int in, int k, int stride, int pad) {
+  int o = (int)(((long long)in + 2 * pad - k + stride - 1) / stride) + 1;
+  if ((long long)(o - 1) * stride >= (long long)in + pad) --o;  // the last window would start in the right padding
+  return o;
+}
+int launch_maxpool2d_ceil(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s);
 
 // F.resize(bilinear, antialias) [+ center_crop] [+ preset tail] (resize.hip)
 int64_t resize_workspace_bytes(int64_t planes, int h, int w, int oh, int ow, int ct, int cl, int ch, int cw);
@@ -370,12 +377,26 @@ int launch_retinanet_decode(const PyramidMaps& m, int classes, const float* imag
 int launch_fcos_topk(const PyramidMaps& m, int classes, int n, int k, float score_thresh, int* idx, void* workspace, hipStream_t s);
 int launch_fcos_decode(const PyramidMaps& m, int classes, const float* image_sizes, const int* idx, int64_t n, int64_t k, float* boxes,
                        float* scores, int64_t* labels, unsigned char* valid, hipStream_t s);
+// SSD's softmax, per-class threshold + top-k and decode (ssd.hip; semantics in mi355vision.h mv_ssd_scores_f32 and below).  The entry
+// points have checked the arguments, the extents and the grids.  scores: the (n, classes, V) class-major matrix, V the anchors of
+// all levels; x_f, y_f: HOST arrays of `levels` floats; wh_pairs: DEVICE (sum of as, 2).
+int launch_ssd_scores(const PyramidMaps& m, int classes, int n, float* scores, hipStream_t s);
+int launch_ssd_topk(const float* scores, int n, int classes, int v, int k, float score_thresh, int* idx, hipStream_t s);
+int launch_ssd_decode(const float* scores, const PyramidMaps& m, int classes, const float* wh_pairs, const float* x_f, const float* y_f,
+                      int batch_h, int batch_w, const float* image_sizes, const int* idx, int64_t n, int64_t k, const DecodeCoef& coef,
+                      float* boxes, float* scores_out, int64_t* labels, unsigned char* valid, hipStream_t s);
 // GroupNorm (+ ReLU) (groupnorm.hip; semantics in mi355vision.h mv_group_norm_act_f32).  The entry point has checked the arguments,
 // the extents, the workspace and the grid; n, c, h, w are positive and m = (c / groups) h w < 2^31.
 constexpr int kGnChunk = 4096;  // elements of a slab per workgroup of the statistics and of the apply launch: 16 per thread
 inline int64_t group_norm_chunks(int64_t m) { return (m + kGnChunk - 1) / kGnChunk; }
 int launch_group_norm_act(const float* x, float* y, const float* gamma, const float* beta, int64_t n, int c, int h, int w, int groups,
                           int64_t x_stride, int64_t y_stride, float eps, int relu, void* workspace, hipStream_t s);
+// weight * F.normalize(x, dim=1) (l2norm.hip; semantics in mi355vision.h mv_l2_normalize_scale_f32).  The entry point has checked
+// the arguments, the extents and the grid; n, c, h, w are positive and c h w < 2^31.
+constexpr int kL2Pixels = 16, kL2Groups = 16;  // a workgroup: 16 consecutive pixels x 16 channel groups
+inline int64_t l2_normalize_blocks(int64_t hw) { return (hw + kL2Pixels - 1) / kL2Pixels; }
+int launch_l2_normalize_scale(const float* x, float* y, const float* weight, int64_t n, int c, int h, int w, int64_t x_stride,
+                              int64_t y_stride, float eps, hipStream_t s);
 // F.interpolate(bilinear) and the detection transform's fused normalize + resize + batch (interp.hip; semantics in mi355vision.h
 // mv_interpolate_bilinear_f32, mv_detection_batch_f32).  The tables are HOST arrays of n <= kMaxDetImages entries, copied into the kernel
 // arguments; mean / stdv: c <= 16 host floats, or both null (no normalisation).  The entry points have checked the arguments, the

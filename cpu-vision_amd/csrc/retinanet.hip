@@ -16,8 +16,8 @@
 //                      for min(k, kRetChunk) keys of every chunk: nothing is dropped, whatever passes.
 // k_retinanet_rank     stage 2, one workgroup per (image, level): select_keys over the pool, the <= k <= 4096 selected keys into
 //                      LDS, ranked pairwise there (position = #{greater keys}); idx[rank] = f, the rest of the segment -1.
-// select_keys          radix select of the k-th greatest key, 8 bits per pass from the top, a 256-bin histogram in LDS per pass
-//                      (hist_add of k_rpn_topk).  It stops as soon as the answer is known: after the first pass when at most k
+// select_keys          (mv_topk.h, shared with ssd.hip) radix select of the k-th greatest key, 8 bits per pass from the top, a
+//                      256-bin histogram in LDS per pass (hist_add of k_rpn_topk).  It stops as soon as the answer is known: after the first pass when at most k
 //                      keys pass at all, after any pass when the bin of the k-th key is taken whole; at most 8 passes.
 // k_retinanet_decode   one lane per idx[i, j]: anchor f / K and label f % K, the anchor in registers, decode_single, clip to the
 //                      image (decode_candidate of mv_boxcoder.h, shared with k_rpn_decode), the score recomputed.
@@ -40,38 +40,6 @@ constexpr int kRetThreads = 1024;
 constexpr int kRetLoads = kRetChunk / kRetThreads;  // elements of a chunk per thread, in registers
 constexpr int kRankLoads = 4;                       // pool keys a thread loads before it works on them
 static_assert(kRetChunk % kRetThreads == 0, "a chunk is a whole number of elements per thread");
-
-// The k greatest of the non-zero keys that `each` visits (it calls f(key) for every key of this thread, the same number of times
-// in every thread of the workgroup; 0 = no key).  Returns T and sets *take = min(k, keys): the selected keys are those >= T.
-template <typename Each>
-__device__ inline u64 select_keys(const Each& each, unsigned k, unsigned* hist, unsigned* sel, int tid, int lane, unsigned* take) {
-  u64 prefix = 0;
-  unsigned rem = k;  // how many of the keys that share `prefix` are taken
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    each([&](u64 key) { hist_add(hist, key != 0 && (pass == 0 || ((key >> shift) >> 8) == prefix), (unsigned)(key >> shift) & 255u, lane); });
-    __syncthreads();
-    if (tid < 256) {
-      unsigned above = 0;
-      for (int j = tid + 1; j < 256; ++j) above += hist[j];
-      const unsigned mine = hist[tid];
-      if (tid == 0) sel[3] = above + mine;  // every key counted in this pass
-      if (above < rem && above + mine >= rem) sel[0] = (unsigned)tid, sel[1] = rem - above, sel[2] = mine;  // at most one digit
-    }
-    __syncthreads();  // hist and sel are next written behind the first barrier of the next pass
-    if (pass == 0 && sel[3] <= k) {
-      *take = sel[3];
-      return 1;
-    }
-    prefix = (prefix << 8) | sel[0];
-    rem = sel[1];
-    if (sel[2] == rem) return *take = k, prefix << shift;  // the whole bin is taken: no need to look inside it
-  }
-  *take = k;
-  return prefix;
-}
 
 // The key of element e (memory order: channel a K + c, position pos) of a level's map with the logit x: 0 when it does not pass.
 // FCOS: the score takes the centerness map's value at the same pos (one anchor per location: ctr has one channel).

@@ -37,9 +37,6 @@ struct RoiDetArgs {
   unsigned char* valid;
 };
 
-// torch.max over a row: any NaN makes the result NaN
-__device__ inline float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-
 __global__ __launch_bounds__(kRoiWaves* kWave) void k_roi_detections(const RoiDetArgs A) {
   extern __shared__ float row_all[];  // kRoiWaves rows of `classes` floats: the logits, then the exponentials
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -22,7 +22,9 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               BoxCoder.decode_single), roi_detections (roi_heads.py postprocess_detections up to the per-image filters),
               retinanet_topk / retinanet_decode (retinanet.py postprocess_detections up to the nms)
               fcos_topk / fcos_decode (fcos.py postprocess_detections up to the nms: the centerness score, BoxLinearCoder.decode)
-  _norm       group_norm_act (torch.nn.functional.group_norm + ReLU: the FCOS towers' norm), group_norm_chunk
+              ssd_scores / ssd_topk / ssd_decode (ssd.py postprocess_detections up to the nms: softmax, per-class top-k, default boxes)
+  _norm       group_norm_act (torch.nn.functional.group_norm + ReLU: the FCOS towers' norm), group_norm_chunk, l2_normalize_scale
+              (weight * F.normalize over the channels: SSD's conv4_3)
   _interp     interpolate (torch.nn.functional.interpolate, plain bilinear) and detection_batch, the fused normalize + resize +
               batch_images in front of a detection model (models/detection/transform.py)
   _mask       paste_masks_in_image / mask_probs (roi_heads.py paste_masks_in_image, maskrcnn_inference) and
@@ -62,7 +64,8 @@ from ._geometry import (affine, _affine_coeffs, affine_image, affine_mask, _affi
                         perspective_video, _PIL_INTERPOLATION, rotate, rotate_image, rotate_mask, rotate_video,
                         _warp, _WARP_KINDS)
 from ._detection import (BBOX_XFORM_CLIP, box_decode, fcos_decode, fcos_topk, MAX_ROI_CLASSES, MAX_RPN_LEVELS,  # noqa: F401
-                         MAX_RPN_TOPK, retinanet_decode, retinanet_topk, retinanet_topk_chunk, roi_detections, rpn_decode, rpn_topk)
+                         MAX_RPN_TOPK, retinanet_decode, retinanet_topk, retinanet_topk_chunk, roi_detections, rpn_decode, rpn_topk,
+                         ssd_decode, ssd_scores, ssd_topk)
 from ._filters import (_adjust_sharpness_image_pil, adjust_sharpness, adjust_sharpness_frames, adjust_sharpness_image,  # noqa: F401
                        adjust_sharpness_video, _blur_with_taps, _border, box_filter, _check_gaussian_args, _compute_dtype,
                        depthwise_conv2d, _DIRECT_2D_MAX_TAPS, _filter_f32_u8, _frames_call, gaussian_blur,
@@ -80,7 +83,7 @@ from ._lib import max_value as _max_value  # noqa: F401
 from ._mask import conv_transpose2d_bias_act, conv_transpose2x2_relayout, mask_probs, paste_masks_in_image  # noqa: F401
 from ._misc import (center_crop, center_crop_image, _mean_std, normalize, normalize_image, resize, resize_image,  # noqa: F401
                     resize_video, to_dtype, to_dtype_image, _to_dtype_tensor_dispatch, to_float_normalize)
-from ._norm import group_norm_act, group_norm_chunk  # noqa: F401
+from ._norm import group_norm_act, group_norm_chunk, l2_normalize_scale  # noqa: F401
 from ._registry import _get_kernel, _register_kernel_internal  # noqa: F401
 
 # uint8 images with a kernel side above 3.  True (default) = ONE 2-D pass, the reference's own formulation

@@ -370,6 +370,10 @@ int mv_conv2d_affine_act_f32(const float* x, const float* weight, const float* b
  * 0 <= pad <= k / 2, else MV_ERR_INVALID_ARGUMENT (torch's own rule), as is a non-positive output size.  NaN: torch's CPU kernel's
  * rule -- m = -inf, then `if (v > m || isnan(v)) m = v` over the window in row-major order. */
 int mv_maxpool2d_pad_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, int pad, void* stream);
+/* The same with ceil_mode=True (SSD's third VGG pool, 75 -> 38): per axis o = ceil((in + 2 pad - k) / stride) + 1, less one when
+ * (o - 1) stride >= in + pad (the last window would start in the right padding); y is planes x oh x ow.  Windows are clipped to the
+ * image, and none is empty.  Arguments, refusals and the NaN rule as for mv_maxpool2d_pad_f32; pad may be 0. */
+int mv_maxpool2d_ceil_f32(const float* x, float* y, int64_t planes, int h, int wdt, int k, int stride, int pad, void* stream);
 
 /* ---- the step BEFORE the path: ImageClassification's tail, transforms/_presets.py:58-60 -------
  * convert_image_dtype(float) = image.to(float32).mul_(1/255) (_misc.py:286-288), then normalize =
@@ -873,6 +877,41 @@ int mv_fcos_decode_f32(const float* const* logits, const float* const* ctrness, 
                        const float* image_sizes, const int* idx, int64_t n, int64_t k, float* boxes, float* scores, int64_t* labels,
                        unsigned char* valid, void* stream);
 
+/* ---- SSD.postprocess_detections (models/detection/ssd.py) up to the nms, on the head's own NCHW maps.  The level tables are HOST arrays
+ * of `levels` <= 8 entries as for mv_rpn_topk_f32: map l holds as[l] anchors per location on an hs[l] x ws[l] grid, anchor
+ * v = start_l + (y ws[l] + x) as[l] + a (start_l: the anchors of the levels before, V their total), class c of anchor a in logit
+ * channel a classes + c, delta channels 4 a .. 4 a + 3; image i of map l at pointer[l] + i stride[l] (elements).
+ *
+ * mv_ssd_scores_f32: scores (n, classes, V), CLASS-MAJOR and dense: scores[i][c][v] = softmax over the classes of anchor v, in
+ *   m = the maximum of the classes' logits (any NaN makes it NaN);  e_j = E(fl(x_j - m)) in float32, E the correctly rounded float32
+ *   exp;  S = ((0 + e_0) + e_1) + e_2 + ..., one chain in ascending class order in FLOAT64 (a float32 chain over 91 classes is less
+ *   accurate than torch's softmax);  p_c = (float)((double)e_c / S), the IEEE float64 division rounded to float32.  A row with a NaN
+ *   or with +inf is NaN throughout, as torch's.  ONE launch for all levels and images.
+ * mv_ssd_topk_f32: scores (n, classes, v) as above -> idx (n, (classes - 1) k) int32.  For image i and class c >= 1 (the background is
+ *   skipped) the candidates are the anchors with scores[i][c][v] > (float)score_thresh (a NaN fails); the min(k, candidates) greatest
+ *   by the key (score bits << 32 | ~v) -- the greater score first, the smaller v first among equal scores; scores are >= +0 -- are
+ *   written in descending key order to idx[i][(c - 1) k ...] as f = v classes + c, the rest of the segment is -1.  Exact and
+ *   deterministic for any input; nothing is read back.  k <= 4096.
+ * mv_ssd_decode_f32: one candidate per idx[i][j] (n rows of k): anchor f / classes, label f % classes.  Its default box, with (w, h)
+ *   = wh_pairs[pair_l + a] (a DEVICE (sum of as, 2) table, level after level, already clamped to [0, 1] where the generator clips),
+ *   x_f[l], y_f[l] the level's grid divisors (HOST floats) and batch_w, batch_h the sides of the batch tensor:
+ *     cx = fl(fl(x + 0.5) / x_f[l]),  x1 = fl(fl(cx - fl(0.5 w)) batch_w),  x2 = fl(fl(cx + fl(0.5 w)) batch_w),  y likewise;
+ *   then BoxCoder.decode_single with the weights and `clip` as for mv_rpn_decode_f32, the clamp to image_sizes[i] = (h, w) (DEVICE,
+ *   n rows), scores_out = scores[i][label][anchor], labels int64, valid 1.  f < 0 or an anchor outside the pyramid: zeros,
+ *   valid 0, and nothing is read through it.
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a negative n, v or k (mv_ssd_topk_f32: k < 1), bad level tables,
+ * classes < 2, an image stride below the map, a null or misaligned pointer, an output overlapping an input or another output,
+ * non-positive grid divisors or batch sides; more than 8 levels, anchors x classes beyond 2^31 - 1, k > 4096, n beyond the launch
+ * grid (MV_ERR_UNSUPPORTED).  n == 0 (and k == 0 for the decode) is a no-op that touches no pointer. */
+int mv_ssd_scores_f32(const float* const* logits, const int* hs, const int* ws, const int* as, const int64_t* img_strides, int levels,
+                      int classes, int64_t n, float* scores, void* stream);
+int mv_ssd_topk_f32(const float* scores, int64_t n, int classes, int64_t v, int k, double score_thresh, int* idx, void* stream);
+int mv_ssd_decode_f32(const float* scores, const float* const* deltas, const int* hs, const int* ws, const int* as,
+                      const int64_t* delta_strides, int levels, int classes, const float* wh_pairs, const float* x_f, const float* y_f,
+                      int batch_h, int batch_w, const float* image_sizes, const int* idx, int64_t n, int64_t k, double wx, double wy,
+                      double ww, double wh, double clip, float* boxes, float* scores_out, int64_t* labels, unsigned char* valid,
+                      void* stream);
+
 /* ---- torch.nn.GroupNorm (+ ReLU) on float32 NCHW: x (n, c, h, w) -> y of the same shape, image i at x + i x_stride / y + i y_stride
  * (elements, >= c h w: a channel slice of a wider tensor is passed as it is), each image dense.  The slab of (image, group g) is the
  * contiguous span of m = (c / groups) h w elements at channel g c / groups.  Two launches, nothing read back:
@@ -903,6 +942,28 @@ int64_t mv_group_norm_workspace_bytes(int64_t n, int c, int h, int w, int groups
 int mv_group_norm_act_f32(const float* x, float* y, const float* weight, const float* bias, int64_t n, int c, int h, int w, int groups,
                           int64_t x_stride, int64_t y_stride, double eps, int relu, void* workspace, int64_t workspace_bytes,
                           void* stream);
+
+/* ---- weight.view(1, -1, 1, 1) * torch.nn.functional.normalize(x) (p = 2, dim = 1) on float32 NCHW: SSD's rescaling of conv4_3
+ * (models/detection/ssd.py).  x (n, c, h, w) -> y of the same shape, image i at x + i x_stride / y + i y_stride (elements, >= c h w:
+ * a channel slice of a wider tensor is passed as it is), each image dense; weight: c device floats.  ONE launch, nothing read back.
+ * Per pixel, with x_c its value in channel c:
+ *
+ *   sum    for g = 0 .. 15:  S_g = the sum of (double)x_c (double)x_c (exact) over c = g, g + 16, g + 32, ... < c, added one
+ *          after the other in ascending c to 0 in float64 (a group without a channel is 0);
+ *          S = S_0 + S_1 + ... + S_15 added in ascending g to 0 in float64;
+ *   apply  nrm = (float)sqrt(S) (the float64 square root rounded to float32);  d = nrm < eps32 ? eps32 : nrm  with
+ *          eps32 = (float)eps -- clamp_min, a NaN nrm stays;  y_c = fl(weight[c] fl(x_c / d)): an IEEE division and an IEEE
+ *          multiplication, never an fma, never a reciprocal.
+ * The result of a pixel is a function of its c values, weight and eps alone: not of n, h, w, of the pixel's place or alignment, or
+ * of the launch.  An all-zero pixel gives weight[c] 0; a NaN or an infinity makes its own pixel NaN (x / inf = 0 for a finite x) and
+ * touches no other.  x is read twice, the second time out of L2.
+ *
+ * y may be x itself with the same stride (in place).  Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said): a negative
+ * size, eps that is not positive and finite as a float32, an image stride below c h w, a null or misaligned x / y / weight, y
+ * overlapping x other than exactly or overlapping weight; an image or a grid beyond 2^31 - 1 (MV_ERR_UNSUPPORTED).
+ * n c h w == 0 is a no-op that touches no pointer. */
+int mv_l2_normalize_scale_f32(const float* x, float* y, const float* weight, int64_t n, int c, int h, int w, int64_t x_stride,
+                              int64_t y_stride, double eps, void* stream);
 
 /* ---- torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False) and the front end of a detection model
  * (models/detection/transform.py: normalize -> resize -> batch_images) on planar float32.
