@@ -92,6 +92,9 @@ __device__ inline void hue_pixel(float& r0, float& g0, float& b0, float hue) {
   float h = (hr + hg) + hb;
   h = __builtin_fmodf(h * (1.f / 6.f) + 1.f, 1.f);
   h = remainder1(h + hue);
+  // a NaN channel, or an infinite one (Inf - Inf, Inf / Inf), leaves the hue NaN.  The reference then takes the sector from
+  // int(NaN), which is INT_MIN on one host and 0 on another: the library's rule (include/mi355vision.h) is a pixel of three NaNs
+  const bool no_hue = h != h;
   const float v = maxc;
   // _hsv_to_rgb
   const float h6 = h * 6.f;
@@ -113,6 +116,7 @@ __device__ inline void hue_pixel(float& r0, float& g0, float& b0, float hue) {
     case 4: ro = t, go = p, bo = v; break;
     default: ro = v, go = p, bo = q; break;
   }
+  if (!U8 && no_hue) ro = go = bo = h;
   if (U8) {
     ro = (float)(uint8_t)(int)(ro * 255.999f);
     go = (float)(uint8_t)(int)(go * 255.999f);

@@ -690,6 +690,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_invres_wide(const IrArgs A) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) wk[i] = wds[c * 9 + i];
         const float na = t2a[c], nb = t2b[c];
+        // a hidden channel past A.hidden (72 = 2 chunks + 8) has zero weights and zero norm terms in all three convolutions.  That
+        // cancels it for finite data only: 0 x Inf = NaN in its expansion, and 0 x NaN = NaN through the projection's zero weight
+        // into every output channel of the pixel.  Its depthwise output is stored as +0 by select -- the value it has on finite data
+        const bool live = ch * kHC + c < A.hidden;
         float rows[3][NV + 2];  // [0]: column ix0 - 1, [1 + i]: column ix0 + i, [NV + 1]: column ix0 + NV (stride 1 only)
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -717,7 +721,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_invres_wide(const IrArgs A) {
           a = fmaf(wk[6], rows[2][j * STRIDE], a);
           a = fmaf(wk[7], rows[2][j * STRIDE + 1], a);
           a = fmaf(wk[8], rows[2][j * STRIDE + 2], a);
-          op[j * kOP] = ir_relu6(ir_norm_t<FMA>(a, na, nb));
+          op[j * kOP] = live ? ir_relu6(ir_norm_t<FMA>(a, na, nb)) : 0.f;
         }
       }
     };

@@ -201,18 +201,25 @@ __global__ __launch_bounds__(256) void k_sepfast(const SepFastArgs A) {
           float ogx[4], ogy[4];
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
-            // Sobel taps [[-1,0,1],[-2,0,2],[-1,0,1]] / transpose as the oracle's 9-tap fma chain from +0;
-            // the zero taps are exact no-ops and the +-1 taps exact adds, so they are written as such
+            // Sobel taps [[-1,0,1],[-2,0,2],[-1,0,1]] / transpose as the oracle's 9-tap fma chain from +0; the +-1 taps are
+            // exact adds and written as such.  The zero taps stay in the chain: they are no-ops for finite data only -- an Inf
+            // or NaN under one makes the output NaN, as in the oracle, in conv2d with these weights and in k_separable
             float a = fmaf(-1.f, tp[p], 0.f);
+            a = fmaf(0.f, tp[p + 1], a);
             a = a + tp[p + 2];
             a = fmaf(-2.f, md[p], a);
+            a = fmaf(0.f, md[p + 1], a);
             a = fmaf(2.f, md[p + 2], a);
             a = a - bt[p];
+            a = fmaf(0.f, bt[p + 1], a);
             a = a + bt[p + 2];
             ogx[p] = a;
             float b = fmaf(-1.f, tp[p], 0.f);
             b = fmaf(-2.f, tp[p + 1], b);
             b = b - tp[p + 2];
+            b = fmaf(0.f, md[p], b);
+            b = fmaf(0.f, md[p + 1], b);
+            b = fmaf(0.f, md[p + 2], b);
             b = b + bt[p];
             b = fmaf(2.f, bt[p + 1], b);
             b = b + bt[p + 2];

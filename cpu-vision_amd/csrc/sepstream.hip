@@ -12,7 +12,10 @@
 //   * COLUMN PASS: systolic fma chain in registers, `acc[k+1] = fma(w[k+1], t, acc[k])`: each new row-pass row is one
 //     tap of the KB pending output rows, taps arrive in ascending order (the oracle's order), no row is ever stored
 //     or recomputed.  KB is the register budget of the chain (15, 23, 31, 47 or 63 stages); a kernel with ky < KB taps
-//     is front-padded with zero taps, which are exact no-ops.
+//     is front-padded with zero taps, which are exact no-ops for finite data.  A row whose row-pass result is not finite in some lane
+//     of the wave (fp32 storage) is repaired behind each pass: the row pass again over the real taps alone, the padded chain
+//     stages set back to +0 (0 x Inf is NaN, and a padded tap lies over real cells of the neighbouring columns and rows).
+//     Kernels of exactly KB x KB taps have no padding and are instantiated without any of this (PADDED = false).
 //   * TAPS: 2*KB wave-uniform floats do not fit the SGPR file next to the addressing state (the compiler spilled them
 //     to VGPR lanes: one v_readlane per fma).  They stay in the kernel-argument segment instead and are streamed
 //     through a two-deep SGPR ring, 8*S taps at a time, by s_load_dwordx8 issued one step ahead of its use (scalar
@@ -36,6 +39,7 @@ typedef float f32x2a __attribute__((ext_vector_type(2), aligned(4)));
 typedef unsigned int u32a __attribute__((aligned(1)));
 typedef unsigned short u16a __attribute__((aligned(1)));
 typedef const char __attribute__((address_space(4))) * kernarg_ptr;
+constexpr float kFltMax = 3.402823466e+38f;
 
 struct StreamArgs {
   const void* x;  // float or uint8 storage (uint8: .to(float32) on load, round_() + narrow on store)
@@ -130,7 +134,7 @@ __device__ inline void static_for(F&& f) {
 }
 
 // S = groups of 8 taps per ring step; PF = rows of raw loads in flight per wave
-template <typename T, int KB, int PX, int S, int PF>
+template <typename T, int KB, int PX, int S, int PF, bool PADDED>
 __global__ __launch_bounds__(256) void k_sepstream(const StreamArgs A) {
   constexpr int KBP = KB + 1;
   static_assert(KBP % (8 * S) == 0, "padded tap count must be a whole number of ring steps");
@@ -247,6 +251,11 @@ __global__ __launch_bounds__(256) void k_sepstream(const StreamArgs A) {
       }
     }
     __builtin_amdgcn_wave_barrier();
+    // PADDED (kx < KB or ky < KB, fp32 storage): the zero taps that pad the kernels to KB are no-ops for finite data only -- 0 x Inf
+    // is NaN, and a padded tap lies over real cells of the neighbouring columns and rows.  A NaN or an Inf under ANY tap of a
+    // lane's window leaves that lane's row-pass result non-finite: a wave that sees one repairs this row's two passes behind
+    // them (the same bits for finite data); every other row runs as before
+    bool repair = false;  // wave-uniform
     // ---- row pass with the KB-tap zero-padded kernel: tmp[p] = sum_j wxp[j] * row[xs + p + j - RB]; the padding taps
     //      are exact no-ops in the fma chain, all indices are static (no window shuffling, taps in SGPRs)
     float tmp[PX];
@@ -294,6 +303,23 @@ __global__ __launch_bounds__(256) void k_sepstream(const StreamArgs A) {
         for (int i = 0; i < S; ++i) cur[i] = nxt[i];
         __builtin_amdgcn_sched_barrier(0);  // this step's fmas stay between the issue of the next group and its wait
       }
+      if constexpr (PADDED && !U8) {
+        bool dirty = false;
+#pragma unroll
+        for (int p = 0; p < PX; ++p) dirty = dirty || !(fabsf(tmp[p]) <= kFltMax);
+        repair = __builtin_amdgcn_ballot_w64(dirty) != 0;
+      }
+      if (repair) {  // the same chain over the kx real taps alone, straight from the row buffer
+        const int padx = (KB - kx) >> 1;
+#pragma unroll
+        for (int p = 0; p < PX; ++p) tmp[p] = 0.f;
+        const float* win = rb + LMAX + lane * PX - RB;
+        for (int j = padx; j < KB - padx; ++j) {
+          const float wj = *reinterpret_cast<const float __attribute__((address_space(4)))*>(ktaps + 4 * j);
+#pragma unroll
+          for (int p = 0; p < PX; ++p) tmp[p] = fmaf(wj, win[p + j], tmp[p]);
+        }
+      }
     }
     __builtin_amdgcn_wave_barrier();
     // ---- column pass (systolic): row t is tap KB-1 of output row t-ry, ..., tap 0 of the row KB-1 stages later;
@@ -332,6 +358,15 @@ __global__ __launch_bounds__(256) void k_sepstream(const StreamArgs A) {
 #pragma unroll
       for (int i = 0; i < S; ++i) cur[i] = nxt[i];
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if (repair) {  // the KB - ky padded stages in front of the chain hold +0: what 0 x tmp left there must not move up the chain
+      const int pady = KB - ky;
+#pragma unroll
+      for (int k = 0; k < KB - 1; ++k)
+        if (k < pady) {
+#pragma unroll
+          for (int p = 0; p < PX; ++p) acc[k][p] = 0.f;
+        }
     }
     const int oy = t - ry;
     bool row_tie = false;  // uint8 storage: this lane's pixels of the row hold a value within tie_thresh of a rounding tie
@@ -413,7 +448,8 @@ static int stream_launch(StreamArgs& a, int64_t planes, const float* k1d_x, cons
   if (a.nitems > 4LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "separable: batch too large for one launch");
   a.nblocks = (unsigned)((a.nitems + 3) / 4);
   constexpr int PF = KB <= 23 ? 2 : 4;  // measured (profiles/r01_perf_separable.log): deeper rings cost a wave per SIMD below KB = 31
-  hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, PF>), dim3(a.nblocks), dim3(256), 0, s, a);
+  if (a.kx == KB && a.ky == KB) hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, PF, false>), dim3(a.nblocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_sepstream<T, KB, PX, S, PF, true>), dim3(a.nblocks), dim3(256), 0, s, a);
   return check_launch("k_sepstream");
 }
 

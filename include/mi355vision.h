@@ -56,6 +56,15 @@
  *   - numerics: fp32 taps and accumulation, one fused multiply-add chain per output in
  *     row-major tap order starting from +0 (bit-identical to oracle/oracle.c); uint8 paths
  *     convert to fp32, accumulate, round half-to-even (torch.round_) and narrow.
+ *   - NaN and Inf: every tap of a filter is multiplied, a zero tap included (Sobel's centre column and row: an Inf under one
+ *     gives NaN, as conv2d with those weights does), and nothing else is: zero padding, the padding of a kernel, a channel
+ *     count or a K chunk to a tile, and cells staged for a neighbouring tile never reach an output, so a NaN or an Inf shows
+ *     exactly in the outputs whose receptive field holds it.  An activation or clamp passes NaN and turns +-Inf into its bound.
+ *     Grid sampling (mv_warp_*, mv_elastic_*), as torch's CPU grid_sample with zero padding: a NaN or infinite SOURCE COORDINATE
+ *     (a perspective whose denominator is 0 inside the output) reads no cell -- a nearest sample is then 0 (or the fill), a
+ *     bilinear sample NaN (its weights are NaN); a bilinear sample reads its four cells with their weights, a weight of 0 too.
+ *     adjust_hue on a pixel with a NaN or infinite channel has no hue (Inf - Inf): all three channels become NaN.  (The
+ *     reference picks the output sector from int(NaN), which differs between hosts.)
  */
 #ifndef MI355VISION_H
 #define MI355VISION_H

@@ -87,6 +87,7 @@ def lib() -> C.CDLL:
         _lib.orc_fold_batchnorm.argtypes = [fp, fp, fp, fp, d, i, fp, fp]
         _lib.orc_fold_batchnorm.restype = None
         _lib.orc_conv2d_affine_act_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp, l, i, i, i, i, i, i, i, i, i, i, i]
+        _lib.orc_conv2d_bias_act_f32.argtypes = [fp, fp, fp, fp, l] + [i] * 14
         _lib.orc_pointwise_sliced_affine_act_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp, l, i, l, i, i, i, i]
         _lib.orc_maxpool2d_f32.argtypes = [fp, fp, l, i, i, i, i]
         _lib.orc_deform_conv2d_f32.argtypes = [fp, fp, fp, fp, fp, fp, l] + [i] * 15
@@ -505,6 +506,24 @@ def conv2d_affine_act(x, w, bias=None, alpha=None, beta=None, res=None, stride=1
 # ------------------------------------------------------------------------------------ deform_conv2d
 def _pair(v):
     return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def conv2d_bias_act(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, act=None):
+    """nn.Conv2d of any geometry -> + bias -> activation, one ascending (c, ky, kx) fmaf chain per output, padding by select.
+    The same bits as deform_conv2d with zero offsets on finite data; a NaN or Inf pixel reaches only the windows that hold it."""
+    x, weight = _f32(x), _f32(weight)
+    n, cin, h, wd = x.shape
+    cout, cg, kh, kw = weight.shape
+    assert cg * groups == cin
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    oh = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+    ow = (wd + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+    b = None if bias is None else _f32(bias)
+    y = np.empty((n, cout, oh, ow), np.float32)
+    if y.size:
+        _check(lib().orc_conv2d_bias_act_f32(_p(x), _p(weight), None if b is None else _p(b), _p(y), n, cin, h, wd, cout, kh, kw, sh, sw,
+                                             ph, pw, dh, dw, int(groups), ACT[act]), "conv2d_bias_act")
+    return y
 
 
 def deform_conv2d(x, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
