@@ -11,7 +11,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
                   channels (SSD's conv4_3), float64 sum of squares, one launch
   _crop, _mix     pad / crop / flip / erase / resized_crop; MixUp / CutMix on a batch
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
-  mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2
+  mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2, SqueezeExcitation
+  mobilenetv3     InvertedResidualConfig, InvertedResidual (5x5 depthwise; the squeeze-excitation gate folded into the projection's loads),
+                  MobileNetV3, mobilenet_v3_large / mobilenet_v3_small; _se: global_avg_pool, linear_act, se_scale (float64 sums)
   resnet          BasicBlock / Bottleneck / ResNet, resnet18 ... resnet152, wide_resnet50_2 / 101_2: one launch per conv + norm (+ add) + ReLU
   fpn             FeaturePyramidNetwork, LastLevelMaxPool, LastLevelP6P7: lateral 1x1 conv + nearest upsample + add in one launch
   backbone_utils  IntermediateLayerGetter, BackboneWithFPN, resnet_fpn_backbone
@@ -50,7 +52,7 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
 The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias package at the repo root).
 """
 from . import (anchor_utils, backbone_utils, faster_rcnn, fcos, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
-               keypoint_rcnn, mask_rcnn, mobilenet, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, ssd, transform, transforms,
+               keypoint_rcnn, mask_rcnn, mobilenet, mobilenetv3, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, ssd, transform, transforms,
                tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
@@ -70,6 +72,7 @@ from .retinanet import (RetinaNet, RetinaNetClassificationHead, RetinaNetHead, R
 from .fcos import FCOS, FCOSClassificationHead, FCOSHead, FCOSRegressionHead, fcos_resnet50_fpn  # noqa: F401
 from .ssd import (SSD, SSDClassificationHead, SSDFeatureExtractorVGG, SSDHead, SSDRegressionHead, SSDScoringHead,  # noqa: F401
                   ssd300_vgg16)
+from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small  # noqa: F401
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
                   generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401

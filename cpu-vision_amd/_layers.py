@@ -242,11 +242,13 @@ def _check_epilogue_terms(out_shape, bias, alpha, beta, residual) -> None:
 def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                   alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                   residual: Optional[torch.Tensor] = None, stride: int = 1, groups: int = 1, affine: Optional[str] = None,
-                  activation: Optional[str] = None) -> torch.Tensor:
+                  activation: Optional[str] = None, *, input_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One Conv2dNormActivation block (ops/misc.py:68-128) as one kernel: conv2d(padding=(k-1)//2) -> + bias ->
     folded norm (`affine`: "mul_add" = FrozenBatchNorm2d, "fma" = BatchNorm2d eval) -> + residual -> activation.
-    Covers the MobileNet family's three shapes: dense 3x3 with cin <= 4 (stem), depthwise 3x3 (groups = C),
-    pointwise 1x1; stride 1 or 2."""
+    Covers the MobileNet family's shapes: dense 3x3 with cin <= 4 (stem), depthwise 3x3 and 5x5 (groups = C),
+    pointwise 1x1; stride 1 or 2.
+    input_scale (pointwise only): a squeeze-excitation gate (N, Cin) or (N, Cin, 1, 1) multiplied into the conv's loads
+    (mv_conv1x1_scaled_f32) -- the same bits as conv_norm_act(se_scale(x, input_scale), ...) without that tensor in memory."""
     if x.ndim != 4 or weight.ndim != 4:
         raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
     _lib.require_device(x)
@@ -260,10 +262,18 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
         kind = 1
     elif groups == 1 and (kh, kw) == (1, 1) and cg == cin:
         kind = 2
+    elif groups == cin and cg == 1 and cout == cin and (kh, kw) == (5, 5):
+        kind = 3  # mv_dwconv_norm_act_f32
     else:
         raise NotImplementedError(
-            f"conv_norm_act covers dense 3x3 with cin <= 4, depthwise 3x3 and pointwise 1x1; got weight {tuple(weight.shape)}, "
+            f"conv_norm_act covers dense 3x3 with cin <= 4, depthwise 3x3 and 5x5 and pointwise 1x1; got weight {tuple(weight.shape)}, "
             f"groups={groups} on {cin} input channels")
+    if input_scale is not None:
+        if kind != 2:
+            raise NotImplementedError("input_scale: pointwise (1x1) weights only")
+        if not isinstance(input_scale, torch.Tensor) or tuple(input_scale.shape) not in ((n, cin), (n, cin, 1, 1)):
+            raise RuntimeError(f"input_scale should have shape ({n}, {cin}) or ({n}, {cin}, 1, 1), got "
+                               f"{tuple(input_scale.shape) if isinstance(input_scale, torch.Tensor) else type(input_scale).__name__}")
     if kind == 2 and stride != 1:
         raise NotImplementedError("pointwise convolution with stride != 1")
     if activation not in _ACT_CODES or affine not in _AFFINE_CODES:
@@ -275,9 +285,17 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     _check_epilogue_terms((n, cout, oh, ow), bc, ac, btc, rc)
     y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
     p = _lib.ptr
-    _lib.launch(lib.mv_conv_norm_act_f32, xc, kind, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
-                n, cin, h, w, cout, stride, _AFFINE_CODES[affine], _ACT_CODES[activation])
-    return _lib.forward_only(y, "conv_norm_act", x, weight, bias, alpha, beta, residual)
+    if input_scale is not None:
+        gc = _lib.f32_on(input_scale, x.device)
+        _lib.launch(lib.mv_conv1x1_scaled_f32, xc, xc.data_ptr(), gc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
+                    n, cin, h, w, cout, _AFFINE_CODES[affine], _ACT_CODES[activation])
+    elif kind == 3:
+        _lib.launch(lib.mv_dwconv_norm_act_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
+                    n, cin, h, w, kh, stride, _AFFINE_CODES[affine], _ACT_CODES[activation])
+    else:
+        _lib.launch(lib.mv_conv_norm_act_f32, xc, kind, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
+                    n, cin, h, w, cout, stride, _AFFINE_CODES[affine], _ACT_CODES[activation])
+    return _lib.forward_only(y, "conv_norm_act", x, weight, bias, alpha, beta, residual, input_scale)
 
 
 def conv1x1_upsample_add(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,

@@ -158,6 +158,11 @@ SYMBOLS = {
     "mv_conv_transpose2x2_bias_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "mv_conv_transpose4x4s2_bias_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "mv_heatmaps_to_keypoints_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "mv_dwconv_norm_act_f32": (_i, [_vp] * 7 + [_i64] + [_i] * 7 + [_vp]),
+    "mv_global_avgpool_f64sum_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i64, _vp]),
+    "mv_linear_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "mv_se_scale_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "mv_conv1x1_scaled_f32": (_i, [_vp] * 8 + [_i64] + [_i] * 6 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

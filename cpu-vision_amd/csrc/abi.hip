@@ -700,6 +700,88 @@ int mv_conv1x1_k_slices(int64_t n, int cin, int h, int wdt, int cout, int* slice
   return slices;
 }
 
+// ---- MobileNetV3: depthwise 3x3 | 5x5, squeeze-excitation, the gated projection (dw5x5.hip, se.hip, convnorm.hip) -------------------
+int mv_dwconv_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta, const float* residual,
+                           float* y, int64_t n, int c, int h, int wdt, int k, int stride, int affine, int act, void* stream) {
+  if (k == 3) return mv_conv_norm_act_f32(MV_CONV_DW3X3, x, w, bias, alpha, beta, residual, y, n, c, h, wdt, c, stride, affine, act, stream);
+  // the refusals of mv_conv_norm_act_f32, in its order
+  if (n < 0 || c <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, c, c, h, wdt);
+  if (stride != 1 && stride != 2) return set_error(MV_ERR_INVALID_ARGUMENT, "stride should be 1 or 2 instead of %d", stride);
+  if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
+  if (k != 5) return set_error(MV_ERR_UNSUPPORTED, "depthwise conv with norm: kernel 3 or 5; got %d", k);
+  if (n == 0) return MV_OK;
+  if (!x || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
+  if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
+  const Epilogue e = {bias, alpha, beta, residual, affine, act};
+  return launch_dwpc5x5(x, w, y, n, c, h, wdt, stride, e, (hipStream_t)stream);
+}
+
+int mv_conv1x1_scaled_f32(const float* x, const float* gate, const float* w, const float* bias, const float* alpha, const float* beta,
+                          const float* residual, float* y, int64_t n, int cin, int h, int wdt, int cout, int affine, int act,
+                          void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, cin, cout, h, wdt);
+  if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
+  if (n == 0) return MV_OK;
+  if (!x || !gate || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
+  const long long hw = (long long)h * wdt, ny = n * cout * hw;
+  if (overlaps(y, ny, x, n * cin * hw) || overlaps(y, ny, w, (long long)cout * cin) || overlaps(y, ny, gate, n * cin) ||
+      (residual && overlaps(y, ny, residual, ny)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, gate, weight or residual");
+  const Epilogue e = {bias, affine ? alpha : nullptr, affine ? beta : nullptr, residual, affine, act};
+  return launch_conv1x1_scaled(x, gate, w, y, n, cin, hw, cout, e, (hipStream_t)stream);
+}
+
+int mv_global_avgpool_f64sum_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int64_t x_stride, void* stream) {
+  if (n < 0 || c <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: bad shape n=%lld c=%d h=%d w=%d", (long long)n, c, h, wdt);
+  const long long hw = (long long)h * wdt;
+  if (hw > 0x7fffffffLL || c * hw > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "global_avgpool: an image of %d x %d x %d elements exceeds the 32-bit index", c, h, wdt);
+  if (x_stride < c * hw)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: image stride %lld, an image has %lld elements", (long long)x_stride, c * hw);
+  if (n == 0) return MV_OK;
+  if (n * c > 4LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "global_avgpool: %lld planes exceed the launch grid", (long long)(n * c));
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: null pointer");
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: x and y must be 4-byte aligned");
+  if (overlaps(y, n * c, x, (n - 1) * x_stride + c * hw)) return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: y must not overlap x");
+  return launch_global_avgpool(x, y, n, c, (int)hw, x_stride, (hipStream_t)stream);
+}
+
+int mv_linear_act_f32(const float* x, const float* w, const float* b, float* y, int64_t n, int k, int m, int act, void* stream) {
+  if (n < 0 || k <= 0 || m <= 0) return set_error(MV_ERR_INVALID_ARGUMENT, "bad linear shape n=%lld k=%d m=%d", (long long)n, k, m);
+  if (act != MV_ACT_NONE && act != MV_ACT_RELU && act != MV_ACT_HARDSWISH && act != MV_ACT_HARDSIGMOID && act != MV_ACT_SIGMOID)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "linear_act: activation code %d (none, ReLU, Hardswish, Hardsigmoid, Sigmoid)", act);
+  if (n == 0) return MV_OK;
+  if (n > 65535) return set_error(MV_ERR_UNSUPPORTED, "linear_act: n = %lld rows exceed the launch grid (65535)", (long long)n);
+  if (!x || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  const long long ny = n * m;
+  if (overlaps(y, ny, x, n * k) || overlaps(y, ny, w, (long long)m * k) || (b && overlaps(y, ny, b, m)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "linear_act: y must not overlap x, w or b");
+  return launch_linear_act(x, w, b, y, n, k, m, act, (hipStream_t)stream);
+}
+
+int mv_se_scale_f32(const float* x, const float* gate, float* y, int64_t n, int c, int h, int wdt, void* stream) {
+  if (n < 0 || c <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "se_scale: bad shape n=%lld c=%d h=%d w=%d", (long long)n, c, h, wdt);
+  const long long hw = (long long)h * wdt;
+  if (hw > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "se_scale: a plane of %d x %d elements exceeds the 32-bit index", h, wdt);
+  if (n == 0) return MV_OK;
+  const long long planes = n * c;
+  if (planes > (1LL << 40) / hw) return set_error(MV_ERR_UNSUPPORTED, "se_scale: %lld planes of %lld elements exceed the launch grid", planes, hw);
+  if (!x || !gate || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "se_scale: null pointer");
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4 || (uintptr_t)gate % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "se_scale: x, gate and y must be 4-byte aligned");
+  if (x != y && overlaps(y, planes * hw, x, planes * hw))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "se_scale: y must be x itself (in place) or must not overlap it");
+  if (overlaps(y, planes * hw, gate, planes)) return set_error(MV_ERR_INVALID_ARGUMENT, "se_scale: y must not overlap gate");
+  return launch_se_scale(x, gate, y, planes, (int)hw, (hipStream_t)stream);
+}
+
 int mv_inverted_residual_k_slices(int64_t n, int cin, int hidden, int cout, int h, int wdt, int stride, int* slice_len) {
   int slices = 0, len = hidden;
   if (!invres_plan(n, cin, hidden, cout, h, wdt, stride, &slices, &len)) slices = 0, len = hidden;

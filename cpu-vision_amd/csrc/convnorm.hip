@@ -513,6 +513,9 @@ struct PwArgs {
   // CT instances only (ConvTranspose2d(2, 2), launch_conv_transpose2x2): the cout = 4 * co + 2 * dy + dx channels are stored as the pixel
   // shuffle y[img][co][2 i + dy][2 j + dx] of input pixel (i, j); wdt is the INPUT's row length there and vec_y says wdt is even
   int shuffle;
+  // SC instances only (squeeze-excitation folded into the projection, launch_conv1x1_scaled): gate[img * cin + k] multiplies row k of
+  // image img's X chunk on its way to LDS
+  const float* gate;
 };
 
 
@@ -671,7 +674,10 @@ __device__ __forceinline__ void pw_store_shuffle(const f32x16 (&acc)[NT], const 
 // second launch; the summation order -- one ascending-k chain per slice from +0, slices added in order -- is stated by
 // mv_conv1x1_k_slices() and restated by the oracle (orc_pointwise_sliced_affine_act_f32): bit-exact against that, within
 // 1e-6 relative of the single chain.
-template <int NT, int MW, int KS, bool UP = false, bool CT = false>
+// SC: the X chunk's row k is multiplied by gate[img * cin + k] (__fmul_rn: one rounding, what mv_se_scale_f32 stores) before it goes
+// to LDS; rows k >= cin stay +0 and the gate is not read for them.  Pixel columns past the plane hold 0 * gate, a NaN when the gate
+// is not finite: each pixel is its own MFMA row and those rows are never stored, so nothing stored can see them.
+template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwArgs A) {
   constexpr int PG = 4 / MW;              // pixel groups (waves along pixels)
   constexpr int PXB = PG * NT * 32;       // pixels per workgroup
@@ -743,6 +749,10 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
           if (p + 1 < HW) v.y = src[1];
           if (p + 2 < HW) v.z = src[2];
           if (p + 3 < HW) v.w = src[3];
+        }
+        if constexpr (SC) {
+          const float g = A.gate[(size_t)img * K + k];
+          v.x = __fmul_rn(g, v.x), v.y = __fmul_rn(g, v.y), v.z = __fmul_rn(g, v.z), v.w = __fmul_rn(g, v.w);
         }
       }
       xreg[u] = v;
@@ -921,6 +931,18 @@ static int pw_launch(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: problem too large for one launch");
   const dim3 grid((unsigned)nb, (unsigned)n);
   const bool up = a.top != nullptr;  // the same plan, the instances that gather their residual from `top`
+  if (a.gate) {  // the same plan, the instances that multiply the gate into their X loads
+    int ks = 1;
+    if constexpr (NT == 1) ks = p.ks;
+    if (ks == 2) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 2, false, false, true>), grid, dim3(512), 0, s, a);
+    } else if (ks == 4) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 4, false, false, true>), grid, dim3(1024), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_conv1x1<NT, MW, 1, false, false, true>), grid, dim3(256), 0, s, a);
+    }
+    return ks > 1 ? check_launchf("k_conv1x1_sc<1,%d,ks%d>", MW, ks) : check_launchf("k_conv1x1_sc<%d,%d>", NT, MW);
+  }
   if (a.shuffle) {  // the same plan, the instances whose store is ConvTranspose2d(2, 2)'s pixel shuffle
     int ks = 1;
     if constexpr (NT == 1) ks = p.ks;
@@ -957,7 +979,7 @@ static int pw_pick_nt(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   return pw_launch<(MW == 1 ? 2 : 4), MW>(a, n, p, s);
 }
 
-// up: null, or the extra fields of an UP / CT instance: the coarser map of launch_conv1x1_upsample_add, or launch_conv_transpose2x2's
+// up: null, or the extra fields of an UP / CT / SC instance: the coarser map of launch_conv1x1_upsample_add, or launch_conv_transpose2x2's
 // shuffle flag and input row length (e.res is null then)
 static int conv1x1(const float* x, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout, const Epilogue& e, hipStream_t s,
                    int64_t x_img_stride, int64_t y_img_stride, bool allow_k_slices, const PwArgs* up) {
@@ -995,6 +1017,13 @@ int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top
   up.top_img_stride = (long long)cout * top_h * top_w;
   up.top_sy = (float)top_h / (float)h, up.top_sx = (float)top_w / (float)wd;
   return conv1x1(x, w, y, n, cin, (int64_t)h * wd, cout, e, s, 0, 0, true, &up);
+}
+
+int launch_conv1x1_scaled(const float* x, const float* gate, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout,
+                          const Epilogue& e, hipStream_t s) {
+  PwArgs sc = {};
+  sc.gate = gate;
+  return conv1x1(x, w, y, n, cin, hw, cout, e, s, 0, 0, true, &sc);
 }
 
 int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,

@@ -262,6 +262,21 @@ void conv1x1_plan(int64_t n, int cin, int64_t hw, int cout, int* slices, int* sl
 // source index of each output pixel (k_conv1x1_up: the same plan, tiles and summation order; e.res must be null)
 int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top, float* y, int64_t n, int cin, int h, int wd, int cout,
                                 int top_h, int top_w, const Epilogue& e, hipStream_t s);
+// the pointwise kernel with a per-(image, input channel) gate multiplied into its X loads (k_conv1x1_sc: the same plan, tiles and
+// summation order): bit for bit launch_conv1x1 on x[i][k][p] * gate[i * cin + k], rounded once, without that tensor in memory
+int launch_conv1x1_scaled(const float* x, const float* gate, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout,
+                          const Epilogue& e, hipStream_t s);
+// depthwise 5x5, a kernel per channel, zero padding 2, stride 1 | 2 (dw5x5.hip).  A thread's strip is kDw5Rows output rows, half of
+// that when the launch has fewer than kDw5ShortLaunch threads
+constexpr int kDw5Rows = 8;
+constexpr int kDw5ShortLaunch = 16384;
+int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, int h, int wd, int stride, const Epilogue& e,
+                   hipStream_t s);
+// squeeze-excitation and the dense layer with an activation (se.hip; the orders are stated in mi355vision.h).  The entry points have
+// checked every argument
+int launch_global_avgpool(const float* x, float* y, int64_t n, int c, int hw, int64_t x_stride, hipStream_t s);
+int launch_linear_act(const float* x, const float* w, const float* b, float* y, int64_t n, int k, int m, int act, hipStream_t s);
+int launch_se_scale(const float* x, const float* gate, float* y, int64_t planes, int hw, hipStream_t s);
 // nn.Conv2d of any geometry and deform_conv2d: mv_conv.h, mv_deform.h
 int launch_maxpool2d(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, hipStream_t s);
 int launch_maxpool2d_pad(const float* x, float* y, int64_t planes, int h, int w, int k, int stride, int pad, hipStream_t s);

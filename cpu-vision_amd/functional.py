@@ -25,6 +25,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               ssd_scores / ssd_topk / ssd_decode (ssd.py postprocess_detections up to the nms: softmax, per-class top-k, default boxes)
   _norm       group_norm_act (torch.nn.functional.group_norm + ReLU: the FCOS towers' norm), group_norm_chunk, l2_normalize_scale
               (weight * F.normalize over the channels: SSD's conv4_3)
+  _se         global_avg_pool / linear_act / se_scale and squeeze_excitation_gate / squeeze_excitation (ops/misc.py SqueezeExcitation;
+              MobileNetV3's Linear -> Hardswish); the gate folded into the projection is conv_norm_act(..., input_scale=gate)
   _interp     interpolate (torch.nn.functional.interpolate, plain bilinear) and detection_batch, the fused normalize + resize +
               batch_images in front of a detection model (models/detection/transform.py)
   _mask       paste_masks_in_image / mask_probs (roi_heads.py paste_masks_in_image, maskrcnn_inference) and
@@ -84,6 +86,7 @@ from ._mask import conv_transpose2d_bias_act, conv_transpose2x2_relayout, mask_p
 from ._misc import (center_crop, center_crop_image, _mean_std, normalize, normalize_image, resize, resize_image,  # noqa: F401
                     resize_video, to_dtype, to_dtype_image, _to_dtype_tensor_dispatch, to_float_normalize)
 from ._norm import group_norm_act, group_norm_chunk, l2_normalize_scale  # noqa: F401
+from ._se import global_avg_pool, linear_act, se_scale, squeeze_excitation, squeeze_excitation_gate  # noqa: F401
 from ._registry import _get_kernel, _register_kernel_internal  # noqa: F401
 
 # uint8 images with a kernel side above 3.  True (default) = ONE 2-D pass, the reference's own formulation

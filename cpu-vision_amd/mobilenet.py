@@ -136,6 +136,42 @@ class Conv2dNormActivation(nn.Sequential):
         return fused_conv_block(x, self[0], norm, act, self._fold, residual)
 
 
+_SE_SCALE_ACTIVATIONS = {nn.Hardsigmoid: "hardsigmoid", nn.Sigmoid: "sigmoid"}
+
+
+class SqueezeExcitation(nn.Module):
+    """ops/misc.py SqueezeExcitation: scale_activation(fc2(activation(fc1(avgpool(x))))) * x.  The children are the reference's
+    parameter containers in its order (avgpool, fc1, fc2, activation, scale_activation); `_scale` is three launches
+    (F.squeeze_excitation_gate) and `forward` a fourth (F.se_scale).  A block that follows the layer with a 1x1 projection
+    (MobileNetV3's InvertedResidual) takes `_gate` and passes it to that conv as `input_scale` instead."""
+
+    def __init__(self, input_channels: int, squeeze_channels: int, activation: Callable[..., nn.Module] = nn.ReLU,
+                 scale_activation: Callable[..., nn.Module] = nn.Sigmoid) -> None:
+        super().__init__()
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.fc1 = nn.Conv2d(input_channels, squeeze_channels, 1)
+        self.fc2 = nn.Conv2d(squeeze_channels, input_channels, 1)
+        self.activation = activation()
+        self.scale_activation = scale_activation()
+        if type(self.activation) is not nn.ReLU:
+            raise NotImplementedError(f"SqueezeExcitation activation {type(self.activation).__name__}: ReLU is on the MI355X path")
+        if type(self.scale_activation) not in _SE_SCALE_ACTIVATIONS:
+            raise NotImplementedError(f"SqueezeExcitation scale activation {type(self.scale_activation).__name__}: Hardsigmoid and Sigmoid "
+                                      "are on the MI355X path")
+
+    def _gate(self, x: torch.Tensor) -> torch.Tensor:
+        """The gate as the (N, C) matrix the kernels pass on."""
+        return F.squeeze_excitation_gate(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, "relu",
+                                         _SE_SCALE_ACTIVATIONS[type(self.scale_activation)])
+
+    def _scale(self, x: torch.Tensor) -> torch.Tensor:
+        gate = self._gate(x)
+        return gate.view(gate.shape[0], gate.shape[1], 1, 1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return F.se_scale(x, self._gate(x))
+
+
 class InvertedResidual(nn.Module):
     """models/mobilenetv2.py:18-63: [1x1 expand + norm + ReLU6] -> 3x3 depthwise + norm + ReLU6 -> 1x1 project + norm
     [+ x]: ONE kernel where mv_inverted_residual_k_slices() names one (_fused_plan), else three launches (two when expand_ratio

@@ -1104,6 +1104,58 @@ int mv_conv_transpose4x4s2_bias_act_f32(const float* x, const float* w2, const f
 int mv_heatmaps_to_keypoints_f32(const float* maps, const float* rois, float* xy, float* scores, int64_t r, int k, int mh, int mw,
                                  void* stream);
 
+/* ---- MobileNetV3 (models/mobilenetv3.py): depthwise 5x5 blocks, squeeze-excitation (ops/misc.py SqueezeExcitation), the dense layer
+ * with Hardswish of the classifier.  All DEVICE pointers, float32, 4-byte aligned; every entry is ONE launch, nothing read back.
+ *
+ * mv_dwconv_norm_act_f32: depthwise conv, a k x k kernel per channel, w (c, 1, k, k), zero padding (k - 1) / 2, stride 1 | 2,
+ *   x (n, c, h, w) -> y (n, c, (h - 1) / stride + 1, (w - 1) / stride + 1), then the epilogue of mv_conv_norm_act_f32 in its order:
+ *   `+ bias` -> folded norm (affine) -> `residual + v` -> activation (MV_ACT_NONE .. MV_ACT_SILU).  k == 3 IS
+ *   mv_conv_norm_act_f32(MV_CONV_DW3X3): the same kernels, the same bits.  k == 5 (k_dwpc5x5): one float32 accumulator per output,
+ *   acc = fmaf(w[ky][kx], x[iy][ix], acc) in ascending (ky, kx) order from +0, a tap in the padding entering the chain as +0 --
+ *   oracle/oracle.c::orc_conv2d_affine_act_f32 with groups = c.  The bits do not depend on the alignment of x or on the launch.
+ *   Any other k is MV_ERR_UNSUPPORTED; the other refusals are those of mv_conv_norm_act_f32.
+ *
+ * mv_global_avgpool_f64sum_f32: y[i][c] = the mean of plane (i, c) of x (n, c, h, w), image i at x + i x_stride (elements, >= c h w: a
+ *   channel slice of a wider tensor is passed as it is), y (n, c) dense.  With P = h w and p the index inside the plane:
+ *     lane   element p belongs to lane l = (p / 4) mod 64;  S[l] = the sum of (double)x[p] over the lane's elements, added one after
+ *            the other in ascending p to 0.0 in float64 (a lane without an element is 0.0);
+ *     tree   for off = 32, 16, 8, 4, 2, 1:  S[l] = S[l] + S[l + off] for every l < off;
+ *     mean   y = (float)(S[0] / (double)P): a float64 division, rounded once to float32.
+ *   The result of a plane is a function of its P values alone: not of n, c, the plane's place or alignment, or the width of the loads.
+ *   NaN / +-inf in a plane reach that plane's mean only.  (mv_adaptive_avgpool_f32 keeps its float32 chain.)
+ *
+ * mv_linear_act_f32: y (n, m) = act(x (n, k) w (m, k)^T + b (m, or NULL)).  Per output (i, j):
+ *     lane   S[l] = the sum of the exact float64 products (double)x[i][q] (double)w[j][q] over q = l, l + 64, l + 128, ... < k, added
+ *            in ascending q to 0.0 in float64;  the tree above;
+ *     v      (float)(S[0] + (double)b[j]), without the addend when b is NULL;
+ *     act    MV_ACT_NONE: v;  MV_ACT_RELU: v < 0 ? 0 : v;  with t = clamp(fl(v + 3), 0, 6) (torch.clamp: a NaN stays)
+ *            MV_ACT_HARDSWISH: fl(fl(v t) / 6),  MV_ACT_HARDSIGMOID: fl(t / 6), IEEE divisions;  MV_ACT_SIGMOID:
+ *            fl(1 / fl(1 + E(-v))) with E the correctly rounded float32 exp (mv_rpn_decode_f32's sigmoid).
+ *   A NaN v gives NaN under every activation; hardswish(-inf) is NaN (-inf * 0), as torch's.  An output depends on its row of x, its
+ *   row of w and b[j] alone: not on n, m or its indices.  Other activation codes are MV_ERR_INVALID_ARGUMENT; n <= 65535.
+ *
+ * mv_se_scale_f32: y[i][c][p] = fl(gate[i][c] x[i][c][p]) on dense (n, c, h, w), gate (n, c).  y may be x itself (in place).
+ *
+ * mv_conv1x1_scaled_f32: the pointwise conv of mv_conv_norm_act_f32 (MV_CONV_PW1X1) on x[i][q][p] scaled by gate[i][q] (n, cin), the
+ *   gate multiplied into the kernel's loads (k_conv1x1_sc): the same tiles, plan and summation order (mv_conv1x1_k_slices(n, cin, h, w,
+ *   cout)), the same epilogue.  Bit for bit mv_conv_norm_act_f32(MV_CONV_PW1X1) on the output of mv_se_scale_f32(x, gate), without that
+ *   tensor in memory.  n <= 65535 as there.
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: a null pointer (bias, residual and b may be null), a
+ * non-positive c / cin / cout / h / w / k / m, a negative n, an unknown affine or activation code, an image stride below c h w, a
+ * misaligned pointer (pool, scale), y overlapping an input (mv_se_scale_f32: other than y == x), a plane, an image or a grid beyond
+ * what one launch indexes (MV_ERR_UNSUPPORTED).  n == 0 is a no-op that touches no pointer. */
+#define MV_ACT_HARDSIGMOID 5 /* mv_linear_act_f32 only */
+#define MV_ACT_SIGMOID 6     /* mv_linear_act_f32 only */
+int mv_dwconv_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta, const float* residual,
+                           float* y, int64_t n, int c, int h, int wdt, int k, int stride, int affine, int act, void* stream);
+int mv_global_avgpool_f64sum_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int64_t x_stride, void* stream);
+int mv_linear_act_f32(const float* x, const float* w, const float* b, float* y, int64_t n, int k, int m, int act, void* stream);
+int mv_se_scale_f32(const float* x, const float* gate, float* y, int64_t n, int c, int h, int wdt, void* stream);
+int mv_conv1x1_scaled_f32(const float* x, const float* gate, const float* w, const float* bias, const float* alpha, const float* beta,
+                          const float* residual, float* y, int64_t n, int cin, int h, int wdt, int cout, int affine, int act,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
