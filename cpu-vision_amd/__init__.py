@@ -38,6 +38,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   ssd             SSDFeatureExtractorVGG (VGG16 with the ceil-mode third pool, conv4_3 rescaled by _norm.l2_normalize_scale, the dilated
                   fc6), SSDHead (one conv launch per level and head), SSD: softmax into a class-major matrix, per-class threshold +
                   top-k on its rows, default boxes + decode of the selected candidates only, then batched_nms; ssd300_vgg16
+  segmentation    FCN / FCNHead, DeepLabV3 / DeepLabHead / ASPP / ASPPConv / ASPPPooling on the dilated ResNets (a 1x1 conv + norm + ReLU one
+                  launch; the heads' 3x3 convs the implicit GEMM at padding = dilation = rate, one launch per 128 input channels), fcn_resnet50 / 101, deeplabv3_resnet50 / 101;
+                  model.labels(x): _segment.interpolate_argmax, the final resize + argmax as one launch that writes only the labels
   ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
                   ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*); box_iou / generalized_box_iou /
                   distance_box_iou, masks_to_boxes, MultiScaleRoIAlign, box_area / box_convert / clip_boxes_to_image /
@@ -52,8 +55,8 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
 The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias package at the repo root).
 """
 from . import (anchor_utils, backbone_utils, faster_rcnn, fcos, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
-               keypoint_rcnn, mask_rcnn, mobilenet, mobilenetv3, nn, ops, presets, resnet, retinanet, roi_heads, rpn, sharding, ssd, transform, transforms,
-               tv_tensors)
+               keypoint_rcnn, mask_rcnn, mobilenet, mobilenetv3, nn, ops, presets, resnet, retinanet, roi_heads, rpn, segmentation, sharding, ssd,
+               transform, transforms, tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
 from .backbone_utils import BackboneWithFPN, IntermediateLayerGetter, resnet_fpn_backbone  # noqa: F401
@@ -73,6 +76,8 @@ from .fcos import FCOS, FCOSClassificationHead, FCOSHead, FCOSRegressionHead, fc
 from .ssd import (SSD, SSDClassificationHead, SSDFeatureExtractorVGG, SSDHead, SSDRegressionHead, SSDScoringHead,  # noqa: F401
                   ssd300_vgg16)
 from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small  # noqa: F401
+from .segmentation import (ASPP, FCN, ASPPConv, ASPPPooling, DeepLabHead, DeepLabV3, FCNHead, deeplabv3_resnet50,  # noqa: F401
+                           deeplabv3_resnet101, fcn_resnet50, fcn_resnet101)
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
                   generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401

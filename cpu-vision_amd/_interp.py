@@ -40,23 +40,22 @@ def interpolate_output_size(in_size: Sequence[int], size=None, scale_factor=None
     return [int(math.floor(float(i) * f)) for i, f in zip(in_size, factors)]
 
 
-def interpolate(input: torch.Tensor, size=None, scale_factor=None, mode: str = "bilinear", align_corners: Optional[bool] = False,
-                recompute_scale_factor: Optional[bool] = None, antialias: bool = False) -> torch.Tensor:
-    """torch.nn.functional.interpolate on a 4-D float32 device tensor for mode="bilinear", align_corners=False, antialias=False, the
-    size given by `size=` or by `scale_factor=` with recompute_scale_factor=True.  Everything else raises NotImplementedError naming
-    the argument (the antialiased bilinear resize is F.resize).  Numerics: mi355vision.h, mv_interpolate_bilinear_f32."""
+def checked_interpolate_shape(name: str, input: torch.Tensor, size, scale_factor, mode: str, align_corners: Optional[bool],
+                              recompute_scale_factor: Optional[bool], antialias: bool) -> Tuple[int, int, int, int, int, int]:
+    """The domain of `interpolate`, shared with interpolate_argmax: (n, c, h, w, oh, ow) of a 4-D float32 tensor for
+    mode="bilinear", align_corners=False, antialias=False; everything else raises, naming the argument."""
     if mode != "bilinear":
-        raise NotImplementedError(f"interpolate: mode={mode!r} is not on the MI355X path (mode='bilinear' is)")
+        raise NotImplementedError(f"{name}: mode={mode!r} is not on the MI355X path (mode='bilinear' is)")
     if align_corners:
-        raise NotImplementedError("interpolate: align_corners=True is not on the MI355X path (align_corners=False is)")
+        raise NotImplementedError(f"{name}: align_corners=True is not on the MI355X path (align_corners=False is)")
     if antialias:
-        raise NotImplementedError("interpolate: antialias=True is not on this entry (F.resize is the antialiased bilinear resize)")
+        raise NotImplementedError(f"{name}: antialias=True is not on this entry (F.resize is the antialiased bilinear resize)")
     if input.dim() != 4:
-        raise NotImplementedError(f"interpolate: input of {input.dim()} dimensions is not on the MI355X path (4-D (N, C, H, W) is)")
+        raise NotImplementedError(f"{name}: input of {input.dim()} dimensions is not on the MI355X path (4-D (N, C, H, W) is)")
     if input.dtype != torch.float32:
-        raise NotImplementedError(f"interpolate: input of dtype {input.dtype} is not on the MI355X path (float32 is)")
+        raise NotImplementedError(f"{name}: input of dtype {input.dtype} is not on the MI355X path (float32 is)")
     if scale_factor is not None and size is None and not recompute_scale_factor:
-        raise NotImplementedError("interpolate: scale_factor without recompute_scale_factor=True is not on the MI355X path (the kernel's "
+        raise NotImplementedError(f"{name}: scale_factor without recompute_scale_factor=True is not on the MI355X path (the kernel's "
                                   "scale is in / out)")
     n, c, h, w = (int(s) for s in input.shape)
     oh, ow = interpolate_output_size((h, w), size, scale_factor)
@@ -64,6 +63,16 @@ def interpolate(input: torch.Tensor, size=None, scale_factor=None, mode: str = "
         raise ValueError("recompute_scale_factor is not meaningful with an explicit size.")
     if h < 1 or w < 1 or oh < 1 or ow < 1:
         raise ValueError(f"Input and output sizes should be greater than 0, but got input (H: {h}, W: {w}) output (H: {oh}, W: {ow})")
+    return n, c, h, w, oh, ow
+
+
+def interpolate(input: torch.Tensor, size=None, scale_factor=None, mode: str = "bilinear", align_corners: Optional[bool] = False,
+                recompute_scale_factor: Optional[bool] = None, antialias: bool = False) -> torch.Tensor:
+    """torch.nn.functional.interpolate on a 4-D float32 device tensor for mode="bilinear", align_corners=False, antialias=False, the
+    size given by `size=` or by `scale_factor=` with recompute_scale_factor=True.  Everything else raises NotImplementedError naming
+    the argument (the antialiased bilinear resize is F.resize).  Numerics: mi355vision.h, mv_interpolate_bilinear_f32."""
+    n, c, h, w, oh, ow = checked_interpolate_shape("interpolate", input, size, scale_factor, mode, align_corners, recompute_scale_factor,
+                                                   antialias)
     _lib.require_device(input)
     if n * c == 0:
         return input.new_empty((n, c, oh, ow))

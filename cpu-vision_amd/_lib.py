@@ -153,6 +153,7 @@ SYMBOLS = {
     "mv_roi_detections_f32": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i64] + [_d] * 7 + [_vp] * 5),
     "mv_interpolate_bilinear_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_detection_batch_f32": (_i, [_vp, _ip, _ip, _ip, _ip, _i64, _i, _fp, _fp, _vp, _i, _i, _vp]),
+    "mv_interpolate_argmax_f32": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "mv_paste_masks_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mv_mask_probs_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "mv_conv_transpose2x2_bias_act_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),

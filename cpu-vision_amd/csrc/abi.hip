@@ -2073,6 +2073,28 @@ int mv_detection_batch_f32(const float* const* xs, const int* hs, const int* ws,
   return MV_OK;
 }
 
+// ---- F.interpolate(bilinear) + argmax over the channels, the labels of a segmentation model: segment.hip --------------------------------
+int mv_interpolate_argmax_f32(const float* x, void* y, int64_t n, int c, int h, int w, int oh, int ow, int out_bytes, void* stream) {
+  if (n < 0 || c < 1 || h < 1 || w < 1 || oh < 1 || ow < 1)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: bad shape n=%lld, c=%d, (%d, %d) -> (%d, %d)", (long long)n, c, h, w, oh, ow);
+  if (out_bytes != 1 && out_bytes != 8)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: out_bytes is 1 (uint8) or 8 (int64), got %d", out_bytes);
+  if (out_bytes == 1 && c > 256)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: %d classes do not fit a uint8 label (up to 256 do)", c);
+  if (n == 0) return MV_OK;
+  if (!x || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: null pointer");
+  if (out_bytes == 8 && (uintptr_t)y % 8) return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: int64 labels must be 8-byte aligned");
+  if (n > 0x7fffffffffffLL / ((int64_t)h * w) / c || n > 0x7fffffffffffLL / ((int64_t)oh * ow) / 8)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: %lld images exceed the address space", (long long)n);
+  const ByteRange in = {x, n * c * h * w * 4}, out = {y, n * oh * ow * out_bytes};
+  if (!outputs_clear(&out, 1, &in, 1)) return set_error(MV_ERR_INVALID_ARGUMENT, "interpolate_argmax: the output must not overlap the input");
+  if ((int64_t)h * w > 0x3fffffffLL)  // a tap's byte offset in its plane is 32-bit
+    return set_error(MV_ERR_UNSUPPORTED, "interpolate_argmax: a source plane of %d x %d elements exceeds the 32-bit byte offset", h, w);
+  if (!interp_argmax_grid_fits(n, oh, ow))
+    return set_error(MV_ERR_UNSUPPORTED, "interpolate_argmax: %lld images of (%d, %d) exceed the launch grid", (long long)n, oh, ow);
+  return launch_interp_argmax(x, y, n, c, h, w, oh, ow, out_bytes, (hipStream_t)stream);
+}
+
 // ---- the mask branch of Mask R-CNN: mask.hip, and convnorm.hip's pixel-shuffle instance of the pointwise kernel --------------------------
 int mv_paste_masks_f32(const float* masks, const float* boxes, float* y, int64_t r, int m, int padding, int h, int w, void* stream) {
   if (r < 0 || m < 1 || padding < 0 || h < 1 || w < 1)

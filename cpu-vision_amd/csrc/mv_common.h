@@ -420,6 +420,11 @@ constexpr int kMaxDetImages = 64;  // 64 x 32 B = 2 KiB of the 4 KiB kernel-argu
 bool interp_grid_fits(int64_t planes, int hp, int wp);
 int launch_interp_batch(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int n, int c,
                         const float* mean, const float* stdv, float* y, int hp, int wp, hipStream_t s);
+// F.interpolate(bilinear) + argmax over the channels, the labels of a segmentation model (segment.hip; semantics in mi355vision.h
+// mv_interpolate_argmax_f32).  out_bytes 1 (uint8) or 8 (int64).  The entry point has checked the arguments, the extents and the
+// grid (interp_argmax_grid_fits); n is positive.
+bool interp_argmax_grid_fits(int64_t n, int oh, int ow);
+int launch_interp_argmax(const float* x, void* y, int64_t n, int c, int h, int w, int oh, int ow, int out_bytes, hipStream_t s);
 // Mask R-CNN's paste_masks_in_image and maskrcnn_inference (mask.hip; semantics in mi355vision.h mv_paste_masks_f32,
 // mv_mask_probs_f32).  The entry points have checked the arguments, the extents and the grids (*_grid_fits); r is positive.
 bool paste_masks_grid_fits(int64_t r, int h, int w);

@@ -33,6 +33,7 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               conv_transpose2d_bias_act, ConvTranspose2d(kernel 2, stride 2) + bias + activation (mask_rcnn.py conv5_mask)
   _keypoint   heatmaps_to_keypoints (roi_heads.py) and conv_transpose2d_bias_act's kernel 4, stride 2, padding 1 geometry
               (keypoint_rcnn.py kps_score_lowres) with its conv_transpose4x4_relayout
+  _segment    interpolate_argmax, interpolate(...).argmax(1) as one launch that writes only the labels (segmentation.py labels)
 The switches (INTEGER_BLUR_*, BATCH_INVARIANT_SUMMATION, CONV2D_*) are set on this module only; the code behind it reads them
 here at call time (_lib.switch).
 
@@ -87,6 +88,7 @@ from ._misc import (center_crop, center_crop_image, _mean_std, normalize, normal
                     resize_video, to_dtype, to_dtype_image, _to_dtype_tensor_dispatch, to_float_normalize)
 from ._norm import group_norm_act, group_norm_chunk, l2_normalize_scale  # noqa: F401
 from ._se import global_avg_pool, linear_act, se_scale, squeeze_excitation, squeeze_excitation_gate  # noqa: F401
+from ._segment import interpolate_argmax, LABEL_DTYPES  # noqa: F401
 from ._registry import _get_kernel, _register_kernel_internal  # noqa: F401
 
 # uint8 images with a kernel side above 3.  True (default) = ONE 2-D pass, the reference's own formulation

@@ -1007,6 +1007,26 @@ int mv_interpolate_bilinear_f32(const float* x, float* y, int64_t planes, int h,
 int mv_detection_batch_f32(const float* const* xs, const int* hs, const int* ws, const int* ohs, const int* ows, int64_t n, int c,
                            const float* mean, const float* stdv, float* y, int hp, int wp, void* stream);
 
+/* ---- The labels of a segmentation model (models/segmentation/_utils.py: the head's logits resized to the input with
+ * F.interpolate(mode="bilinear", align_corners=False), then the argmax over the classes that users take of it) as ONE pass.
+ *
+ * mv_interpolate_argmax_f32: x (n, c, h, w) DEVICE float32 -> y (n, oh, ow) DEVICE labels of out_bytes 1 (uint8) or 8 (int64):
+ *   y[b, Y, X] = argmax over k of v_k,   v_k = element (Y, X) of mv_interpolate_bilinear_f32's (h, w) -> (oh, ow) resize of plane (b, k)
+ * The v_k are exactly that entry's float32 values (its per-axis taps and its three-step blend, every product and fma rounded once);
+ * the upsampled planes never reach memory.  The taps and weights of a pixel are computed once for its c planes.  The order is
+ * torch.argmax's: the lowest index among equal maxima (-0.0 == +0.0 is a tie); a NaN is greater than every number and the first NaN
+ * wins.  A NaN or an infinity in a source pixel therefore reaches exactly the output pixels whose taps read it, zero-weight taps
+ * included (0 * inf is NaN).  c == 1 gives all zeros.
+ *
+ * y is stored as one dword (uint8) or two 16-byte stores (int64) per four labels when ow is a multiple of 4 and y is 4-byte resp.
+ * 16-byte aligned, else element by element (mv_last_kernel says which: k_interp_argmax<u8|i64,vec|scalar>); x may start at any 4-byte
+ * address.  Element and byte offsets are 64-bit (n oh ow 8 may pass 2^32).
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: n < 0, c < 1, a size below 1, out_bytes other
+ * than 1 or 8, c > 256 with out_bytes 1, a null pointer, int64 labels that are not 8-byte aligned, an output that overlaps the input,
+ * sizes that exceed the address space; a source plane of 2^30 elements or more, or more workgroups than one launch grid holds
+ * (MV_ERR_UNSUPPORTED).  n == 0 is a no-op that touches no pointer. */
+int mv_interpolate_argmax_f32(const float* x, void* y, int64_t n, int c, int h, int w, int oh, int ow, int out_bytes, void* stream);
+
 /* ---- The mask branch of Mask R-CNN (models/detection/roi_heads.py maskrcnn_inference, paste_masks_in_image; mask_rcnn.py's
  * ConvTranspose2d(kernel 2, stride 2)).  All tensors DEVICE float32 unless said.
  *
