@@ -13,7 +13,8 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   functional_v1   the v1 tensor backend's gaussian_blur / adjust_sharpness, resize / center_crop
   mobilenet       Conv2dNormActivation with a folded norm, InvertedResidual, MobileNetV2, SqueezeExcitation
   mobilenetv3     InvertedResidualConfig, InvertedResidual (5x5 depthwise; the squeeze-excitation gate folded into the projection's loads),
-                  MobileNetV3, mobilenet_v3_large / mobilenet_v3_small; _se: global_avg_pool, linear_act, se_scale (float64 sums)
+                  MobileNetV3, mobilenet_v3_large / mobilenet_v3_small (dilated=True: a segmentation backbone, its depthwise 5x5 convs
+                  at dilation 2 one launch each); _se: global_avg_pool, linear_act, se_scale (float64 sums)
   resnet          BasicBlock / Bottleneck / ResNet, resnet18 ... resnet152, wide_resnet50_2 / 101_2: one launch per conv + norm (+ add) + ReLU
   fpn             FeaturePyramidNetwork, LastLevelMaxPool, LastLevelP6P7: lateral 1x1 conv + nearest upsample + add in one launch
   backbone_utils  IntermediateLayerGetter, BackboneWithFPN, resnet_fpn_backbone
@@ -40,6 +41,8 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
                   top-k on its rows, default boxes + decode of the selected candidates only, then batched_nms; ssd300_vgg16
   segmentation    FCN / FCNHead, DeepLabV3 / DeepLabHead / ASPP / ASPPConv / ASPPPooling on the dilated ResNets (a 1x1 conv + norm + ReLU one
                   launch; the heads' 3x3 convs the implicit GEMM at padding = dilation = rate, one launch per 128 input channels), fcn_resnet50 / 101, deeplabv3_resnet50 / 101;
+                  LRASPP / LRASPPHead (five launches: the gate product and the upsample in the high classifier's loads, the low
+                  classifier as its residual), lraspp_mobilenet_v3_large, deeplabv3_mobilenet_v3_large on the dilated MobileNetV3;
                   model.labels(x): _segment.interpolate_argmax, the final resize + argmax as one launch that writes only the labels
   ops             deform_conv2d / DeformConv2d, nms / batched_nms, roi_align / RoIAlign, roi_pool / RoIPool, ps_roi_pool / PSRoIPool,
                   ps_roi_align / PSRoIAlign (+ registration behind torch.ops.torchvision.*); box_iou / generalized_box_iou /
@@ -76,8 +79,9 @@ from .fcos import FCOS, FCOSClassificationHead, FCOSHead, FCOSRegressionHead, fc
 from .ssd import (SSD, SSDClassificationHead, SSDFeatureExtractorVGG, SSDHead, SSDRegressionHead, SSDScoringHead,  # noqa: F401
                   ssd300_vgg16)
 from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small  # noqa: F401
-from .segmentation import (ASPP, FCN, ASPPConv, ASPPPooling, DeepLabHead, DeepLabV3, FCNHead, deeplabv3_resnet50,  # noqa: F401
-                           deeplabv3_resnet101, fcn_resnet50, fcn_resnet101)
+from .segmentation import (ASPP, FCN, LRASPP, ASPPConv, ASPPPooling, DeepLabHead, DeepLabV3, FCNHead, LRASPPHead,  # noqa: F401
+                           deeplabv3_mobilenet_v3_large, deeplabv3_resnet50, deeplabv3_resnet101, fcn_resnet50, fcn_resnet101,
+                           lraspp_mobilenet_v3_large)
 from .ops import (MultiScaleRoIAlign, box_area, box_convert, box_iou, clip_boxes_to_image, distance_box_iou,  # noqa: F401
                   generalized_box_iou, masks_to_boxes, remove_small_boxes)
 from .functional import (adjust_sharpness, adjust_sharpness_image, box_filter, conv2d_bias_relu,  # noqa: F401

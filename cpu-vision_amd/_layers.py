@@ -242,15 +242,23 @@ def _check_epilogue_terms(out_shape, bias, alpha, beta, residual) -> None:
 def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                   alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                   residual: Optional[torch.Tensor] = None, stride: int = 1, groups: int = 1, affine: Optional[str] = None,
-                  activation: Optional[str] = None, *, input_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  activation: Optional[str] = None, *, input_scale: Optional[torch.Tensor] = None, dilation: int = 1) -> torch.Tensor:
     """One Conv2dNormActivation block (ops/misc.py:68-128) as one kernel: conv2d(padding=(k-1)//2) -> + bias ->
     folded norm (`affine`: "mul_add" = FrozenBatchNorm2d, "fma" = BatchNorm2d eval) -> + residual -> activation.
     Covers the MobileNet family's shapes: dense 3x3 with cin <= 4 (stem), depthwise 3x3 and 5x5 (groups = C),
     pointwise 1x1; stride 1 or 2.
     input_scale (pointwise only): a squeeze-excitation gate (N, Cin) or (N, Cin, 1, 1) multiplied into the conv's loads
-    (mv_conv1x1_scaled_f32) -- the same bits as conv_norm_act(se_scale(x, input_scale), ...) without that tensor in memory."""
+    (mv_conv1x1_scaled_f32) -- the same bits as conv_norm_act(se_scale(x, input_scale), ...) without that tensor in memory.
+    dilation (depthwise 5x5 at stride 1 only): 2 is the dilated block of MobileNetV3 as a segmentation backbone, padding 4
+    (mv_dwconv_dilated_norm_act_f32); every other dilated geometry raises NotImplementedError."""
     if x.ndim != 4 or weight.ndim != 4:
         raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if not isinstance(dilation, int) or isinstance(dilation, bool) or dilation < 1:
+        raise ValueError(f"dilation should be a positive int, got {dilation!r}")
+    if dilation != 1 and not (dilation == 2 and stride == 1 and tuple(weight.shape[1:]) == (1, 5, 5)
+                              and groups == int(x.shape[1]) == int(weight.shape[0])):
+        raise NotImplementedError(f"conv_norm_act: dilation {dilation} with weight {tuple(weight.shape)}, groups={groups}, stride={stride}; the "
+                                  "one dilated geometry is depthwise 5x5 at dilation 2 and stride 1 (every other conv runs at dilation 1)")
     _lib.require_device(x)
     _lib.require_device(weight, "weight")
     _lib.require_f32_layer("conv_norm_act", x, weight)
@@ -290,8 +298,8 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
         _lib.launch(lib.mv_conv1x1_scaled_f32, xc, xc.data_ptr(), gc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
                     n, cin, h, w, cout, _AFFINE_CODES[affine], _ACT_CODES[activation])
     elif kind == 3:
-        _lib.launch(lib.mv_dwconv_norm_act_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
-                    n, cin, h, w, kh, stride, _AFFINE_CODES[affine], _ACT_CODES[activation])
+        _lib.launch(lib.mv_dwconv_dilated_norm_act_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
+                    n, cin, h, w, kh, stride, dilation, _AFFINE_CODES[affine], _ACT_CODES[activation])
     else:
         _lib.launch(lib.mv_conv_norm_act_f32, xc, kind, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), p(rc), y.data_ptr(),
                     n, cin, h, w, cout, stride, _AFFINE_CODES[affine], _ACT_CODES[activation])
@@ -335,6 +343,39 @@ def conv1x1_upsample_add(x: torch.Tensor, weight: torch.Tensor, bias: Optional[t
     _lib.launch(lib.mv_conv1x1_upsample_add_f32, xc, xc.data_ptr(), wc.data_ptr(), p(bc), p(ac), p(btc), tc.data_ptr(), y.data_ptr(),
                 n, cin, h, w, cout, int(tc.shape[2]), int(tc.shape[3]), _AFFINE_CODES[affine], _ACT_CODES[activation])
     return _lib.forward_only(y, "conv1x1_upsample_add", x, weight, bias, alpha, beta, top)
+
+
+def conv1x1_gated_upsample(x: torch.Tensor, gate: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                           residual: Optional[torch.Tensor] = None, size=None) -> torch.Tensor:
+    """LRASPPHead's tail (models/segmentation/lraspp.py: low_classifier(low) + high_classifier(interpolate(cbr(high) * scale(high),
+    size=low.shape[-2:]))) as ONE launch (mv_conv1x1_gated_upsample_f32): the pointwise conv `weight` (Cout, Cin, 1, 1) + `bias` over
+    the bilinear (align_corners=False) resize to `size` of x (N, Cin, h, w) scaled by gate (N, Cin) or (N, Cin, 1, 1), plus `residual`
+    (N, Cout, *size).  The gate product and the four-tap blend happen in the kernel's loads: neither the gated nor the resized tensor
+    reaches memory.  The same bits as conv_norm_act(interpolate(se_scale(x, gate), size=size), weight, bias, residual=residual);
+    summation order: conv1x1_k_slices(N, Cin, *size, Cout)."""
+    from ._interp import checked_interpolate_shape
+    if x.ndim != 4 or weight.ndim != 4:
+        raise RuntimeError(f"Expected 4D input and weight. Got {tuple(x.shape)} and {tuple(weight.shape)}")
+    n, cin, h, w = (int(d) for d in x.shape)
+    cout, cg, kh, kw = (int(d) for d in weight.shape)
+    if (kh, kw) != (1, 1) or cg != cin:
+        raise NotImplementedError(f"conv1x1_gated_upsample covers pointwise 1x1 convs; got weight {tuple(weight.shape)} on {cin} input channels")
+    if not isinstance(gate, torch.Tensor) or tuple(gate.shape) not in ((n, cin), (n, cin, 1, 1)):
+        raise RuntimeError(f"input_scale should have shape ({n}, {cin}) or ({n}, {cin}, 1, 1), got "
+                           f"{tuple(gate.shape) if isinstance(gate, torch.Tensor) else type(gate).__name__}")
+    oh, ow = checked_interpolate_shape("conv1x1_gated_upsample", x, size, None, "bilinear", False, None, False)[4:]
+    _lib.require_device(x)
+    _lib.require_device(weight, "weight")
+    _lib.require_f32_layer("conv1x1_gated_upsample", x, weight)
+    lib = _lib.load()
+    xc, wc = x.contiguous(), weight.detach().contiguous()
+    gc, bc, rc = (_lib.f32_on(t, x.device) for t in (gate, bias, residual))
+    _check_epilogue_terms((n, cout, oh, ow), bc, None, None, rc)
+    y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
+    p = _lib.ptr
+    _lib.launch(lib.mv_conv1x1_gated_upsample_f32, xc, xc.data_ptr(), gc.data_ptr(), wc.data_ptr(), p(bc), p(rc), y.data_ptr(),
+                n, cin, h, w, oh, ow, cout)
+    return _lib.forward_only(y, "conv1x1_gated_upsample", x, gate, weight, bias, residual)
 
 
 def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,

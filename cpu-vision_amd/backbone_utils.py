@@ -5,7 +5,8 @@ resnet_fpn_backbone, _resnet_fpn_extractor, _validate_trainable_layers) of the r
 (body.conv1 ... body.layer4, fpn.inner_blocks ...), state-dict keys and messages.  In this package the parameter containers' own
 forward is never called, so the getter does not call its children one by one: it runs the fused path the models run --
 a Conv2d, norm[, ReLU] run of children is ONE resnet.fused_conv_norm launch, MaxPool2d is F.max_pool2d, a Sequential of the
-package's blocks is called as it is.  A model with any other child is refused at construction.  Inference only.
+package's blocks is called as it is, and so is a block on its own (the children "0" ... "16" of a MobileNetV3's `features`, the
+backbone of LRASPP and deeplabv3_mobilenet_v3_large).  A model with any other child is refused at construction.  Inference only.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 from torch import nn
 
-from . import _lib, resnet
+from . import _lib, mobilenetv3, resnet
 from . import functional as F
 from .fpn import ExtraFPNBlock, FeaturePyramidNetwork, LastLevelMaxPool
 from .mobilenet import Conv2dNormActivation, FrozenBatchNorm2d, InvertedResidual, _FoldedNorm
@@ -24,7 +25,7 @@ from .mobilenet import Conv2dNormActivation, FrozenBatchNorm2d, InvertedResidual
 __all__ = ["IntermediateLayerGetter", "BackboneWithFPN", "resnet_fpn_backbone"]
 
 _NORMS = (nn.BatchNorm2d, FrozenBatchNorm2d)
-_BLOCKS = (resnet.BasicBlock, resnet.Bottleneck, Conv2dNormActivation, InvertedResidual)
+_BLOCKS = (resnet.BasicBlock, resnet.Bottleneck, Conv2dNormActivation, InvertedResidual, mobilenetv3.InvertedResidual)
 
 
 def _fused_plan(children: "OrderedDict[str, nn.Module]", returned) -> list:

@@ -701,22 +701,33 @@ int mv_conv1x1_k_slices(int64_t n, int cin, int h, int wdt, int cout, int* slice
 }
 
 // ---- MobileNetV3: depthwise 3x3 | 5x5, squeeze-excitation, the gated projection (dw5x5.hip, se.hip, convnorm.hip) -------------------
-int mv_dwconv_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta, const float* residual,
-                           float* y, int64_t n, int c, int h, int wdt, int k, int stride, int affine, int act, void* stream) {
-  if (k == 3) return mv_conv_norm_act_f32(MV_CONV_DW3X3, x, w, bias, alpha, beta, residual, y, n, c, h, wdt, c, stride, affine, act, stream);
+int mv_dwconv_dilated_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta,
+                                   const float* residual, float* y, int64_t n, int c, int h, int wdt, int k, int stride, int dilation,
+                                   int affine, int act, void* stream) {
+  if (dilation < 1) return set_error(MV_ERR_INVALID_ARGUMENT, "dilation should be at least 1 instead of %d", dilation);
+  if (k == 3 && dilation == 1)
+    return mv_conv_norm_act_f32(MV_CONV_DW3X3, x, w, bias, alpha, beta, residual, y, n, c, h, wdt, c, stride, affine, act, stream);
   // the refusals of mv_conv_norm_act_f32, in its order
   if (n < 0 || c <= 0 || h <= 0 || wdt <= 0)
     return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, c, c, h, wdt);
   if (stride != 1 && stride != 2) return set_error(MV_ERR_INVALID_ARGUMENT, "stride should be 1 or 2 instead of %d", stride);
   if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
     return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
-  if (k != 5) return set_error(MV_ERR_UNSUPPORTED, "depthwise conv with norm: kernel 3 or 5; got %d", k);
+  if (dilation == 1 && k != 5) return set_error(MV_ERR_UNSUPPORTED, "depthwise conv with norm: kernel 3 or 5; got %d", k);
+  if (dilation != 1 && !(dilation == 2 && k == 5 && stride == 1))
+    return set_error(MV_ERR_UNSUPPORTED, "dilated depthwise conv with norm: kernel 5, dilation 2, stride 1; got kernel %d, dilation %d, stride %d",
+                     k, dilation, stride);
   if (n == 0) return MV_OK;
   if (!x || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
   if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
   if (x == y) return set_error(MV_ERR_INVALID_ARGUMENT, "output must not alias input");
   const Epilogue e = {bias, alpha, beta, residual, affine, act};
-  return launch_dwpc5x5(x, w, y, n, c, h, wdt, stride, e, (hipStream_t)stream);
+  return launch_dwpc5x5(x, w, y, n, c, h, wdt, stride, dilation, e, (hipStream_t)stream);
+}
+
+int mv_dwconv_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta, const float* residual,
+                           float* y, int64_t n, int c, int h, int wdt, int k, int stride, int affine, int act, void* stream) {
+  return mv_dwconv_dilated_norm_act_f32(x, w, bias, alpha, beta, residual, y, n, c, h, wdt, k, stride, 1, affine, act, stream);
 }
 
 int mv_conv1x1_scaled_f32(const float* x, const float* gate, const float* w, const float* bias, const float* alpha, const float* beta,
@@ -735,6 +746,21 @@ int mv_conv1x1_scaled_f32(const float* x, const float* gate, const float* w, con
     return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, gate, weight or residual");
   const Epilogue e = {bias, affine ? alpha : nullptr, affine ? beta : nullptr, residual, affine, act};
   return launch_conv1x1_scaled(x, gate, w, y, n, cin, hw, cout, e, (hipStream_t)stream);
+}
+
+// ---- LRASPP's head: high_classifier over the resized gated map, low_classifier's output as the residual (convnorm.hip, k_conv1x1_gu) ---
+int mv_conv1x1_gated_upsample_f32(const float* x, const float* gate, const float* w, const float* bias, const float* residual, float* y,
+                                  int64_t n, int cin, int h, int wdt, int oh, int ow, int cout, void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h <= 0 || wdt <= 0 || oh <= 0 || ow <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d (%d, %d) -> (%d, %d)", (long long)n, cin, cout, h, wdt, oh, ow);
+  if (n == 0) return MV_OK;
+  if (!x || !gate || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  const long long hw = (long long)h * wdt, ohw = (long long)oh * ow, ny = n * cout * ohw;
+  if (overlaps(y, ny, x, n * cin * hw) || overlaps(y, ny, w, (long long)cout * cin) || overlaps(y, ny, gate, n * cin) ||
+      (residual && residual != y && overlaps(y, ny, residual, ny)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, gate or weight, nor a residual other than itself");
+  const Epilogue e = {bias, nullptr, nullptr, residual, MV_AFFINE_NONE, MV_ACT_NONE};
+  return launch_conv1x1_gated_upsample(x, gate, w, y, n, cin, h, wdt, oh, ow, cout, e, (hipStream_t)stream);
 }
 
 int mv_global_avgpool_f64sum_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int64_t x_stride, void* stream) {

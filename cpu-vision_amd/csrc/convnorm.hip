@@ -12,6 +12,7 @@
 
 #include "mv_common.h"
 #include "mv_epilogue.h"
+#include "mv_bilinear.h"
 
 namespace mv {
 
@@ -516,6 +517,11 @@ struct PwArgs {
   // SC instances only (squeeze-excitation folded into the projection, launch_conv1x1_scaled): gate[img * cin + k] multiplies row k of
   // image img's X chunk on its way to LDS
   const float* gate;
+  // GU instances only (LRASPP's head, launch_conv1x1_gated_upsample): x is (n, cin, src_h, src_w), the X chunk's element (k, p) is the
+  // bilinear blend at output pixel p of the (oh, ow = wdt) plane of the four taps fl(gate[img * cin + k] * x[img][k][tap]); `gate` above
+  // and `wdt` are shared with the SC / UP fields.  src_sy / src_sx: (float)src_h / (float)oh and (float)src_w / (float)ow, on the host
+  int src_h, src_w;
+  float src_sy, src_sx;
 };
 
 
@@ -677,7 +683,12 @@ __device__ __forceinline__ void pw_store_shuffle(const f32x16 (&acc)[NT], const 
 // SC: the X chunk's row k is multiplied by gate[img * cin + k] (__fmul_rn: one rounding, what mv_se_scale_f32 stores) before it goes
 // to LDS; rows k >= cin stay +0 and the gate is not read for them.  Pixel columns past the plane hold 0 * gate, a NaN when the gate
 // is not finite: each pixel is its own MFMA row and those rows are never stored, so nothing stored can see them.
-template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false>
+// GU: the X chunk is GATHERED: element (k, p) = bilinear_blend of the four taps fl(gate[img * cin + k] * x[img][k][iy][ix]) (__fmul_rn,
+// as SC) with mv_bilinear.h's bilinear_tap per axis of output pixel p = oy * ow + ox -- the bits of mv_interpolate_bilinear_f32 on the
+// output of mv_se_scale_f32.  A thread's four consecutive pixels are the same in every chunk (256 is a multiple of PXB / 4) and may
+// cross a row end: their four tap offsets and weights are computed once, before the first chunk.  Pixels past the plane and rows
+// k >= cin stay +0 and read neither x nor the gate.
+template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false, bool GU = false>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwArgs A) {
   constexpr int PG = 4 / MW;              // pixel groups (waves along pixels)
   constexpr int PXB = PG * NT * 32;       // pixels per workgroup
@@ -712,6 +723,26 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
 
+  // GU: tap offsets inside a source plane ([0] (y0, x0), [1] (y0, x1), [2] (y1, x0), [3] (y1, x1)) and the weights (x0, x1, y0, y1)
+  // of pixels p0 + 4 q + i, q = tid % (PXB / 4) -- the q of every X unit of this thread
+  static_assert(!GU || 256 % (PXB / 4) == 0, "a thread's pixel quad must not depend on the unit");
+  int goff[GU ? 4 : 1][4];
+  float gwt[GU ? 4 : 1][4];
+  (void)goff, (void)gwt;
+  if constexpr (GU) {
+    const int p = p0 + 4 * (tid % (PXB / 4));
+    int oy = p / A.wdt, ox = p - oy * A.wdt;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool in = p + i < HW;  // past the plane: offsets 0, never read
+      const BilinearTap ty = bilinear_tap(in ? oy : 0, A.src_sy, A.src_h), tx = bilinear_tap(in ? ox : 0, A.src_sx, A.src_w);
+      goff[i][0] = ty.i0 * A.src_w + tx.i0, goff[i][1] = ty.i0 * A.src_w + tx.i1;
+      goff[i][2] = ty.i1 * A.src_w + tx.i0, goff[i][3] = ty.i1 * A.src_w + tx.i1;
+      gwt[i][0] = tx.w0, gwt[i][1] = tx.w1, gwt[i][2] = ty.w0, gwt[i][3] = ty.w1;
+      if (++ox == A.wdt) ox = 0, ++oy;
+    }
+  }
+
   f32x4 wreg[WU], xreg[XU];
   auto gload = [&](int ch) {
     const int kc = ch * kPK;
@@ -740,7 +771,22 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
       const int row = idx / (PXB / 4), q = idx % (PXB / 4);
       const int k = kc + row, p = p0 + 4 * q;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (k < K) {
+      if constexpr (GU) {
+        if (k < K) {
+          const float* src = X + (size_t)k * (A.src_h * A.src_w);
+          const float g = A.gate[(size_t)img * K + k];
+          float e[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (p + i < HW) {
+              BilinearTap ty, tx;
+              tx.w0 = gwt[i][0], tx.w1 = gwt[i][1], ty.w0 = gwt[i][2], ty.w1 = gwt[i][3];
+              e[i] = bilinear_blend(ty, tx, __fmul_rn(g, src[goff[i][0]]), __fmul_rn(g, src[goff[i][1]]), __fmul_rn(g, src[goff[i][2]]),
+                                    __fmul_rn(g, src[goff[i][3]]));
+            }
+          v = (f32x4){e[0], e[1], e[2], e[3]};
+        }
+      } else if (k < K) {
         const float* src = X + (size_t)k * HW + p;
         if (A.vec_x && p + 3 < HW) {
           v = *reinterpret_cast<const f32x4*>(src);
@@ -931,6 +977,18 @@ static int pw_launch(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: problem too large for one launch");
   const dim3 grid((unsigned)nb, (unsigned)n);
   const bool up = a.top != nullptr;  // the same plan, the instances that gather their residual from `top`
+  if (a.src_h) {  // the same plan, the instances that gather their X chunk from the gated coarser map
+    int ks = 1;
+    if constexpr (NT == 1) ks = p.ks;
+    if (ks == 2) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 2, false, false, false, true>), grid, dim3(512), 0, s, a);
+    } else if (ks == 4) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 4, false, false, false, true>), grid, dim3(1024), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_conv1x1<NT, MW, 1, false, false, false, true>), grid, dim3(256), 0, s, a);
+    }
+    return ks > 1 ? check_launchf("k_conv1x1_gu<1,%d,ks%d>", MW, ks) : check_launchf("k_conv1x1_gu<%d,%d>", NT, MW);
+  }
   if (a.gate) {  // the same plan, the instances that multiply the gate into their X loads
     int ks = 1;
     if constexpr (NT == 1) ks = p.ks;
@@ -989,7 +1047,7 @@ static int conv1x1(const float* x, const float* w, float* y, int64_t n, int cin,
   if (up) a = *up;
   a.x = x, a.w = w, a.y = y, a.e = e;
   a.cin = cin, a.cout = cout, a.hw = (int)hw;
-  a.x_img_stride = x_img_stride > 0 ? x_img_stride : (long long)cin * hw;
+  a.x_img_stride = x_img_stride > 0 ? x_img_stride : (long long)cin * (a.src_h ? (long long)a.src_h * a.src_w : hw);
   a.y_img_stride = y_img_stride > 0 ? y_img_stride : (long long)cout * hw;
   a.chunks = (cin + kPK - 1) / kPK;
   a.vec_w = (cin % 4 == 0) && ((uintptr_t)w % 16 == 0);
@@ -1024,6 +1082,16 @@ int launch_conv1x1_scaled(const float* x, const float* gate, const float* w, flo
   PwArgs sc = {};
   sc.gate = gate;
   return conv1x1(x, w, y, n, cin, hw, cout, e, s, 0, 0, true, &sc);
+}
+
+int launch_conv1x1_gated_upsample(const float* x, const float* gate, const float* w, float* y, int64_t n, int cin, int h, int wd, int oh,
+                                  int ow, int cout, const Epilogue& e, hipStream_t s) {
+  // tap offsets inside a source plane and a channel's plane offset k * h * wd are ints
+  if ((long long)cin * h * wd > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: source image too large");
+  PwArgs gu = {};
+  gu.gate = gate, gu.src_h = h, gu.src_w = wd, gu.wdt = ow;
+  gu.src_sy = (float)h / (float)oh, gu.src_sx = (float)wd / (float)ow;
+  return conv1x1(x, w, y, n, cin, (int64_t)oh * ow, cout, e, s, 0, 0, true, &gu);
 }
 
 int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,

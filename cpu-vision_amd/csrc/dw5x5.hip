@@ -11,6 +11,12 @@
 // need dword alignment only, so the same instruction serves rows that are 16-byte aligned (W a multiple of 4 on an aligned x) and
 // rows that are not (7- and 14-pixel maps, an x at a 4-byte offset); a quad that crosses an end of the row is read element by
 // element under its bounds.  Either way a register holds x[iy][ix] or +0: the two ways cannot differ in a bit.
+//
+// DIL = 2 (the dilated blocks of MobileNetV3 as a segmentation backbone: kernel 5, dilation 2, stride 1, padding 4 -- the one dilated
+// geometry): acc = fmaf(w[ky][kx], x[oy - 4 + 2 ky][ox - 4 + 2 kx], acc) in the same order.  The columns of a thread's 4 outputs,
+// ox0 - 4 .. ox0 + 7, are exactly the three quads of stride 1; output j, tap kx reads register j + 2 kx.  A strip walks the output
+// rows of ONE PARITY of a block of 2 * rows rows (oy0, oy0 + 2, ...), so that the five input rows oy - 4, oy - 2, .., oy + 4 roll
+// through the registers as at dilation 1: a strip is a (row block, parity) pair, strip index 2 * block + parity.
 #include "mv_common.h"
 #include "mv_epilogue.h"
 
@@ -26,13 +32,17 @@ struct Dw5Args {
   Epilogue e;
   long long total;  // planes * strips * groups_x
   int c, h, wd, oh, ow;
-  int rows, strips, groups_x;
+  int rows, strips, groups_x;  // DIL = 2: rows per parity of a row block; strips = 2 * row blocks
 };
 
-template <int STRIDE>
-__global__ __launch_bounds__(256) void k_dwpc5x5(const Dw5Args A) {
+// DIL = 2 asks for 4 workgroups per CU (4 waves per SIMD): left alone the instance takes 130 VGPRs, two above that occupancy; the
+// dilation-1 instances keep the allocation they had (125 and 142 VGPRs)
+template <int STRIDE, int DIL = 1>
+__global__ __launch_bounds__(256, DIL == 2 ? 4 : 1) void k_dwpc5x5(const Dw5Args A) {
+  static_assert(DIL == 1 || (DIL == 2 && STRIDE == 1), "the dilated geometry is kernel 5, dilation 2, stride 1");
   constexpr int NQ = 2 + STRIDE;  // quads per row: columns ox0 * STRIDE - 4 .. + 4 NQ - 1
   constexpr int NC = 4 * NQ;
+  constexpr int B0 = DIL == 1 ? 2 : 0;  // output j, tap kx reads r[B0 + j * STRIDE + kx * DIL]
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= A.total) return;
   const int gx = (int)(idx % A.groups_x);
@@ -44,8 +54,10 @@ __global__ __launch_bounds__(256) void k_dwpc5x5(const Dw5Args A) {
   const float* xp = A.x + (size_t)plane * H * W;
   float* yp = A.y + (size_t)plane * A.oh * OW;
   const float* rp = A.e.res ? A.e.res + (size_t)plane * A.oh * OW : nullptr;
-  const int ox0 = 4 * gx, c0 = ox0 * STRIDE - 4;  // r[i] holds column c0 + i; output j, tap kx reads r[2 + j * STRIDE + kx]
-  const int oy0 = st * A.rows, oy1 = min(oy0 + A.rows, A.oh);
+  const int ox0 = 4 * gx, c0 = ox0 * STRIDE - 4;  // r[i] holds column c0 + i
+  const int blk0 = (DIL == 1 ? st : st >> 1) * (A.rows * DIL);  // first row of the strip's row block
+  const int oy0 = blk0 + (DIL == 1 ? 0 : st & 1), oy1 = min(blk0 + A.rows * DIL, A.oh);
+  if (DIL > 1 && oy0 >= oy1) return;  // the odd-parity strip of a last block of one row
 
   float wk[25];
 #pragma unroll
@@ -73,27 +85,27 @@ __global__ __launch_bounds__(256) void k_dwpc5x5(const Dw5Args A) {
   };
 
   float r0[NC], r1[NC], r2[NC], r3[NC], r4[NC];
-  load_row(oy0 * STRIDE - 2, r0);
-  load_row(oy0 * STRIDE - 1, r1);
+  load_row(oy0 * STRIDE - 2 * DIL, r0);
+  load_row(oy0 * STRIDE - DIL, r1);
   load_row(oy0 * STRIDE, r2);
-  load_row(oy0 * STRIDE + 1, r3);
-  for (int oy = oy0; oy < oy1; ++oy) {
-    load_row(oy * STRIDE + 2, r4);
+  load_row(oy0 * STRIDE + DIL, r3);
+  for (int oy = oy0; oy < oy1; oy += DIL) {
+    load_row(oy * STRIDE + 2 * DIL, r4);
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int b = 2 + j * STRIDE;
+      const int b = B0 + j * STRIDE;
       float acc = 0.f;
 #pragma unroll
-      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[kx], r0[b + kx], acc);
+      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[kx], r0[b + kx * DIL], acc);
 #pragma unroll
-      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[5 + kx], r1[b + kx], acc);
+      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[5 + kx], r1[b + kx * DIL], acc);
 #pragma unroll
-      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[10 + kx], r2[b + kx], acc);
+      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[10 + kx], r2[b + kx * DIL], acc);
 #pragma unroll
-      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[15 + kx], r3[b + kx], acc);
+      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[15 + kx], r3[b + kx * DIL], acc);
 #pragma unroll
-      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[20 + kx], r4[b + kx], acc);
+      for (int kx = 0; kx < 5; ++kx) acc = fmaf(wk[20 + kx], r4[b + kx * DIL], acc);
       v[j] = epi_norm(acc, ct, A.e);
     }
     const size_t o = (size_t)oy * OW + ox0;
@@ -129,8 +141,8 @@ __global__ __launch_bounds__(256) void k_dwpc5x5(const Dw5Args A) {
 
 }  // namespace
 
-int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, int h, int wd, int stride, const Epilogue& e,
-                   hipStream_t s) {
+int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, int h, int wd, int stride, int dilation,
+                   const Epilogue& e, hipStream_t s) {
   Dw5Args a = {};
   a.x = x, a.w = w, a.y = y, a.e = e;
   a.c = c, a.h = h, a.wd = wd;
@@ -139,13 +151,19 @@ int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, i
   // strip height: kDw5Rows rows amortise the four halo rows (12 row loads for 8 outputs rows at stride 1); launches that would leave
   // the chip short of threads (the 14- and 7-pixel maps at batch 1) take half
   const long long planes = (long long)n * c;
+  // dilation 2 (stride 1): a row block is 2 * rows output rows, one strip per parity -- the same rule on its strip count
+  auto strips_of = [&](int rows) { return dilation * ((a.oh + dilation * rows - 1) / (dilation * rows)); };
   a.rows = kDw5Rows;
-  if (planes * ((a.oh + a.rows - 1) / a.rows) * a.groups_x < kDw5ShortLaunch) a.rows = kDw5Rows / 2;
-  a.strips = (a.oh + a.rows - 1) / a.rows;
+  if (planes * strips_of(a.rows) * a.groups_x < kDw5ShortLaunch) a.rows = kDw5Rows / 2;
+  a.strips = strips_of(a.rows);
   a.total = planes * a.strips * a.groups_x;
   if (a.total > 256LL * 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "depthwise 5x5: batch too large for one launch");
   if (a.total == 0) return MV_OK;
   const unsigned nb = (unsigned)((a.total + 255) / 256);
+  if (dilation == 2) {
+    hipLaunchKernelGGL((k_dwpc5x5<1, 2>), dim3(nb), dim3(256), 0, s, a);
+    return check_launchf("k_dwpc5x5<s1,d2,rows%d>", a.rows);
+  }
   if (stride == 1)
     hipLaunchKernelGGL((k_dwpc5x5<1>), dim3(nb), dim3(256), 0, s, a);
   else

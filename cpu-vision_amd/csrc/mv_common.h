@@ -266,11 +266,16 @@ int launch_conv1x1_upsample_add(const float* x, const float* w, const float* top
 // summation order): bit for bit launch_conv1x1 on x[i][k][p] * gate[i * cin + k], rounded once, without that tensor in memory
 int launch_conv1x1_scaled(const float* x, const float* gate, const float* w, float* y, int64_t n, int cin, int64_t hw, int cout,
                           const Epilogue& e, hipStream_t s);
-// depthwise 5x5, a kernel per channel, zero padding 2, stride 1 | 2 (dw5x5.hip).  A thread's strip is kDw5Rows output rows, half of
-// that when the launch has fewer than kDw5ShortLaunch threads
+// the pointwise kernel over U = the bilinear (align_corners = False) resize to (oh, ow) of fl(gate[i][k] * x[i][k]) (n, cin, h, wd), the
+// product and the four-tap blend computed in its X loads (k_conv1x1_gu: the plan, tiles and summation order of launch_conv1x1 on
+// (n, cin, oh * ow, cout)); neither the gated nor the resized tensor reaches memory.  LRASPP's head
+int launch_conv1x1_gated_upsample(const float* x, const float* gate, const float* w, float* y, int64_t n, int cin, int h, int wd, int oh,
+                                  int ow, int cout, const Epilogue& e, hipStream_t s);
+// depthwise 5x5, a kernel per channel, stride 1 | 2 with zero padding 2, or dilation 2 at stride 1 with zero padding 4 (dw5x5.hip).  A
+// thread's strip is kDw5Rows output rows (of one parity at dilation 2), half of that when the launch has fewer than kDw5ShortLaunch threads
 constexpr int kDw5Rows = 8;
 constexpr int kDw5ShortLaunch = 16384;
-int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, int h, int wd, int stride, const Epilogue& e,
+int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, int h, int wd, int stride, int dilation, const Epilogue& e,
                    hipStream_t s);
 // squeeze-excitation and the dense layer with an activation (se.hip; the orders are stated in mi355vision.h).  The entry points have
 // checked every argument

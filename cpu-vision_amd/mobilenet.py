@@ -92,9 +92,13 @@ def fused_conv_block(x: torch.Tensor, conv: nn.Conv2d, norm: Optional[nn.Module]
                      residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv -> norm -> (+ residual) -> activation as one launch; the modules only hold the parameters."""
     k = conv.kernel_size
-    if conv.dilation != (1, 1) or conv.padding != ((k[0] - 1) // 2, (k[1] - 1) // 2) or conv.stride[0] != conv.stride[1] or \
-            conv.padding_mode != "zeros":
-        raise NotImplementedError(f"{conv}: the MI355X blocks cover dilation 1, 'same'-style zero padding and square strides")
+    # the one dilated geometry: MobileNetV3's dilated blocks (depthwise 5x5, dilation 2, padding 4, stride 1: k_dwpc5x5<1, 2>)
+    dilated = conv.groups == conv.in_channels == conv.out_channels and k == (5, 5) and conv.dilation == (2, 2) and \
+        conv.padding == (4, 4) and conv.stride == (1, 1) and conv.padding_mode == "zeros"
+    if not dilated and (conv.dilation != (1, 1) or conv.padding != ((k[0] - 1) // 2, (k[1] - 1) // 2) or conv.stride[0] != conv.stride[1]
+                        or conv.padding_mode != "zeros"):
+        raise NotImplementedError(f"{conv}: the MI355X blocks cover dilation 1, 'same'-style zero padding and square strides (and the "
+                                  "depthwise 5x5 conv at dilation 2, padding 4, stride 1)")
     if act is not None and type(act) not in _ACTIVATIONS:
         raise NotImplementedError(f"activation {type(act).__name__}")
     if norm is None and residual is None and type(act) in (nn.ReLU, type(None)) and k == (3, 3) and conv.stride == (1, 1) and conv.groups == 1:
@@ -103,7 +107,7 @@ def fused_conv_block(x: torch.Tensor, conv: nn.Conv2d, norm: Optional[nn.Module]
         return F.conv2d_bias_relu(x, conv.weight, conv.bias, relu=act is not None)
     alpha, beta, mode = cache.get(norm, x.device)
     return F.conv_norm_act(x, conv.weight, conv.bias, alpha, beta, residual, stride=conv.stride[0], groups=conv.groups,
-                           affine=mode, activation=None if act is None else _ACTIVATIONS[type(act)])
+                           affine=mode, activation=None if act is None else _ACTIVATIONS[type(act)], dilation=2 if dilated else 1)
 
 
 class Conv2dNormActivation(nn.Sequential):

@@ -11,8 +11,11 @@ torch's RNG like the reference's).  Only `forward` differs:
     reaches memory;
   * the classifier is F.global_avg_pool, F.linear_act(..., "hardswish") and F.linear_bias_relu.
 
-Inference only (norms in eval mode).  dilated=True builds the reference's tree; its forward raises NotImplementedError at the first
-dilated depthwise conv (mobilenet.fused_conv_block).
+Inference only (norms in eval mode).  dilated=True builds the reference's tree, whose last three blocks hold a depthwise 5x5 conv at
+dilation 2, padding 4 and stride 1 (k_dwpc5x5<1, 2>, F.conv_norm_act(..., dilation=2)).  Here a dilated MobileNetV3 is a SEGMENTATION
+BACKBONE: its `.features` run, every block with the launches it has undilated, and that is all the reference's segmentation builders
+(lraspp_mobilenet_v3_large, deeplabv3_mobilenet_v3_large: segmentation.py) call.  Its classification forward raises
+NotImplementedError, before any launch; lifting that is a later change.
 """
 from __future__ import annotations
 
@@ -74,6 +77,7 @@ class InvertedResidual(nn.Module):
         self.block = nn.Sequential(*layers)
         self.out_channels = cnf.out_channels
         self._is_cn = cnf.stride > 1
+        self._dilated = cnf.dilation > 1
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         y, gate = input, None
@@ -134,6 +138,9 @@ class MobileNetV3(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.training:
             raise RuntimeError("the MI355X MobileNetV3 is inference only: call .eval()")
+        if any(getattr(m, "_dilated", False) for m in self.features):
+            raise NotImplementedError("a dilated MobileNetV3 is a segmentation backbone here: its .features run (lraspp_mobilenet_v3_large, "
+                                      "deeplabv3_mobilenet_v3_large), its classification forward does not")
         inp = x
         fc1, fc2 = self.classifier[0], self.classifier[3]  # Dropout is the identity in eval mode
         with torch.no_grad():  # no autograd bookkeeping per layer; the result is marked once (its backward raises)

@@ -1,7 +1,8 @@
-"""FCN and DeepLabV3 on the ResNet backbones, on the MI355X kernels.
+"""FCN, DeepLabV3 and LRASPP on the ResNet and MobileNetV3 backbones, on the MI355X kernels: all of models/segmentation.
 
-Mirrors models/segmentation/_utils.py (_SimpleSegmentationModel), fcn.py (FCN, FCNHead, fcn_resnet50 / 101) and deeplabv3.py
-(DeepLabV3, DeepLabHead, ASPP, ASPPConv, ASPPPooling, deeplabv3_resnet50 / 101) of the reference: the same module tree, constructor
+Mirrors models/segmentation/_utils.py (_SimpleSegmentationModel), fcn.py (FCN, FCNHead, fcn_resnet50 / 101), deeplabv3.py
+(DeepLabV3, DeepLabHead, ASPP, ASPPConv, ASPPPooling, deeplabv3_resnet50 / 101, deeplabv3_mobilenet_v3_large) and lraspp.py (LRASPP,
+LRASPPHead, lraspp_mobilenet_v3_large) of the reference: the same module tree, constructor
 arguments and state-dict keys, torch's own nn.Conv2d / nn.BatchNorm2d / nn.ReLU / nn.Dropout / nn.AdaptiveAvgPool2d as PARAMETER
 CONTAINERS built in the reference's order, so its state dicts load as they are and a seeded construction consumes torch's RNG like
 the reference's.  Only `forward` differs; the containers' own forward is never called.  Inference only (Dropout is the identity).
@@ -16,7 +17,11 @@ size), torch.cat, 1 for the projection; DeepLabHead that + 2 + 1.  The model add
 Beyond the reference: `labels(x)` = forward(x)["out"].argmax(1) bit for bit, the resize and the argmax as ONE launch
 (F.interpolate_argmax) that writes only the labels, and without running the aux head.
 
-Not here: LRASPP and deeplabv3_mobilenet_v3_large, which need MobileNetV3's dilated depthwise convs.
+The two mobile models run on mobilenet_v3_large(dilated=True).features through IntermediateLayerGetter (children "0" ... "16"; the
+last three blocks' depthwise 5x5 convs at dilation 2 are k_dwpc5x5<1, 2>).  LRASPPHead is FIVE launches: cbr (the pointwise kernel),
+F.global_avg_pool, F.linear_act(..., "sigmoid") for the gate, low_classifier, and F.conv1x1_gated_upsample -- high_classifier over the
+resized gated map with low_classifier's output as its residual; neither the gated nor the upsampled tensor reaches memory
+(DESIGN.md 3.34).
 """
 from __future__ import annotations
 
@@ -26,13 +31,14 @@ from typing import Any, Dict, Optional, Sequence
 import torch
 from torch import nn
 
-from . import _lib, resnet
+from . import _lib, mobilenetv3, resnet
 from . import functional as F
 from .backbone_utils import IntermediateLayerGetter
 from .mobilenet import _FoldedNorm, _tensor_versions
 
 __all__ = ["FCN", "FCNHead", "DeepLabV3", "DeepLabHead", "ASPP", "ASPPConv", "ASPPPooling", "fcn_resnet50", "fcn_resnet101",
-           "deeplabv3_resnet50", "deeplabv3_resnet101"]
+           "deeplabv3_resnet50", "deeplabv3_resnet101", "LRASPP", "LRASPPHead", "lraspp_mobilenet_v3_large",
+           "deeplabv3_mobilenet_v3_large"]
 
 
 def _inference_only(module: nn.Module) -> None:
@@ -83,7 +89,18 @@ def _classify(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
     return F.conv_norm_act(x, conv.weight, conv.bias, None, None, None, stride=1, groups=1, affine=None, activation=None)
 
 
-class _SimpleSegmentationModel(nn.Module):
+class _Labels:
+    """labels(x) of a segmentation model, on its `_out_logits(x)`: the "out" head's logits before the final resize."""
+
+    def labels(self, x: torch.Tensor, dtype: torch.dtype = torch.int64) -> torch.Tensor:
+        """forward(x)["out"].argmax(1) bit for bit as (N, H, W) of `dtype` (int64, or uint8 for up to 256 classes): the resize and the
+        argmax are one launch (F.interpolate_argmax), the upsampled logits never reach memory and the aux head does not run."""
+        _inference_only(self)
+        with torch.no_grad():
+            return F.interpolate_argmax(self._out_logits(x), size=x.shape[-2:], dtype=dtype)
+
+
+class _SimpleSegmentationModel(_Labels, nn.Module):
     """models/segmentation/_utils.py: backbone -> classifier (-> aux_classifier) -> resize to the input."""
     __constants__ = ["aux_classifier"]
 
@@ -108,13 +125,8 @@ class _SimpleSegmentationModel(nn.Module):
         dep = next((p for p in self.parameters() if p.requires_grad), None)
         return OrderedDict((k, _lib.forward_only(v, f"{type(self).__name__}.forward", x, dep)) for k, v in result.items())
 
-    def labels(self, x: torch.Tensor, dtype: torch.dtype = torch.int64) -> torch.Tensor:
-        """forward(x)["out"].argmax(1) bit for bit as (N, H, W) of `dtype` (int64, or uint8 for up to 256 classes): the resize and the
-        argmax are one launch (F.interpolate_argmax), the upsampled logits never reach memory and the aux head does not run."""
-        _inference_only(self)
-        with torch.no_grad():
-            y = self.classifier(self.backbone(x)["out"])
-            return F.interpolate_argmax(y, size=x.shape[-2:], dtype=dtype)
+    def _out_logits(self, x: torch.Tensor) -> torch.Tensor:
+        return self.classifier(self.backbone(x)["out"])
 
 
 class FCN(_SimpleSegmentationModel):
@@ -228,6 +240,94 @@ def _segmentation_resnet(name: str, model, head, depth: str, weights, num_classe
     body = IntermediateLayerGetter(backbone, return_layers=return_layers)
     aux_classifier = FCNHead(1024, num_classes) if aux_loss else None
     return model(body, head(2048, num_classes), aux_classifier)
+
+
+class LRASPPHead(nn.Module):
+    """lraspp.py LRASPPHead: low_classifier(low) + high_classifier(interpolate(cbr(high) * scale(high), size=low.shape[-2:])) as five
+    launches: cbr is the pointwise kernel; the gate scale(high) is F.global_avg_pool and F.linear_act(..., "sigmoid") (float64 sums,
+    as a squeeze-excitation's); low_classifier with its bias; then F.conv1x1_gated_upsample: high_classifier over the resized gated
+    map, the gate product and the four-tap blend in its loads, low_classifier's output as its residual."""
+
+    def __init__(self, low_channels: int, high_channels: int, num_classes: int, inter_channels: int) -> None:
+        super().__init__()
+        self.cbr = nn.Sequential(nn.Conv2d(high_channels, inter_channels, 1, bias=False), nn.BatchNorm2d(inter_channels),
+                                 nn.ReLU(inplace=True))
+        self.scale = nn.Sequential(nn.AdaptiveAvgPool2d(1), nn.Conv2d(high_channels, inter_channels, 1, bias=False), nn.Sigmoid())
+        self.low_classifier = nn.Conv2d(low_channels, num_classes, 1)
+        self.high_classifier = nn.Conv2d(inter_channels, num_classes, 1)
+        self._fold = _FoldedNorm()
+        self.eval()
+
+    def forward(self, input: Dict[str, torch.Tensor]) -> torch.Tensor:
+        _inference_only(self)
+        low, high = input["low"], input["high"]
+        x = resnet.fused_conv_norm(high, self.cbr[0], self.cbr[1], self._fold, relu=True)
+        gate = F.linear_act(F.global_avg_pool(high), self.scale[1].weight, None, "sigmoid")
+        return F.conv1x1_gated_upsample(x, gate, self.high_classifier.weight, self.high_classifier.bias,
+                                        _classify(low, self.low_classifier), size=low.shape[-2:])
+
+
+class LRASPP(_Labels, nn.Module):
+    """lraspp.py LRASPP: a backbone returning "low" and "high", an LRASPPHead, the resize to the input."""
+
+    def __init__(self, backbone: nn.Module, low_channels: int, high_channels: int, num_classes: int, inter_channels: int = 128) -> None:
+        super().__init__()
+        self.backbone = backbone
+        self.classifier = LRASPPHead(low_channels, high_channels, num_classes, inter_channels)
+        self.eval()
+
+    def _out_logits(self, x: torch.Tensor) -> torch.Tensor:
+        return self.classifier(self.backbone(x))
+
+    def forward(self, input: torch.Tensor) -> Dict[str, torch.Tensor]:
+        _inference_only(self)
+        with torch.no_grad():  # no autograd bookkeeping per layer; the result is marked once (its backward raises)
+            out = F.interpolate(self._out_logits(input), size=input.shape[-2:], mode="bilinear", align_corners=False)
+        dep = next((p for p in self.parameters() if p.requires_grad), None)
+        return OrderedDict(out=_lib.forward_only(out, "LRASPP.forward", input, dep))
+
+
+def _mobilenet_v3_stages(name: str, weights, weights_backbone):
+    """mobilenet_v3_large(dilated=True).features and the reference's stage_indices on it: [0, 2, 4, 7, 13, 16]."""
+    if weights is not None or weights_backbone is not None:
+        raise ValueError(f"{name}: the package ships no weight files, weights and weights_backbone must be None; "
+                         "load a state dict with load_state_dict")
+    backbone = mobilenetv3.mobilenet_v3_large(dilated=True).features
+    stage_indices = [0] + [i for i, b in enumerate(backbone) if getattr(b, "_is_cn", False)] + [len(backbone) - 1]
+    return backbone, stage_indices
+
+
+def lraspp_mobilenet_v3_large(*, weights: Optional[Any] = None, progress: bool = True, num_classes: Optional[int] = None,
+                              weights_backbone: Optional[Any] = None, **kwargs: Any) -> LRASPP:
+    """lraspp.py lraspp_mobilenet_v3_large: LRASPP on the dilated MobileNetV3-large: "low" = stage_indices[-4] (features.4: 40 channels,
+    stride 8), "high" = the last feature (960 channels, stride 16), 21 classes unless `num_classes` says otherwise.  Weights as for
+    fcn_resnet50."""
+    if kwargs.pop("aux_loss", False):
+        raise NotImplementedError("This model does not use auxiliary loss")
+    backbone, stage_indices = _mobilenet_v3_stages("lraspp_mobilenet_v3_large", weights, weights_backbone)
+    if num_classes is None:
+        num_classes = 21
+    low_pos, high_pos = stage_indices[-4], stage_indices[-1]
+    low_channels, high_channels = backbone[low_pos].out_channels, backbone[high_pos].out_channels
+    body = IntermediateLayerGetter(backbone, return_layers={str(low_pos): "low", str(high_pos): "high"})
+    return LRASPP(body, low_channels, high_channels, num_classes)
+
+
+def deeplabv3_mobilenet_v3_large(*, weights: Optional[Any] = None, progress: bool = True, num_classes: Optional[int] = None,
+                                 aux_loss: Optional[bool] = None, weights_backbone: Optional[Any] = None, **kwargs: Any) -> DeepLabV3:
+    """deeplabv3.py deeplabv3_mobilenet_v3_large: DeepLabV3 (DeepLabHead(960)) on the dilated MobileNetV3-large's last feature, an
+    FCNHead(40) on features.4 as "aux" when `aux_loss`, 21 classes unless `num_classes` says otherwise.  Weights as for fcn_resnet50."""
+    backbone, stage_indices = _mobilenet_v3_stages("deeplabv3_mobilenet_v3_large", weights, weights_backbone)
+    if num_classes is None:
+        num_classes = 21
+    out_pos, aux_pos = stage_indices[-1], stage_indices[-4]
+    out_inplanes, aux_inplanes = backbone[out_pos].out_channels, backbone[aux_pos].out_channels
+    return_layers = {str(out_pos): "out"}
+    if aux_loss:
+        return_layers[str(aux_pos)] = "aux"
+    body = IntermediateLayerGetter(backbone, return_layers=return_layers)
+    aux_classifier = FCNHead(aux_inplanes, num_classes) if aux_loss else None  # before the head, as the reference draws
+    return DeepLabV3(body, DeepLabHead(out_inplanes, num_classes), aux_classifier)
 
 
 def fcn_resnet50(*, weights: Optional[Any] = None, progress: bool = True, num_classes: Optional[int] = None,

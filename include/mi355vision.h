@@ -1133,7 +1133,14 @@ int mv_heatmaps_to_keypoints_f32(const float* maps, const float* rois, float* xy
  *   mv_conv_norm_act_f32(MV_CONV_DW3X3): the same kernels, the same bits.  k == 5 (k_dwpc5x5): one float32 accumulator per output,
  *   acc = fmaf(w[ky][kx], x[iy][ix], acc) in ascending (ky, kx) order from +0, a tap in the padding entering the chain as +0 --
  *   oracle/oracle.c::orc_conv2d_affine_act_f32 with groups = c.  The bits do not depend on the alignment of x or on the launch.
- *   Any other k is MV_ERR_UNSUPPORTED; the other refusals are those of mv_conv_norm_act_f32.
+ *   Any other k is MV_ERR_UNSUPPORTED; the other refusals are those of mv_conv_norm_act_f32.  It is the dilation == 1 call of:
+ *
+ * mv_dwconv_dilated_norm_act_f32: the same with a dilation.  dilation == 1 IS mv_dwconv_norm_act_f32: the same kernels, the same bits,
+ *   the same refusals in the same order.  dilation == 2 needs k == 5 and stride == 1 (the dilated blocks of MobileNetV3 as a segmentation
+ *   backbone; zero padding 4, y (n, c, h, w)); every other dilated geometry is MV_ERR_UNSUPPORTED, dilation < 1 MV_ERR_INVALID_ARGUMENT.
+ *   Arithmetic (k_dwpc5x5<1, 2>): one float32 accumulator per output, acc = fmaf(w[ky][kx], x[oy - 4 + 2 ky][ox - 4 + 2 kx], acc) in
+ *   ascending (ky, kx) order from +0, a tap in the padding entering the chain as +0, then the epilogue above -- orc_conv2d_affine_act_f32
+ *   with groups = c on the kernel zero-stuffed to 9 x 9.  The bits do not depend on the alignment of x, on the launch or on n.
  *
  * mv_global_avgpool_f64sum_f32: y[i][c] = the mean of plane (i, c) of x (n, c, h, w), image i at x + i x_stride (elements, >= c h w: a
  *   channel slice of a wider tensor is passed as it is), y (n, c) dense.  With P = h w and p the index inside the plane:
@@ -1161,20 +1168,35 @@ int mv_heatmaps_to_keypoints_f32(const float* maps, const float* rois, float* xy
  *   cout)), the same epilogue.  Bit for bit mv_conv_norm_act_f32(MV_CONV_PW1X1) on the output of mv_se_scale_f32(x, gate), without that
  *   tensor in memory.  n <= 65535 as there.
  *
+ * mv_conv1x1_gated_upsample_f32 (LRASPP's head, models/segmentation/lraspp.py: high_classifier over the resized gated map, plus
+ *   low_classifier's output): y (n, cout, oh, ow) = residual + (w (cout, cin) . U + bias), U (n, cin, oh, ow) = mv_interpolate_bilinear_f32's
+ *   (h, w) -> (oh, ow) resize of mv_se_scale_f32(x, gate), x (n, cin, h, w), gate (n, cin).  U is computed in the kernel's loads
+ *   (k_conv1x1_gu): each of the four taps is fl(gate[i][q] x[i][q][tap]), taps and weights per axis and the three-step blend are those
+ *   stated for mv_interpolate_bilinear_f32, every product and fma rounded once; then the pointwise chain in the summation order
+ *   mv_conv1x1_k_slices(n, cin, oh, ow, cout) states, `+ bias`, `residual + v`.  No norm, no activation.  Bit for bit, NaN included,
+ *   mv_conv_norm_act_f32(MV_CONV_PW1X1) on mv_interpolate_bilinear_f32 of mv_se_scale_f32(x, gate), with neither tensor in memory.
+ *   bias and residual may be null; the residual may be y itself (each element is read before it is written) but must not otherwise
+ *   overlap it.  n <= 65535; cin h w < 2^31.
+ *
  * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: a null pointer (bias, residual and b may be null), a
- * non-positive c / cin / cout / h / w / k / m, a negative n, an unknown affine or activation code, an image stride below c h w, a
+ * non-positive c / cin / cout / h / w / oh / ow / k / m, a negative n, an unknown affine or activation code, an image stride below c h w, a
  * misaligned pointer (pool, scale), y overlapping an input (mv_se_scale_f32: other than y == x), a plane, an image or a grid beyond
  * what one launch indexes (MV_ERR_UNSUPPORTED).  n == 0 is a no-op that touches no pointer. */
 #define MV_ACT_HARDSIGMOID 5 /* mv_linear_act_f32 only */
 #define MV_ACT_SIGMOID 6     /* mv_linear_act_f32 only */
 int mv_dwconv_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta, const float* residual,
                            float* y, int64_t n, int c, int h, int wdt, int k, int stride, int affine, int act, void* stream);
+int mv_dwconv_dilated_norm_act_f32(const float* x, const float* w, const float* bias, const float* alpha, const float* beta,
+                                   const float* residual, float* y, int64_t n, int c, int h, int wdt, int k, int stride, int dilation,
+                                   int affine, int act, void* stream);
 int mv_global_avgpool_f64sum_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int64_t x_stride, void* stream);
 int mv_linear_act_f32(const float* x, const float* w, const float* b, float* y, int64_t n, int k, int m, int act, void* stream);
 int mv_se_scale_f32(const float* x, const float* gate, float* y, int64_t n, int c, int h, int wdt, void* stream);
 int mv_conv1x1_scaled_f32(const float* x, const float* gate, const float* w, const float* bias, const float* alpha, const float* beta,
                           const float* residual, float* y, int64_t n, int cin, int h, int wdt, int cout, int affine, int act,
                           void* stream);
+int mv_conv1x1_gated_upsample_f32(const float* x, const float* gate, const float* w, const float* bias, const float* residual, float* y,
+                                  int64_t n, int cin, int h, int wdt, int oh, int ow, int cout, void* stream);
 
 #ifdef __cplusplus
 }
