@@ -1,5 +1,7 @@
-"""Seeded random-shape sweep of every entry point against the oracle (`-m gpu`): ragged widths, tiny images, odd batch
-dims, every border mode -- the shapes nobody writes by hand.  Everything must be bit-exact."""
+"""Seeded random-shape sweep of the filters, conv2d_bias_relu, linear_bias_relu, the 2x2 pool, resize and the preset, the three
+original conv_norm_act kernels, deform_conv2d and conv2d_bias_act against the oracle (`-m gpu`): ragged widths, tiny images, odd batch
+dims, every border mode -- the shapes nobody writes by hand.  Everything must be bit-exact.  The layer kernels added since are swept by
+tests/test_gpu_fuzz_layers.py, the RoI and detection kernels by tests/test_gpu_fuzz_ops.py (cases: tests/_fuzz_cases.py)."""
 import numpy as np
 import pytest
 import torch
