@@ -3,7 +3,7 @@
 Python host layer (the reference is Python) over the C ABI in include/mi355vision.h:
   functional      the one namespace of the functional surface: the module-level switches, and re-exports of
   _filters        gaussian_blur / adjust_sharpness (+ _image/_video kernels, *_frames), box / separable / Sobel
-  _layers         conv+ReLU, pools, linear, conv_norm_act, inverted_residual (what nn and mobilenet run on)
+  _layers         conv+ReLU, pools, linear, conv_norm_act, dwconv_pointwise, inverted_residual (what nn, mobilenet and ssdlite run on)
   _misc           resize / center_crop / to_dtype / normalize (+ kernels), to_float_normalize
   _detection      rpn_topk / rpn_decode / box_decode (what rpn runs on), roi_detections (what roi_heads runs on), retinanet_topk /
                   retinanet_decode (what retinanet runs on), fcos_topk / fcos_decode (what fcos runs on)
@@ -39,6 +39,9 @@ Python host layer (the reference is Python) over the C ABI in include/mi355visio
   ssd             SSDFeatureExtractorVGG (VGG16 with the ceil-mode third pool, conv4_3 rescaled by _norm.l2_normalize_scale, the dilated
                   fc6), SSDHead (one conv launch per level and head), SSD: softmax into a class-major matrix, per-class threshold +
                   top-k on its rows, default boxes + decode of the selected candidates only, then batched_nms; ssd300_vgg16
+  ssdlite         SSDLiteFeatureExtractorMobileNet (MobileNetV3-Large split at the C4 expansion, four extra blocks), SSDLiteHead: every
+                  depthwise-separable block (depthwise 3x3 + norm + ReLU6 -> 1x1 conv) one launch, the depthwise stage computed in the
+                  pointwise kernel's loads (_layers.dwconv_pointwise); ssdlite320_mobilenet_v3_large on ssd.SSD
   segmentation    FCN / FCNHead, DeepLabV3 / DeepLabHead / ASPP / ASPPConv / ASPPPooling on the dilated ResNets (a 1x1 conv + norm + ReLU one
                   launch; the heads' 3x3 convs the implicit GEMM at padding = dilation = rate, one launch per 128 input channels), fcn_resnet50 / 101, deeplabv3_resnet50 / 101;
                   LRASPP / LRASPPHead (five launches: the gate product and the upsample in the high classifier's loads, the low
@@ -59,7 +62,7 @@ The directory is named `cpu-vision_amd`; import it as `cpu_vision_amd` (alias pa
 """
 from . import (anchor_utils, backbone_utils, faster_rcnn, fcos, fpn, functional, functional_v1, generalized_rcnn, graphs, image_list,  # noqa: F401
                keypoint_rcnn, mask_rcnn, mobilenet, mobilenetv3, nn, ops, presets, resnet, retinanet, roi_heads, rpn, segmentation, sharding, ssd,
-               transform, transforms, tv_tensors)
+               ssdlite, transform, transforms, tv_tensors)
 from ._lib import LIB_PATH, Mi355VisionError, load as load_library  # noqa: F401
 from ._registry import register_kernel  # noqa: F401
 from .backbone_utils import BackboneWithFPN, IntermediateLayerGetter, resnet_fpn_backbone  # noqa: F401
@@ -78,6 +81,8 @@ from .retinanet import (RetinaNet, RetinaNetClassificationHead, RetinaNetHead, R
 from .fcos import FCOS, FCOSClassificationHead, FCOSHead, FCOSRegressionHead, fcos_resnet50_fpn  # noqa: F401
 from .ssd import (SSD, SSDClassificationHead, SSDFeatureExtractorVGG, SSDHead, SSDRegressionHead, SSDScoringHead,  # noqa: F401
                   ssd300_vgg16)
+from .ssdlite import (SSDLiteClassificationHead, SSDLiteFeatureExtractorMobileNet, SSDLiteHead, SSDLiteRegressionHead,  # noqa: F401
+                      ssdlite320_mobilenet_v3_large)
 from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small  # noqa: F401
 from .segmentation import (ASPP, FCN, LRASPP, ASPPConv, ASPPPooling, DeepLabHead, DeepLabV3, FCNHead, LRASPPHead,  # noqa: F401
                            deeplabv3_mobilenet_v3_large, deeplabv3_resnet50, deeplabv3_resnet101, fcn_resnet50, fcn_resnet101,

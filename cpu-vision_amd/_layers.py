@@ -1,6 +1,6 @@
 """The CNN layers behind nn.py, mobilenet.py and presets.py -- none of them a transforms.v2.functional function: conv2d_bias_relu
 (models/vgg.py:81-85, ops/misc.py:97-119), max_pool2d*, conv2d_bias_act, conv2d_affine_act (models/resnet.py), adaptive_avg_pool2d,
-linear_bias_relu, conv_norm_act / inverted_residual / fold_batchnorm (ops/misc.py:68-128, models/mobilenetv2.py:39-63), normalized_conv2d_bias_relu and the
+linear_bias_relu, conv_norm_act / dwconv_pointwise / inverted_residual / fold_batchnorm (ops/misc.py:68-128, models/mobilenetv2.py:39-63), normalized_conv2d_bias_relu and the
 *_k_slices queries.  All compute in float32 and are forward-only.  The pools launch through _lib.launch_xy; the layers with
 several input tensors prepare them with _lib.f32_on / ptr / workspace and call _lib.launch.
 
@@ -376,6 +376,63 @@ def conv1x1_gated_upsample(x: torch.Tensor, gate: torch.Tensor, weight: torch.Te
     _lib.launch(lib.mv_conv1x1_gated_upsample_f32, xc, xc.data_ptr(), gc.data_ptr(), wc.data_ptr(), p(bc), p(rc), y.data_ptr(),
                 n, cin, h, w, oh, ow, cout)
     return _lib.forward_only(y, "conv1x1_gated_upsample", x, gate, weight, bias, residual)
+
+
+def dwconv_pointwise(x: torch.Tensor, dw_weight: torch.Tensor, dw_bias: Optional[torch.Tensor] = None,
+                     dw_alpha: Optional[torch.Tensor] = None, dw_beta: Optional[torch.Tensor] = None,
+                     weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                     alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                     residual: Optional[torch.Tensor] = None, *, stride: int = 1, dw_affine: Optional[str] = None,
+                     dw_activation: Optional[str] = None, affine: Optional[str] = None, activation: Optional[str] = None) -> torch.Tensor:
+    """A depthwise-separable block (models/detection/ssdlite.py _prediction_block, the back half of _extra_block) as ONE launch
+    (mv_dwconv3x3_conv1x1_f32): depthwise 3x3 (padding 1, `stride` 1 or 2) `dw_weight` (C, 1, 3, 3) -> + dw_bias -> folded norm
+    (`dw_affine`) -> `dw_activation`, then the pointwise conv `weight` (Cout, C, 1, 1) with conv_norm_act's whole epilogue (bias, alpha /
+    beta under `affine`, residual (N, Cout, oh, ow), `activation`).  The depthwise stage is computed in the pointwise kernel's loads: the
+    hidden tensor never reaches memory.  The same bits as
+        conv_norm_act(conv_norm_act(x, dw_weight, dw_bias, dw_alpha, dw_beta, stride=stride, groups=C, affine=dw_affine,
+                                    activation=dw_activation),
+                      weight, bias, alpha, beta, residual, affine=affine, activation=activation);
+    summation order of the pointwise stage: conv1x1_k_slices(N, C, oh, ow, Cout)."""
+    if weight is None:
+        raise ValueError("dwconv_pointwise needs the pointwise `weight`; conv_norm_act is the depthwise conv alone")
+    if x.ndim != 4 or dw_weight.ndim != 4 or weight.ndim != 4:
+        raise RuntimeError(f"Expected 4D input and weights. Got {tuple(x.shape)}, {tuple(dw_weight.shape)} and {tuple(weight.shape)}")
+    n, cin, h, w = (int(d) for d in x.shape)
+    if tuple(dw_weight.shape) != (cin, 1, 3, 3):
+        raise NotImplementedError(f"dwconv_pointwise covers depthwise 3x3 convs: dw_weight should have shape ({cin}, 1, 3, 3), got "
+                                  f"{tuple(dw_weight.shape)}")
+    cout, cg, kh, kw = (int(d) for d in weight.shape)
+    if (kh, kw) != (1, 1) or cg != cin:
+        raise NotImplementedError(f"dwconv_pointwise covers pointwise 1x1 convs; got weight {tuple(weight.shape)} on {cin} input channels")
+    if stride not in (1, 2):
+        raise ValueError(f"stride should be 1 or 2, got {stride!r}")
+    if activation not in _ACT_CODES or affine not in _AFFINE_CODES:
+        raise ValueError(f"unknown activation {activation!r} / affine {affine!r}")
+    if dw_activation not in _ACT_CODES or dw_affine not in _AFFINE_CODES:
+        raise ValueError(f"unknown dw_activation {dw_activation!r} / dw_affine {dw_affine!r}")
+    if _AFFINE_CODES[dw_affine] != 0 and (dw_alpha is None or dw_beta is None):
+        raise ValueError(f"dw_affine={dw_affine!r} needs dw_alpha and dw_beta")
+    if _AFFINE_CODES[affine] != 0 and (alpha is None or beta is None):
+        raise ValueError(f"affine={affine!r} needs alpha and beta")
+    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
+    for t, name in ((dw_bias, "dw_bias"), (dw_alpha, "dw_alpha"), (dw_beta, "dw_beta")):
+        if t is not None and t.numel() != cin:
+            raise RuntimeError(f"{name} has {t.numel()} elements for {cin} depthwise channels")
+    _check_epilogue_terms((n, cout, oh, ow), bias, alpha, beta, residual)
+    _lib.require_device(x)
+    _lib.require_device(dw_weight, "dw_weight")
+    _lib.require_device(weight, "weight")
+    _lib.require_f32_layer("dwconv_pointwise", x, dw_weight)
+    _lib.require_f32_layer("dwconv_pointwise", x, weight)
+    lib = _lib.load()
+    xc, dwc, wc = x.contiguous(), dw_weight.detach().contiguous(), weight.detach().contiguous()
+    dbc, dac, dbtc, bc, ac, btc, rc = (_lib.f32_on(t, x.device) for t in (dw_bias, dw_alpha, dw_beta, bias, alpha, beta, residual))
+    y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device)
+    p = _lib.ptr
+    _lib.launch(lib.mv_dwconv3x3_conv1x1_f32, xc, xc.data_ptr(), dwc.data_ptr(), p(dbc), p(dac), p(dbtc), wc.data_ptr(), p(bc), p(ac), p(btc),
+                p(rc), y.data_ptr(), n, cin, h, w, cout, int(stride), _AFFINE_CODES[dw_affine], _ACT_CODES[dw_activation],
+                _AFFINE_CODES[affine], _ACT_CODES[activation])
+    return _lib.forward_only(y, "dwconv_pointwise", x, dw_weight, dw_bias, dw_alpha, dw_beta, weight, bias, alpha, beta, residual)
 
 
 def conv2d_affine_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,

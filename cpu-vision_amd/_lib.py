@@ -166,6 +166,7 @@ SYMBOLS = {
     "mv_conv1x1_scaled_f32": (_i, [_vp] * 8 + [_i64] + [_i] * 6 + [_vp]),
     "mv_dwconv_dilated_norm_act_f32": (_i, [_vp] * 7 + [_i64] + [_i] * 8 + [_vp]),
     "mv_conv1x1_gated_upsample_f32": (_i, [_vp] * 6 + [_i64] + [_i] * 6 + [_vp]),
+    "mv_dwconv3x3_conv1x1_f32": (_i, [_vp] * 11 + [_i64] + [_i] * 9 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -763,6 +763,38 @@ int mv_conv1x1_gated_upsample_f32(const float* x, const float* gate, const float
   return launch_conv1x1_gated_upsample(x, gate, w, y, n, cin, h, wdt, oh, ow, cout, e, (hipStream_t)stream);
 }
 
+// ---- SSDlite's depthwise-separable block: depthwise 3x3 + norm + activation in the loads of the pointwise conv (convnorm.hip, k_conv1x1_dw)
+int mv_dwconv3x3_conv1x1_f32(const float* x, const float* w_dw, const float* bias_dw, const float* alpha_dw, const float* beta_dw,
+                             const float* w, const float* bias, const float* alpha, const float* beta, const float* residual, float* y,
+                             int64_t n, int cin, int h, int wdt, int cout, int stride, int affine_dw, int act_dw, int affine, int act,
+                             void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h <= 0 || wdt <= 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, cin, cout, h, wdt);
+  if (stride != 1 && stride != 2) return set_error(MV_ERR_INVALID_ARGUMENT, "stride should be 1 or 2 instead of %d", stride);
+  if (affine_dw < MV_AFFINE_NONE || affine_dw > MV_AFFINE_FMA || act_dw < MV_ACT_NONE || act_dw > MV_ACT_SILU)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad depthwise affine (%d) / activation (%d) code", affine_dw, act_dw);
+  if (affine < MV_AFFINE_NONE || affine > MV_AFFINE_FMA || act < MV_ACT_NONE || act > MV_ACT_SILU)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad affine (%d) / activation (%d) code", affine, act);
+  if (n == 0) return MV_OK;
+  if (!x || !w_dw || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if (affine_dw != MV_AFFINE_NONE && (!alpha_dw || !beta_dw))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "depthwise affine without alpha / beta");
+  if (affine != MV_AFFINE_NONE && (!alpha || !beta)) return set_error(MV_ERR_INVALID_ARGUMENT, "affine without alpha / beta");
+  // tap offsets inside a source plane and a channel's plane offset are ints
+  if ((long long)cin * h * wdt > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "dwconv3x3_conv1x1: an image of %d x %d x %d elements exceeds the 32-bit index", cin, h, wdt);
+  const long long oh = (h - 1) / stride + 1, ow = (wdt - 1) / stride + 1, ny = n * cout * oh * ow;
+  const bool adw = affine_dw != MV_AFFINE_NONE, apw = affine != MV_AFFINE_NONE;
+  if (overlaps(y, ny, x, n * cin * (long long)h * wdt) || overlaps(y, ny, w_dw, 9LL * cin) || overlaps(y, ny, w, (long long)cout * cin) ||
+      (bias_dw && overlaps(y, ny, bias_dw, cin)) || (adw && (overlaps(y, ny, alpha_dw, cin) || overlaps(y, ny, beta_dw, cin))) ||
+      (bias && overlaps(y, ny, bias, cout)) || (apw && (overlaps(y, ny, alpha, cout) || overlaps(y, ny, beta, cout))) ||
+      (residual && overlaps(y, ny, residual, ny)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap an input, weight, epilogue term or residual");
+  const Epilogue e_dw = {bias_dw, adw ? alpha_dw : nullptr, adw ? beta_dw : nullptr, nullptr, affine_dw, act_dw};
+  const Epilogue e = {bias, apw ? alpha : nullptr, apw ? beta : nullptr, residual, affine, act};
+  return launch_dwconv3x3_conv1x1(x, w_dw, e_dw, w, y, n, cin, h, wdt, cout, stride, e, (hipStream_t)stream);
+}
+
 int mv_global_avgpool_f64sum_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int64_t x_stride, void* stream) {
   if (n < 0 || c <= 0 || h <= 0 || wdt <= 0)
     return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: bad shape n=%lld c=%d h=%d w=%d", (long long)n, c, h, wdt);

@@ -522,6 +522,12 @@ struct PwArgs {
   // and `wdt` are shared with the SC / UP fields.  src_sy / src_sx: (float)src_h / (float)oh and (float)src_w / (float)ow, on the host
   int src_h, src_w;
   float src_sy, src_sx;
+  // DW instances only (SSDlite's depthwise-separable block, launch_dwconv3x3_conv1x1): x is (n, cin, src_h, src_w), the X chunk's element
+  // (k, p) is the depthwise 3x3 conv (padding 1, stride dw_stride) of plane k at output pixel p of the (oh, ow = wdt) plane, through the
+  // depthwise epilogue dw_e (per INPUT channel k of the pointwise conv; dw_e.res is null).  src_h / src_w / wdt are shared with GU
+  const float* dw_w;  // [cin][3][3]
+  Epilogue dw_e;
+  int dw_stride;
 };
 
 
@@ -688,7 +694,13 @@ __device__ __forceinline__ void pw_store_shuffle(const f32x16 (&acc)[NT], const 
 // output of mv_se_scale_f32.  A thread's four consecutive pixels are the same in every chunk (256 is a multiple of PXB / 4) and may
 // cross a row end: their four tap offsets and weights are computed once, before the first chunk.  Pixels past the plane and rows
 // k >= cin stay +0 and read neither x nor the gate.
-template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false, bool GU = false>
+// DW: the X chunk is COMPUTED: element (k, p) = act_dw(affine_dw(dw3x3(x[img][k])[p] (+ bias_dw[k]))), the arithmetic of k_dwpc3x3 -- one
+// fmaf chain over the nine taps in (ky, kx) order from +0, a tap in the padding entering as fmaf(w, +0, acc) (never skipped: a NaN or
+// Inf weight reaches the border pixels), then epi_norm and the activation of mv_epilogue.h with channel k's terms -- the bits of
+// mv_conv_norm_act_f32(MV_CONV_DW3X3).  As for GU a thread's four pixels are the same in every chunk: the offset of their window's top
+// left tap (negative in the padding) and a 9-bit in-frame mask are computed once, before the first chunk; a padding tap loads element 0
+// of the plane and selects +0.  Pixels past the plane and rows k >= cin stay +0 and read neither x nor the depthwise terms.
+template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false, bool GU = false, bool DW = false>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwArgs A) {
   constexpr int PG = 4 / MW;              // pixel groups (waves along pixels)
   constexpr int PXB = PG * NT * 32;       // pixels per workgroup
@@ -743,6 +755,29 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
     }
   }
 
+  // DW: offset of tap (0, 0) of the window of pixel p0 + 4 q + i inside a source plane, and bit 3 ky + kx set when that tap is in the frame
+  static_assert(!DW || 256 % (PXB / 4) == 0, "a thread's pixel quad must not depend on the unit");
+  int doff[DW ? 4 : 1];
+  unsigned dmask[DW ? 4 : 1];
+  (void)doff, (void)dmask;
+  if constexpr (DW) {
+    const int p = p0 + 4 * (tid % (PXB / 4));
+    int oy = p / A.wdt, ox = p - oy * A.wdt;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int iy0 = oy * A.dw_stride - 1, ix0 = ox * A.dw_stride - 1;
+      unsigned m = 0;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+          if (iy0 + ky >= 0 && iy0 + ky < A.src_h && ix0 + kx >= 0 && ix0 + kx < A.src_w) m |= 1u << (3 * ky + kx);
+      doff[i] = iy0 * A.src_w + ix0;
+      dmask[i] = p + i < HW ? m : 0u;  // past the plane: never read
+      if (++ox == A.wdt) ox = 0, ++oy;
+    }
+  }
+
   f32x4 wreg[WU], xreg[XU];
   auto gload = [&](int ch) {
     const int kc = ch * kPK;
@@ -784,6 +819,45 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
               e[i] = bilinear_blend(ty, tx, __fmul_rn(g, src[goff[i][0]]), __fmul_rn(g, src[goff[i][1]]), __fmul_rn(g, src[goff[i][2]]),
                                     __fmul_rn(g, src[goff[i][3]]));
             }
+          v = (f32x4){e[0], e[1], e[2], e[3]};
+        }
+      } else if constexpr (DW) {
+        if (k < K) {
+          const float* src = X + (size_t)k * (A.src_h * A.src_w);
+          float wk[9];
+#pragma unroll
+          for (int t = 0; t < 9; ++t) wk[t] = A.dw_w[(size_t)k * 9 + t];
+          const ChannelTerms ct = channel_terms(A.dw_e, k);
+          // two pixels per trip (their doff / dmask picked by selects, so that the arrays stay in registers).  KS = 4, 1024 threads and
+          // 128 registers: the loop is NOT unrolled, 18 taps in flight -- unrolled, the 36 taps of a unit with their addresses spill
+          // (76-108 bytes per lane).  KS <= 2: unrolled, every tap of the chunk in flight at once (156-195 registers, no scratch)
+          float e[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll(KS == 4 ? 1 : 2)
+          for (int half = 0; half < 2; ++half) {
+            float r[2] = {0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const int off = half ? doff[2 + j] : doff[j];
+              const unsigned msk = half ? dmask[2 + j] : dmask[j];
+              if (p + 2 * half + j < HW) {
+                float tap[9];
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                  for (int kx = 0; kx < 3; ++kx) {
+                    const bool in = (msk >> (3 * ky + kx)) & 1u;
+                    const float xv = src[in ? off + ky * A.src_w + kx : 0];
+                    tap[3 * ky + kx] = in ? xv : 0.f;
+                  }
+                float a = 0.f;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) a = fmaf(wk[t], tap[t], a);
+                r[j] = epi_apply(a, ct, 0, A.dw_e);
+              }
+            }
+            if (half) e[2] = r[0], e[3] = r[1];
+            else e[0] = r[0], e[1] = r[1];
+          }
           v = (f32x4){e[0], e[1], e[2], e[3]};
         }
       } else if (k < K) {
@@ -977,6 +1051,18 @@ static int pw_launch(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: problem too large for one launch");
   const dim3 grid((unsigned)nb, (unsigned)n);
   const bool up = a.top != nullptr;  // the same plan, the instances that gather their residual from `top`
+  if (a.dw_w) {  // the same plan, the instances that compute their X chunk as a depthwise 3x3 conv of the source map
+    int ks = 1;
+    if constexpr (NT == 1) ks = p.ks;
+    if (ks == 2) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 2, false, false, false, false, true>), grid, dim3(512), 0, s, a);
+    } else if (ks == 4) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 4, false, false, false, false, true>), grid, dim3(1024), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_conv1x1<NT, MW, 1, false, false, false, false, true>), grid, dim3(256), 0, s, a);
+    }
+    return ks > 1 ? check_launchf("k_conv1x1_dw<1,%d,ks%d>", MW, ks) : check_launchf("k_conv1x1_dw<%d,%d>", NT, MW);
+  }
   if (a.src_h) {  // the same plan, the instances that gather their X chunk from the gated coarser map
     int ks = 1;
     if constexpr (NT == 1) ks = p.ks;
@@ -1092,6 +1178,17 @@ int launch_conv1x1_gated_upsample(const float* x, const float* gate, const float
   gu.gate = gate, gu.src_h = h, gu.src_w = wd, gu.wdt = ow;
   gu.src_sy = (float)h / (float)oh, gu.src_sx = (float)wd / (float)ow;
   return conv1x1(x, w, y, n, cin, (int64_t)oh * ow, cout, e, s, 0, 0, true, &gu);
+}
+
+int launch_dwconv3x3_conv1x1(const float* x, const float* w_dw, const Epilogue& e_dw, const float* w, float* y, int64_t n, int cin, int h,
+                             int wd, int cout, int stride, const Epilogue& e, hipStream_t s) {
+  // tap offsets inside a source plane and a channel's plane offset k * h * wd are ints
+  if ((long long)cin * h * wd > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: source image too large");
+  const int oh = (h - 1) / stride + 1, ow = (wd - 1) / stride + 1;
+  PwArgs dw = {};
+  dw.dw_w = w_dw, dw.dw_e = e_dw, dw.dw_e.res = nullptr, dw.dw_stride = stride;
+  dw.src_h = h, dw.src_w = wd, dw.wdt = ow;
+  return conv1x1(x, w, y, n, cin, (int64_t)oh * ow, cout, e, s, 0, 0, true, &dw);
 }
 
 int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,

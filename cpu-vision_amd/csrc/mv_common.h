@@ -271,6 +271,11 @@ int launch_conv1x1_scaled(const float* x, const float* gate, const float* w, flo
 // (n, cin, oh * ow, cout)); neither the gated nor the resized tensor reaches memory.  LRASPP's head
 int launch_conv1x1_gated_upsample(const float* x, const float* gate, const float* w, float* y, int64_t n, int cin, int h, int wd, int oh,
                                   int ow, int cout, const Epilogue& e, hipStream_t s);
+// the pointwise kernel over H = the depthwise 3x3 conv (padding 1, stride 1 | 2) of x (n, cin, h, wd) through the depthwise epilogue e_dw
+// (its res is ignored), computed in its X loads (k_conv1x1_dw: the plan, tiles and summation order of launch_conv1x1 on
+// (n, cin, oh * ow, cout)); H never reaches memory.  Bit for bit launch_dwpc3x3 followed by launch_conv1x1.  SSDlite's prediction blocks
+int launch_dwconv3x3_conv1x1(const float* x, const float* w_dw, const Epilogue& e_dw, const float* w, float* y, int64_t n, int cin, int h,
+                             int wd, int cout, int stride, const Epilogue& e, hipStream_t s);
 // depthwise 5x5, a kernel per channel, stride 1 | 2 with zero padding 2, or dilation 2 at stride 1 with zero padding 4 (dw5x5.hip).  A
 // thread's strip is kDw5Rows output rows (of one parity at dilation 2), half of that when the launch has fewer than kDw5ShortLaunch threads
 constexpr int kDw5Rows = 8;

@@ -10,7 +10,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               depthwise_conv2d, box_filter, separable_gaussian_blur, sobel, gaussian_sobel
   _layers     the CNN layers (models/vgg.py:81-85, ops/misc.py:68-128, models/mobilenetv2.py:39-63): conv2d_bias_relu,
               conv2d_bias_act, conv2d_affine_act, max_pool2d*, adaptive_avg_pool2d, linear_bias_relu, conv_norm_act,
-              conv1x1_upsample_add (FPN's top-down merge), conv1x1_gated_upsample (LRASPP's head), inverted_residual,
+              conv1x1_upsample_add (FPN's top-down merge), conv1x1_gated_upsample (LRASPP's head), dwconv_pointwise (SSDlite's
+              depthwise-separable block), inverted_residual,
               fold_batchnorm, normalized_conv2d_bias_relu, the *_k_slices queries
   _misc       resize / center_crop / to_dtype / normalize and their kernels, to_float_normalize
   _geometry   elastic / affine / rotate / perspective and their _image / _mask / _video kernels
@@ -79,7 +80,7 @@ from ._interp import detection_batch, interpolate, interpolate_output_size, MAX_
 from ._layers import (_ACT_CODES, adaptive_avg_pool2d, _AFFINE_CODES, conv1x1_gated_upsample, conv1x1_k_slices,  # noqa: F401
                       conv1x1_upsample_add,
                       conv2d_affine_act, conv2d_bias_act, conv2d_bias_relu,
-                      conv3x3_k_slices, conv_norm_act, _CONV_WORKSPACE_BYTES, fold_batchnorm, inverted_residual,
+                      conv3x3_k_slices, conv_norm_act, _CONV_WORKSPACE_BYTES, dwconv_pointwise, fold_batchnorm, inverted_residual,
                       inverted_residual_k_slices, _inverted_residual_workspace_bytes, linear_bias_relu, linear_k_slices,
                       max_pool2d, max_pool2d_2x2, normalized_conv2d_bias_relu)
 from ._keypoint import conv_transpose4x4_relayout, heatmaps_to_keypoints, MAX_HEATMAP_ELEMENTS  # noqa: F401

@@ -80,16 +80,24 @@ class InvertedResidual(nn.Module):
         self._dilated = cnf.dilation > 1
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
-        y, gate = input, None
-        for layer in list(self.block)[:-1]:
-            if isinstance(layer, SqueezeExcitation):
-                gate = layer._gate(y)  # multiplied into the projection's loads below
-            else:
-                y = layer(y)
-        project = self.block[-1]
-        alpha, beta, mode = project._fold.get(project[1] if project._has_norm else None, y.device)
-        return F.conv_norm_act(y, project[0].weight, project[0].bias, alpha, beta, input if self.use_res_connect else None, stride=1,
-                               groups=1, affine=mode, activation=None, input_scale=gate)
+        return _run_block(self.block, input, input if self.use_res_connect else None)
+
+
+def _run_block(layers, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The layers of an InvertedResidual's `block` (or a tail of them: SSDlite splits the C4 block behind its expansion) on the kernels:
+    one launch per Conv2dNormActivation, the squeeze-excitation's gate multiplied into the projection's loads, `residual` in its
+    epilogue."""
+    layers = list(layers)
+    y, gate = x, None
+    for layer in layers[:-1]:
+        if isinstance(layer, SqueezeExcitation):
+            gate = layer._gate(y)  # multiplied into the projection's loads below
+        else:
+            y = layer(y)
+    project = layers[-1]
+    alpha, beta, mode = project._fold.get(project[1] if project._has_norm else None, y.device)
+    return F.conv_norm_act(y, project[0].weight, project[0].bias, alpha, beta, residual, stride=1, groups=1, affine=mode, activation=None,
+                           input_scale=gate)
 
 
 class MobileNetV3(nn.Module):

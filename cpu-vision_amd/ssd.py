@@ -269,7 +269,10 @@ def _vgg_extractor(backbone: VGG, highres: bool, trainable_layers: int):
 def _retrieve_out_channels(model: nn.Module, size: Tuple[int, int]) -> List[int]:
     """_utils.py retrieve_out_channels.  This package's SSDFeatureExtractorVGG is read off its modules (512 for conv4_3, then the last
     conv of every `extra` block): its forward needs the MI355X.  Any other backbone gets the reference's probing forward on zeros, on
-    the backbone's own device."""
+    the backbone's own device.  An extractor of this package that states its channels itself (`_module_out_channels`: SSDlite's) is
+    asked."""
+    if hasattr(model, "_module_out_channels"):
+        return model._module_out_channels()
     if isinstance(model, SSDFeatureExtractorVGG):
         out_channels = [int(model.scale_weight.numel())]
         for block in model.extra:

@@ -1198,6 +1198,26 @@ int mv_conv1x1_scaled_f32(const float* x, const float* gate, const float* w, con
 int mv_conv1x1_gated_upsample_f32(const float* x, const float* gate, const float* w, const float* bias, const float* residual, float* y,
                                   int64_t n, int cin, int h, int wdt, int oh, int ow, int cout, void* stream);
 
+/* ---- SSDlite's depthwise-separable block (models/detection/ssdlite.py _prediction_block, the back half of _extra_block) ----------------
+ * mv_dwconv3x3_conv1x1_f32: y (n, cout, oh, ow) = the pointwise conv w (cout, cin) of mv_conv_norm_act_f32 (MV_CONV_PW1X1) with its whole
+ *   epilogue (bias, alpha / beta under `affine`, residual (n, cout, oh, ow), `act`) over H (n, cin, oh, ow) = mv_conv_norm_act_f32
+ *   (MV_CONV_DW3X3) of x (n, cin, h, w): depthwise 3 x 3, zero padding 1, stride 1 | 2 (oh = (h - 1) / stride + 1), w_dw (cin, 3, 3), with
+ *   the depthwise epilogue bias_dw / alpha_dw / beta_dw (cin each) under `affine_dw`, then `act_dw`.  H is computed in the kernel's loads
+ *   (k_conv1x1_dw) and never reaches memory: per element one float32 accumulator, acc = fmaf(w_dw[ky][kx], x[oy s - 1 + ky][ox s - 1 + kx],
+ *   acc) in ascending (ky, kx) order from +0, a tap in the padding entering the chain as fmaf(w_dw, +0, acc) (a NaN or infinite weight
+ *   reaches the border pixels), then `+ bias_dw`, the affine and the activation as stated for mv_conv_norm_act_f32; then the pointwise
+ *   chain in the summation order mv_conv1x1_k_slices(n, cin, oh, ow, cout) states.  Bit for bit, NaN included, mv_conv_norm_act_f32
+ *   (MV_CONV_PW1X1) on the output of mv_conv_norm_act_f32(MV_CONV_DW3X3), in ONE launch.  Any epilogue pointer may be null as its affine
+ *   code allows.  n <= 65535; cin h w < 2^31.
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: null x / w_dw / w / y, a non-positive cin / cout / h /
+ * w, a negative n, a stride other than 1 or 2, an unknown affine or activation code of either stage, an affine code without its alpha and
+ * beta, y overlapping any input, cin h w beyond the int range of the tap offsets, a plane or a batch beyond what one launch indexes
+ * (MV_ERR_UNSUPPORTED).  n == 0 is a no-op that touches no pointer. */
+int mv_dwconv3x3_conv1x1_f32(const float* x, const float* w_dw, const float* bias_dw, const float* alpha_dw, const float* beta_dw,
+                             const float* w, const float* bias, const float* alpha, const float* beta, const float* residual, float* y,
+                             int64_t n, int cin, int h, int wdt, int cout, int stride, int affine_dw, int act_dw, int affine, int act,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
