@@ -5,6 +5,10 @@ mv_roi_detections_f32 (csrc/roi_heads.hip), retinanet_topk and retinanet_decode 
 BoxLinearCoder.decode), ssd_scores, ssd_topk and ssd_decode over mv_ssd_scores_f32 / mv_ssd_topk_f32 / mv_ssd_decode_f32 (csrc/ssd.hip:
 ssd.py's softmax, per-class top-k and default boxes).  float32, forward-only; the argument checks fire before a device is needed.  Every name
 here is re-exported by `functional`.
+
+Stated once: the checks of per-level maps (_level_maps, _class_maps, _fcos_maps), of k, idx, strides and the four weights (_check_*);
+the pyramid top-k and decode of the rpn and retinanet (_topk, _decode); a decode entry's four outputs and its return (_candidate_outputs,
+_candidates).  fcos_topk and fcos_decode keep bodies of their own: routed through _topk / _decode they measured slower.
 """
 from __future__ import annotations
 
@@ -75,20 +79,49 @@ def _image_sizes(name: str, image_sizes, fits, rows: str) -> torch.Tensor:
     return sizes
 
 
-def _topk(name: str, logits, shapes, k, classes: Optional[int] = None, score_thresh=None) -> torch.Tensor:
-    """What rpn_topk and retinanet_topk share behind the checks of their maps: the checks of k, the workspace of
-    mv_<name>_workspace_bytes and the launch of mv_<name>_f32.  classes and score_thresh: retinanet's, arguments of its entries only."""
-    if not isinstance(k, int) or k < 1:
+def _check_k(name: str, k, reject_bool: bool = False) -> None:
+    if not isinstance(k, int) or (reject_bool and isinstance(k, bool)) or k < 1:
         raise ValueError(f"{name}: k must be a positive int, got {k!r}")
     if k > MAX_RPN_TOPK:
         raise _lib.Mi355VisionError(f"{name}: k up to {MAX_RPN_TOPK}, got {k}")
+
+
+def _check_idx(name: str, idx, n: int, cols: str = "K") -> None:
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
+        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, {cols})")
+
+
+def _check_strides(name: str, strides, num: int) -> None:
+    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
+        raise RuntimeError(f"{name}: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
+
+
+def _check_weights(name: str, weights) -> None:
+    if len(weights) != 4:
+        raise ValueError(f"{name}: four weights (wx, wy, ww, wh), got {weights!r}")
+
+
+def _candidate_outputs(shape: Tuple[int, int], device):
+    """The four outputs of a decode entry, uninitialised: boxes (*shape, 4) and scores float32, the int64 output, valid uint8."""
+    return (torch.empty((*shape, 4), dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device),
+            torch.empty(shape, dtype=torch.int64, device=device), torch.empty(shape, dtype=torch.uint8, device=device))
+
+
+def _candidates(name: str, deps, boxes, scores, third, valid):
+    """What a decode entry returns: boxes and scores forward-only in `deps`, the int64 output, valid as bool."""
+    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(scores, name, *deps), third, valid.view(torch.bool)
+
+
+def _topk(name: str, logits, shapes, k, classes: Optional[int] = None, score_thresh=None) -> torch.Tensor:
+    """What rpn_topk and retinanet_topk share behind the checks of their maps: the checks of k, the workspace of
+    mv_<name>_workspace_bytes and the launch of mv_<name>_f32.  classes and score_thresh: retinanet's, arguments of its entries only."""
+    _check_k(name, k)
     per_anchor = 1 if classes is None else classes
     classes, thresh = (() if classes is None else (classes,)), (() if score_thresh is None else (float(score_thresh),))
     for m in logits:
         _lib.require_device(m, "logits")
     lib = _lib.load()
-    l0 = logits[0]
-    n = shapes[0][0]
+    l0, n = logits[0], shapes[0][0]
     total = sum(min(k, a * h * w * per_anchor) for _, a, h, w in shapes)
     with _lib.on_device_of(l0):
         maps = [_dense_images(m) for m in logits]
@@ -113,30 +146,23 @@ def _decode(name: str, logits, shapes, deltas, idx, cell_anchors, strides, image
     if dshapes is None or any(d[2:] != s[2:] or d[0] != s[0] for d, s in zip(dshapes, shapes)):
         raise RuntimeError(f"{name}: deltas should hold one map per level of logits, of the same batch and size with 4 channels per anchor")
     num, n = len(shapes), shapes[0][0]
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
-        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, K)")
+    _check_idx(name, idx, n)
     if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or \
             any(tuple(c.shape) != (a, 4) for c, a in zip(cell_anchors, anchors)):
         raise RuntimeError(f"{name}: cell_anchors should hold one (A, 4) tensor per level, A = {anchors}")
-    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
-        raise RuntimeError(f"{name}: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
-    if len(weights) != 4:
-        raise ValueError(f"{name}: four weights (wx, wy, ww, wh), got {weights!r}")
+    _check_strides(name, strides, num)
+    _check_weights(name, weights)
     sizes = _image_sizes(name, image_sizes, lambda t: tuple(t.shape) == (n, 2), f"{n} rows")
     for m in (*logits, *deltas, idx):
         _lib.require_device(m, f"{name} input")
     lib = _lib.load()
-    l0 = logits[0]
-    k = int(idx.shape[1])
+    l0, k = logits[0], int(idx.shape[1])
     with _lib.on_device_of(l0):
         lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
         base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
         sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
         ix = idx.contiguous()
-        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
-        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
-        third = torch.empty((n, k), dtype=torch.int64, device=l0.device)
-        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
+        boxes, scores, third, valid = _candidate_outputs((n, k), l0.device)
         if n and k:
             hs, ws, as_ = _tables(shapes)
             sh = (C.c_int * num)(*[int(s[0]) for s in strides])
@@ -145,8 +171,7 @@ def _decode(name: str, logits, shapes, deltas, idx, cell_anchors, strides, image
                         _img_strides(lmaps), _img_strides(dmaps), sh, sw, num, *classes, base.data_ptr(), sizes.data_ptr(), ix.data_ptr(), n, k,
                         *[float(w) for w in weights], float(clip), *[float(f) for f in filters], boxes.data_ptr(), scores.data_ptr(),
                         third.data_ptr(), valid.data_ptr())
-    deps = (*logits, *deltas)
-    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(scores, name, *deps), third, valid.view(torch.bool)
+    return _candidates(name, (*logits, *deltas), boxes, scores, third, valid)
 
 
 def rpn_topk(logits: List[torch.Tensor], k: int) -> torch.Tensor:
@@ -225,10 +250,7 @@ def fcos_topk(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], num_c
     Ktot = sum_l min(k, H_l W_l num_classes), as retinanet_topk: per image, level after level, the flat indices position * num_classes +
     class (offset by the positions of the levels before) of the min(k, passing) greatest scores in stable descending order, then -1."""
     shapes = _fcos_maps("fcos_topk", cls_logits, ctrness, num_classes)
-    if not isinstance(k, int) or k < 1:
-        raise ValueError(f"fcos_topk: k must be a positive int, got {k!r}")
-    if k > MAX_RPN_TOPK:
-        raise _lib.Mi355VisionError(f"fcos_topk: k up to {MAX_RPN_TOPK}, got {k}")
+    _check_k("fcos_topk", k)
     for m in (*cls_logits, *ctrness):
         _lib.require_device(m, "fcos_topk input")
     lib = _lib.load()
@@ -263,27 +285,21 @@ def fcos_decode(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], bbo
     if dshapes is None or dshapes != shapes:
         raise RuntimeError(f"{name}: bbox_regression should hold one map per level of cls_logits, of the same batch and size with 4 channels")
     num, n = len(shapes), shapes[0][0]
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
-        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, K)")
+    _check_idx(name, idx, n)
     if not isinstance(cell_anchors, (list, tuple)) or len(cell_anchors) != num or any(tuple(c.shape) != (1, 4) for c in cell_anchors):
         raise RuntimeError(f"{name}: cell_anchors should hold one (1, 4) tensor per level")
-    if len(strides) != num or any(len(s) != 2 or int(s[0]) < 0 or int(s[1]) < 0 for s in strides):
-        raise RuntimeError(f"{name}: strides should hold one non-negative (stride_h, stride_w) per level, got {strides!r}")
+    _check_strides(name, strides, num)
     sizes = _image_sizes(name, image_sizes, lambda t: tuple(t.shape) == (n, 2), f"{n} rows")
     for m in (*cls_logits, *ctrness, *bbox_regression, idx):
         _lib.require_device(m, f"{name} input")
     lib = _lib.load()
-    l0 = cls_logits[0]
-    k = int(idx.shape[1])
+    l0, k = cls_logits[0], int(idx.shape[1])
     with _lib.on_device_of(l0):
         lmaps, cmaps, dmaps = ([_dense_images(m) for m in maps] for maps in (cls_logits, ctrness, bbox_regression))
         base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
         sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
         ix = idx.contiguous()
-        boxes = torch.empty((n, k, 4), dtype=torch.float32, device=l0.device)
-        scores = torch.empty((n, k), dtype=torch.float32, device=l0.device)
-        labels = torch.empty((n, k), dtype=torch.int64, device=l0.device)
-        valid = torch.empty((n, k), dtype=torch.uint8, device=l0.device)
+        boxes, scores, labels, valid = _candidate_outputs((n, k), l0.device)
         if n and k:
             hs, ws, as_ = _tables(shapes)
             sh = (C.c_int * num)(*[int(s[0]) for s in strides])
@@ -291,8 +307,7 @@ def fcos_decode(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], bbo
             _lib.launch(lib.mv_fcos_decode_f32, l0, _lib.pointer_table(lmaps), _lib.pointer_table(cmaps), _lib.pointer_table(dmaps), hs, ws, as_,
                         _img_strides(lmaps), _img_strides(cmaps), _img_strides(dmaps), sh, sw, num, num_classes, base.data_ptr(),
                         sizes.data_ptr(), ix.data_ptr(), n, k, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
-    deps = (*cls_logits, *ctrness, *bbox_regression)
-    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(scores, name, *deps), labels, valid.view(torch.bool)
+    return _candidates(name, (*cls_logits, *ctrness, *bbox_regression), boxes, scores, labels, valid)
 
 
 def ssd_scores(cls_logits: List[torch.Tensor], num_classes: int) -> torch.Tensor:
@@ -330,10 +345,7 @@ def ssd_topk(scores: torch.Tensor, k: int, score_thresh: float) -> torch.Tensor:
     n, classes, v = (int(d) for d in scores.shape)
     if classes < 2:
         raise ValueError(f"ssd_topk: at least 2 classes (the background and one more), got {classes}")
-    if not isinstance(k, int) or isinstance(k, bool) or k < 1:
-        raise ValueError(f"ssd_topk: k must be a positive int, got {k!r}")
-    if k > MAX_RPN_TOPK:
-        raise _lib.Mi355VisionError(f"ssd_topk: k up to {MAX_RPN_TOPK}, got {k}")
+    _check_k("ssd_topk", k, reject_bool=True)
     if v * classes >= 2 ** 31:
         raise _lib.Mi355VisionError(f"ssd_topk: {v} anchors x {classes} classes exceed the 32-bit index")
     _lib.require_device(scores, "scores")
@@ -377,14 +389,12 @@ def ssd_decode(scores: torch.Tensor, bbox_regression: List[torch.Tensor], idx: t
         raise ValueError(f"{name}: at least 2 classes (the background and one more), got {classes}")
     if total * classes >= 2 ** 31:
         raise _lib.Mi355VisionError(f"{name}: the anchors of all levels x {classes} classes exceed the 32-bit index")
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32 or int(idx.shape[0]) != n:
-        raise RuntimeError(f"{name}: idx should be an int32 tensor of shape ({n}, M)")
+    _check_idx(name, idx, n, "M")
     if steps is not None and (len(steps) != num or any(not float(s) > 0 for s in steps)):
         raise ValueError(f"{name}: steps should hold one positive step per level, got {steps!r}")
     if len(batch_size) != 2 or int(batch_size[0]) < 1 or int(batch_size[1]) < 1:
         raise ValueError(f"{name}: batch_size should be the (height, width) of the batch tensor, got {batch_size!r}")
-    if len(weights) != 4:
-        raise ValueError(f"{name}: four weights (wx, wy, ww, wh), got {weights!r}")
+    _check_weights(name, weights)
     sizes = _image_sizes(name, image_sizes, lambda t: tuple(t.shape) == (n, 2), f"{n} rows")
     for m in (scores, *bbox_regression, idx):
         _lib.require_device(m, f"{name} input")
@@ -401,10 +411,7 @@ def ssd_decode(scores: torch.Tensor, bbox_regression: List[torch.Tensor], idx: t
         sc = scores.detach().contiguous()
         sizes = sizes.detach().to(d0.device, torch.float32).contiguous()
         ix = idx.contiguous()
-        boxes = torch.empty((n, m_, 4), dtype=torch.float32, device=d0.device)
-        out_scores = torch.empty((n, m_), dtype=torch.float32, device=d0.device)
-        labels = torch.empty((n, m_), dtype=torch.int64, device=d0.device)
-        valid = torch.empty((n, m_), dtype=torch.uint8, device=d0.device)
+        out = _candidate_outputs((n, m_), d0.device)
         if n and m_:
             hs, ws, as_ = _tables(dshapes)
             # the reference divides a float32 tensor by the Python double image side / step (or by the grid's int side)
@@ -412,9 +419,8 @@ def ssd_decode(scores: torch.Tensor, bbox_regression: List[torch.Tensor], idx: t
             y_f = (C.c_float * num)(*[bh / steps[l] if steps is not None else float(dshapes[l][2]) for l in range(num)])
             _lib.launch(lib.mv_ssd_decode_f32, d0, sc.data_ptr(), _lib.pointer_table(dmaps), hs, ws, as_, _img_strides(dmaps), num, classes,
                         pairs.data_ptr(), x_f, y_f, bh, bw, sizes.data_ptr(), ix.data_ptr(), n, m_, *[float(w) for w in weights],
-                        float(bbox_xform_clip), boxes.data_ptr(), out_scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
-    deps = (scores, *bbox_regression)
-    return _lib.forward_only(boxes, name, *deps), _lib.forward_only(out_scores, name, *deps), labels, valid.view(torch.bool)
+                        float(bbox_xform_clip), *[o.data_ptr() for o in out])
+    return _candidates(name, (scores, *bbox_regression), *out)
 
 
 def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[float, float, float, float],
@@ -427,8 +433,7 @@ def box_decode(boxes: torch.Tensor, rel_codes: torch.Tensor, weights: Tuple[floa
         raise RuntimeError(f"box_decode: rel_codes should have shape ({boxes.size(0)}, 4 C), got {tuple(rel_codes.shape)}")
     if boxes.dtype != torch.float32 or rel_codes.dtype != torch.float32:
         raise TypeError(f"box_decode computes in float32. Got boxes {boxes.dtype}, rel_codes {rel_codes.dtype}")
-    if len(weights) != 4:
-        raise ValueError(f"box_decode: four weights (wx, wy, ww, wh), got {weights!r}")
+    _check_weights("box_decode", weights)
     _lib.require_device(rel_codes, "rel_codes")
     _lib.require_device(boxes, "boxes")
     lib = _lib.load()
@@ -475,8 +480,7 @@ def roi_detections(class_logits: torch.Tensor, box_regression: torch.Tensor, roi
         raise _lib.Mi355VisionError(f"roi_detections: up to {MAX_ROI_CLASSES} classes, got {c}")
     if r * c >= 2 ** 31:
         raise _lib.Mi355VisionError(f"roi_detections: {r} rois x {c} classes exceed the 32-bit index")
-    if len(weights) != 4:
-        raise ValueError(f"roi_detections: four weights (wx, wy, ww, wh), got {weights!r}")
+    _check_weights("roi_detections", weights)
     sizes = _image_sizes("roi_detections", image_sizes, lambda t: t.dim() == 2 and t.shape[1] == 2 and (r == 0 or t.shape[0] >= 1),
                          "at least one row")
     for m in (class_logits, box_regression, rois):
@@ -487,15 +491,10 @@ def roi_detections(class_logits: torch.Tensor, box_regression: torch.Tensor, roi
         lg, dl = _rows(class_logits), _rows(box_regression)
         rs = rois.detach().to(dev).contiguous()
         sizes = sizes.detach().to(dev, torch.float32).contiguous()
-        boxes = torch.empty((r, c - 1, 4), dtype=torch.float32, device=dev)
-        scores = torch.empty((r, c - 1), dtype=torch.float32, device=dev)
-        labels = torch.empty((r, c - 1), dtype=torch.int64, device=dev)
-        valid = torch.empty((r, c - 1), dtype=torch.uint8, device=dev)
+        out = _candidate_outputs((r, c - 1), dev)
         if r:
             _lib.launch(lib.mv_roi_detections_f32, lg, lg.data_ptr(), int(lg.stride(0)) if r > 1 else c, dl.data_ptr(),
                         int(dl.stride(0)) if r > 1 else 4 * c, rs.data_ptr(), sizes.data_ptr(), r, c, int(sizes.shape[0]),
-                        *[float(w) for w in weights], float(bbox_xform_clip), float(score_thresh), float(min_size), boxes.data_ptr(),
-                        scores.data_ptr(), labels.data_ptr(), valid.data_ptr())
-    deps = (class_logits, box_regression, rois)
-    return (_lib.forward_only(boxes, "roi_detections", *deps), _lib.forward_only(scores, "roi_detections", *deps), labels,
-            valid.view(torch.bool))
+                        *[float(w) for w in weights], float(bbox_xform_clip), float(score_thresh), float(min_size),
+                        *[o.data_ptr() for o in out])
+    return _candidates("roi_detections", (class_logits, box_regression, rois), *out)

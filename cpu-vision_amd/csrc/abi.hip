@@ -1450,6 +1450,26 @@ static PyramidMaps topk_maps(const float* const* logits, const int* hs, const in
   m.logits = logits, m.hs = hs, m.ws = ws, m.as = as, m.logit_strides = img_strides, m.levels = levels;
   return m;
 }
+// Level l's map p, n images of `elems` elements, `stride` elements apart: kMapOk and *r, the bytes they span, or the first refusal
+// (unaligned only where `aligned` asks for 4-byte pointers: the SSD entries do, the RPN family's do not), for the entry's words.
+enum LevelMap { kMapOk = 0, kMapNull, kMapUnaligned, kMapStride };
+static LevelMap level_map(const float* p, int64_t stride, int64_t elems, int64_t n, bool aligned, ByteRange* r) {
+  if (!p) return kMapNull;
+  if (aligned && (uintptr_t)p % 4) return kMapUnaligned;
+  if (stride < elems || stride > 0x7fffffffffffLL / n) return kMapStride;
+  *r = {p, ((n - 1) * stride + elems) * 4};
+  return kMapOk;
+}
+// level_map with the words that the entries with one map per level share
+static int level_map_check(const char* op, const char* of_what, int l, const float* p, int64_t stride, int64_t elems, int64_t n, bool aligned,
+                           ByteRange* r) {
+  const LevelMap rc = level_map(p, stride, elems, n, aligned, r);
+  if (rc == kMapNull) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+  if (rc == kMapUnaligned) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the maps must be 4-byte aligned (level %d)", op, l);
+  if (rc == kMapOk) return MV_OK;
+  return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of %slevel %d, its map has %lld elements", op, (long long)stride, of_what, l,
+                   (long long)elems);
+}
 // ctr: the entry takes centerness maps too (FCOS): one anchor per location, m.ctrness[l] a map (n, 1, hs[l], ws[l]).
 static int one_anchor_check(const char* op, const PyramidMaps& m) {
   for (int l = 0; l < m.levels; ++l)
@@ -1458,14 +1478,9 @@ static int one_anchor_check(const char* op, const PyramidMaps& m) {
 }
 static int ctr_check(const char* op, const PyramidMaps& m, int64_t n, ByteRange* ins) {
   if (!m.ctrness || !m.ctr_strides) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
-  for (int l = 0; l < m.levels; ++l) {
-    const int64_t hw = (int64_t)m.hs[l] * m.ws[l];
-    if (!m.ctrness[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
-    if (m.ctr_strides[l] < hw || m.ctr_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of the centerness of level %d, its map has %lld elements", op,
-                       (long long)m.ctr_strides[l], l, (long long)hw);
-    ins[l] = {m.ctrness[l], ((n - 1) * m.ctr_strides[l] + hw) * 4};
-  }
+  for (int l = 0; l < m.levels; ++l)
+    if (int rc = level_map_check(op, "the centerness of ", l, m.ctrness[l], m.ctr_strides[l], (int64_t)m.hs[l] * m.ws[l], n, false, ins + l))
+      return rc;
   return MV_OK;
 }
 static int topk_check(const char* op, TopkBytes bytes, const PyramidMaps& m, int classes, int64_t n, int k, const int* idx, const void* workspace,
@@ -1484,14 +1499,9 @@ static int topk_check(const char* op, TopkBytes bytes, const PyramidMaps& m, int
   ByteRange ins[2 * kMaxRpnLevels];
   if (ctr)
     if (int rc = ctr_check(op, m, n, ins + m.levels)) return rc;
-  for (int l = 0; l < m.levels; ++l) {
-    const int64_t nl = (int64_t)m.as[l] * m.hs[l] * m.ws[l] * classes;
-    if (!m.logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
-    if (m.logit_strides[l] < nl || m.logit_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of level %d, its map has %lld elements", op,
-                       (long long)m.logit_strides[l], l, (long long)nl);
-    ins[l] = {m.logits[l], ((n - 1) * m.logit_strides[l] + nl) * 4};
-  }
+  for (int l = 0; l < m.levels; ++l)
+    if (int rc = level_map_check(op, "", l, m.logits[l], m.logit_strides[l], (int64_t)m.as[l] * m.hs[l] * m.ws[l] * classes, n, false, ins + l))
+      return rc;
   if (!workspace) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: needs a workspace", op);
   if (workspace_bytes < need)
     return set_error(MV_ERR_INVALID_ARGUMENT, "%s: workspace of %lld bytes, need %lld (mv_%s_workspace_bytes)", op, (long long)workspace_bytes,
@@ -1537,12 +1547,11 @@ static int decode_check(const char* op, const char* out64_name, const PyramidMap
   for (int l = 0; l < m.levels; ++l) {
     const int64_t al = (int64_t)m.as[l] * m.hs[l] * m.ws[l], nl = al * classes;
     const int64_t ls = m.logit_strides[l], ds = m.delta_strides[l];
-    if (!m.logits[l] || !m.deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
-    if (ls < nl || ds < 4 * al || ls > 0x7fffffffffffLL / n || ds > 0x7fffffffffffLL / n)
+    const LevelMap lg = level_map(m.logits[l], ls, nl, n, false, ins + 2 * l), dl = level_map(m.deltas[l], ds, 4 * al, n, false, ins + 2 * l + 1);
+    if (lg == kMapNull || dl == kMapNull) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
+    if (lg || dl)  // the two maps of a level are refused in one message
       return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image strides (%lld, %lld) of level %d, its maps have %lld and %lld elements", op,
                        (long long)ls, (long long)ds, l, (long long)nl, (long long)(4 * al));
-    ins[2 * l] = {m.logits[l], ((n - 1) * ls + nl) * 4};
-    ins[2 * l + 1] = {m.deltas[l], ((n - 1) * ds + 4 * al) * 4};
     base_rows += m.as[l];
   }
   ins[2 * m.levels] = {m.base_anchors, base_rows * 16}, ins[2 * m.levels + 1] = {image_sizes, n * 8}, ins[2 * m.levels + 2] = {idx, n * k * 4};
@@ -1688,13 +1697,8 @@ int mv_ssd_scores_f32(const float* const* logits, const int* hs, const int* ws, 
   ByteRange ins[kMaxRpnLevels];
   int64_t anchors = 0;
   for (int l = 0; l < levels; ++l) {
-    const int64_t al = (int64_t)as[l] * hs[l] * ws[l], nl = al * classes;
-    if (!logits[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
-    if ((uintptr_t)logits[l] % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the maps must be 4-byte aligned (level %d)", op, l);
-    if (img_strides[l] < nl || img_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of level %d, its map has %lld elements", op, (long long)img_strides[l], l,
-                       (long long)nl);
-    ins[l] = {logits[l], ((n - 1) * img_strides[l] + nl) * 4};
+    const int64_t al = (int64_t)as[l] * hs[l] * ws[l];
+    if (int rc = level_map_check(op, "", l, logits[l], img_strides[l], al * classes, n, true, ins + l)) return rc;
     anchors += al;
   }
   const ByteRange out = {scores, n * anchors * classes * 4};
@@ -1748,12 +1752,7 @@ int mv_ssd_decode_f32(const float* scores, const float* const* deltas, const int
   int64_t anchors = 0, pairs = 0;
   for (int l = 0; l < levels; ++l) {
     const int64_t al = (int64_t)as[l] * hs[l] * ws[l];
-    if (!deltas[l]) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer (level %d)", op, l);
-    if ((uintptr_t)deltas[l] % 4) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: the maps must be 4-byte aligned (level %d)", op, l);
-    if (delta_strides[l] < 4 * al || delta_strides[l] > 0x7fffffffffffLL / n)
-      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: image stride %lld of level %d, its map has %lld elements", op, (long long)delta_strides[l],
-                       l, (long long)(4 * al));
-    ins[l] = {deltas[l], ((n - 1) * delta_strides[l] + 4 * al) * 4};
+    if (int rc = level_map_check(op, "", l, deltas[l], delta_strides[l], 4 * al, n, true, ins + l)) return rc;
     anchors += al, pairs += as[l];
   }
   ins[levels] = {scores, n * anchors * classes * 4}, ins[levels + 1] = {wh_pairs, pairs * 8}, ins[levels + 2] = {image_sizes, n * 8};

@@ -1,10 +1,12 @@
 // mv_boxcoder.h -- BoxCoder.decode_single (_utils.py) as one device function, shared by rpn.hip (k_rpn_decode, k_box_decode),
-// roi_heads.hip (k_roi_detections) and retinanet.hip (k_retinanet_decode); the anchor of a flat index, built in registers from the
-// level tables (anchor_at), the sigmoid (sigmoid_cr) and the decode of one candidate of a pyramid (PyramidDecode, decode_candidate),
-// shared by k_rpn_decode and k_retinanet_decode.  Every float operation is written with __f*_rn: the reference is a chain of float32
-// torch ops, one rounding each, never an fma.  exp is the CORRECTLY ROUNDED float32 exp, (float)exp((double)v): torch's CPU exp is a
-// 1-ulp vector routine whose bits no other implementation reproduces, so the library states the one value that does not depend on
-// an implementation (mi355vision.h, mv_rpn_decode_f32).
+// roi_heads.hip (k_roi_detections), retinanet.hip (k_retinanet_decode) and ssd.hip (k_ssd_decode); the level, anchor and position of
+// a flat index from the level tables (PyramidLevels, level_at: k_ssd_scores, k_ssd_decode) and, with an anchor generator's tables,
+// the anchor built in registers (AnchorLevels, anchor_at: decode_candidate, k_fcos_decode); the sigmoid (sigmoid_cr); the decode of
+// one candidate of a pyramid (PyramidDecode, decode_candidate: k_rpn_decode, k_retinanet_decode); the outputs of an index that is no
+// candidate (store_no_candidate: k_rpn_decode, k_retinanet_decode, k_ssd_decode).  Every float operation is written with __f*_rn:
+// the reference is a chain of float32 torch ops, one rounding each, never an fma.  exp is the CORRECTLY ROUNDED float32 exp,
+// (float)exp((double)v): torch's CPU exp is a 1-ulp vector routine whose bits no other implementation reproduces, so the library
+// states the one value that does not depend on an implementation (mi355vision.h, mv_rpn_decode_f32).
 #pragma once
 
 #include "mv_common.h"
@@ -55,27 +57,40 @@ __device__ inline void decode_linear(float x1, float y1, float x2, float y2, flo
   out[2] = __fadd_rn(ctr_x, __fmul_rn(r2, w)), out[3] = __fadd_rn(ctr_y, __fmul_rn(r3, h));
 }
 
-// The pyramid of an anchor generator, by value in the kernel arguments (kMaxRpnLevels entries, `levels` used).
-struct AnchorLevels {
+// The levels of a pyramid, by value in the kernel arguments (kMaxRpnLevels entries, `levels` used): what a kernel needs to find the
+// level, the anchor and the position of a flat index.  ssd.hip's kernels take this alone (their boxes come from other tables, and
+// tables a kernel does not read still cost it SGPRs); AnchorLevels adds an anchor generator's base anchors and strides.
+struct PyramidLevels {
   int h[kMaxRpnLevels], w[kMaxRpnLevels], a[kMaxRpnLevels];
-  int start[kMaxRpnLevels];     // flat index of the level's first anchor
+  int start[kMaxRpnLevels];  // flat index of the level's first anchor
+  int levels, total;         // total: anchors of all levels
+};
+struct AnchorLevels {
+  PyramidLevels py;
   int base_off[kMaxRpnLevels];  // row of the level's first base anchor
   int stride_h[kMaxRpnLevels], stride_w[kMaxRpnLevels];
-  int levels, total;            // total: anchors of all levels
   const float* base_anchors;
 };
-inline void fill_anchor_levels(AnchorLevels& t, const PyramidMaps& m) {
-  int start = 0, base = 0;
+inline void fill_pyramid_levels(PyramidLevels& t, const PyramidMaps& m) {
+  int start = 0;
   for (int l = 0; l < m.levels; ++l) {
-    t.h[l] = m.hs[l], t.w[l] = m.ws[l], t.a[l] = m.as[l], t.start[l] = start, t.base_off[l] = base;
-    t.stride_h[l] = m.strides_h[l], t.stride_w[l] = m.strides_w[l];
-    start += m.as[l] * m.hs[l] * m.ws[l], base += m.as[l];
+    t.h[l] = m.hs[l], t.w[l] = m.ws[l], t.a[l] = m.as[l], t.start[l] = start;
+    start += m.as[l] * m.hs[l] * m.ws[l];
   }
-  t.levels = m.levels, t.total = start, t.base_anchors = m.base_anchors;
+  t.levels = m.levels, t.total = start;
+}
+inline void fill_anchor_levels(AnchorLevels& t, const PyramidMaps& m) {
+  fill_pyramid_levels(t.py, m);
+  int base = 0;
+  for (int l = 0; l < m.levels; ++l) {
+    t.base_off[l] = base, t.stride_h[l] = m.strides_h[l], t.stride_w[l] = m.strides_w[l];
+    base += m.as[l];
+  }
+  t.base_anchors = m.base_anchors;
 }
 
-// What k_rpn_decode and k_retinanet_decode take alike, by value in the kernel arguments: the head's maps (logit channel
-// a * classes + c, delta channels 4 a .. 4 a + 3 of anchor a), the pyramid, the n * k candidates and the outputs both write.
+// What k_rpn_decode, k_retinanet_decode and k_fcos_decode take alike, by value in the kernel arguments: the head's maps (logit
+// channel a * classes + c, delta channels 4 a .. 4 a + 3 of anchor a), the pyramid, the n * k candidates and the outputs all write.
 struct PyramidDecode {
   const float* logits[kMaxRpnLevels];
   const float* deltas[kMaxRpnLevels];
@@ -100,26 +115,49 @@ inline void fill_pyramid_decode(PyramidDecode& p, const PyramidMaps& m, int clas
 }
 
 // Anchor v (0 <= v < T.total) of the concatenated (y, x, a) layout: its level, its anchor a and position s = y W + x in the level's
-// map of hw = H W elements, and the box (x sw + b[a][0], y sh + b[a][1], x sw + b[a][2], y sh + b[a][3]).
+// map of width W and hw = H W elements.  more(l): the caller's own picks from tables of level l, in the same pass over the levels
+// -- anchor_at's: picked in a second pass they cost k_rpn_decode 8 more SGPRs (106) and left a SIMD 7 waves for 8.
+struct LevelAt {
+  int level, a, s, W;
+  size_t hw;
+};
+template <typename More>
+__device__ inline LevelAt level_at(const PyramidLevels& T, int v, const More& more) {
+  int level = 0;
+#pragma unroll
+  for (int l = 1; l < kMaxRpnLevels; ++l)
+    if (l < T.levels && v >= T.start[l]) level = l;
+  int H = 1, W = 1, A = 1, start = 0;
+#pragma unroll
+  for (int l = 0; l < kMaxRpnLevels; ++l)
+    if (l == level) H = T.h[l], W = T.w[l], A = T.a[l], start = T.start[l], more(l);
+  const int flat = v - start;
+  return {level, flat % A, flat / A, W, (size_t)H * W};
+}
+__device__ inline LevelAt level_at(const PyramidLevels& T, int v) {
+  return level_at(T, v, [](int) {});
+}
+
+// level_at, and the anchor's box (x sw + b[a][0], y sh + b[a][1], x sw + b[a][2], y sh + b[a][3]).
 struct AnchorAt {
   int level, a, s;
   size_t hw;
   float x1, y1, x2, y2;
 };
 __device__ inline AnchorAt anchor_at(const AnchorLevels& T, int v) {
-  int level = 0;
-#pragma unroll
-  for (int l = 1; l < kMaxRpnLevels; ++l)
-    if (l < T.levels && v >= T.start[l]) level = l;
-  int H = 1, W = 1, A = 1, start = 0, base_off = 0, sh = 0, sw = 0;
-#pragma unroll
-  for (int l = 0; l < kMaxRpnLevels; ++l)
-    if (l == level)
-      H = T.h[l], W = T.w[l], A = T.a[l], start = T.start[l], base_off = T.base_off[l], sh = T.stride_h[l], sw = T.stride_w[l];
-  const int flat = v - start, a = flat % A, s = flat / A, y = s / W, x = s % W;
-  const float* const b = T.base_anchors + (size_t)(base_off + a) * 4;
+  int base_off = 0, sh = 0, sw = 0;
+  const LevelAt at = level_at(T.py, v, [&](int l) { base_off = T.base_off[l], sh = T.stride_h[l], sw = T.stride_w[l]; });
+  const int y = at.s / at.W, x = at.s % at.W;
+  const float* const b = T.base_anchors + (size_t)(base_off + at.a) * 4;
   const float fx = (float)(x * sw), fy = (float)(y * sh);  // the reference's int32 shifts, converted as its int + float add does
-  return {level, a, s, (size_t)H * W, __fadd_rn(fx, b[0]), __fadd_rn(fy, b[1]), __fadd_rn(fx, b[2]), __fadd_rn(fy, b[3])};
+  return {at.level, at.a, at.s, at.hw, __fadd_rn(fx, b[0]), __fadd_rn(fy, b[1]), __fadd_rn(fx, b[2]), __fadd_rn(fy, b[3])};
+}
+
+// What a decode kernel writes at t for an index that is no candidate of its pyramid: zeros, `fill` in the int64 output, valid = 0
+// (k_fcos_decode writes the same itself: see there).
+__device__ inline void store_no_candidate(float* boxes, float* scores, long long* out64, unsigned char* valid, long long t, long long fill) {
+  for (int q = 0; q < 4; ++q) boxes[t * 4 + q] = 0.f;
+  scores[t] = 0.f, out64[t] = fill, valid[t] = 0;
 }
 
 // Candidate t of P (0 <= t < P.count), flat index f = P.idx[t] = anchor * classes + class.  in_pyramid: f is a candidate of this
@@ -134,7 +172,7 @@ template <int CLASSES>
 __device__ inline bool in_pyramid(const PyramidDecode& P, long long t) {
   const int K = CLASSES ? CLASSES : P.classes;
   const int f = P.idx[t];
-  return f >= 0 && f / K < P.lv.total;
+  return f >= 0 && f / K < P.lv.py.total;
 }
 template <int CLASSES>
 __device__ inline Candidate decode_candidate(const PyramidDecode& P, long long t) {

@@ -1,5 +1,7 @@
-// mv_topk.h -- the wave-level histogram step of the radix selects (rpn.hip k_rpn_topk, retinanet.hip, ssd.hip) and the radix select
-// of the k greatest 64-bit keys of a workgroup (retinanet.hip, ssd.hip).
+// mv_topk.h -- the wave-level histogram step of the radix selects (hist_add: rpn.hip k_rpn_topk, and select_keys here), the radix
+// select of the k greatest 64-bit keys of a workgroup (select_keys: retinanet.hip k_retinanet_chunks and k_retinanet_rank, ssd.hip
+// k_ssd_topk) and the stage behind it, the selected keys gathered into LDS, ranked pairwise and stored (rank_selected:
+// k_retinanet_rank and k_ssd_topk).  k_rpn_topk keeps its own compaction and ranking: its equal keys are taken in index order.
 #pragma once
 
 #include "mv_common.h"
@@ -49,6 +51,36 @@ __device__ inline unsigned long long select_keys(const Each& each, unsigned k, u
   }
   *take = k;
   return prefix;
+}
+
+// The stage behind select_keys, called by the whole workgroup with its results (thr, take): the `take` keys >= thr among
+// key_at(0 .. count - 1) go to cand (LDS, room for take <= kRpnMaxK keys; n_out: an LDS counter) in any order and are ranked
+// pairwise there, position = #{greater keys} -- the keys are pairwise distinct, so that is their descending order;
+// out[rank] = stored(key), and out[take .. seg - 1] = -1.  THREADS: the workgroup's; Index: the type key_at counts in.
+template <int THREADS, typename Index, typename KeyAt, typename Stored>
+__device__ inline void rank_selected(const KeyAt& key_at, Index count, unsigned long long thr, unsigned take, unsigned long long* cand,
+                                     unsigned* n_out, int* out, int seg, const Stored& stored) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *n_out = 0;
+  __syncthreads();
+  for (Index i = tid; i < count; i += THREADS) {
+    const unsigned long long key = key_at(i);
+    if (key >= thr && key != 0) {  // exactly `take` keys
+      const unsigned slot = atomicAdd(n_out, 1u);
+      if (slot < take) cand[slot] = key;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < seg; i += THREADS) {
+    if (i >= (int)take) {
+      out[i] = -1;
+      continue;
+    }
+    const unsigned long long ki = cand[i];
+    int rank = 0;
+    for (int j = 0; j < (int)take; ++j) rank += cand[j] > ki ? 1 : 0;
+    out[rank] = stored(ki);
+  }
 }
 
 }  // namespace mv

@@ -15,16 +15,20 @@
 //                      chunk reserves the room, so the pool's ORDER varies from run to run and its content does not.  A pool has room
 //                      for min(k, kRetChunk) keys of every chunk: nothing is dropped, whatever passes.
 // k_retinanet_rank     stage 2, one workgroup per (image, level): select_keys over the pool, the <= k <= 4096 selected keys into
-//                      LDS, ranked pairwise there (position = #{greater keys}); idx[rank] = f, the rest of the segment -1.
+//                      LDS, ranked pairwise there (position = #{greater keys}); idx[rank] = f, the rest of the segment -1
+//                      (rank_selected of mv_topk.h, shared with k_ssd_topk).
 // select_keys          (mv_topk.h, shared with ssd.hip) radix select of the k-th greatest key, 8 bits per pass from the top, a
 //                      256-bin histogram in LDS per pass (hist_add of k_rpn_topk).  It stops as soon as the answer is known: after the first pass when at most k
 //                      keys pass at all, after any pass when the bin of the k-th key is taken whole; at most 8 passes.
 // k_retinanet_decode   one lane per idx[i, j]: anchor f / K and label f % K, the anchor in registers, decode_single, clip to the
-//                      image (decode_candidate of mv_boxcoder.h, shared with k_rpn_decode), the score recomputed.
+//                      image (decode_candidate of mv_boxcoder.h, shared with k_rpn_decode), the score recomputed.  An index that
+//                      is no candidate gets store_no_candidate's outputs, as in k_rpn_decode and k_ssd_decode.
 //
 // FCOS (models/detection/fcos.py postprocess_detections) is the same selection with another score, sqrt(sigmoid(cls) *
 // sigmoid(centerness)), the centerness map read at the candidate's position: the chunk and rank kernels are instantiated with
-// FCOS = true, where only candidate_key differs, and k_fcos_decode decodes with BoxLinearCoder's decode_linear.
+// FCOS = true, where only candidate_key differs, and k_fcos_decode decodes with BoxLinearCoder's decode_linear.  It shares
+// anchor_at (mv_boxcoder.h) with decode_candidate and keeps its own pick of the level's maps, clamp and not-a-candidate branch:
+// with the shared helpers it compiles to other registers than before.
 //
 // Every float operation is written with __f*_rn and exp is the correctly rounded float32 exp, as in rpn.hip.
 #include "mv_boxcoder.h"
@@ -180,39 +184,16 @@ __global__ __launch_bounds__(kRetThreads) void k_retinanet_rank(const RetTopkArg
   };
   unsigned take_u;
   const u64 thr = select_keys(each, (unsigned)T.k, hist, sel, tid, lane, &take_u);
-  const int take = (int)take_u;
-  if (tid == 0) n_out = 0;
-  __syncthreads();
-  for (long long i = tid; i < total; i += kRetThreads) {
-    const u64 key = key_at(i);
-    if (key >= thr) {  // exactly `take` keys, each != 0
-      const unsigned slot = atomicAdd(&n_out, 1u);
-      if (slot < take_u) cand[slot] = key;
-    }
-  }
-  __syncthreads();
-  int* const out = T.idx + (size_t)img * T.k_total + out_start;
-  for (int i = tid; i < seg; i += kRetThreads) {
-    if (i >= take) {
-      out[i] = -1;
-      continue;
-    }
-    const u64 ki = cand[i];
-    int rank = 0;
-    for (int j = 0; j < take; ++j) rank += cand[j] > ki ? 1 : 0;
-    out[rank] = (int)~(unsigned)ki;
-  }
+  // every key >= thr is a candidate's, != 0, so rank_selected's `key != 0` selects the same set
+  rank_selected<kRetThreads>(key_at, total, thr, take_u, cand, &n_out, T.idx + (size_t)img * T.k_total + out_start, seg,
+                             [](u64 key) { return (int)~(unsigned)key; });
 }
 
 // amdgpu_waves_per_eu(8): left alone the compiler keeps the tables of all eight levels in 102 SGPRs, which leaves a SIMD 7 waves
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_retinanet_decode(const PyramidDecode P, long long* labels) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= P.count) return;
-  if (!in_pyramid<0>(P, t)) {  // not a candidate of this pyramid (the -1 padding): nothing is read for it
-    for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = 0.f;
-    P.scores[t] = 0.f, labels[t] = 0, P.valid[t] = 0;
-    return;
-  }
+  if (!in_pyramid<0>(P, t)) return store_no_candidate(P.boxes, P.scores, labels, P.valid, t, 0);  // the -1 padding: nothing is read for it
   const Candidate c = decode_candidate<0>(P, t);
   for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = c.box[q];
   P.scores[t] = sigmoid_cr(c.logit);

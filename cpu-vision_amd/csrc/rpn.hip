@@ -163,15 +163,11 @@ __global__ __launch_bounds__(kTopkThreads) void k_rpn_topk(const TopkArgs T) {
   }
 }
 
-// ---- the decode of a candidate: decode_candidate of mv_boxcoder.h (shared with retinanet.hip), here with one class -----------------
+// ---- the decode of a candidate: decode_candidate and store_no_candidate of mv_boxcoder.h (shared with retinanet.hip), one class ----
 __global__ __launch_bounds__(256) void k_rpn_decode(const PyramidDecode P, long long* levels_out, float min_size, float score_thresh) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= P.count) return;
-  if (!in_pyramid<1>(P, t)) {  // not an anchor of this pyramid: nothing is read for it
-    for (int q = 0; q < 4; ++q) P.boxes[t * 4 + q] = 0.f;
-    P.scores[t] = 0.f, levels_out[t] = -1, P.valid[t] = 0;
-    return;
-  }
+  if (!in_pyramid<1>(P, t)) return store_no_candidate(P.boxes, P.scores, levels_out, P.valid, t, -1);  // nothing is read for it
   const Candidate c = decode_candidate<1>(P, t);
   const float score = sigmoid_cr(c.logit);
   const float bw = __fsub_rn(c.box[2], c.box[0]), bh = __fsub_rn(c.box[3], c.box[1]);

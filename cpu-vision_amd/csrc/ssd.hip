@@ -13,12 +13,13 @@
 //                parked words.  Maximum and exponentials are k_roi_detections' (roi_heads.hip).
 // k_ssd_topk     one workgroup per (image, class >= 1) walks its contiguous row of V scores: key (score bits << 32 | ~v), 0 when
 //                `score > thresh` fails (a NaN fails); select_keys (mv_topk.h) picks the k greatest, which go to LDS and are ranked
-//                pairwise there, as in k_retinanet_rank; idx[i][(c - 1) k + rank] = v K + c, the rest of the segment -1.  Keys of
+//                pairwise there (rank_selected, shared with k_retinanet_rank); idx[i][(c - 1) k + rank] = v K + c, the rest -1.  Keys of
 //                distinct anchors differ, so the result is one set in one order whatever the order of the visits; nothing is read
 //                back and no atomic touches global memory.
 // k_ssd_decode   one lane per idx[i, j]: anchor f / K and label f % K, the default box built in registers (DefaultBoxGenerator's
 //                float32 chain, anchor_utils.py), decode_single with delta channels 4 a .. 4 a + 3, the clamp to the image, the score
-//                read from the matrix.
+//                read from the matrix.  The level tables and the (level, a, position) of an anchor are PyramidLevels / level_at of
+//                mv_boxcoder.h (k_ssd_scores too), the outputs of the padding its store_no_candidate.
 //
 // Every float operation is written with __f*_rn and exp is the correctly rounded float32 exp, as in rpn.hip.
 #include "mv_boxcoder.h"
@@ -33,34 +34,10 @@ typedef unsigned long long u64;
 constexpr int kSsdTopkThreads = 1024;
 constexpr int kSsdTopkLoads = 4;  // scores a thread loads before it works on them
 
-struct SsdLevels {
-  int h[kMaxRpnLevels], w[kMaxRpnLevels], a[kMaxRpnLevels];
-  int start[kMaxRpnLevels];  // flat index of the level's first anchor
-  int levels, total;         // total: anchors of all levels
-};
-
-// Anchor v (0 <= v < T.total): its level, its anchor a and its position s = y W + x in the level's map
-struct SsdAt {
-  int level, a, s, W;
-  size_t hw;
-};
-__device__ inline SsdAt ssd_at(const SsdLevels& T, int v) {
-  int level = 0;
-#pragma unroll
-  for (int l = 1; l < kMaxRpnLevels; ++l)
-    if (l < T.levels && v >= T.start[l]) level = l;
-  int H = 1, W = 1, A = 1, start = 0;
-#pragma unroll
-  for (int l = 0; l < kMaxRpnLevels; ++l)
-    if (l == level) H = T.h[l], W = T.w[l], A = T.a[l], start = T.start[l];
-  const int flat = v - start;
-  return {level, flat % A, flat / A, W, (size_t)H * W};
-}
-
 struct SsdScoresArgs {
   const float* logits[kMaxRpnLevels];
   long long img_stride[kMaxRpnLevels];
-  SsdLevels lv;
+  PyramidLevels lv;
   int classes;
   float* scores;  // (n, classes, total)
 };
@@ -69,7 +46,7 @@ __global__ __launch_bounds__(256) void k_ssd_scores(const SsdScoresArgs S) {
   const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
   if (v >= S.lv.total) return;
   const int img = blockIdx.y, K = S.classes;
-  const SsdAt at = ssd_at(S.lv, (int)v);
+  const LevelAt at = level_at(S.lv, (int)v);
   const float* p = nullptr;
   long long stride = 0;
 #pragma unroll
@@ -126,35 +103,15 @@ __global__ __launch_bounds__(kSsdTopkThreads) void k_ssd_topk(const SsdTopkArgs 
   };
   unsigned take_u;
   const u64 thr = select_keys(each, (unsigned)T.k, hist, sel, tid, lane, &take_u);
-  const int take = (int)take_u;
-  if (tid == 0) n_out = 0;
-  __syncthreads();
-  for (int i = tid; i < total; i += kSsdTopkThreads) {
-    const u64 key = key_at(i);
-    if (key >= thr && key != 0) {  // exactly `take` keys
-      const unsigned slot = atomicAdd(&n_out, 1u);
-      if (slot < take_u) cand[slot] = key;
-    }
-  }
-  __syncthreads();
-  int* const out = T.idx + ((size_t)img * (K - 1) + (c - 1)) * (size_t)T.k;
-  for (int i = tid; i < T.k; i += kSsdTopkThreads) {
-    if (i >= take) {
-      out[i] = -1;
-      continue;
-    }
-    const u64 ki = cand[i];
-    int rank = 0;
-    for (int j = 0; j < take; ++j) rank += cand[j] > ki ? 1 : 0;
-    out[rank] = (int)(~(unsigned)ki) * K + c;
-  }
+  rank_selected<kSsdTopkThreads>(key_at, total, thr, take_u, cand, &n_out, T.idx + ((size_t)img * (K - 1) + (c - 1)) * (size_t)T.k, T.k,
+                                 [&](u64 key) { return (int)(~(unsigned)key) * K + c; });
 }
 
 struct SsdDecodeArgs {
   const float* scores;  // (n, classes, total)
   const float* deltas[kMaxRpnLevels];
   long long delta_stride[kMaxRpnLevels];
-  SsdLevels lv;
+  PyramidLevels lv;
   int pair_off[kMaxRpnLevels];              // row of the level's first (w, h) pair
   float x_f[kMaxRpnLevels], y_f[kMaxRpnLevels];
   float img_w, img_h;                       // the batch tensor's sides
@@ -175,14 +132,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
   if (t >= D.count) return;
   const int K = D.classes;
   const int f = D.idx[t];
-  if (f < 0 || f / K >= D.lv.total) {  // not a candidate of this pyramid (the -1 padding): nothing is read for it
-    for (int q = 0; q < 4; ++q) D.boxes[t * 4 + q] = 0.f;
-    D.scores_out[t] = 0.f, D.labels[t] = 0, D.valid[t] = 0;
-    return;
-  }
+  // not a candidate of this pyramid (the -1 padding): nothing is read for it
+  if (f < 0 || f / K >= D.lv.total) return store_no_candidate(D.boxes, D.scores_out, D.labels, D.valid, t, 0);
   const long long img = t / D.k;
   const int v = f / K, c = f - v * K;
-  const SsdAt at = ssd_at(D.lv, v);
+  const LevelAt at = level_at(D.lv, v);
   const float* dl = nullptr;
   long long ds = 0;
   int pair_off = 0;
@@ -209,21 +163,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
   D.valid[t] = 1;
 }
 
-void fill_ssd_levels(SsdLevels& t, const int* hs, const int* ws, const int* as, int levels) {
-  int start = 0;
-  for (int l = 0; l < levels; ++l) {
-    t.h[l] = hs[l], t.w[l] = ws[l], t.a[l] = as[l], t.start[l] = start;
-    start += as[l] * hs[l] * ws[l];
-  }
-  t.levels = levels, t.total = start;
-}
-
 }  // namespace
 
 int launch_ssd_scores(const PyramidMaps& m, int classes, int n, float* scores, hipStream_t s) {
   SsdScoresArgs a = {};
   for (int l = 0; l < m.levels; ++l) a.logits[l] = m.logits[l], a.img_stride[l] = m.logit_strides[l];
-  fill_ssd_levels(a.lv, m.hs, m.ws, m.as, m.levels);
+  fill_pyramid_levels(a.lv, m);
   a.classes = classes, a.scores = scores;
   hipLaunchKernelGGL(k_ssd_scores, dim3((unsigned)((a.lv.total + 255) / 256), n), dim3(256), 0, s, a);
   return check_launchf("k_ssd_scores<levels%d,classes%d>", m.levels, classes);
@@ -245,7 +190,7 @@ int launch_ssd_decode(const float* scores, const PyramidMaps& m, int classes, co
     d.deltas[l] = m.deltas[l], d.delta_stride[l] = m.delta_strides[l], d.pair_off[l] = pairs, d.x_f[l] = x_f[l], d.y_f[l] = y_f[l];
     pairs += m.as[l];
   }
-  fill_ssd_levels(d.lv, m.hs, m.ws, m.as, m.levels);
+  fill_pyramid_levels(d.lv, m);
   d.img_w = (float)batch_w, d.img_h = (float)batch_h, d.wh_pairs = wh_pairs, d.classes = classes, d.image_sizes = image_sizes, d.idx = idx;
   d.count = n * k, d.k = k, d.coef = coef, d.boxes = boxes, d.scores_out = scores_out, d.labels = reinterpret_cast<long long*>(labels);
   d.valid = valid;

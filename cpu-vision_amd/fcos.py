@@ -17,7 +17,6 @@ files, as in retinanet.py.
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
 from functools import partial
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
@@ -26,8 +25,8 @@ from torch import nn, Tensor
 
 from . import _lib
 from . import functional as F
-from . import ops as box_ops
 from . import resnet
+from ._one_stage import OneStageDetector, pyramid_strides
 from .anchor_utils import AnchorGenerator
 from .backbone_utils import _resnet_fpn_extractor, _validate_trainable_layers
 from .fpn import LastLevelP6P7
@@ -167,7 +166,7 @@ class FCOSHead(nn.Module):
         return {"cls_logits": cls_logits, "bbox_regression": bbox_regression, "bbox_ctrness": bbox_ctrness}
 
 
-class FCOS(nn.Module):
+class FCOS(OneStageDetector):
     """fcos.py FCOS.  forward(images: List[Tensor (C, H, W) float32 in 0..1]) -> List[{boxes (N, 4) as (x1, y1, x2, y2), scores (N,),
     labels (N,) int64}], the boxes in the coordinates of the images as given.  `**kwargs` go to GeneralizedRCNNTransform.
     center_sampling_radius is the training half's and only kept."""
@@ -175,6 +174,7 @@ class FCOS(nn.Module):
     __annotations__ = {
         "box_coder": BoxLinearCoder,
     }
+    _name = "FCOS"
 
     def __init__(self, backbone: nn.Module, num_classes: int,
                  # transform parameters
@@ -229,23 +229,12 @@ class FCOS(nn.Module):
         self._has_warned = False
         self.eval()
 
-    def eager_outputs(self, losses, detections):
-        if self.training:
-            return losses
-
-        return detections
-
     def candidates(self, head_outputs: Dict[str, List[Tensor]], padded_size, image_shapes) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
         """postprocess_detections up to the nms for the whole batch and all levels, two calls: (idx, boxes, scores, labels, valid)."""
         cls, reg, ctr = head_outputs["cls_logits"], head_outputs["bbox_regression"], head_outputs["bbox_ctrness"]
         cell_anchors = self.anchor_generator.cell_anchors
-        torch._assert(len(cell_anchors) == len(cls),
-                      "Anchors should be Tuple[Tuple[int]] because each feature "
-                      "map could potentially have different sizes and aspect ratios. "
-                      "There needs to be a match between the number of "
-                      "feature maps passed and the number of sizes / aspect ratios specified.")
+        strides = pyramid_strides(cell_anchors, cls, padded_size)
         num_classes = int(cls[0].shape[1])
-        strides = [(int(padded_size[0]) // int(m.shape[-2]), int(padded_size[1]) // int(m.shape[-1])) for m in cls]
         idx = F.fcos_topk(cls, ctr, num_classes, self.topk_candidates, self.score_thresh)
         boxes, scores, labels, valid = F.fcos_decode(cls, ctr, reg, idx, cell_anchors, strides, image_shapes, num_classes)
         return idx, boxes, scores, labels, valid
@@ -253,50 +242,10 @@ class FCOS(nn.Module):
     def postprocess_detections(self, head_outputs: Dict[str, List[Tensor]], padded_size, image_shapes) -> List[Dict[str, Tensor]]:
         """fcos.py postprocess_detections on the head's per-level NCHW maps: `candidates`, then per image the boolean indexing by
         `valid`, ops.batched_nms over the labels and the slice."""
-        _, boxes, scores, labels, valid = self.candidates(head_outputs, padded_size, image_shapes)
-        detections: List[Dict[str, Tensor]] = []
-        for b, s, lab, v in zip(boxes, scores, labels, valid):
-            b, s, lab = b[v], s[v], lab[v]
-            # non-maximum suppression
-            keep = box_ops.batched_nms(b, s, lab, self.nms_thresh)
-            keep = keep[: self.detections_per_img]
-            detections.append({"boxes": b[keep], "scores": s[keep], "labels": lab[keep]})
-        return detections
+        return self._nms_tail(*self.candidates(head_outputs, padded_size, image_shapes)[1:])
 
-    def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None) -> List[Dict[str, Tensor]]:
-        if self.training or targets is not None:
-            raise RuntimeError("the MI355X FCOS is inference only: call .eval() and pass no targets")
-
-        original_image_sizes: List[Tuple[int, int]] = []
-        for img in images:
-            val = img.shape[-2:]
-            torch._assert(len(val) == 2, f"expecting the last two dimensions of the Tensor to be H and W instead got {img.shape[-2:]}")
-            original_image_sizes.append((val[0], val[1]))
-
-        # transform the input
-        images, targets = self.transform(images, targets)
-
-        # get the features from the backbone
-        features = self.backbone(images.tensors)
-        if isinstance(features, Tensor):
-            features = OrderedDict([("0", features)])
-
-        features = list(features.values())
-        for f in features:
-            if f.dtype != torch.float32:
-                raise TypeError(f"FCOS computes in float32. Got features {f.dtype}")
-
-        with torch.no_grad():
-            # compute the fcos heads outputs using the features
-            head_outputs = self.head(features)
-            # compute the detections
-            detections = self.postprocess_detections(head_outputs, images.tensors.shape[-2:], images.image_sizes)
-        deps = (*features, *self.head.parameters())
-        detections = [{"boxes": _lib.forward_only(d["boxes"], "FCOS.forward", *deps),
-                       "scores": _lib.forward_only(d["scores"], "FCOS.forward", *deps), "labels": d["labels"]} for d in detections]
-        detections = self.transform.postprocess(detections, images.image_sizes, original_image_sizes)
-
-        return self.eager_outputs({}, detections)
+    def _detect(self, head_outputs, features, images):
+        return self.postprocess_detections(head_outputs, images.tensors.shape[-2:], images.image_sizes)
 
 
 def fcos_resnet50_fpn(*, weights: Optional[Any] = None, progress: bool = True, num_classes: Optional[int] = None,

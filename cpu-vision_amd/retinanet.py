@@ -19,7 +19,6 @@ files, as in faster_rcnn.py.
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -27,8 +26,8 @@ from torch import nn, Tensor
 
 from . import _lib
 from . import functional as F
-from . import ops as box_ops
 from . import resnet
+from ._one_stage import OneStageDetector, pyramid_strides
 from .anchor_utils import AnchorGenerator
 from .backbone_utils import _resnet_fpn_extractor, _validate_trainable_layers
 from .fpn import LastLevelP6P7
@@ -233,7 +232,7 @@ class RetinaNetHead(nn.Module):
                 "bbox_regression": [_lib.forward_only(v, "RetinaNetHead.forward", *deps) for v in reg]}
 
 
-class RetinaNet(nn.Module):
+class RetinaNet(OneStageDetector):
     """retinanet.py:291-669.  forward(images: List[Tensor (C, H, W) float32 in 0..1]) -> List[{boxes (N, 4) as (x1, y1, x2, y2),
     scores (N,), labels (N,) int64}], the boxes in the coordinates of the images as given.  The images may have any sizes: the
     transform resizes them to min_size / max_size (transform.py).  `**kwargs` go to GeneralizedRCNNTransform (`_skip_resize=True`
@@ -243,6 +242,7 @@ class RetinaNet(nn.Module):
     __annotations__ = {
         "box_coder": BoxCoder,
     }
+    _name = "RetinaNet"
 
     def __init__(self, backbone, num_classes,
                  # transform parameters
@@ -293,23 +293,12 @@ class RetinaNet(nn.Module):
         self._has_warned = False
         self.eval()
 
-    def eager_outputs(self, losses, detections):
-        if self.training:
-            return losses
-
-        return detections
-
     def candidates(self, head_outputs: Dict[str, List[Tensor]], padded_size, image_shapes) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
         """postprocess_detections up to the nms for the whole batch and all levels, two calls: (idx, boxes, scores, labels, valid)."""
         cls, reg = head_outputs["cls_logits"], head_outputs["bbox_regression"]
         cell_anchors = self.anchor_generator.cell_anchors
-        torch._assert(len(cell_anchors) == len(cls),
-                      "Anchors should be Tuple[Tuple[int]] because each feature "
-                      "map could potentially have different sizes and aspect ratios. "
-                      "There needs to be a match between the number of "
-                      "feature maps passed and the number of sizes / aspect ratios specified.")
+        strides = pyramid_strides(cell_anchors, cls, padded_size)
         num_classes = int(cls[0].shape[1]) // int(cell_anchors[0].shape[0])
-        strides = [(int(padded_size[0]) // int(m.shape[-2]), int(padded_size[1]) // int(m.shape[-1])) for m in cls]
         idx = F.retinanet_topk(cls, num_classes, self.topk_candidates, self.score_thresh)
         boxes, scores, labels, valid = F.retinanet_decode(cls, reg, idx, cell_anchors, strides, image_shapes, num_classes,
                                                           self.box_coder.weights, self.box_coder.bbox_xform_clip)
@@ -318,51 +307,10 @@ class RetinaNet(nn.Module):
     def postprocess_detections(self, head_outputs: Dict[str, List[Tensor]], padded_size, image_shapes) -> List[Dict[str, Tensor]]:
         """retinanet.py:494-560 on the head's per-level NCHW maps: `candidates`, then per image the boolean indexing by `valid` (the
         one read-back besides the nms's count), ops.batched_nms over the labels and the slice."""
-        _, boxes, scores, labels, valid = self.candidates(head_outputs, padded_size, image_shapes)
-        detections: List[Dict[str, Tensor]] = []
-        for b, s, lab, v in zip(boxes, scores, labels, valid):
-            b, s, lab = b[v], s[v], lab[v]
-            # non-maximum suppression
-            keep = box_ops.batched_nms(b, s, lab, self.nms_thresh)
-            keep = keep[: self.detections_per_img]
-            detections.append({"boxes": b[keep], "scores": s[keep], "labels": lab[keep]})
-        return detections
+        return self._nms_tail(*self.candidates(head_outputs, padded_size, image_shapes)[1:])
 
-    def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None) -> List[Dict[str, Tensor]]:
-        if self.training or targets is not None:
-            raise RuntimeError("the MI355X RetinaNet is inference only: call .eval() and pass no targets")
-
-        # get the original image sizes
-        original_image_sizes: List[Tuple[int, int]] = []
-        for img in images:
-            val = img.shape[-2:]
-            torch._assert(len(val) == 2, f"expecting the last two dimensions of the Tensor to be H and W instead got {img.shape[-2:]}")
-            original_image_sizes.append((val[0], val[1]))
-
-        # transform the input
-        images, targets = self.transform(images, targets)
-
-        # get the features from the backbone
-        features = self.backbone(images.tensors)
-        if isinstance(features, Tensor):
-            features = OrderedDict([("0", features)])
-
-        features = list(features.values())
-        for f in features:
-            if f.dtype != torch.float32:
-                raise TypeError(f"RetinaNet computes in float32. Got features {f.dtype}")
-
-        with torch.no_grad():
-            # compute the retinanet heads outputs using the features
-            head_outputs = self.head(features)
-            # compute the detections
-            detections = self.postprocess_detections(head_outputs, images.tensors.shape[-2:], images.image_sizes)
-        deps = (*features, *self.head.parameters())
-        detections = [{"boxes": _lib.forward_only(d["boxes"], "RetinaNet.forward", *deps),
-                       "scores": _lib.forward_only(d["scores"], "RetinaNet.forward", *deps), "labels": d["labels"]} for d in detections]
-        detections = self.transform.postprocess(detections, images.image_sizes, original_image_sizes)
-
-        return self.eager_outputs({}, detections)
+    def _detect(self, head_outputs, features, images):
+        return self.postprocess_detections(head_outputs, images.tensors.shape[-2:], images.image_sizes)
 
 
 def retinanet_resnet50_fpn(*, weights: Optional[Any] = None, progress: bool = True, num_classes: Optional[int] = None,

@@ -26,7 +26,7 @@ from torch import nn, Tensor
 
 from . import _lib
 from . import functional as F
-from . import ops as box_ops
+from ._one_stage import OneStageDetector
 from .anchor_utils import DefaultBoxGenerator
 from .backbone_utils import _validate_trainable_layers
 from .image_list import ImageList
@@ -297,7 +297,7 @@ def _retrieve_out_channels(model: nn.Module, size: Tuple[int, int]) -> List[int]
     return out_channels
 
 
-class SSD(nn.Module):
+class SSD(OneStageDetector):
     """ssd.py SSD.  forward(images: List[Tensor (C, H, W) float32 in 0..1]) -> List[{boxes (N, 4) as (x1, y1, x2, y2), scores (N,),
     labels (N,) int64}], the boxes in the coordinates of the images as given.  `**kwargs` go to GeneralizedRCNNTransform.  iou_thresh
     and positive_fraction are the training half's and only kept (iou_thresh, neg_to_pos_ratio)."""
@@ -305,6 +305,7 @@ class SSD(nn.Module):
     __annotations__ = {
         "box_coder": BoxCoder,
     }
+    _name = "SSD"
 
     def __init__(self, backbone: nn.Module, anchor_generator: DefaultBoxGenerator, size: Tuple[int, int], num_classes: int,
                  image_mean: Optional[List[float]] = None, image_std: Optional[List[float]] = None, head: Optional[nn.Module] = None,
@@ -356,12 +357,6 @@ class SSD(nn.Module):
         self._has_warned = False
         self.eval()
 
-    def eager_outputs(self, losses: Dict[str, Tensor], detections: List[Dict[str, Tensor]]):
-        if self.training:
-            return losses
-
-        return detections
-
     def candidates(self, head_outputs: Dict[str, List[Tensor]], features: List[Tensor],
                    images: ImageList) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
         """postprocess_detections up to the nms for the whole batch, three calls: (idx, boxes, scores, labels, valid), one row of
@@ -381,50 +376,10 @@ class SSD(nn.Module):
                                images: ImageList) -> List[Dict[str, Tensor]]:
         """ssd.py postprocess_detections on the head's per-level NCHW maps: `candidates`, then per image the boolean indexing by
         `valid`, ops.batched_nms over the labels and the slice."""
-        _, boxes, scores, labels, valid = self.candidates(head_outputs, features, images)
-        detections: List[Dict[str, Tensor]] = []
-        for b, s, lab, v in zip(boxes, scores, labels, valid):
-            b, s, lab = b[v], s[v], lab[v]
-            # non-maximum suppression
-            keep = box_ops.batched_nms(b, s, lab, self.nms_thresh)
-            keep = keep[: self.detections_per_img]
-            detections.append({"boxes": b[keep], "scores": s[keep], "labels": lab[keep]})
-        return detections
+        return self._nms_tail(*self.candidates(head_outputs, features, images)[1:])
 
-    def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None) -> List[Dict[str, Tensor]]:
-        if self.training or targets is not None:
-            raise RuntimeError("the MI355X SSD is inference only: call .eval() and pass no targets")
-
-        # get the original image sizes
-        original_image_sizes: List[Tuple[int, int]] = []
-        for img in images:
-            val = img.shape[-2:]
-            torch._assert(len(val) == 2, f"expecting the last two dimensions of the Tensor to be H and W instead got {img.shape[-2:]}")
-            original_image_sizes.append((val[0], val[1]))
-
-        # transform the input
-        images, targets = self.transform(images, targets)
-
-        # get the features from the backbone
-        features = self.backbone(images.tensors)
-        if isinstance(features, torch.Tensor):
-            features = OrderedDict([("0", features)])
-
-        features = list(features.values())
-        for f in features:
-            if f.dtype != torch.float32:
-                raise TypeError(f"SSD computes in float32. Got features {f.dtype}")
-
-        with torch.no_grad():
-            # compute the ssd heads outputs using the features
-            head_outputs = self.head(features)
-            detections = self.postprocess_detections(head_outputs, features, images)
-        deps = (*features, *self.head.parameters())
-        detections = [{"boxes": _lib.forward_only(d["boxes"], "SSD.forward", *deps),
-                       "scores": _lib.forward_only(d["scores"], "SSD.forward", *deps), "labels": d["labels"]} for d in detections]
-        detections = self.transform.postprocess(detections, images.image_sizes, original_image_sizes)
-
-        return self.eager_outputs({}, detections)
+    def _detect(self, head_outputs, features, images):
+        return self.postprocess_detections(head_outputs, features, images)
 
 
 def ssd300_vgg16(*, weights: Optional[Any] = None, progress: bool = True, num_classes: Optional[int] = None,
