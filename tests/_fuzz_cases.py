@@ -27,9 +27,9 @@ Families (the reference of each in parentheses):
   paste      F.paste_masks_in_image (_mask_ref.paste)
   keypoints  F.heatmaps_to_keypoints (_keypoint_ref.keypoints)
 
-Out of scope: the top-k and decode kernels of RPN / RetinaNet / FCOS / SSD (their tests sweep score patterns, and a random sweep
-needs a tie-stable reference of its own), the box-IoU family, and the pointwise image ops -- colour, crop, mix, autoaugment -- whose
-guard-band suites already run the ragged widths.
+The top-k, score and decode kernels of RPN / RetinaNet / FCOS / SSD / RoIHeads have sweeps of their own, on the tie-stable references
+of their test files: tests/_fuzz_detect_cases.py.  Out of scope: the box-IoU family, and the pointwise image ops -- colour, crop, mix,
+autoaugment -- whose guard-band suites already run the ragged widths.
 """
 import functools
 import itertools
