@@ -25,7 +25,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 TUNING_INC = HERE.parent / "tools" / "tuning"
-SOURCES = ["abi.hip", "dw3x3.hip", "dw3x3_u8.hip", "dwk_u8.hip", "tiefix_u8.hip", "dwtile.hip", "dwf64.hip", "separable.hip", "sepfast.hip", "sepstream.hip", "conv3x3_mfma.hip", "conv3x3_c3.hip", "conv3x3_gen.hip", "cnn_ops.hip", "linear_mfma.hip", "resize.hip", "convnorm.hip", "conv_igemm.hip", "invres.hip", "deform.hip", "deform_fused.hip", "elastic.hip", "warp.hip", "color.hip", "autoaug.hip", "crop.hip", "batchmix.hip", "detect.hip", "roi_pool.hip", "boxes.hip", "rpn.hip", "roi_heads.hip", "retinanet.hip", "ssd.hip", "groupnorm.hip", "l2norm.hip", "dw5x5.hip", "se.hip", "interp.hip", "mask.hip", "keypoint.hip", "segment.hip"]
+SOURCES = ["abi.hip", "dw3x3.hip", "dw3x3_u8.hip", "dwk_u8.hip", "tiefix_u8.hip", "dwtile.hip", "dwf64.hip", "separable.hip", "sepfast.hip", "sepstream.hip", "conv3x3_mfma.hip", "conv3x3_c3.hip", "conv3x3_gen.hip", "cnn_ops.hip", "linear_mfma.hip", "resize.hip", "convnorm.hip", "conv_igemm.hip", "invres.hip", "deform.hip", "deform_fused.hip", "elastic.hip", "warp.hip", "color.hip", "autoaug.hip", "crop.hip", "batchmix.hip", "detect.hip", "roi_pool.hip", "boxes.hip", "rpn.hip", "roi_heads.hip", "retinanet.hip", "ssd.hip", "groupnorm.hip", "l2norm.hip", "dw5x5.hip", "dw7x7.hip", "layernorm.hip", "se.hip", "interp.hip", "mask.hip", "keypoint.hip", "segment.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -34,6 +34,9 @@ FLAGS = [
     "-ffp-contract=off", "-fno-fast-math",
     "-Wall", "-Wno-unused-function",
 ]
+# flags of single sources.  dw7x7.hip: the SLP vectoriser pairs the fmaf chains of neighbouring outputs into v_pk_fma_f32, whose
+# operands must sit in aligned register pairs -- 549 moves and 266 registers (one wave per SIMD) instead of 168 (three), the same bits
+SOURCE_FLAGS = {"dw7x7.hip": ["-fno-slp-vectorize"]}
 
 
 def _paths(variant: str):
@@ -58,6 +61,7 @@ def build_id(flags) -> str:
             h.update(f.read_bytes())
     h.update((HERE.parent / "include" / "mi355vision.h").read_bytes())
     h.update(" ".join(flags).encode())
+    h.update(repr(sorted(SOURCE_FLAGS.items())).encode())
     return h.hexdigest()[:16]
 
 
@@ -96,7 +100,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
             extra = ["-Rpass-analysis=kernel-resource-usage"] if verbose else []
             if src == "abi.hip":
                 extra.append(f'-DMV_BUILD_ID="{bid}"')
-            jobs.append([HIPCC, *flags, *extra, "-c", str(CSRC / src), "-o", str(obj)])
+            jobs.append([HIPCC, *flags, *SOURCE_FLAGS.get(src, []), *extra, "-c", str(CSRC / src), "-o", str(obj)])
 
     def run(cmd):
         r = subprocess.run(cmd, capture_output=True, text=True)

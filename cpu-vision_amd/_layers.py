@@ -306,6 +306,77 @@ def conv_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return _lib.forward_only(y, "conv_norm_act", x, weight, bias, alpha, beta, residual, input_scale)
 
 
+def dwconv7x7(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.Conv2d(C, C, 7, padding=3, groups=C) of a ConvNeXt block (models/convnext.py CNBlock.block[0]) as ONE launch
+    (mv_dwconv7x7_bias_f32, k_dwpc7x7): x (N, C, H, W) float32, weight (C, 1, 7, 7), bias (C,) or None -> (N, C, H, W).  One fmaf
+    chain per output in (ky, kx) order from +0, the padding taps through the chain as zeros, then `+ bias`: the oracle's bits."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.ndim != 4 or weight.ndim != 4:
+        raise RuntimeError("dwconv7x7: expected a 4-D input (N, C, H, W) and a 4-D weight (C, 1, 7, 7)")
+    n, c, h, w = (int(d) for d in x.shape)
+    if tuple(weight.shape) != (c, 1, 7, 7):
+        raise RuntimeError(f"dwconv7x7: weight should have shape ({c}, 1, 7, 7), got {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (c,):
+        raise RuntimeError(f"dwconv7x7: bias should have shape ({c},), got {tuple(bias.shape)}")
+    _lib.require_f32_layer("dwconv7x7", x, weight)
+    _lib.require_device(x)
+    _lib.require_device(weight, "weight")
+    lib = _lib.load()
+    xc, wc, bc = x.contiguous(), weight.detach().contiguous(), _lib.f32_on(bias, x.device)
+    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    if n and c and h and w:
+        _lib.launch(lib.mv_dwconv7x7_bias_f32, xc, xc.data_ptr(), wc.data_ptr(), _lib.ptr(bc), y.data_ptr(), n, c, h, w)
+    return _lib.forward_only(y, "dwconv7x7", x, weight, bias)
+
+
+def conv1x1_gelu(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, norm=None, gelu: bool = True) -> torch.Tensor:
+    """The per-pixel nn.Linear(Cin, Cout) [+ nn.GELU()] of a ConvNeXt block on the NCHW map, as the pointwise MFMA kernel
+    (mv_conv1x1_ln_gelu_f32, k_conv1x1_ln): x (N, Cin, H, W) float32, weight (Cout, Cin) as nn.Linear stores it or (Cout, Cin, 1, 1),
+    bias (Cout,) or None -> (N, Cout, H, W).  Summation order: conv1x1_k_slices; then `+ bias`; then the exact (erf) GELU stated in
+    mi355vision.h, or nothing with gelu=False.
+    norm: None, or (mean, rstd, ln_weight, ln_bias) -- layer_norm2d_stats(x, eps)'s pair (N, H, W) and the LayerNorm's terms (Cin,) or
+    None: the LayerNorm over the channels is applied in the conv's loads, the same bits as conv1x1_gelu(layer_norm2d(x, ln_weight,
+    ln_bias, eps), weight, bias) without that tensor in memory."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.ndim != 4:
+        raise RuntimeError("conv1x1_gelu: expected a 4-D input (N, C, H, W)")
+    if weight.ndim == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight.reshape(weight.shape[0], weight.shape[1])
+    n, cin, h, w = (int(d) for d in x.shape)
+    if weight.ndim != 2 or int(weight.shape[1]) != cin:
+        raise RuntimeError(f"conv1x1_gelu: weight should have shape (Cout, {cin}) or (Cout, {cin}, 1, 1), got {tuple(weight.shape)}")
+    cout = int(weight.shape[0])
+    if cin == 0 or cout == 0:
+        raise RuntimeError(f"conv1x1_gelu: no channels (weight {tuple(weight.shape)})")
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise RuntimeError(f"conv1x1_gelu: bias should have shape ({cout},), got {tuple(bias.shape)}")
+    mean = rstd = ln_w = ln_b = None
+    if norm is not None:
+        if not isinstance(norm, (tuple, list)) or len(norm) != 4:
+            raise ValueError("conv1x1_gelu: norm is (mean, rstd, ln_weight, ln_bias) or None")
+        mean, rstd, ln_w, ln_b = norm
+        for what, t in (("mean", mean), ("rstd", rstd)):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n, h, w):
+                raise RuntimeError(f"conv1x1_gelu: norm's {what} should have shape ({n}, {h}, {w}), got "
+                                   f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"conv1x1_gelu computes in float32. Got {what} {t.dtype}")
+        for what, t in (("ln_weight", ln_w), ("ln_bias", ln_b)):
+            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (cin,)):
+                raise RuntimeError(f"conv1x1_gelu: norm's {what} should have shape ({cin},), got "
+                                   f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    _lib.require_f32_layer("conv1x1_gelu", x, weight)
+    _lib.require_device(x)
+    _lib.require_device(weight, "weight")
+    lib = _lib.load()
+    xc, wc, bc = x.contiguous(), weight.detach().contiguous(), _lib.f32_on(bias, x.device)
+    mc, rc, lw, lb = (_lib.f32_on(t, x.device) for t in (mean, rstd, ln_w, ln_b))
+    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
+    p = _lib.ptr
+    if n and h and w:
+        _lib.launch(lib.mv_conv1x1_ln_gelu_f32, xc, xc.data_ptr(), p(mc), p(rc), p(lw), p(lb), wc.data_ptr(), p(bc), y.data_ptr(),
+                    n, cin, h, w, cout, int(bool(gelu)))
+    return _lib.forward_only(y, "conv1x1_gelu", x, weight, bias, ln_w, ln_b)
+
+
 def conv1x1_upsample_add(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                          alpha: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                          top: Optional[torch.Tensor] = None, affine: Optional[str] = None,

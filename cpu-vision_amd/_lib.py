@@ -167,6 +167,10 @@ SYMBOLS = {
     "mv_dwconv_dilated_norm_act_f32": (_i, [_vp] * 7 + [_i64] + [_i] * 8 + [_vp]),
     "mv_conv1x1_gated_upsample_f32": (_i, [_vp] * 6 + [_i64] + [_i] * 6 + [_vp]),
     "mv_dwconv3x3_conv1x1_f32": (_i, [_vp] * 11 + [_i64] + [_i] * 9 + [_vp]),
+    "mv_dwconv7x7_bias_f32": (_i, [_vp] * 4 + [_i64, _i, _i, _i, _vp]),
+    "mv_layer_norm2d_stats_f32": (_i, [_vp] * 3 + [_i64, _i, _i, _i, _d, _vp]),
+    "mv_layer_norm2d_f32": (_i, [_vp] * 4 + [_i64, _i, _i, _i, _d, _vp]),
+    "mv_conv1x1_ln_gelu_f32": (_i, [_vp] * 8 + [_i64] + [_i] * 5 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -795,6 +795,79 @@ int mv_dwconv3x3_conv1x1_f32(const float* x, const float* w_dw, const float* bia
   return launch_dwconv3x3_conv1x1(x, w_dw, e_dw, w, y, n, cin, h, wdt, cout, stride, e, (hipStream_t)stream);
 }
 
+// ---- ConvNeXt: depthwise 7x7 + bias, LayerNorm over the channels, the pointwise conv with the norm in its loads and GELU in its
+//      epilogue (dw7x7.hip, layernorm.hip, convnorm.hip k_conv1x1_ln) ------------------------------------------------------------------
+int mv_dwconv7x7_bias_f32(const float* x, const float* w, const float* bias, float* y, int64_t n, int c, int h, int wdt, void* stream) {
+  if (n < 0 || c < 0 || h < 0 || wdt < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "dwconv7x7: negative size (n=%lld c=%d h=%d w=%d)", (long long)n, c, h, wdt);
+  const long long hw = (long long)h * wdt;
+  if (hw > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "dwconv7x7: a plane of %d x %d elements exceeds the 32-bit index", h, wdt);
+  if (n == 0 || c == 0 || hw == 0) return MV_OK;
+  if (n * c > (1LL << 40) / hw) return set_error(MV_ERR_UNSUPPORTED, "dwconv7x7: %lld planes of %lld elements exceed the launch grid", (long long)(n * c), hw);
+  if (!x || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "dwconv7x7: null pointer");
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4 || (uintptr_t)w % 4 || (uintptr_t)bias % 4)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "dwconv7x7: x, w, bias and y must be 4-byte aligned");
+  const long long ny = n * c * hw;
+  if (overlaps(y, ny, x, ny) || overlaps(y, ny, w, 49LL * c) || (bias && overlaps(y, ny, bias, c)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "dwconv7x7: y must not overlap x, w or bias");
+  return launch_dwpc7x7(x, w, bias, y, n, c, h, wdt, (hipStream_t)stream);
+}
+
+// apply: mv_layer_norm2d_f32 (y); otherwise mv_layer_norm2d_stats_f32 (mean / rstd)
+static int layer_norm2d(const char* op, bool apply, const float* x, const float* weight, const float* bias, float* y, float* mean, float* rstd, int64_t n,
+                        int c, int h, int w, double eps, void* stream) {
+  if (n < 0 || c < 0 || h < 0 || w < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: negative size (n=%lld c=%d h=%d w=%d)", op, (long long)n, c, h, w);
+  if (!(eps >= 0) || eps > 3.0e38) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: eps must be non-negative and finite in float32, got %g", op, eps);
+  const int64_t hw = (int64_t)h * w, image = (int64_t)c * hw;
+  if (hw > 0x7fffffffLL || image > 0x7fffffffLL)
+    return set_error(MV_ERR_UNSUPPORTED, "%s: an image of %d x %d x %d elements exceeds the 32-bit index", op, c, h, w);
+  if (n == 0 || hw == 0) return MV_OK;
+  if (c == 0) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: no channels to normalise over", op);
+  const int64_t blocks = n * layer_norm_blocks(hw);
+  if (n > 0x7fffffffLL || blocks > 0x7fffffffLL) return set_error(MV_ERR_UNSUPPORTED, "%s: %lld workgroups exceed the launch grid", op, (long long)blocks);
+  if (!x || (apply ? !y : (!mean || !rstd))) return set_error(MV_ERR_INVALID_ARGUMENT, "%s: null pointer", op);
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4 || (uintptr_t)weight % 4 || (uintptr_t)bias % 4 || (uintptr_t)mean % 4 || (uintptr_t)rstd % 4)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: every pointer must be 4-byte aligned", op);
+  const long long nx = n * image, ns = n * hw;
+  if (apply) {
+    if (overlaps(y, nx, x, nx) || (weight && overlaps(y, nx, weight, c)) || (bias && overlaps(y, nx, bias, c)))
+      return set_error(MV_ERR_INVALID_ARGUMENT, "%s: y must not overlap x, weight or bias", op);
+  } else if (overlaps(mean, ns, x, nx) || overlaps(rstd, ns, x, nx) || overlaps(mean, ns, rstd, ns)) {
+    return set_error(MV_ERR_INVALID_ARGUMENT, "%s: mean and rstd must not overlap x or each other", op);
+  }
+  return launch_layer_norm2d(x, weight, bias, y, mean, rstd, n, c, hw, (float)eps, (hipStream_t)stream);
+}
+
+int mv_layer_norm2d_stats_f32(const float* x, float* mean, float* rstd, int64_t n, int c, int h, int w, double eps, void* stream) {
+  return layer_norm2d("layer_norm2d_stats", false, x, nullptr, nullptr, nullptr, mean, rstd, n, c, h, w, eps, stream);
+}
+
+int mv_layer_norm2d_f32(const float* x, const float* weight, const float* bias, float* y, int64_t n, int c, int h, int w, double eps,
+                        void* stream) {
+  return layer_norm2d("layer_norm2d", true, x, weight, bias, y, nullptr, nullptr, n, c, h, w, eps, stream);
+}
+
+int mv_conv1x1_ln_gelu_f32(const float* x, const float* mean, const float* rstd, const float* ln_w, const float* ln_b, const float* w,
+                           const float* bias, float* y, int64_t n, int cin, int h, int wdt, int cout, int gelu, void* stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || h < 0 || wdt < 0)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "bad conv shape n=%lld cin=%d cout=%d h=%d w=%d", (long long)n, cin, cout, h, wdt);
+  if (gelu != 0 && gelu != 1) return set_error(MV_ERR_INVALID_ARGUMENT, "conv1x1_ln_gelu: gelu should be 0 or 1 instead of %d", gelu);
+  if ((mean == nullptr) != (rstd == nullptr)) return set_error(MV_ERR_INVALID_ARGUMENT, "conv1x1_ln_gelu: mean and rstd come together");
+  if (!mean && (ln_w || ln_b)) return set_error(MV_ERR_INVALID_ARGUMENT, "conv1x1_ln_gelu: LayerNorm terms without mean and rstd");
+  if (n == 0 || h == 0 || wdt == 0) return MV_OK;
+  if (!x || !w || !y) return set_error(MV_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((uintptr_t)x % 4 || (uintptr_t)y % 4 || (uintptr_t)w % 4 || (uintptr_t)bias % 4 || (uintptr_t)mean % 4 || (uintptr_t)rstd % 4 ||
+      (uintptr_t)ln_w % 4 || (uintptr_t)ln_b % 4)
+    return set_error(MV_ERR_INVALID_ARGUMENT, "conv1x1_ln_gelu: every pointer must be 4-byte aligned");
+  const long long hw = (long long)h * wdt, ny = n * cout * hw, ns = n * hw;
+  if (overlaps(y, ny, x, n * cin * hw) || overlaps(y, ny, w, (long long)cout * cin) || (bias && overlaps(y, ny, bias, cout)) ||
+      (mean && (overlaps(y, ny, mean, ns) || overlaps(y, ny, rstd, ns))) || (ln_w && overlaps(y, ny, ln_w, cin)) ||
+      (ln_b && overlaps(y, ny, ln_b, cin)))
+    return set_error(MV_ERR_INVALID_ARGUMENT, "output must not overlap input, statistics, LayerNorm terms, weight or bias");
+  return launch_conv1x1_ln_gelu(x, mean, rstd, ln_w, ln_b, w, bias, y, n, cin, hw, cout, gelu, (hipStream_t)stream);
+}
+
 int mv_global_avgpool_f64sum_f32(const float* x, float* y, int64_t n, int c, int h, int wdt, int64_t x_stride, void* stream) {
   if (n < 0 || c <= 0 || h <= 0 || wdt <= 0)
     return set_error(MV_ERR_INVALID_ARGUMENT, "global_avgpool: bad shape n=%lld c=%d h=%d w=%d", (long long)n, c, h, wdt);

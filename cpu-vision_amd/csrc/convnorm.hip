@@ -528,6 +528,11 @@ struct PwArgs {
   const float* dw_w;  // [cin][3][3]
   Epilogue dw_e;
   int dw_stride;
+  // LN instances only (ConvNeXt's block, launch_conv1x1_ln_gelu): ln != 0 selects the family; with ln_mean / ln_rstd [img * hw + p] the X
+  // chunk's element (k, p) is the LayerNorm over the channels of x[img][k][p], with ln_w / ln_b [k] (either may be null) -- four float32
+  // roundings, written out at the loads below; with ln_mean null the loads are the plain ones.  e.act is MV_ACT_NONE or kActGelu
+  int ln;
+  const float *ln_mean, *ln_rstd, *ln_w, *ln_b;
 };
 
 
@@ -700,7 +705,12 @@ __device__ __forceinline__ void pw_store_shuffle(const f32x16 (&acc)[NT], const 
 // mv_conv_norm_act_f32(MV_CONV_DW3X3).  As for GU a thread's four pixels are the same in every chunk: the offset of their window's top
 // left tap (negative in the padding) and a 9-bit in-frame mask are computed once, before the first chunk; a padding tap loads element 0
 // of the plane and selects +0.  Pixels past the plane and rows k >= cin stay +0 and read neither x nor the depthwise terms.
-template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false, bool GU = false, bool DW = false>
+// LN (k_conv1x1_ln): with A.ln_mean set, the X chunk's element (k, p) is fl(fl(fl(fl(x - mean[img][p]) rstd[img][p]) ln_w[k]) + ln_b[k])
+// (__fsub_rn / __fmul_rn / __fadd_rn: never an fma; the steps of a null ln_w / ln_b are dropped) before it goes to LDS -- the bits
+// mv_layer_norm2d_f32 stores.  A thread's four pixels are the same in every chunk: their mean / rstd are read once, before the first chunk.
+// Pixels past the plane and rows k >= cin stay +0 and read neither x nor the statistics nor the terms.  The epilogue of this family is
+// `+ bias` and none or GELU (epi_act<3>); every other instance compiles as if the flag did not exist.
+template <int NT, int MW, int KS, bool UP = false, bool CT = false, bool SC = false, bool GU = false, bool DW = false, bool LN = false>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwArgs A) {
   constexpr int PG = 4 / MW;              // pixel groups (waves along pixels)
   constexpr int PXB = PG * NT * 32;       // pixels per workgroup
@@ -775,6 +785,23 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
       doff[i] = iy0 * A.src_w + ix0;
       dmask[i] = p + i < HW ? m : 0u;  // past the plane: never read
       if (++ox == A.wdt) ox = 0, ++oy;
+    }
+  }
+
+  // LN: mean / rstd of pixels p0 + 4 q + i, q = tid % (PXB / 4) -- the q of every X unit of this thread
+  static_assert(!LN || 256 % (PXB / 4) == 0, "a thread's pixel quad must not depend on the unit");
+  float lmean[LN ? 4 : 1], lrstd[LN ? 4 : 1];
+  (void)lmean, (void)lrstd;
+  bool lnorm = false;
+  (void)lnorm;
+  if constexpr (LN) {
+    lnorm = A.ln_mean != nullptr;  // launch-uniform
+    const int p = p0 + 4 * (tid % (PXB / 4));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool in = lnorm && p + i < HW;  // past the plane: never read
+      lmean[i] = in ? A.ln_mean[(size_t)img * HW + p + i] : 0.f;
+      lrstd[i] = in ? A.ln_rstd[(size_t)img * HW + p + i] : 0.f;
     }
   }
 
@@ -873,6 +900,20 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
         if constexpr (SC) {
           const float g = A.gate[(size_t)img * K + k];
           v.x = __fmul_rn(g, v.x), v.y = __fmul_rn(g, v.y), v.z = __fmul_rn(g, v.z), v.w = __fmul_rn(g, v.w);
+        }
+        if constexpr (LN) {
+          if (lnorm) {
+            const float gw = A.ln_w ? A.ln_w[k] : 1.f, gb = A.ln_b ? A.ln_b[k] : 0.f;
+            float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              float t = __fmul_rn(__fsub_rn(e[i], lmean[i]), lrstd[i]);
+              if (A.ln_w) t = __fmul_rn(t, gw);
+              if (A.ln_b) t = __fadd_rn(t, gb);
+              e[i] = p + i < HW ? t : 0.f;
+            }
+            v = (f32x4){e[0], e[1], e[2], e[3]};
+          }
         }
       }
       xreg[u] = v;
@@ -982,6 +1023,11 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv1x1(const PwA
     pw_store_shuffle<NT>(acc, tile, A, tb, lane);
     return;
   }
+  if constexpr (LN) {  // `+ bias`, then none or GELU; no norm, no residual
+    if (A.e.act == kActGelu) pw_store<NT, 3, false, false>(acc, tile, A, tb, lane);
+    else pw_store<NT, 0, false, false>(acc, tile, A, tb, lane);
+    return;
+  }
   const bool res = UP || A.e.res != nullptr;  // UP instances always add `top`: their other halves fold away
   if (A.e.act <= 2 && A.e.affine == 2 && A.e.bias == nullptr) {
     res ? pw_store<NT, 0, true, true, UP>(acc, tile, A, tb, lane) : pw_store<NT, 0, false, true, UP>(acc, tile, A, tb, lane);
@@ -1051,6 +1097,19 @@ static int pw_launch(PwArgs& a, int64_t n, const PwPlan& p, hipStream_t s) {
   if (nb > 0x7fffffffLL || n > 65535) return set_error(MV_ERR_UNSUPPORTED, "conv1x1: problem too large for one launch");
   const dim3 grid((unsigned)nb, (unsigned)n);
   const bool up = a.top != nullptr;  // the same plan, the instances that gather their residual from `top`
+  if (a.ln) {  // the same plan, the instances that normalise their X loads over the channels and end in `+ bias` [GELU]
+    int ks = 1;
+    if constexpr (NT == 1) ks = p.ks;
+    if (ks == 2) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 2, false, false, false, false, false, true>), grid, dim3(512), 0, s, a);
+    } else if (ks == 4) {
+      if constexpr (NT == 1) hipLaunchKernelGGL((k_conv1x1<1, MW, 4, false, false, false, false, false, true>), grid, dim3(1024), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_conv1x1<NT, MW, 1, false, false, false, false, false, true>), grid, dim3(256), 0, s, a);
+    }
+    const char* loads = a.ln_mean ? "norm" : "plain";
+    return ks > 1 ? check_launchf("k_conv1x1_ln<1,%d,ks%d,%s>", MW, ks, loads) : check_launchf("k_conv1x1_ln<%d,%d,%s>", NT, MW, loads);
+  }
   if (a.dw_w) {  // the same plan, the instances that compute their X chunk as a depthwise 3x3 conv of the source map
     int ks = 1;
     if constexpr (NT == 1) ks = p.ks;
@@ -1189,6 +1248,14 @@ int launch_dwconv3x3_conv1x1(const float* x, const float* w_dw, const Epilogue& 
   dw.dw_w = w_dw, dw.dw_e = e_dw, dw.dw_e.res = nullptr, dw.dw_stride = stride;
   dw.src_h = h, dw.src_w = wd, dw.wdt = ow;
   return conv1x1(x, w, y, n, cin, (int64_t)oh * ow, cout, e, s, 0, 0, true, &dw);
+}
+
+int launch_conv1x1_ln_gelu(const float* x, const float* mean, const float* rstd, const float* ln_w, const float* ln_b, const float* w,
+                           const float* bias, float* y, int64_t n, int cin, int64_t hw, int cout, int gelu, hipStream_t s) {
+  PwArgs ln = {};
+  ln.ln = 1, ln.ln_mean = mean, ln.ln_rstd = rstd, ln.ln_w = ln_w, ln.ln_b = ln_b;
+  const Epilogue e = {bias, nullptr, nullptr, nullptr, MV_AFFINE_NONE, gelu ? kActGelu : MV_ACT_NONE};
+  return conv1x1(x, w, y, n, cin, hw, cout, e, s, 0, 0, true, &ln);
 }
 
 int launch_conv_transpose2x2(const float* x, const float* w4, float* y, int64_t n, int cin, int h, int wd, int cout, const Epilogue& e,

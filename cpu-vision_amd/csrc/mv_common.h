@@ -282,6 +282,25 @@ constexpr int kDw5Rows = 8;
 constexpr int kDw5ShortLaunch = 16384;
 int launch_dwpc5x5(const float* x, const float* w, float* y, int64_t n, int c, int h, int wd, int stride, int dilation, const Epilogue& e,
                    hipStream_t s);
+// depthwise 7x7, a kernel per channel, stride 1 with zero padding 3, `+ bias` (dw7x7.hip: ConvNeXt's blocks).  A thread's strip is
+// kDw7Rows output rows, half of that when the launch has fewer than kDw7ShortLaunch threads
+constexpr int kDw7Rows = 8;
+constexpr int kDw7ShortLaunch = 16384;
+int launch_dwpc7x7(const float* x, const float* w, const float* bias, float* y, int64_t n, int c, int h, int wd, hipStream_t s);
+// LayerNorm over the channels of dense NCHW images (layernorm.hip; semantics in mi355vision.h mv_layer_norm2d_f32).  y non-null: the
+// normalised map (mean / rstd unused); y null: the statistics alone into mean / rstd (n, hw).  The entry points have checked the
+// arguments, the extents and the grid; n, c, hw are positive and c hw < 2^31.
+constexpr int kLnPixels = 16, kLnGroups = 16;  // a workgroup: 16 consecutive pixels x 16 channel groups
+inline int64_t layer_norm_blocks(int64_t hw) { return (hw + kLnPixels - 1) / kLnPixels; }
+int launch_layer_norm2d(const float* x, const float* weight, const float* bias, float* y, float* mean, float* rstd, int64_t n, int c,
+                        int64_t hw, float eps, hipStream_t s);
+// the pointwise kernel of a ConvNeXt block (k_conv1x1_ln: the plan, tiles and summation order of launch_conv1x1): with mean / rstd
+// (n, hw) the X chunk's element (k, p) is fl(fl(fl(fl(x - mean[p]) rstd[p]) ln_w[k]) + ln_b[k]) (ln_w / ln_b may be null: their step is
+// dropped), computed in the loads; with mean null the plain loads.  Epilogue: `+ bias`, then the erf GELU (gelu != 0) or nothing.
+// kActGelu is this family's activation code inside Epilogue::act; no public entry point accepts it.
+constexpr int kActGelu = 7;
+int launch_conv1x1_ln_gelu(const float* x, const float* mean, const float* rstd, const float* ln_w, const float* ln_b, const float* w,
+                           const float* bias, float* y, int64_t n, int cin, int64_t hw, int cout, int gelu, hipStream_t s);
 // squeeze-excitation and the dense layer with an activation (se.hip; the orders are stated in mi355vision.h).  The entry points have
 // checked every argument
 int launch_global_avgpool(const float* x, float* y, int64_t n, int c, int hw, int64_t x_stride, hipStream_t s);

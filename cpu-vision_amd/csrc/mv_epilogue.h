@@ -29,7 +29,16 @@ __device__ inline float epi_norm(float acc, const ChannelTerms& c, const Epilogu
   return e.affine == 2 ? one : (e.affine == 1 ? two : v);
 }
 
-// activation kinds: 0 = none / ReLU / ReLU6 as one compare-select pair against (lo, hi), 1 = Hardswish, 2 = SiLU
+// activation kinds: 0 = none / ReLU / ReLU6 as one compare-select pair against (lo, hi), 1 = Hardswish, 2 = SiLU, 3 = GELU (erf form;
+// k_conv1x1_ln only: no public activation code reaches it)
+// GELU: t = fl(v / sqrt(2)) as a product with the float32 constant, e = the correctly rounded float32 erf(t) through float64 (as exp_cr
+// in mv_boxcoder.h: erf's float64 result is within an ulp of the true value, 2^29 times finer than the float32 grid), then
+// fl(fl(0.5 v) fl(1 + e)).  NaN gives NaN, +inf gives +inf, -inf gives NaN (-inf * 0): whatever the formula gives.
+__device__ inline float gelu_erf(float v) {
+  const float t = __fmul_rn(v, 0.70710678118654752440f);
+  const float e = (float)erf((double)t);
+  return __fmul_rn(__fmul_rn(0.5f, v), __fadd_rn(1.f, e));
+}
 struct Clamp {
   float lo, hi;
 };
@@ -47,6 +56,7 @@ __device__ inline float epi_act(float v, const Clamp& c) {
     return v * t / 6.f;
   }
   if (ACTK == 2) return v / (1.f + expf(-v));
+  if (ACTK == 3) return gelu_erf(v);
   return clamp_f32(v, c.lo, c.hi);
 }
 

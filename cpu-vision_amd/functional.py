@@ -11,7 +11,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
   _layers     the CNN layers (models/vgg.py:81-85, ops/misc.py:68-128, models/mobilenetv2.py:39-63): conv2d_bias_relu,
               conv2d_bias_act, conv2d_affine_act, max_pool2d*, adaptive_avg_pool2d, linear_bias_relu, conv_norm_act,
               conv1x1_upsample_add (FPN's top-down merge), conv1x1_gated_upsample (LRASPP's head), dwconv_pointwise (SSDlite's
-              depthwise-separable block), inverted_residual,
+              depthwise-separable block), inverted_residual, dwconv7x7 and conv1x1_gelu (ConvNeXt's block: depthwise 7x7 + bias; the
+              per-pixel Linear with the LayerNorm in its loads and GELU in its epilogue),
               fold_batchnorm, normalized_conv2d_bias_relu, the *_k_slices queries
   _misc       resize / center_crop / to_dtype / normalize and their kernels, to_float_normalize
   _geometry   elastic / affine / rotate / perspective and their _image / _mask / _video kernels
@@ -25,7 +26,8 @@ split as the reference splits transforms/v2/functional/, plus the layers, which 
               fcos_topk / fcos_decode (fcos.py postprocess_detections up to the nms: the centerness score, BoxLinearCoder.decode)
               ssd_scores / ssd_topk / ssd_decode (ssd.py postprocess_detections up to the nms: softmax, per-class top-k, default boxes)
   _norm       group_norm_act (torch.nn.functional.group_norm + ReLU: the FCOS towers' norm), group_norm_chunk, l2_normalize_scale
-              (weight * F.normalize over the channels: SSD's conv4_3)
+              (weight * F.normalize over the channels: SSD's conv4_3), layer_norm2d / layer_norm2d_stats (LayerNorm over the channels of
+              an NCHW map: ConvNeXt's LayerNorm2d)
   _se         global_avg_pool / linear_act / se_scale and squeeze_excitation_gate / squeeze_excitation (ops/misc.py SqueezeExcitation;
               MobileNetV3's Linear -> Hardswish); the gate folded into the projection is conv_norm_act(..., input_scale=gate)
   _interp     interpolate (torch.nn.functional.interpolate, plain bilinear) and detection_batch, the fused normalize + resize +
@@ -77,8 +79,8 @@ from ._filters import (_adjust_sharpness_image_pil, adjust_sharpness, adjust_sha
                        gaussian_sobel, _get_gaussian_kernel1d, _get_gaussian_kernel2d, _host_taps, _pair_f32, _planes,
                        _same_frames, separable_gaussian_blur, _sharpness, sobel, _taps_dtype, _use_separable)
 from ._interp import detection_batch, interpolate, interpolate_output_size, MAX_NORMALIZE_CHANNELS  # noqa: F401
-from ._layers import (_ACT_CODES, adaptive_avg_pool2d, _AFFINE_CODES, conv1x1_gated_upsample, conv1x1_k_slices,  # noqa: F401
-                      conv1x1_upsample_add,
+from ._layers import (_ACT_CODES, adaptive_avg_pool2d, _AFFINE_CODES, conv1x1_gated_upsample, conv1x1_gelu, conv1x1_k_slices,  # noqa: F401
+                      conv1x1_upsample_add, dwconv7x7,
                       conv2d_affine_act, conv2d_bias_act, conv2d_bias_relu,
                       conv3x3_k_slices, conv_norm_act, _CONV_WORKSPACE_BYTES, dwconv_pointwise, fold_batchnorm, inverted_residual,
                       inverted_residual_k_slices, _inverted_residual_workspace_bytes, linear_bias_relu, linear_k_slices,
@@ -88,7 +90,7 @@ from ._lib import max_value as _max_value  # noqa: F401
 from ._mask import conv_transpose2d_bias_act, conv_transpose2x2_relayout, mask_probs, paste_masks_in_image  # noqa: F401
 from ._misc import (center_crop, center_crop_image, _mean_std, normalize, normalize_image, resize, resize_image,  # noqa: F401
                     resize_video, to_dtype, to_dtype_image, _to_dtype_tensor_dispatch, to_float_normalize)
-from ._norm import group_norm_act, group_norm_chunk, l2_normalize_scale  # noqa: F401
+from ._norm import group_norm_act, group_norm_chunk, l2_normalize_scale, layer_norm2d, layer_norm2d_stats  # noqa: F401
 from ._se import global_avg_pool, linear_act, se_scale, squeeze_excitation, squeeze_excitation_gate  # noqa: F401
 from ._segment import interpolate_argmax, LABEL_DTYPES  # noqa: F401
 from ._registry import _get_kernel, _register_kernel_internal  # noqa: F401

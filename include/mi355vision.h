@@ -1218,6 +1218,52 @@ int mv_dwconv3x3_conv1x1_f32(const float* x, const float* w_dw, const float* bia
                              int64_t n, int cin, int h, int wdt, int cout, int stride, int affine_dw, int act_dw, int affine, int act,
                              void* stream);
 
+/* ---- ConvNeXt (models/convnext.py): depthwise 7x7, LayerNorm over the channels of an NCHW map, the per-pixel Linear + GELU ------------
+ * All DEVICE pointers, float32, 4-byte aligned, dense NCHW; every entry is ONE launch, nothing read back.
+ *
+ * mv_dwconv7x7_bias_f32: depthwise conv, a 7 x 7 kernel per channel, w (c, 1, 7, 7), zero padding 3, stride 1, x (n, c, h, w) -> y of the
+ *   same shape (k_dwpc7x7).  One float32 accumulator per output, acc = fmaf(w[ky][kx], x[oy - 3 + ky][ox - 3 + kx], acc) in ascending
+ *   (ky, kx) order from +0, a tap in the padding entering the chain as +0 (never skipped: a NaN or infinite weight reaches the border
+ *   pixels), then `+ bias[c]` (bias may be null: no addition) -- oracle/oracle.c::orc_conv2d_affine_act_f32 with groups = c.  The bits do
+ *   not depend on the alignment of x, on the launch or on n.  mv_conv_norm_act_f32 and mv_dwconv_norm_act_f32 keep refusing k == 7.
+ *
+ * mv_layer_norm2d_stats_f32: mean, rstd (n, h, w) of every pixel's c values of x (n, c, h, w).  With e = (double)(float)eps:
+ *     part   for g = 0 .. 15:  P[g] = the sum of (double)x[q] over the channels q = g, g + 16, g + 32, ... < c, added one after the
+ *            other in ascending q to 0.0 in float64 (a group without a channel is 0.0);
+ *     S      = P[0] + P[1] + ... + P[15], added in ascending g to 0.0;      m = S / (double)c
+ *     Q      the same two steps over d d with d = (double)x[q] - m: the subtraction, the square and every add one float64 rounding
+ *            each, never an fma
+ *     mean   = (float)m,      rstd = (float)(1.0 / sqrt(Q / (double)c + e)), IEEE float64 divisions and square root.
+ *   The order is the same for every shape: a pixel's pair is a function of its c values, c and eps alone -- not of n, h, w, the pixel's
+ *   place or the launch.  c == 1 gives mean = x, rstd = (float)(1 / sqrt(e)); eps == 0 with a constant pixel gives rstd = +inf.
+ * mv_layer_norm2d_f32 (LayerNorm2d: permute, F.layer_norm over C, permute back): with the pixel's mean and rstd as above,
+ *     y[q] = fl(fl(fl(fl(x[q] - mean) rstd) weight[q]) + bias[q]),
+ *   four float32 roundings, never an fma; a null weight / bias drops its step.  NaN and +-inf follow from the formula (a constant pixel
+ *   at eps == 0 is 0 * inf = NaN).  torch's CPU layer_norm sums in float32 and multiplies by another association: it differs by a few
+ *   float32 ulps of the result's scale, and this statement is the closer one to the float64 evaluation.
+ *
+ * mv_conv1x1_ln_gelu_f32: y (n, cout, h, w) = act(w (cout, cin) . Z + bias), the pointwise kernel of mv_conv_norm_act_f32 (MV_CONV_PW1X1)
+ *   (k_conv1x1_ln): the same tiles, plan and summation order (mv_conv1x1_k_slices(n, cin, h, w, cout)), then `+ bias[j]` (null: no addition),
+ *   then, with gelu == 1, GELU in its erf form: t = fl(v * 0.70710678118654752440f), E = (float)erf((double)t) -- the correctly rounded
+ *   float32 erf, through float64 as the exp of mv_rpn_decode_f32 --, y = fl(fl(0.5f v) fl(1 + E)).  NaN gives NaN, +inf gives +inf and -inf
+ *   gives NaN (-inf * 0): what the formula gives, not what another library's vector routine gives.  gelu == 0: no activation.
+ *   Z = x (n, cin, h, w) when mean is null.  Otherwise Z = mv_layer_norm2d_f32's value on x, computed in the kernel's loads from mean, rstd
+ *   (n, h, w) -- the outputs of mv_layer_norm2d_stats_f32 -- and ln_w, ln_b (cin each, either may be null) with the four roundings above:
+ *   bit for bit, NaN included, mv_conv1x1_ln_gelu_f32(mean = NULL) on the output of mv_layer_norm2d_f32, without that tensor in memory.
+ *   GELU is reachable through this entry point only: every other entry keeps refusing activation codes beyond its own.  n <= 65535.
+ *
+ * Refused before any launch (MV_ERR_INVALID_ARGUMENT unless said), writing nothing: a null x / w / y / mean / rstd where it is required
+ * (bias, weight, ln_w, ln_b may be null; mean and rstd are both null or both set, and ln_w / ln_b need them), a negative size, cin or
+ * cout or (for the norms) c of 0 on a non-empty map, eps negative, NaN or beyond float32, gelu other than 0 / 1, a misaligned pointer,
+ * an output that overlaps an input or the other output, a plane, an image or a grid beyond what one launch indexes
+ * (MV_ERR_UNSUPPORTED).  n == 0 or an empty plane is a no-op that touches no pointer. */
+int mv_dwconv7x7_bias_f32(const float* x, const float* w, const float* bias, float* y, int64_t n, int c, int h, int wdt, void* stream);
+int mv_layer_norm2d_stats_f32(const float* x, float* mean, float* rstd, int64_t n, int c, int h, int w, double eps, void* stream);
+int mv_layer_norm2d_f32(const float* x, const float* weight, const float* bias, float* y, int64_t n, int c, int h, int w, double eps,
+                        void* stream);
+int mv_conv1x1_ln_gelu_f32(const float* x, const float* mean, const float* rstd, const float* ln_w, const float* ln_b, const float* w,
+                           const float* bias, float* y, int64_t n, int cin, int h, int wdt, int cout, int gelu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
