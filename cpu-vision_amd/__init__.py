@@ -83,6 +83,7 @@ from .ssd import (SSD, SSDClassificationHead, SSDFeatureExtractorVGG, SSDHead, S
                   ssd300_vgg16)
 from .ssdlite import (SSDLiteClassificationHead, SSDLiteFeatureExtractorMobileNet, SSDLiteHead, SSDLiteRegressionHead,  # noqa: F401
                       ssdlite320_mobilenet_v3_large)
+from .mobilenet import refresh_parameters  # noqa: F401
 from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small  # noqa: F401
 from .segmentation import (ASPP, FCN, LRASPP, ASPPConv, ASPPPooling, DeepLabHead, DeepLabV3, FCNHead, LRASPPHead,  # noqa: F401
                            deeplabv3_mobilenet_v3_large, deeplabv3_resnet50, deeplabv3_resnet101, fcn_resnet50, fcn_resnet101,

@@ -159,8 +159,8 @@ def _decode(name: str, logits, shapes, deltas, idx, cell_anchors, strides, image
     l0, k = logits[0], int(idx.shape[1])
     with _lib.on_device_of(l0):
         lmaps, dmaps = [_dense_images(m) for m in logits], [_dense_images(m) for m in deltas]
-        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
-        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
+        base = torch.cat([_lib.table_on(c, l0.device) for c in cell_anchors]).contiguous()
+        sizes = _lib.table_on(sizes, l0.device)
         ix = idx.contiguous()
         boxes, scores, third, valid = _candidate_outputs((n, k), l0.device)
         if n and k:
@@ -296,8 +296,8 @@ def fcos_decode(cls_logits: List[torch.Tensor], ctrness: List[torch.Tensor], bbo
     l0, k = cls_logits[0], int(idx.shape[1])
     with _lib.on_device_of(l0):
         lmaps, cmaps, dmaps = ([_dense_images(m) for m in maps] for maps in (cls_logits, ctrness, bbox_regression))
-        base = torch.cat([c.detach().to(l0.device, torch.float32) for c in cell_anchors]).contiguous()
-        sizes = sizes.detach().to(l0.device, torch.float32).contiguous()
+        base = torch.cat([_lib.table_on(c, l0.device) for c in cell_anchors]).contiguous()
+        sizes = _lib.table_on(sizes, l0.device)
         ix = idx.contiguous()
         boxes, scores, labels, valid = _candidate_outputs((n, k), l0.device)
         if n and k:
@@ -407,9 +407,9 @@ def ssd_decode(scores: torch.Tensor, bbox_regression: List[torch.Tensor], idx: t
         pairs = torch.cat([p.detach().to(torch.float32) for p in wh_pairs])
         if clip:
             pairs = pairs.clamp(min=0, max=1)
-        pairs = pairs.to(d0.device).contiguous()
+        pairs = _lib.table_on(pairs, d0.device)
         sc = scores.detach().contiguous()
-        sizes = sizes.detach().to(d0.device, torch.float32).contiguous()
+        sizes = _lib.table_on(sizes, d0.device)
         ix = idx.contiguous()
         out = _candidate_outputs((n, m_), d0.device)
         if n and m_:
@@ -490,7 +490,7 @@ def roi_detections(class_logits: torch.Tensor, box_regression: torch.Tensor, roi
     with _lib.on_device_of(class_logits):
         lg, dl = _rows(class_logits), _rows(box_regression)
         rs = rois.detach().to(dev).contiguous()
-        sizes = sizes.detach().to(dev, torch.float32).contiguous()
+        sizes = _lib.table_on(sizes, dev)
         out = _candidate_outputs((r, c - 1), dev)
         if r:
             _lib.launch(lib.mv_roi_detections_f32, lg, lg.data_ptr(), int(lg.stride(0)) if r > 1 else c, dl.data_ptr(),

@@ -396,12 +396,12 @@ def depthwise_conv2d(image: torch.Tensor, weight: torch.Tensor, border: str = "r
     if image.dtype == torch.float64:
         # a float64 image is filtered in float64, like conv2d of a float64 tensor (the weight is widened exactly if it is float32)
         _lib.require_device(image)
-        wd = weight.detach().to(image.device, torch.float64).contiguous()
+        wd = _lib.table_on(weight, image.device, torch.float64)
         return _lib.launch_xy(lib.mv_depthwise_conv2d_f64, image, (wd.data_ptr(), planes, h, w, ky, kx, b), out_shape=out_shape,
                               out_dtype=torch.float64)
     on_device = ky * kx > _lib.MAX_HOST_TAPS_2D
     if on_device:
-        wt = weight.detach().to(image.device, torch.float32).contiguous()
+        wt = _lib.table_on(weight, image.device, torch.float32)
         wp = wt.data_ptr()
     else:
         wp = _lib.taps_from_tensor(weight)

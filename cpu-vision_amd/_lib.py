@@ -7,6 +7,7 @@ memory, streams and dtype plumbing only.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import sys
 from pathlib import Path
@@ -350,6 +351,23 @@ def f32_on(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     if t is None or (t.device == device and t.dtype == torch.float32 and t.is_contiguous()):
         return t
     return t.detach().to(device, torch.float32).contiguous()
+
+
+@functools.lru_cache(maxsize=256)
+def _uploaded_table(values: tuple, shape: tuple, dtype: torch.dtype, device: str) -> torch.Tensor:
+    return torch.tensor(values, dtype=dtype).reshape(shape).to(device)
+
+
+def table_on(t: torch.Tensor, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """A small table a wrapper takes from the host or the device -- cell anchors, image sizes, default-box pairs, a filter's taps --
+    as a contiguous `dtype` tensor on `device`, read-only.  One that lies on a device is used as it is (moved, if it lies on
+    another).  A host table is uploaded once per distinct contents, shape, dtype and device and cached, as _geometry.py and
+    _color.py cache their tables: an upload per call synchronises the stream and cannot be captured into a graph (the first call
+    with new contents still uploads: a warm-up outside the capture, as graphs.capture makes)."""
+    t = t.detach()
+    if t.device.type != "cpu":
+        return t.to(device, dtype).contiguous()
+    return _uploaded_table(tuple(t.reshape(-1).tolist()), tuple(t.shape), dtype, str(device))
 
 
 def require_f32_layer(name: str, x: torch.Tensor, weight: torch.Tensor) -> None:

@@ -20,7 +20,7 @@
 //
 // Contrast's mean takes two more launches before k_color: k_color_sum recomputes the ops in front of contrast and sums the
 // image's grey values per workgroup -- uint8 as an exact integer, one 64-bit atomic add per workgroup into a slot zeroed on the
-// stream (integer addition is order-free); float32 as a double partial per workgroup, reduced in a fixed order -- and
+// stream by k_color_zero (integer addition is order-free); float32 as a double partial per workgroup, reduced in a fixed order -- and
 // k_color_mean turns each image's sum into its float32 mean: uint8 (float)S / (float)N, float32 the double sum of the
 // partials, in index order, divided by N and rounded once.  Nothing goes back to the host; the results are the same bits on
 // every run.
@@ -212,6 +212,13 @@ __global__ __launch_bounds__(kThreads) void k_color_sum(const T* __restrict__ x,
   }
 }
 
+// the images' uint8 sums to zero, one slot per lane (a kernel rather than hipMemsetAsync: in a captured graph the memset node did
+// not zero the slots again on the second replay and the sums of the replays added up -- see k_zero_hist, autoaug.hip)
+__global__ __launch_bounds__(kThreads) void k_color_zero(unsigned long long* __restrict__ sums_u8, long long images) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i < images) sums_u8[i] = 0;
+}
+
 // Pass 2: the mean of each image (one workgroup per image)
 __global__ __launch_bounds__(kThreads) void k_color_mean(bool u8, long long hw, int chunks,
                                                         const unsigned long long* __restrict__ sums_u8,
@@ -287,8 +294,8 @@ int launch_chain(const T* x, T* y, long long images, long long hw, const Chain& 
     auto* partials = reinterpret_cast<double*>(rest);
     const long long chunks = sum_chunks(hw, U8);
     if (U8) {
-      const hipError_t e = hipMemsetAsync(sums, 0, (size_t)images * sizeof(unsigned long long), s);
-      if (e != hipSuccess) return set_error(MV_ERR_LAUNCH, "color: zeroing the workspace: %s", hipGetErrorString(e));
+      hipLaunchKernelGGL(k_color_zero, dim3((unsigned)((images + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, sums, images);
+      if (int rc = check_launch("k_color_zero")) return rc;
     }
     hipLaunchKernelGGL((k_color_sum<T, C, VEC>), dim3((unsigned)(images * chunks)), dim3(kThreads), 0, s, x, hw, groups,
                        (int)chunks, ch, form, sums, partials);

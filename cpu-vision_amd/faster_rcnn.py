@@ -21,7 +21,7 @@ from . import resnet
 from .anchor_utils import AnchorGenerator
 from .backbone_utils import _resnet_fpn_extractor, _validate_trainable_layers
 from .generalized_rcnn import GeneralizedRCNN
-from .mobilenet import _tensor_versions, FrozenBatchNorm2d
+from .mobilenet import _ParameterCache, _tensor_versions, FrozenBatchNorm2d
 from .ops import MultiScaleRoIAlign
 from .roi_heads import RoIHeads
 from .rpn import RegionProposalNetwork, RPNHead
@@ -143,7 +143,7 @@ class FastRCNNPredictor(nn.Module):
         super().__init__()
         self.cls_score = nn.Linear(in_channels, num_classes)
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
-        self._joint_key, self._joint = None, None
+        self._joint = _ParameterCache()
         self.eval()
 
     def joint_linear(self, device) -> Tuple[Tensor, Tensor]:
@@ -151,12 +151,12 @@ class FastRCNNPredictor(nn.Module):
         (the cache of RPNHead.joint_pointwise)."""
         tensors = (self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias)
         key = _tensor_versions(*tensors) + (str(device),)
-        if key != self._joint_key:
+
+        def joint():
             with torch.no_grad():
-                w = torch.cat([self.cls_score.weight, self.bbox_pred.weight]).to(device, torch.float32).contiguous()
-                b = torch.cat([self.cls_score.bias, self.bbox_pred.bias]).to(device, torch.float32).contiguous()
-            self._joint_key, self._joint = key, (w, b)
-        return self._joint
+                return (torch.cat([self.cls_score.weight, self.bbox_pred.weight]).to(device, torch.float32).contiguous(),
+                        torch.cat([self.cls_score.bias, self.bbox_pred.bias]).to(device, torch.float32).contiguous())
+        return self._joint.lookup(key, joint)
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         if self.training:

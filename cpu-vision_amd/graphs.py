@@ -5,6 +5,13 @@ synchronises, so a forward built from them can be captured once into a HIP graph
 replayed: one graph launch instead of ~55 kernel launches + their Python (MobileNetV2), which is what bounds the
 latency of a batch-1 request.  The Python wrappers' output / workspace allocations happen at capture time in the
 graph's private pool and are reused by every replay.
+
+Parameters after a capture: the model classes cache derived weights per module (folded norms, sliced and joint head
+weights, relaid transposed-conv weights: mobilenet._tensor_versions), and the graph holds POINTERS to the cached tensors
+of the time of the capture.  An eager forward notices a parameter update and recomputes them into new tensors; a replay
+does not and keeps reading the old ones (and the parameters a kernel reads directly through their old pointers).  After
+any parameter update -- load_state_dict, an optimiser step, a replaced Parameter, a device or dtype move,
+refresh_parameters -- capture the forward again.
 """
 from __future__ import annotations
 

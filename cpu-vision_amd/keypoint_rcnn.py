@@ -21,7 +21,7 @@ from . import functional as F
 from . import resnet
 from .backbone_utils import _resnet_fpn_extractor, _validate_trainable_layers
 from .faster_rcnn import FasterRCNN
-from .mobilenet import _tensor_versions, FrozenBatchNorm2d
+from .mobilenet import _ParameterCache, _tensor_versions, FrozenBatchNorm2d
 from .ops import MultiScaleRoIAlign
 from .roi_heads import check_keypoint_modules
 
@@ -133,7 +133,7 @@ class KeypointRCNNPredictor(nn.Module):
         nn.init.constant_(self.kps_score_lowres.bias, 0)
         self.up_scale = 2
         self.out_channels = num_keypoints
-        self._relaid_key, self._relaid = None, None
+        self._relaid = _ParameterCache()
         self.eval()
 
     def relaid(self, device) -> Tuple[Tensor, Optional[Tensor]]:
@@ -141,9 +141,7 @@ class KeypointRCNNPredictor(nn.Module):
         times on `device` (F.conv_transpose4x4_relayout), rebuilt when a parameter changes (the cache of MaskRCNNPredictor.relaid)."""
         conv = self.kps_score_lowres
         key = _tensor_versions(conv.weight, conv.bias) + (str(device),)
-        if key != self._relaid_key:
-            self._relaid_key, self._relaid = key, F.conv_transpose4x4_relayout(conv.weight, conv.bias, device)
-        return self._relaid
+        return self._relaid.lookup(key, lambda: F.conv_transpose4x4_relayout(conv.weight, conv.bias, device))
 
     def forward(self, x: Tensor) -> Tensor:
         if self.training:

@@ -22,7 +22,7 @@ from . import functional as F
 from . import resnet
 from .backbone_utils import _resnet_fpn_extractor, _validate_trainable_layers
 from .faster_rcnn import FasterRCNN
-from .mobilenet import _tensor_versions, Conv2dNormActivation, FrozenBatchNorm2d
+from .mobilenet import _ParameterCache, _tensor_versions, Conv2dNormActivation, FrozenBatchNorm2d
 from .ops import MultiScaleRoIAlign
 
 __all__ = ["MaskRCNN", "MaskRCNNHeads", "MaskRCNNPredictor", "maskrcnn_resnet50_fpn"]
@@ -151,7 +151,7 @@ class MaskRCNNPredictor(nn.Sequential):
                 nn.init.kaiming_normal_(param, mode="fan_out", nonlinearity="relu")
             # elif "bias" in name:
             #     nn.init.constant_(param, 0)
-        self._relaid_key, self._relaid = None, None
+        self._relaid = _ParameterCache()
         self.eval()
 
     def relaid(self, device) -> Tuple[Tensor, Optional[Tensor]]:
@@ -159,9 +159,7 @@ class MaskRCNNPredictor(nn.Sequential):
         when a parameter changes (the cache of FastRCNNPredictor.joint_linear)."""
         conv = self.conv5_mask
         key = _tensor_versions(conv.weight, conv.bias) + (str(device),)
-        if key != self._relaid_key:
-            self._relaid_key, self._relaid = key, F.conv_transpose2x2_relayout(conv.weight, conv.bias, device)
-        return self._relaid
+        return self._relaid.lookup(key, lambda: F.conv_transpose2x2_relayout(conv.weight, conv.bias, device))
 
     def forward(self, x: Tensor) -> Tensor:
         if self.training:

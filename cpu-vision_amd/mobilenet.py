@@ -58,14 +58,53 @@ _ACTIVATIONS = {nn.ReLU: "relu", nn.ReLU6: "relu6", nn.Hardswish: "hardswish", n
 
 
 def _tensor_versions(*tensors):
+    """The key of every derived-weight cache of the package: (data_ptr, _version, device) per tensor -- three attribute reads, no
+    device read.  It changes with an in-place update through the tensor (add_ / copy_ under no_grad, load_state_dict), a replaced
+    Parameter, a dtype round trip and a device move.  It does NOT change with a write through `p.data` (p.data.copy_(v),
+    p.data.mul_(a)): `.data` is a detached alias whose writes leave p._version alone.  Call refresh_parameters(module) after
+    such a write."""
     return tuple((t.data_ptr(), t._version, str(t.device)) for t in tensors if t is not None)
 
 
-class _FoldedNorm:
-    """Device-resident (alpha, beta) of a norm layer, recomputed when its tensors change."""
+class _ParameterCache:
+    """A per-module cache of tensors derived from parameters, keyed by _tensor_versions; reset() forgets it.  Every such cache of
+    the package is one of these (or a subclass), held as an attribute of its module or inside a list / tuple attribute: that is how
+    refresh_parameters finds them."""
 
     def __init__(self):
         self.key, self.value = None, None
+
+    def reset(self) -> None:
+        self.key = None
+
+    def lookup(self, key, compute):
+        """The cached value of `key`, computed by compute() when the key has changed."""
+        if key != self.key:
+            self.key, self.value = key, compute()
+        return self.value
+
+
+def _caches_in(v):
+    if isinstance(v, _ParameterCache):
+        yield v
+    elif isinstance(v, (list, tuple)):  # IntermediateLayerGetter keeps its caches in the steps of `_plan`
+        for item in v:
+            yield from _caches_in(item)
+
+
+def refresh_parameters(module: nn.Module) -> nn.Module:
+    """Forget every derived-weight cache under `module` (folded norms, sliced and joint head weights, relaid transposed-conv
+    weights): the next forward recomputes them.  The call that follows a write through `p.data`, the one parameter update
+    _tensor_versions cannot see.  A captured graph holds pointers to the old values: capture again (graphs.py)."""
+    for m in module.modules():
+        for v in vars(m).values():
+            for cache in _caches_in(v):
+                cache.reset()
+    return module
+
+
+class _FoldedNorm(_ParameterCache):
+    """Device-resident (alpha, beta) of a norm layer, recomputed when its tensors change."""
 
     def get(self, norm: Optional[nn.Module], device):
         if norm is None:

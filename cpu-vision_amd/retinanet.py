@@ -31,7 +31,7 @@ from ._one_stage import OneStageDetector, pyramid_strides
 from .anchor_utils import AnchorGenerator
 from .backbone_utils import _resnet_fpn_extractor, _validate_trainable_layers
 from .fpn import LastLevelP6P7
-from .mobilenet import _tensor_versions, Conv2dNormActivation, FrozenBatchNorm2d
+from .mobilenet import _ParameterCache, _tensor_versions, Conv2dNormActivation, FrozenBatchNorm2d
 from .rpn import BoxCoder
 from .transform import GeneralizedRCNNTransform
 
@@ -189,7 +189,7 @@ class RetinaNetHead(nn.Module):
         super().__init__()
         self.classification_head = RetinaNetClassificationHead(in_channels, num_anchors, num_classes, norm_layer=norm_layer)
         self.regression_head = RetinaNetRegressionHead(in_channels, num_anchors, norm_layer=norm_layer)
-        self._joint_key, self._joint = None, None
+        self._joint = _ParameterCache()
         self.eval()
 
     def joint_first_layer(self, device) -> Tuple[Tensor, Tensor]:
@@ -197,12 +197,12 @@ class RetinaNetHead(nn.Module):
         changes (the cache of RPNHead.joint_pointwise)."""
         c, r = self.classification_head.conv[0][0], self.regression_head.conv[0][0]
         key = _tensor_versions(c.weight, c.bias, r.weight, r.bias) + (str(device),)
-        if key != self._joint_key:
+
+        def joint():
             with torch.no_grad():
-                w = torch.cat([c.weight, r.weight]).to(device, torch.float32).contiguous()
-                b = torch.cat([c.bias, r.bias]).to(device, torch.float32).contiguous()
-            self._joint_key, self._joint = key, (w, b)
-        return self._joint
+                return (torch.cat([c.weight, r.weight]).to(device, torch.float32).contiguous(),
+                        torch.cat([c.bias, r.bias]).to(device, torch.float32).contiguous())
+        return self._joint.lookup(key, joint)
 
     @staticmethod
     def joint_sums_alike(x: Tensor) -> bool:

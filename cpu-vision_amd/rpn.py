@@ -28,7 +28,7 @@ from . import functional as F
 from . import ops as box_ops
 from .anchor_utils import AnchorGenerator
 from .image_list import ImageList
-from .mobilenet import _tensor_versions, Conv2dNormActivation
+from .mobilenet import _ParameterCache, _tensor_versions, Conv2dNormActivation
 
 __all__ = ["BoxCoder", "RPNHead", "RegionProposalNetwork", "concat_box_prediction_layers", "permute_and_flatten"]
 
@@ -80,7 +80,7 @@ class RPNHead(nn.Module):
                 torch.nn.init.normal_(layer.weight, std=0.01)  # type: ignore[arg-type]
                 if layer.bias is not None:
                     torch.nn.init.constant_(layer.bias, 0)  # type: ignore[arg-type]
-        self._joint_key, self._joint = None, None
+        self._joint = _ParameterCache()
         self.eval()
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -100,12 +100,12 @@ class RPNHead(nn.Module):
         (the cache of resnet.py / fpn.py's folded norms)."""
         tensors = (self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight, self.bbox_pred.bias)
         key = _tensor_versions(*tensors) + (str(device),)
-        if key != self._joint_key:
+
+        def joint():
             with torch.no_grad():
-                w = torch.cat([self.cls_logits.weight, self.bbox_pred.weight]).to(device, torch.float32).contiguous()
-                b = torch.cat([self.cls_logits.bias, self.bbox_pred.bias]).to(device, torch.float32).contiguous()
-            self._joint_key, self._joint = key, (w, b)
-        return self._joint
+                return (torch.cat([self.cls_logits.weight, self.bbox_pred.weight]).to(device, torch.float32).contiguous(),
+                        torch.cat([self.cls_logits.bias, self.bbox_pred.bias]).to(device, torch.float32).contiguous())
+        return self._joint.lookup(key, joint)
 
     def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
         if self.training:

@@ -34,7 +34,7 @@ from torch import nn
 from . import _lib, mobilenetv3, resnet
 from . import functional as F
 from .backbone_utils import IntermediateLayerGetter
-from .mobilenet import _FoldedNorm, _tensor_versions
+from .mobilenet import _FoldedNorm, _ParameterCache, _tensor_versions
 
 __all__ = ["FCN", "FCNHead", "DeepLabV3", "DeepLabHead", "ASPP", "ASPPConv", "ASPPPooling", "fcn_resnet50", "fcn_resnet101",
            "deeplabv3_resnet50", "deeplabv3_resnet101", "LRASPP", "LRASPPHead", "lraspp_mobilenet_v3_large",
@@ -49,12 +49,16 @@ def _inference_only(module: nn.Module) -> None:
 SLICE_CHANNELS = 128  # input channels per summation slice of a head's 3x3 conv: chains of 9 x 128 = 1152 terms
 
 
-class _SlicedConv:
+class _SlicedConv(_ParameterCache):
     """What a head's 3x3 conv + norm + ReLU needs per call, recomputed when the tensors change: the folded norm, a zero shift and
     the weight cut into contiguous slices of SLICE_CHANNELS input channels."""
 
     def __init__(self):
-        self.fold, self.key, self.weights, self.zero = _FoldedNorm(), None, None, None
+        self.fold, self.key, self.weights, self.zero, self.beta = _FoldedNorm(), None, None, None, None
+
+    def reset(self) -> None:
+        self.key = None
+        self.fold.reset()
 
     def get(self, conv: nn.Conv2d, norm: nn.Module, device):
         alpha, beta, mode = self.fold.get(norm, device)
@@ -62,7 +66,9 @@ class _SlicedConv:
         if key != self.key:
             w = conv.weight.detach()
             self.weights = [w[:, c:c + SLICE_CHANNELS].contiguous() for c in range(0, w.shape[1], SLICE_CHANNELS)]
-            self.key, self.zero = key, torch.zeros_like(beta)
+            self.key = key
+        if beta is not self.beta:  # the zero shift follows the folded norm (its device and length), not the conv's weight
+            self.beta, self.zero = beta, torch.zeros_like(beta)
         return alpha, beta, mode, self.weights, self.zero
 
 
